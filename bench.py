@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the hot path: HEM mixture levels + coarse-to-fine ICP on a synthetic splat pair.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--splats n] [--mode replicas|c4|c5] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--splats n] [--mode replicas|c4|c5] [--dump-outputs DIR] [--full [--no-cpu-baseline]]
 
 One STEP = one pass of the whole hot path over one pair of clouds that is already resident in HBM:
   3 HEM levels on the source cloud and on the target cloud (rho=3, delta=3, kappa=2.5, tau=1 --
@@ -20,14 +20,23 @@ Modes (one process per GPU, launched by torch.distributed.run for N > 1):
             (synth.make_block_cloud_torch), halo rows + integer partial sums per level through the library's communicator,
             the levels stay distributed --, ICP on every rank's piece with one all-reduce of 32 float64 per iteration.
 
-With --gpus N > 1 in the default (replica) mode the line also carries a "strong" object: after the replica timing every rank
+A plain run does only what its headline figure needs: set-up, warm-up, the K timed steps, --dump-outputs if given, the line.
+--full adds every side measurement (each outside the timed region, each a run of its own): one more pass of the levels with every
+phase event on, the device-copy bandwidth, a single-level ICP on the full clouds, the surfel and clustered levels (--no-aniso
+leaves them out), the CPU baseline (--no-cpu-baseline leaves it out) and, with --gpus N > 1, the strong-scaling children.
+
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float32 / float64, < 64 MB in all): every HEM
+level's arrays and normals at a fixed, seeded sample of rows plus float64 column sums over all rows, the level sizes, and the ICP
+result of every schedule entry.  The inputs depend on the arguments only, so two builds can be compared output for output.
+
+With --gpus N > 1 in the default (replica) mode, --full also puts a "strong" object into the line: after the replica timing every rank
 starts a CHILD process (same RANK / WORLD_SIZE, its own rendezvous port) that runs --mode c5 with 5 M x N splats (and --mode c4
 when N = 2), under a host-side deadline; a hang, a crash or an RCCL error there ends up as {"error": ...} inside "strong" and can
 never lose the replica line.  (A child process, not an exec: this process has initialised the GPU.)
 
 Prints ONE JSON line on rank 0.  `value` = level-input Gaussians per second through the HEM levels (whole job);
 `icp_iters_per_sec` rides along; `roofline` is for the dominant kernel of the step (algorithmic bytes of SURVEY.md 8(d));
-`cpu_baseline` is the reference's own compiled extension (oracle/_ref) -- or the oracle port when that is absent --
+`cpu_baseline` (--full) is the reference's own compiled extension (oracle/_ref) -- or the oracle port when that is absent --
 timed on this box's host cores on a bounded ladder of sizes.
 """
 from __future__ import annotations
@@ -99,11 +108,12 @@ def pmc_summary(kernel_prefix):
     return None, "no profiles/*_pmc.json taken with the current kernel sources (kernel_build %s)" % build
 
 
-def hem_levels(m, cloud, borrow=True, arenas=None, key=None, normals=False):
+def hem_levels(m, cloud, borrow=True, arenas=None, key=None, normals=False, raw=None):
     """3 HEM levels of one cloud on context m, ONE library call (gsr_hem_run_levels = MixtureCreator::CreateMixture, mixture_wrapper.cpp:10-18);
     returns (level list for ICP, per-level stats).  arenas / key: a dict that keeps this cloud's output arenas from step to step (no
     allocation in steady state).  normals: the levels' normals leave with the levels (computed on the library's side stream beside the next
-    level) and level 0's with them -- the target side of point-to-plane ICP (point_cloud_converter.py:40-43)."""
+    level) and level 0's with them -- the target side of point-to-plane ICP (point_cloud_converter.py:40-43).  raw: a dict that receives
+    every level's arrays ("levels") and level 0's normals ("normals0") -- what --dump-outputs writes."""
     import torch
     from gaussiansplattingregistration_amd.models.point_cloud import PointCloud
     m.set_level0(cloud["xyz"], cloud["color"], cloud["opacity"], cloud["cov6"], cloud["sh"], borrow=borrow)     # resident in HBM: read in place
@@ -122,6 +132,8 @@ def hem_levels(m, cloud, borrow=True, arenas=None, key=None, normals=False):
         arena = m.new_arena(LEVELS * (n0 + 64), normals=True)
         nrm0 = torch.empty((n0, 3), dtype=torch.float64, device=arena["xyz"].device)
     levels, stats = m.run_levels(LEVELS, arena=arena, normals0=nrm0)       # zero-copy: every level is written into the arena and read from it by the next
+    if raw is not None:
+        raw.update(levels=levels, normals0=nrm0)
     lv = [PointCloud(xyz32=cloud["xyz"], cov6=cloud["cov6"], normals=nrm0)]
     for d in levels:
         lv.append(PointCloud(xyz32=d["xyz"], cov6=d["cov6"], normals=d.get("normals")))
@@ -151,7 +163,8 @@ def coarse_to_fine(lru, ctx, clouds_src, clouds_tgt, device, sharded=None, comm=
         for e, r in zip(entries, res):
             out["icp_iters"] += r["iterations"]
             out["levels"].append({"ns": int(e[0].shape[0]), "nt": int(e[1].shape[0]), "iterations": r["iterations"], "ms_iters": r["ms_iters"],
-                                  "evals": r["evaluations"], "ms_build": r["ms_build"]})
+                                  "evals": r["evaluations"], "ms_build": r["ms_build"],
+                                  "T": r["transformation"], "fitness": r["fitness"], "rmse": r["inlier_rmse"]})
         out["T"], out["fitness"], out["rmse"] = res[-1]["transformation"], res[-1]["fitness"], res[-1]["inlier_rmse"]
         return out
     for k in range(LEVELS + 1):
@@ -170,7 +183,8 @@ def coarse_to_fine(lru, ctx, clouds_src, clouds_tgt, device, sharded=None, comm=
         T = r.transformation
         out["icp_iters"] += r.iterations
         out["levels"].append({"ns": len(s), "nt": len(t), "iterations": r.iterations, "ms_iters": r.timing["ms_iters"],
-                              "evals": r.timing["iter_kernels"], "ms_build": r.timing["ms_build"]})
+                              "evals": r.timing["iter_kernels"], "ms_build": r.timing["ms_build"],
+                              "T": r.transformation, "fitness": r.fitness, "rmse": r.inlier_rmse})
     out["T"], out["fitness"], out["rmse"] = T, r.fitness, r.inlier_rmse
     return out
 
@@ -192,14 +206,16 @@ def step_replicas(ctxs, lru, src, tgt, device, sync):
     out = {"hem_gaussians": 0, "kern": []}
     t0 = time.perf_counter()
     if ctxs.get("serial"):
-        clouds = []
+        clouds, out["outputs"] = [], []
         m = ctxs["hem"]
         m.set_rng("glibc", 1, 0)                       # a fresh reference process: cloud 1 then cloud 2 on one stream
         for ci, c in enumerate((src, tgt)):
-            lv, st = hem_levels(m, c, arenas=ctxs.setdefault("arenas", {}), key=ci, normals=(ci == 1))       # the target's normals leave with its levels
+            raw = {}
+            lv, st = hem_levels(m, c, arenas=ctxs.setdefault("arenas", {}), key=ci, normals=(ci == 1), raw=raw)       # the target's normals leave with its levels
             out["hem_gaussians"] += sum(s["n_in"] for s in st)
             out["kern"] += st
             clouds.append(lv)
+            out["outputs"].append(raw)
         sync()
         t1 = time.perf_counter()
         out["hem_s"] = t1 - t0
@@ -214,7 +230,8 @@ def step_replicas(ctxs, lru, src, tgt, device, sync):
         try:
             with torch.cuda.stream(ctxs["stream_a"]):
                 ctxs["hem"].set_rng("glibc", 1, 0)
-                res["src"] = hem_levels(ctxs["hem"], src)
+                res["src_raw"] = {}
+                res["src"] = hem_levels(ctxs["hem"], src, raw=res["src_raw"])
                 ctxs["stream_a"].synchronize()
         except BaseException as e:  # pragma: no cover
             err.append(e)
@@ -230,16 +247,18 @@ def step_replicas(ctxs, lru, src, tgt, device, sync):
 
                 lv = [PointCloud(xyz32=tgt["xyz"], cov6=tgt["cov6"])]
                 m.set_level0(tgt["xyz"], tgt["color"], tgt["opacity"], tgt["cov6"], tgt["sh"], borrow=True)
-                stats = []
+                stats, levels = [], []
                 for j in range(1, LEVELS + 1):
                     m.run_level()
                     stats.append(m.stats())
                     d = m.get_level(as_torch=True)
+                    levels.append(d)
                     lv.append(PointCloud(xyz32=d["xyz"], cov6=d["cov6"]))
                     prepare(lv[j], j)
                 prepare(lv[0], 0)                          # the finest entry last: it is needed last
                 ctxs["stream_b"].synchronize()
                 res["tgt"] = (lv, stats)
+                res["tgt_raw"] = {"levels": [dict(d, normals=p.normals) for d, p in zip(levels, lv[1:])], "normals0": lv[0].normals}
         except BaseException as e:  # pragma: no cover
             err.append(e)
 
@@ -257,6 +276,7 @@ def step_replicas(ctxs, lru, src, tgt, device, sync):
         out["hem_gaussians"] += sum(s["n_in"] for s in res[key][1])
         out["kern"] += res[key][1]
     out["level_sizes"] = [len(p) for p in res["src"][0]]
+    out["outputs"] = [res["src_raw"], res["tgt_raw"]]
     out.update(coarse_to_fine(lru, ctxs["icp"], res["src"][0], res["tgt"][0], device))
     sync()
     out["icp_s"] = time.perf_counter() - t1
@@ -315,6 +335,7 @@ def step_c4(ctxs, lru, src, tgt, device, sync, rank, world, comm=None):
     out.update(coarse_to_fine(lru, ctxs["icp"], lists[0], lists[1], device, sharded=(rank, world), comm=comm))
     sync()
     out["icp_s"] = time.perf_counter() - t2
+    out["outputs"] = [_pc_outputs(p) for p in lists]
     return out
 
 
@@ -354,7 +375,64 @@ def step_c5(lru, ctxs, blk, tgt, device, sync, rank, world, comm=None, owned=Non
     out.update(coarse_to_fine(lru, ctxs["icp"], src_list, tgt_list, device, comm=comm, src_global_sizes=sizes))
     sync()
     out["icp_s"] = time.perf_counter() - t1
+    out["outputs"] = [_pc_outputs(src_list), _pc_outputs(tgt_list)]          # (the source levels: this rank's pieces)
     return out
+
+
+def _pc_outputs(pcs):
+    """The arrays of a level list of PointClouds (level 0 = the input cloud: its normals only), as --dump-outputs takes them."""
+    levels = []
+    for p in pcs[1:]:
+        d = {"xyz": p.xyz32, "cov6": p.cov6}
+        if p.normals is not None:
+            d["normals"] = p.normals
+        levels.append(d)
+    return {"levels": levels, "normals0": pcs[0].normals}
+
+
+DUMP_ROWS = 16384          # rows of every level that --dump-outputs writes (a fixed, seeded sample; all rows of a smaller level)
+DUMP_SEED = 2024
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, last):
+    """--dump-outputs: what the LAST timed step computed, as dirname/<name>.npy in float32 / float64.  Per cloud (source, target) and
+    level k = 1..3 every array the level carries at the same DUMP_ROWS rows (drawn with DUMP_SEED from the level's size, so two builds
+    that agree on the sizes sample the same rows), and the float64 column sums of every array over ALL rows; level 0's normals likewise;
+    the level sizes (one row per cloud); the ICP result of every schedule entry (coarsest first).  Returns the names written."""
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {"level_sizes": np.array([[int(lv["xyz"].shape[0]) for lv in raw["levels"]] for raw in last["outputs"]], dtype=np.float64)}
+
+    def put(name, t):
+        n = int(t.shape[0])
+        rows = np.arange(n) if n <= DUMP_ROWS else np.sort(np.random.default_rng(DUMP_SEED + n).choice(n, DUMP_ROWS, replace=False))
+        if isinstance(t, torch.Tensor):
+            sample = t.index_select(0, torch.from_numpy(rows).to(t.device)).cpu().numpy()
+            colsum = t.double().sum(0).cpu().numpy()
+        else:
+            t = np.asarray(t)
+            sample, colsum = t[rows], t.astype(np.float64).sum(0)
+        arrays[name] = sample if sample.dtype in (np.float32, np.float64) else sample.astype(np.float64)
+        arrays[name + "_colsum"] = np.asarray(colsum, dtype=np.float64)
+
+    for cloud, raw in zip(("source", "target"), last["outputs"]):
+        if raw.get("normals0") is not None:
+            put(f"{cloud}_level0_normals", raw["normals0"])
+        for k, lv in enumerate(raw["levels"], start=1):
+            for f, t in lv.items():
+                if t is not None:
+                    put(f"{cloud}_level{k}_{f}", t)
+    ent = last["levels"]
+    arrays["icp_transformation"] = np.asarray(last["T"], dtype=np.float64)
+    arrays["icp_entry_transformations"] = np.stack([np.asarray(e["T"], dtype=np.float64) for e in ent])
+    arrays["icp_entry_iterations_fitness_rmse"] = np.array([[e["iterations"], e["fitness"], e["rmse"]] for e in ent], dtype=np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_MAX_BYTES}-byte limit")
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    return sorted(arrays)
 
 
 def run_strong_children(a, rank, world, barrier):
@@ -508,22 +586,29 @@ def main():
     ap.add_argument("--splats", "--n", dest="n", type=int, default=None, help="splats per cloud (c5: of the LARGE cloud); use --splats under torchrun")
     ap.add_argument("--target-splats", type=int, default=5_000_000, help="c5: splats of the target cloud")
     ap.add_argument("--mode", choices=["replicas", "c4", "c5"], default="replicas")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, every side measurement too (the phase pass, the copy bandwidth, the single-level "
+                    "ICP, the surfel and clustered levels, the CPU baseline, with --gpus N > 1 the strong-scaling children); a plain run does only what the "
+                    "headline figure needs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed to DIR/<name>.npy (float32 / float64, a "
+                    "fixed seeded sample of every level's rows, < 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--workload", choices=["iso", "aniso", "clustered"], default="iso",
                     help="splat shapes of the pair: SURVEY 8(d)'s isotropic recipe, or the surfel recipe (synth.make_cloud(shape='aniso'): 60 %% discs, "
                          "15 %% needles, covariance condition numbers 1e2 .. 1e5 on a smooth orientation field), or the large-scene recipe "
                          "(shape='clustered': 60 %% of the splats in 40 clumps of 30 .. 100 x the background density, giants, far outliers)")
-    ap.add_argument("--no-aniso", action="store_true", help="skip the anisotropic and clustered side measurements of the default run")
+    ap.add_argument("--no-aniso", action="store_true", help="--full: skip the anisotropic and clustered side measurements")
     ap.add_argument("--concurrent-clouds", action="store_true", help="replica mode: the two clouds' HEM levels side by side on two contexts / streams / host "
                     "threads (each cloud's rand() stream at position 0) and the target levels' normals computed in that phase, instead of cloud 1 then "
                     "cloud 2 on ONE context and one shared rand() stream (the default: what a single reference process does).  Measured (profiles/archive/r04c_*, "
                     "r04d_*): the HEM levels alone overlap to 27.0 instead of 28.9 ms in a bare harness, but the full step does not gain (37.7 - 43 ms "
                     "against 39.0): the two clouds' big kernels each fill the chip, and two Python threads add jitter")
-    ap.add_argument("--no-strong", action="store_true", help="--gpus N > 1, replica mode: skip the strong-scaling children (c5, and c4 at N = 2)")
+    ap.add_argument("--no-strong", action="store_true", help="--full with --gpus N > 1, replica mode: skip the strong-scaling children (c5, and c4 at N = 2)")
     ap.add_argument("--strong-splats", type=int, default=5_000_000, help="strong block: splats per GPU of the c5 source (x N) and per cloud of c4")
     ap.add_argument("--strong-steps", type=int, default=2)
     ap.add_argument("--strong-timeout", type=float, default=300.0, help="host-side deadline of one strong child, seconds")
     a = ap.parse_args()
+    if a.steps < 1:
+        raise SystemExit("--steps must be at least 1")
 
     import torch
     import __graft_entry__ as g
@@ -646,7 +731,14 @@ def main():
         one_step()
     sync(); barrier()
     t0 = time.perf_counter()
-    runs = [one_step() for _ in range(a.steps)]
+    runs, last_outputs = [], None
+    for _ in range(a.steps):
+        r = one_step()
+        o = r.pop("outputs")
+        if a.dump_outputs:                  # the arrays of the last step only, and only for --dump-outputs
+            last_outputs = o
+        del o
+        runs.append(r)
     sync(); barrier()
     elapsed = time.perf_counter() - t0
     hem_s, icp_s = sum(r["hem_s"] for r in runs), sum(r["icp_s"] for r in runs)
@@ -662,12 +754,15 @@ def main():
         # counted once, by rank 0)
         hem_gauss = float(tg)
     icp_iters = sum(r["icp_iters"] for r in runs) * (world if a.mode == "replicas" else 1)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, dict(runs[-1], outputs=last_outputs))
+    del last_outputs
 
     # The phases of a level: the timed steps above record only the events a result needs (the level and the launches of k_select and
     # k_mstep -- gsr_hem_set_timing 1, the library's default: every event between two kernels is a packet of its own, 22 per level).
     # ONE more pass of the two clouds' levels, outside the timed region, with every phase event on, gives the breakdown.
     phase_pass = None
-    if rank == 0 and a.mode == "replicas" and ctxs.get("serial"):
+    if a.full and rank == 0 and a.mode == "replicas" and ctxs.get("serial"):
         m = ctxs["hem"]
         m.set_timing(2)
         m.set_rng("glibc", 1, 0)
@@ -680,7 +775,7 @@ def main():
     # measured device-copy bandwidth of this very GPU (SURVEY 8d asks for the fraction of both the nominal and a measured
     # figure): 1 GiB device-to-device, read + write traffic
     copy_gbs = None
-    if rank == 0:
+    if a.full and rank == 0:
         try:
             src_t = torch.empty(1 << 28, dtype=torch.float32, device=dev)
             dst_t = torch.empty_like(src_t)
@@ -695,7 +790,7 @@ def main():
             copy_gbs = None
 
     strong = None
-    if world > 1 and a.mode == "replicas" and not a.no_strong:
+    if a.full and world > 1 and a.mode == "replicas" and not a.no_strong:
         # the replica measurement is complete: free its clouds, then the strong-scaling children (guarded: nothing that happens in
         # them can lose the line below)
         del src, tgt
@@ -841,7 +936,7 @@ def main():
             line["exchange_s_per_step"] = sum(r["exchange_s"] for r in runs) / a.steps
         if "part" in last:
             line["partition_rank0"] = last["part"]
-        if world == 1 and a.mode == "replicas" and a.workload == "iso":
+        if a.full and world == 1 and a.mode == "replicas" and a.workload == "iso":
             # ONE local registration on the full clouds (the LocalRegistrator path, qt_local_registrator.py:26-32: do_icp_registration(pc1, pc2, init,
             # params) with LocalRegistrationParams' defaults, registration_parameters.py:7-15 -- point-to-point, 30 iterations, 1e-6 / 1e-6) from a start
             # 0.5 degrees and 0.5 max_corr off the answer: the fine-level search kernel over its whole budget instead of the two iterations the
@@ -867,7 +962,7 @@ def main():
                                                "fitness": r1.fitness, "inlier_rmse": r1.inlier_rmse, "T_err_vs_ground_truth_F": float(np.linalg.norm(r1.transformation - T_gt))}
             except Exception as e:  # pragma: no cover
                 line["icp_single_level_5m"] = {"error": str(e)[:200]}
-        if world == 1 and a.mode == "replicas" and a.workload == "iso" and not a.no_aniso:
+        if a.full and world == 1 and a.mode == "replicas" and a.workload == "iso" and not a.no_aniso:
             # the same level on the surfel workload (real 3DGS splats are flat discs and needles, far outside the condition numbers of the
             # isotropic recipe): one 5 M-splat cloud, level 1, beside the isotropic level above
             try:
@@ -924,7 +1019,7 @@ def main():
                 ctxs["hem"] = hem.HemMixture(device=device, rng_mode="glibc", **HEM_PARAMS)
             except Exception as e:  # pragma: no cover
                 line["clustered_level"] = {"error": str(e)[:200]}
-        if world == 1 and a.mode == "replicas" and not a.no_cpu_baseline:
+        if a.full and world == 1 and a.mode == "replicas" and not a.no_cpu_baseline:
             def gpu_level1_rate(nn):
                 c = synth.make_cloud(nn, seed=0)
                 dc = {k: torch.from_numpy(v).to(dev) for k, v in c.items() if isinstance(v, np.ndarray)}

@@ -8,7 +8,7 @@
 # Steps (each may carry arguments after a colon, comma separated):
 #   tests[:PYTEST_ARGS]      pytest -q -m gpu (default: tests -x, the whole suite); e.g. tests:tests/test_hem_gpu.py,--maxfail=5
 #   smoke                    __graft_entry__.smoke()
-#   bench[:ARGS]             python bench.py ARGS            -> bench.json (e.g. bench:--steps,10)
+#   bench[:ARGS]             python bench.py --full ARGS     -> bench.json (e.g. bench:--steps,10)
 #   c2                       bench.py --splats 1000000 (BASELINE configs[1])
 #   stats                    rocprofv3 --kernel-trace --stats of the bench command -> kernel_stats.csv, bench_prof.json
 #   pmc[:aniso]              the separate --pmc passes (FETCH_SIZE | WRITE_SIZE | L2 | SQ | SQ2) over scripts/prof_hem.py 5000000 1 2 [aniso]
@@ -54,9 +54,9 @@ for step in "$@"; do
               python -m pytest $a -q -m gpu > "$OUT/pytest_gpu.log" 2>&1; echo "exit $?"; tail -5 "$OUT/pytest_gpu.log" ;;
     smoke)    python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1; tail -2 "$OUT/smoke.log" ;;
     bench)    a=$( [ "$step" = "$name" ] && echo "" || args "$step" )
-              python bench.py $a > "$OUT/bench.json" 2> "$OUT/bench.err"; tail -c 700 "$OUT/bench.json"; echo ;;
-    c2)       python bench.py --splats 1000000 --no-cpu-baseline --no-aniso > "$OUT/bench_c2.json" 2> "$OUT/bench_c2.err"; tail -c 300 "$OUT/bench_c2.json"; echo ;;
-    stats)    ( cd /tmp; rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_stats" -- python3 "$ABS/bench.py" --no-cpu-baseline --no-aniso \
+              python bench.py --full $a > "$OUT/bench.json" 2> "$OUT/bench.err"; tail -c 700 "$OUT/bench.json"; echo ;;
+    c2)       python bench.py --full --splats 1000000 --no-cpu-baseline --no-aniso > "$OUT/bench_c2.json" 2> "$OUT/bench_c2.err"; tail -c 300 "$OUT/bench_c2.json"; echo ;;
+    stats)    ( cd "$SCRATCH"; rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_stats" -- python3 "$ABS/bench.py" --full --no-cpu-baseline --no-aniso \
                   > "$OUT/bench_prof.json" 2> "$OUT/bench_prof.err" )
               f=$(ls "$OUT"/prof_stats/*/*kernel_stats.csv 2>/dev/null | head -1); [ -n "$f" ] && cp "$f" "$OUT/kernel_stats.csv" && head -12 "$OUT/kernel_stats.csv" | cut -c1-150 ;;
     pmc)      if [ "$step" = "pmc:aniso" ]; then pmc_passes pmc_aniso_ "$ABS/scripts/prof_hem.py" 5000000 1 2 aniso; else pmc_passes pmc_ "$ABS/scripts/prof_hem.py" 5000000 1 2; fi ;;

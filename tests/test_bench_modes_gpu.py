@@ -1,5 +1,5 @@
-"""bench.py end to end at a small size: the default (replica) line and the multi-GPU modes of BASELINE configs[3] / [4]
-(`--mode c4`, `--mode c5`), the latter with two ranks sharing the one GPU of the test box over gloo."""
+"""bench.py end to end at a small size: the default (replica) line, its --full side measurements, --dump-outputs, and the multi-GPU
+modes of BASELINE configs[3] / [4] (`--mode c4`, `--mode c5`), the latter with two ranks sharing the one GPU of the test box over gloo."""
 import json
 import os
 import subprocess
@@ -40,6 +40,54 @@ def test_default_line_small():
     assert ro["level1"]["n_in"] == 200000 and ro["icp_finest"]["ns"] == 200000
     assert d["icp_result"]["T_err_vs_ground_truth_F"] < 1e-3
     assert d["config"]["clouds"].startswith("serial")
+    # a plain run: the timed steps and nothing else
+    assert d["steps"] == 1 and d["ms_per_step"] > 0 and d["higher_is_better"] is True and d["dtype"] == "f32 (HEM) / f64 (ICP)"
+    assert not SIDE_MEASUREMENTS & set(d) and ro["measured_copy_GBps"] is None and "note" not in d["hem_phase_ms_per_step"]
+
+
+SIDE_MEASUREMENTS = {"icp_single_level_5m", "aniso_level", "clustered_level", "cpu_baseline", "strong"}
+
+
+def test_full_line_small():
+    """--full: the side measurements of the line, each outside the timed region -- the phase pass, the copy bandwidth, the single-level
+    ICP on the full clouds, the surfel and clustered levels (the CPU baseline has a test of its own cost: left out here)."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--splats", "200000", "--steps", "1", "--warmup", "1", "--full", "--no-cpu-baseline"],
+                       cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-3000:]
+    d = _line(r.stdout)
+    assert d["value"] > 1e6 and d["icp_result"]["T_err_vs_ground_truth_F"] < 1e-3
+    for k in ("icp_single_level_5m", "aniso_level", "clustered_level"):
+        assert "error" not in d[k], (k, d[k])
+    assert d["aniso_level"]["ms_level"] > 0 and d["clustered_level"]["ms_level"] > 0 and d["icp_single_level_5m"]["iterations"] > 0
+    assert d["roofline"]["measured_copy_GBps"] > 100 and d["hem_phase_ms_per_step"]["ms_level_with_every_phase_event"] > 0
+    assert "cpu_baseline" not in d
+
+
+def test_dump_outputs_small(tmp_path):
+    """--dump-outputs DIR: the last timed step's levels (a fixed sample of rows + column sums) and ICP results as float .npy files,
+    identical for two runs with the same arguments; --steps sets the number of timed steps."""
+    dirs, lines = [tmp_path / "a", tmp_path / "b"], []
+    for d, steps in zip(dirs, ("2", "3")):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--splats", "200000", "--steps", steps, "--warmup", "1", "--dump-outputs", str(d)],
+                           cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines.append(_line(r.stdout))
+    assert [l["steps"] for l in lines] == [2, 3]
+    names = sorted(p.name for p in dirs[0].iterdir())
+    assert names == sorted(p.name for p in dirs[1].iterdir())
+    for f in ("source_level1_xyz.npy", "source_level3_sh.npy", "target_level2_normals.npy", "target_level0_normals.npy", "icp_transformation.npy",
+              "icp_entry_iterations_fitness_rmse.npy", "level_sizes.npy"):
+        assert f in names, (f, names)
+    assert sum((dirs[0] / f).stat().st_size for f in names) < 64 << 20
+    for f in names:
+        a, b = np.load(dirs[0] / f), np.load(dirs[1] / f)
+        assert a.dtype in (np.float32, np.float64) and a.dtype == b.dtype and a.shape == b.shape, f
+        assert np.array_equal(a, b, equal_nan=True), f
+    sizes = np.load(dirs[0] / "level_sizes.npy")
+    assert sizes.shape == (2, 3) and list(sizes[0]) == lines[0]["config"]["level_sizes"][1:]
+    assert np.load(dirs[0] / "source_level1_xyz.npy").shape == (min(16384, int(sizes[0, 0])), 3)
+    it = np.load(dirs[0] / "icp_entry_iterations_fitness_rmse.npy")
+    assert list(it[:, 0]) == [l["iterations"] for l in lines[0]["icp_per_level"]] and it[-1, 1] == lines[0]["icp_result"]["fitness"]
 
 
 @pytest.mark.parametrize("workload", ["aniso", "clustered"])
@@ -87,10 +135,10 @@ def test_mode_c5_two_ranks():
 
 
 def test_replica_line_carries_the_strong_block():
-    """`bench.py --gpus 2` (what the driver's SCALE tier launches): the replica line, and inside it the strong-scaling children --
+    """`bench.py --gpus 2 --full`: the replica line, and inside it the strong-scaling children --
     configs[4] (c5, partitioned HEM of one cloud over both ranks) and configs[3] (c4, N = 2) -- each with its own accuracy."""
-    d = _torchrun(["--splats", "120000", "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--strong-splats", "100000", "--strong-steps", "1",
-                   "--strong-timeout", "400"], port=29717)
+    d = _torchrun(["--splats", "120000", "--steps", "1", "--warmup", "1", "--full", "--no-cpu-baseline", "--strong-splats", "100000",
+                   "--strong-steps", "1", "--strong-timeout", "400"], port=29717)
     assert d["n_gpus"] == 2 and d["scaling"] == "weak" and d["config"]["mode"] == "replicas"
     st = d["strong"]
     for name in ("c5", "c4"):
@@ -102,6 +150,6 @@ def test_replica_line_carries_the_strong_block():
 
 def test_a_failing_strong_child_cannot_lose_the_replica_line():
     """The guard: a deadline far too short for the children -- the replica line still comes out, with the error recorded."""
-    d = _torchrun(["--splats", "120000", "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--strong-splats", "100000", "--strong-steps", "1",
-                   "--strong-timeout", "0.5"], port=29719)
+    d = _torchrun(["--splats", "120000", "--steps", "1", "--warmup", "0", "--full", "--no-cpu-baseline", "--strong-splats", "100000",
+                   "--strong-steps", "1", "--strong-timeout", "0.5"], port=29719)
     assert d["value"] > 1e5 and "deadline" in d["strong"]["c5"]["error"] and "deadline" in d["strong"]["c4"]["error"]
