@@ -112,6 +112,10 @@ SIGNATURES = {
     "gsr_plane_score": (_i32, [_vp, _vp, _i64, _vp, _i32, _f32, _f32, _vp, _vp, C.POINTER(_i32), _i32, _i32, _vp]),
     "gsr_icp_solve": (_i32, [_vp, _i32, _vp, _vp]),
     "gsr_icp_get_centre": (_i32, [_vp, _vp]),
+    "gsr_hybrid_search": (_i32, [_vp, _i64, _f64, _i32, _vp, _vp, _i32, _i32, _vp]),
+    "gsr_fpfh": (_i32, [_vp, _vp, _i64, _f64, _i32, _vp, _i32, _i32, _vp]),
+    "gsr_feature_match": (_i32, [_vp, _i64, _vp, _i64, _i32, _i32, _vp, C.POINTER(_i64), C.POINTER(_i32), _vp, _vp, _i32, _i32, _vp]),
+    "gsr_ransac_correspondence": (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _i32, _i32, _vp]),
 }
 # private test hooks (csrc/gsr_test_hooks.h): exported by the library, not part of the public header
 TEST_HOOKS = {
@@ -119,6 +123,7 @@ TEST_HOOKS = {
     "gsr_debug_kld": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _i32]),
     "gsr_debug_kl_gate": (_i32, [_vp, _vp, _vp, _i64, _f32, _vp, _vp, _vp, _i32]),
     "gsr_debug_stage1": (_i32, [_vp, _vp, _vp, _vp, _i64, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _i32]),
+    "gsr_debug_ransac_sample": (_i32, [_u64, _i64, _i64, _i64, _i32, _vp]),
 }
 
 _lib = None
@@ -140,6 +145,26 @@ class IcpEntryResult(C.Structure):
     """gsr_icp_entry_result (include/gsr_hip.h)."""
     _fields_ = [("init_T", C.c_double * 16), ("T", C.c_double * 16), ("fitness", C.c_double), ("inlier_rmse", C.c_double),
                 ("iterations", C.c_int32), ("evaluations", C.c_int32), ("ms_build", C.c_float), ("ms_iters", C.c_float)]
+
+
+class RansacParams(C.Structure):
+    """gsr_ransac_params (include/gsr_hip.h)."""
+    _fields_ = [("kind", C.c_int32), ("ransac_n", C.c_int32), ("max_corr", C.c_double), ("max_iteration", C.c_int64),
+                ("confidence", C.c_double), ("seed", C.c_uint64), ("batch", C.c_int32), ("n_checkers", C.c_int32),
+                ("checker_kind", C.c_int32 * 4), ("checker_param", C.c_double * 4)]
+
+
+class RansacResult(C.Structure):
+    """gsr_ransac_result (include/gsr_hip.h)."""
+    _fields_ = [("T", C.c_double * 16), ("fitness", C.c_double), ("inlier_rmse", C.c_double), ("best_index", C.c_int64),
+                ("n_evaluated", C.c_int64), ("n_valid", C.c_int64), ("exit_index", C.c_int64)]
+
+
+GSR_CHECK_EDGE_LENGTH = 0
+GSR_CHECK_DISTANCE = 1
+GSR_CHECK_NORMAL = 2
+GSR_RANSAC_MAX_N = 16
+GSR_HYBRID_MAX_NN = 512
 
 
 def load(require_device: bool = False):

@@ -1,7 +1,9 @@
-"""Headless ``RegistrationController`` (reference ``src/controllers/registration_controller.py:24-28,93-120,145-163``)."""
+"""Headless ``RegistrationController`` (reference ``src/controllers/registration_controller.py:24-28,47-68,93-120,145-163``)."""
 from __future__ import annotations
 
-from ..workers.registrators import LocalRegistrator, MultiScaleRegistratorMixture, MultiScaleRegistratorVoxel
+import numpy as np
+
+from ..workers.registrators import LocalRegistrator, MultiScaleRegistratorMixture, MultiScaleRegistratorVoxel, RANSACRegistrator
 
 
 class RegistrationController:
@@ -17,6 +19,15 @@ class RegistrationController:
         worker = LocalRegistrator(pc1, pc2, self.ui_repository.transformation_matrix, params)
         result = worker.run()
         self.handle_registration_result_local(result)
+        return result
+
+    def execute_ransac_registration_normal(self, params):       # :47-52, 61-68
+        repo = self.data_repository
+        pc1 = repo.pc_open3d_list_first[repo.current_index]
+        pc2 = repo.pc_open3d_list_second[repo.current_index]
+        worker = RANSACRegistrator(pc1, pc2, self.ui_repository.transformation_matrix, params)
+        result = worker.run()
+        self.handle_registration_result_global(result)
         return result
 
     def execute_multiscale_registration(self, use_corresponding, sparse_first, sparse_second, registration_type,
@@ -43,3 +54,6 @@ class RegistrationController:
 
     def handle_registration_result_local(self, result_data):       # :145-163
         self.ui_repository.transformation_matrix = result_data.result.transformation
+
+    def handle_registration_result_global(self, results):      # :150-152
+        self.ui_repository.transformation_matrix = np.dot(results.transformation, self.ui_repository.transformation_matrix)

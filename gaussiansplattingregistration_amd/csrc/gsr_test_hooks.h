@@ -25,6 +25,9 @@ int32_t gsr_debug_kl_gate(const float* s2, const float* det_c, const float* det_
 int32_t gsr_debug_stage1(const float* parent_mean, const float* parent_cov6, const float* child_mean, const float* child_cov6, int64_t n,
                          float kld_thr, uint8_t* parent_regular, uint8_t* child_regular, uint8_t* white, uint8_t* reject, float* T1,
                          uint8_t* clip_on, int32_t device);
+/* The RANSAC sampler's raw draws (csrc/features.hip, formula in include/gsr_hip.h), on the host by the same __host__ __device__
+ * function the kernels call: out[t * n + j] = row j of hypothesis k0 + t among m correspondences, before sorting. */
+int32_t gsr_debug_ransac_sample(uint64_t seed, int64_t k0, int64_t count, int64_t m, int32_t n, int32_t* out);
 #ifdef __cplusplus
 }
 #endif

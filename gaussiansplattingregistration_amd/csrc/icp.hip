@@ -28,6 +28,8 @@
 // Accumulator layout (GSR_ICP_ACC_LEN = 32 doubles), see include/gsr_hip.h.
 #include "gsr_common.h"
 #include "gsr_normals.h"
+#include "gsr_solve.h"
+#include "gsr_features.h"
 
 #include <float.h>
 #include <math.h>
@@ -1101,169 +1103,6 @@ __global__ __launch_bounds__(256) void k_knn_normals(int64_t nt, IcpGrid g, cons
         double v[3];
         normal_of_cov_d(c00, c01, c02, c11, c12, c22, v);
         o[0] = v[0]; o[1] = v[1]; o[2] = v[2];
-    }
-}
-
-// ---- float64 solves (host and device: the device-resident ICP loop runs them in one thread) ----------
-__host__ __device__ static void svd3(const double Ain[3][3], double U[3][3], double s[3], double V[3][3]) {
-    double B[3][3];
-    for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) { B[i][j] = Ain[i][j]; V[i][j] = i == j; }
-    for (int sweep = 0; sweep < 60; ++sweep) {
-        double off = 0;
-        for (int p = 0; p < 2; ++p)
-            for (int q = p + 1; q < 3; ++q) {
-                double alpha = 0, beta = 0, gamma = 0;
-                for (int i = 0; i < 3; ++i) { alpha += B[i][p] * B[i][p]; beta += B[i][q] * B[i][q]; gamma += B[i][p] * B[i][q]; }
-                if (gamma == 0) continue;
-                off = fmax(off, fabs(gamma) / sqrt(alpha * beta + 1e-300));
-                const double zeta = (beta - alpha) / (2 * gamma);
-                const double t = (zeta >= 0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1 + zeta * zeta));
-                const double c = 1 / sqrt(1 + t * t), sn = c * t;
-                for (int i = 0; i < 3; ++i) {
-                    const double bp = B[i][p], bq = B[i][q];
-                    B[i][p] = c * bp - sn * bq; B[i][q] = sn * bp + c * bq;
-                    const double vp = V[i][p], vq = V[i][q];
-                    V[i][p] = c * vp - sn * vq; V[i][q] = sn * vp + c * vq;
-                }
-            }
-        if (off < 1e-17) break;
-    }
-    int order[3] = {0, 1, 2};
-    double nrm[3];
-    for (int j = 0; j < 3; ++j) nrm[j] = sqrt(B[0][j] * B[0][j] + B[1][j] * B[1][j] + B[2][j] * B[2][j]);
-    for (int a = 0; a < 2; ++a) for (int b = a + 1; b < 3; ++b) if (nrm[order[b]] > nrm[order[a]]) { int t = order[a]; order[a] = order[b]; order[b] = t; }
-    double Vs[3][3], Bs[3][3];
-    for (int j = 0; j < 3; ++j) { s[j] = nrm[order[j]]; for (int i = 0; i < 3; ++i) { Vs[i][j] = V[i][order[j]]; Bs[i][j] = B[i][order[j]]; } }
-    for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) V[i][j] = Vs[i][j];
-    if (!(s[0] > 0)) { for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) U[i][j] = i == j; return; }
-    for (int j = 0; j < 3; ++j) for (int i = 0; i < 3; ++i) U[i][j] = s[j] > 0 ? Bs[i][j] / s[j] : 0.0;
-    if (s[1] <= 1e-12 * s[0]) {
-        double u0[3] = {U[0][0], U[1][0], U[2][0]};
-        int k = fabs(u0[0]) < fabs(u0[1]) ? (fabs(u0[0]) < fabs(u0[2]) ? 0 : 2) : (fabs(u0[1]) < fabs(u0[2]) ? 1 : 2);
-        double e[3] = {0, 0, 0};
-        e[k] = 1;
-        const double d = u0[k];
-        double v[3] = {e[0] - d * u0[0], e[1] - d * u0[1], e[2] - d * u0[2]};
-        const double n = sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
-        for (int i = 0; i < 3; ++i) U[i][1] = v[i] / n;
-    }
-    if (s[2] <= 1e-12 * s[0]) {
-        U[0][2] = U[1][0] * U[2][1] - U[2][0] * U[1][1];
-        U[1][2] = U[2][0] * U[0][1] - U[0][0] * U[2][1];
-        U[2][2] = U[0][0] * U[1][1] - U[1][0] * U[0][1];
-    }
-}
-__host__ __device__ static double det3(const double m[3][3]) {
-    return m[0][0] * (m[1][1] * m[2][2] - m[1][2] * m[2][1]) - m[0][1] * (m[1][0] * m[2][2] - m[1][2] * m[2][0]) +
-           m[0][2] * (m[1][0] * m[2][1] - m[1][1] * m[2][0]);
-}
-// x = A^-1 b by LDL^T with diagonal pivoting (what Eigen's LDLT, which Open3D's solvers call, does).  Every index below
-// is a compile-time constant once the loops are unrolled -- the pivot's row / column exchange is a chain of tests against
-// the constant candidates -- so on the device the 36 + 15 + 18 doubles live in registers: with run-time indices the
-// arrays went to scratch memory (720 bytes per lane) and the single-thread solve of k_icp_step took ~15 us.
-__host__ __device__ static void solve6(const double A_[6][6], const double b_[6], double x[6]) {
-    double A[6][6], L[6][6], D[6], bp[6];
-    int perm[6];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-        perm[i] = i; bp[i] = b_[i];
-#pragma unroll
-        for (int j = 0; j < 6; ++j) { A[i][j] = A_[i][j]; L[i][j] = 0.0; }
-    }
-#pragma unroll
-    for (int k = 0; k < 6; ++k) {
-        int piv = k;
-        double best = fabs(A[k][k]);
-#pragma unroll
-        for (int i = k + 1; i < 6; ++i) { const double v = fabs(A[i][i]); if (v > best) { best = v; piv = i; } }
-#pragma unroll
-        for (int c = k + 1; c < 6; ++c) {
-            if (piv == c) {
-#pragma unroll
-                for (int j = 0; j < 6; ++j) { const double t = A[k][j]; A[k][j] = A[c][j]; A[c][j] = t; }
-#pragma unroll
-                for (int i = 0; i < 6; ++i) { const double t = A[i][k]; A[i][k] = A[i][c]; A[i][c] = t; }
-#pragma unroll
-                for (int j = 0; j < k; ++j) { const double t = L[k][j]; L[k][j] = L[c][j]; L[c][j] = t; }
-                const int t = perm[k]; perm[k] = perm[c]; perm[c] = t;
-                const double tb = bp[k]; bp[k] = bp[c]; bp[c] = tb;        // bp[i] == b[perm[i]] throughout
-            }
-        }
-        D[k] = A[k][k];
-        L[k][k] = 1;
-#pragma unroll
-        for (int i = k + 1; i < 6; ++i) L[i][k] = A[i][k] / D[k];
-#pragma unroll
-        for (int i = k + 1; i < 6; ++i)
-#pragma unroll
-            for (int j = k + 1; j < 6; ++j) A[i][j] -= L[i][k] * D[k] * L[j][k];
-    }
-    double y[6], z[6];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-        double s = bp[i];
-#pragma unroll
-        for (int j = 0; j < i; ++j) s -= L[i][j] * y[j];
-        y[i] = s;
-    }
-#pragma unroll
-    for (int i = 0; i < 6; ++i) y[i] /= D[i];
-#pragma unroll
-    for (int i = 5; i >= 0; --i) {
-        double s = y[i];
-#pragma unroll
-        for (int j = i + 1; j < 6; ++j) s -= L[j][i] * z[j];
-        z[i] = s;
-    }
-#pragma unroll
-    for (int i = 0; i < 6; ++i)
-#pragma unroll
-        for (int c = 0; c < 6; ++c)
-            if (perm[i] == c) x[c] = z[i];
-}
-__host__ __device__ static void mat4_identity(double T[16]) { for (int i = 0; i < 16; ++i) T[i] = (i % 5 == 0) ? 1.0 : 0.0; }
-__host__ __device__ static void mat4_mul(const double A[16], const double B[16], double C[16]) {
-    double R[16];
-    for (int i = 0; i < 4; ++i) for (int j = 0; j < 4; ++j) { double s = 0; for (int k = 0; k < 4; ++k) s += A[4 * i + k] * B[4 * k + j]; R[4 * i + j] = s; }
-    for (int i = 0; i < 16; ++i) C[i] = R[i];
-}
-
-// estimator update from the reduced accumulators (Open3D TransformationEstimation*.ComputeTransformation)
-__host__ __device__ static void estimate_update(const double ctr[3], int kind, const double* acc, double update[16]) {
-    mat4_identity(update);
-    const double n = acc[0];
-    if (!(n > 0)) return;                                   // no correspondences -> identity
-    if (kind == GSR_ICP_POINT_TO_POINT) {                   // Eigen::umeyama(src, dst, false)
-        const double mp[3] = {acc[2] / n, acc[3] / n, acc[4] / n}, mq[3] = {acc[5] / n, acc[6] / n, acc[7] / n};
-        double sigma[3][3], U[3][3], V[3][3], s[3];
-        for (int r = 0; r < 3; ++r)
-            for (int col = 0; col < 3; ++col) sigma[r][col] = acc[8 + 3 * col + r] / n - mq[r] * mp[col];   // dst x src^T
-        svd3(sigma, U, s, V);
-        double S[3] = {1, 1, 1};
-        if (det3(U) * det3(V) < 0) S[2] = -1;
-        double R[3][3];
-        for (int r = 0; r < 3; ++r)
-            for (int col = 0; col < 3; ++col) { double v = 0; for (int k = 0; k < 3; ++k) v += U[r][k] * S[k] * V[col][k]; R[r][col] = v; }
-        for (int r = 0; r < 3; ++r) {
-            for (int col = 0; col < 3; ++col) update[4 * r + col] = R[r][col];
-            double Rp = 0;
-            for (int col = 0; col < 3; ++col) Rp += R[r][col] * (mp[col] + ctr[col]);
-            update[4 * r + 3] = mq[r] + ctr[r] - Rp;
-        }
-    } else {                                                 // x = solve(JTJ, -JTr); Rz(x2) Ry(x1) Rx(x0), t = x3..5
-        double JTJ[6][6], nb[6], x[6];
-        int t = 2;
-#pragma unroll
-        for (int a = 0; a < 6; ++a)
-#pragma unroll
-            for (int b = a; b < 6; ++b) { JTJ[a][b] = acc[t]; JTJ[b][a] = acc[t]; ++t; }
-#pragma unroll
-        for (int a = 0; a < 6; ++a) nb[a] = -acc[23 + a];
-        solve6(JTJ, nb, x);
-        const double ca = cos(x[0]), sa = sin(x[0]), cb = cos(x[1]), sb = sin(x[1]), cg = cos(x[2]), sg = sin(x[2]);
-        update[0] = cg * cb; update[1] = cg * sb * sa - sg * ca; update[2] = cg * sb * ca + sg * sa; update[3] = x[3];
-        update[4] = sg * cb; update[5] = sg * sb * sa + cg * ca; update[6] = sg * sb * ca - cg * sa; update[7] = x[4];
-        update[8] = -sb;     update[9] = cb * sa;                update[10] = cb * ca;               update[11] = x[5];
     }
 }
 
@@ -2398,3 +2237,128 @@ int32_t gsr_normals_knn(const float* xyz, int64_t n, int32_t knn, double* normal
 }
 
 }  // extern "C"
+
+// ---- hybrid radius / count search (FPFH neighbourhoods, csrc/features.hip) ------------------------------------------------
+// One wave per query point over the ICP target grid of the cloud itself: every cell within ceil(radius / cell) + 1 rings is read as
+// contiguous row spans, the lanes test d^2 <= radius^2 and append the hits to an LDS list by ballot.  When the list would overflow it
+// is cut to the max_nn best by rank (keys (d^2, index) are unique), and from then on only candidates ahead of the max_nn-th key are
+// taken.  At the end each entry's rank among the list is its slot: the output is sorted by (d^2, index) without a sort.
+namespace gsr {
+
+__device__ __forceinline__ bool hyb_less(double da, unsigned ia, double db, unsigned ib) { return da < db || (da == db && ia < ib); }
+
+// keeps the min(cnt, keep) best entries of sd / si[0..cnt) at slots 0..keep-1 in (d^2, index) order; returns the new count.
+// With `out` the kept entries are written there instead (the final pass).  One wave; the list lives in LDS.
+__device__ int hyb_rank_cut(double* sd, unsigned* si, int cnt, int keep, int* out) {
+    const int lane = threadIdx.x;
+    constexpr int PER = GSR_HYBRID_CAP / 64;
+    double md[PER];
+    unsigned mi[PER];
+    int rk[PER];
+#pragma unroll
+    for (int t = 0; t < PER; ++t) {
+        const int e = lane + 64 * t;
+        md[t] = e < cnt ? sd[e] : 0.0;
+        mi[t] = e < cnt ? si[e] : 0u;
+        rk[t] = 0;
+    }
+    for (int f = 0; f < cnt; ++f) {
+        const double fd = sd[f];
+        const unsigned fi = si[f];
+#pragma unroll
+        for (int t = 0; t < PER; ++t) rk[t] += hyb_less(fd, fi, md[t], mi[t]) ? 1 : 0;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int t = 0; t < PER; ++t) {
+        const int e = lane + 64 * t;
+        if (e < cnt && rk[t] < keep) {
+            if (out) out[rk[t]] = (int)mi[t];
+            else { sd[rk[t]] = md[t]; si[rk[t]] = mi[t]; }
+        }
+    }
+    __syncthreads();
+    return cnt < keep ? cnt : keep;
+}
+
+__global__ __launch_bounds__(64) void k_hybrid_search(int64_t n, IcpGrid g, const int* __restrict__ cellStart, const float4* __restrict__ Tq,
+                                                      double r2, int R, int max_nn, int* __restrict__ nbr, int* __restrict__ cnt_out) {
+    __shared__ double sd[GSR_HYBRID_CAP];
+    __shared__ unsigned si[GSR_HYBRID_CAP];
+    const int lane = threadIdx.x;
+    for (int64_t jq = blockIdx.x; jq < n; jq += gridDim.x) {
+        const float4 qv = Tq[jq];
+        const int64_t row = (int64_t)__float_as_uint(qv.w);          // input index of the query
+        const double px = (double)qv.x, py = (double)qv.y, pz = (double)qv.z;
+        int cnt = 0;
+        bool pruned = false;
+        double thr_d = 0.0;
+        unsigned thr_i = 0u;
+        if (px == px && py == py && pz == pz) {
+            const int cx = icp_cell(px, g.ox, g.inv_c, g.gx), cy = icp_cell(py, g.oy, g.inv_c, g.gy), cz = icp_cell(pz, g.oz, g.inv_c, g.gz);
+            const int z0 = cz - R > 0 ? cz - R : 0, z1 = cz + R < g.gz - 1 ? cz + R : g.gz - 1;
+            const int y0 = cy - R > 0 ? cy - R : 0, y1 = cy + R < g.gy - 1 ? cy + R : g.gy - 1;
+            const int x0 = cx - R > 0 ? cx - R : 0, x1 = cx + R < g.gx - 1 ? cx + R : g.gx - 1;
+            for (int z = z0; z <= z1; ++z)
+                for (int y = y0; y <= y1; ++y) {
+                    const int rowbase = (z * g.gy + y) * g.gx;
+                    const int s0 = cellStart[rowbase + x0], e0 = cellStart[rowbase + x1 + 1];
+                    for (int base = s0; base < e0; base += 64) {
+                        const int j = base + lane;
+                        double d2 = 0.0;
+                        unsigned qi = 0u;
+                        bool take = false;
+                        if (j < e0) {
+                            const float4 q = Tq[j];
+                            const double dx = px - (double)q.x, dy = py - (double)q.y, dz = pz - (double)q.z;
+                            d2 = dx * dx + dy * dy + dz * dz;
+                            qi = __float_as_uint(q.w);
+                            take = d2 <= r2 && (!pruned || hyb_less(d2, qi, thr_d, thr_i));
+                        }
+                        unsigned long long mask = __ballot(take);
+                        int nt = __popcll(mask);
+                        if (cnt + nt > GSR_HYBRID_CAP) {
+                            cnt = hyb_rank_cut(sd, si, cnt, max_nn, nullptr);
+                            pruned = true;
+                            thr_d = sd[max_nn - 1]; thr_i = si[max_nn - 1];
+                            take = take && hyb_less(d2, qi, thr_d, thr_i);
+                            mask = __ballot(take);
+                            nt = __popcll(mask);
+                        }
+                        if (take) {
+                            const int pos = cnt + __popcll(mask & ((1ull << lane) - 1ull));
+                            sd[pos] = d2; si[pos] = qi;
+                        }
+                        cnt += nt;
+                        __syncthreads();
+                    }
+                }
+        }
+        const int keep = cnt < max_nn ? cnt : max_nn;
+        hyb_rank_cut(sd, si, cnt, max_nn, nbr + row * max_nn);
+        if (lane == 0) cnt_out[row] = keep;
+        __syncthreads();
+    }
+}
+
+int32_t hybrid_search_dev(const float* xyz_dev, int64_t n, double radius, int max_nn, int device, hipStream_t stream, int* nbr_dev, int* cnt_dev) {
+    if (n <= 0) return GSR_OK;
+    gsr_icp_ctx* c = nullptr;
+    GSR_TRY(gsr_icp_create(&c, device, stream));
+    int32_t r = gsr_icp_set_target(c, xyz_dev, nullptr, n, radius, 1);       // grid: about two points per cell, no finer than radius / 64
+    if (r == GSR_OK) {
+        const IcpGrid g = c->grid;
+        const double rc = ceil(radius * g.inv_c) + 1.0;                     // +1: a cell index rounded across a boundary
+        const int R = rc > (double)(1 << 20) ? (1 << 20) : (int)rc;
+        const int blocks = n < 16384 ? (int)n : 16384;
+        hipLaunchKernelGGL(k_hybrid_search, dim3(blocks), dim3(64), 0, c->stream, n, g, c->cellStart.as<int>(), c->Tq.as<float4>(), radius * radius, R,
+                           max_nn, nbr_dev, cnt_dev);
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess) r = fail(GSR_E_HIP, "hybrid search: %s", hipGetErrorString(e));
+    }
+    (void)gsr_icp_destroy(c);
+    return r;
+}
+
+}  // namespace gsr

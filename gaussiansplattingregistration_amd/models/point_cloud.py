@@ -81,10 +81,38 @@ class PointCloud:
         return PointCloud(xyz32=f32(xyz), colors=f32(col), cov6=f32(cov6))
 
     def transform(self, T):
+        """``o3d.geometry.PointCloud.transform``: points p -> R p + t, normals n -> R n, covariances C -> R C R^T (Open3D's
+        PointCloud::Transform).  Every array keeps its placement and dtype (a cuda tensor stays a cuda tensor)."""
         T = np.asarray(T, dtype=np.float64)
-        p = self.points @ T[:3, :3].T + T[:3, 3]
-        self.xyz32 = p.astype(np.float32)
+        R, t = T[:3, :3], T[:3, 3]
+
+        def _pts(a):
+            if _is_tensor(a):
+                Rt, tt = torch.as_tensor(R, device=a.device), torch.as_tensor(t, device=a.device)
+                return (a.detach().double() @ Rt.T + tt).to(a.dtype)
+            return (np.asarray(a, np.float64) @ R.T + t).astype(np.asarray(a).dtype)
+
+        def _vec(a):
+            if _is_tensor(a):
+                return (a.detach().double() @ torch.as_tensor(R, device=a.device).T).to(a.dtype)
+            return (np.asarray(a, np.float64) @ R.T).astype(np.asarray(a).dtype)
+
+        def _cov(c):
+            idx = [[0, 1, 2], [1, 3, 4], [2, 4, 5]]
+            if _is_tensor(c):
+                Rt = torch.as_tensor(R, device=c.device)
+                cd = c.detach().double()
+                M = torch.stack([cd[:, idx[0]], cd[:, idx[1]], cd[:, idx[2]]], dim=1)
+                M = Rt[None] @ M @ Rt.T[None]
+                return torch.stack([M[:, 0, 0], M[:, 0, 1], M[:, 0, 2], M[:, 1, 1], M[:, 1, 2], M[:, 2, 2]], dim=1).to(c.dtype)
+            cd = np.asarray(c, np.float64)
+            M = np.stack([cd[:, idx[0]], cd[:, idx[1]], cd[:, idx[2]]], axis=1)
+            M = R[None] @ M @ R.T[None]
+            return np.stack([M[:, 0, 0], M[:, 0, 1], M[:, 0, 2], M[:, 1, 1], M[:, 1, 2], M[:, 2, 2]], axis=1).astype(np.asarray(c).dtype)
+
+        self.xyz32 = _pts(self.xyz32)
         if self.normals is not None:
-            n = self.normals.detach().cpu().numpy() if _is_tensor(self.normals) else self.normals
-            self.normals = n @ T[:3, :3].T
+            self.normals = _vec(self.normals)
+        if self.cov6 is not None:
+            self.cov6 = _cov(self.cov6)
         return self

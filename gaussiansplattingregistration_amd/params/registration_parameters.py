@@ -1,7 +1,8 @@
-"""ICP parameters: field names and defaults of the reference's ``src/params/registration_parameters.py:7-15``."""
+"""Registration parameters: field names and defaults of the reference's ``src/params/registration_parameters.py:7-15,31-40``."""
 from dataclasses import dataclass, field
 from typing import List
 
+from ..utils.global_registration_util import RANSACEstimationMethod
 from ..utils.local_registration_util import KernelLossFunctionType, LocalRegistrationType
 
 
@@ -31,3 +32,17 @@ class MultiScaleRegistrationParams:
     rejection_type: KernelLossFunctionType = KernelLossFunctionType.Loss_None
     k_value: float = 0.0
     use_mixture: bool = True
+
+
+@dataclass
+class RANSACRegistrationParams:
+    """The reference's fields and defaults, plus ``seed``: the RANSAC sampler is counter-based and deterministic here."""
+    voxel_size: float = 0.05
+    mutual_filter: bool = False
+    max_correspondence: float = 5.0
+    estimation_method: RANSACEstimationMethod = RANSACEstimationMethod.TransformationEstimationPointToPoint
+    ransac_n: int = 3
+    checkers: list = field(default_factory=list)
+    max_iteration: int = 100000
+    confidence: float = 0.999
+    seed: int = 0

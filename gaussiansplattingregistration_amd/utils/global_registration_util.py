@@ -1,0 +1,249 @@
+"""Global registration: the reference's ``src/utils/global_registration_util.py`` on the GPU (``features.py``,
+``csrc/features.hip``), with Open3D-named shims for what it reaches through open3d==0.16.0.
+
+``preprocess_point_cloud`` follows the project's conventions: ``PointCloud.voxel_down_sample`` then ``estimate_normals()`` (the
+averaged covariances of a splat cloud, KNN-30 without covariances -- so the reference's normal radius ``2 * voxel`` is inert, as
+for the voxel multiscale path), then every normal is turned towards the cloud's centroid, then FPFH at (5 * voxel, 100).  The
+orientation is a deviation from the reference, whose normals keep the eigen-solver's arbitrary sign: FPFH is not invariant under a
+normal's sign, and with arbitrary signs only ~7 % of the mutual feature matches of the project's test scene are right (57 % oriented,
+DESIGN.md section 12).  The centroid moves with the cloud, so the orientation is the same for a cloud and its rigidly moved copy.
+FGR (``do_fgr_registration``) is not part of this backend.
+"""
+from __future__ import annotations
+
+from enum import Enum
+
+import numpy as np
+
+from .. import features as _F
+
+try:
+    import torch
+except Exception:  # pragma: no cover
+    torch = None
+
+
+class GlobalRegistrationType(Enum):
+    def __new__(cls, *args, **kwds):
+        value = len(cls.__members__)
+        obj = object.__new__(cls)
+        obj._value_ = value
+        return obj
+
+    def __init__(self, name):
+        self.instance_name = name
+
+    RANSAC = "RANSAC"
+    FGR = "FGR"
+
+
+class RANSACEstimationMethod(Enum):
+    def __new__(cls, *args, **kwds):
+        value = len(cls.__members__)
+        obj = object.__new__(cls)
+        obj._value_ = value
+        return obj
+
+    def __init__(self, name):
+        self.instance_name = name
+
+    TransformationEstimationPointToPoint = "Point-To-Point"
+    TransformationEstimationPointToPlane = "Point-To-Plane"
+    TransformationEstimationForGeneralizedICP = "For GICP"
+    TransformationEstimationForColoredICP = "For CICP"
+
+
+class TransformationEstimationPointToPoint:
+    kind = _F.KIND_POINT_TO_POINT
+
+
+class TransformationEstimationPointToPlane:
+    kind = _F.KIND_POINT_TO_PLANE
+
+
+class _Unsupported:
+    kind = -1
+
+    def __init__(self, name):
+        self.name = name
+
+
+def get_estimation_method_from_enum(estimation_method):
+    """The estimator of each enum value.  GICP / CICP are not valid RANSAC estimators (the reference even swaps the two,
+    ``global_registration_util.py:44-47``); they give an object that ``registration_ransac_*`` rejects with RuntimeError."""
+    if estimation_method == RANSACEstimationMethod.TransformationEstimationPointToPoint:
+        return TransformationEstimationPointToPoint()
+    if estimation_method == RANSACEstimationMethod.TransformationEstimationPointToPlane:
+        return TransformationEstimationPointToPlane()
+    if estimation_method == RANSACEstimationMethod.TransformationEstimationForGeneralizedICP:
+        return _Unsupported("TransformationEstimationForGeneralizedICP")
+    if estimation_method == RANSACEstimationMethod.TransformationEstimationForColoredICP:
+        return _Unsupported("TransformationEstimationForColoredICP")
+    raise ValueError(f"unknown estimation method {estimation_method!r}")
+
+
+class Feature:
+    """``o3d.pipelines.registration.Feature``: ``data`` is (33, n) like Open3D's; ``rows`` the (n, 33) array the library wrote."""
+
+    def __init__(self, rows):
+        self.rows = rows
+
+    @property
+    def data(self):
+        return self.rows.T
+
+    def dimension(self):
+        return int(self.rows.shape[1])
+
+    def num(self):
+        return int(self.rows.shape[0])
+
+
+class KDTreeSearchParamHybrid:
+    def __init__(self, radius, max_nn):
+        self.radius, self.max_nn = float(radius), int(max_nn)
+
+
+class RANSACConvergenceCriteria:
+    def __init__(self, max_iteration=100000, confidence=0.999):
+        self.max_iteration, self.confidence = int(max_iteration), float(confidence)
+
+
+class CorrespondenceCheckerBasedOnEdgeLength:
+    code = _F.CHECK_EDGE_LENGTH
+
+    def __init__(self, similarity_threshold=0.9):
+        self.similarity_threshold = float(similarity_threshold)
+
+    @property
+    def param(self):
+        return self.similarity_threshold
+
+
+class CorrespondenceCheckerBasedOnDistance:
+    code = _F.CHECK_DISTANCE
+
+    def __init__(self, distance_threshold):
+        self.distance_threshold = float(distance_threshold)
+
+    @property
+    def param(self):
+        return self.distance_threshold
+
+
+class CorrespondenceCheckerBasedOnNormal:
+    code = _F.CHECK_NORMAL
+
+    def __init__(self, normal_angle_threshold):
+        self.normal_angle_threshold = float(normal_angle_threshold)
+
+    @property
+    def param(self):
+        return self.normal_angle_threshold
+
+
+class RegistrationResult:
+    def __init__(self, transformation=None, fitness=0.0, inlier_rmse=0.0, correspondence_set=None, info=None):
+        self.transformation = np.eye(4) if transformation is None else np.asarray(transformation, dtype=np.float64)
+        self.fitness, self.inlier_rmse = float(fitness), float(inlier_rmse)
+        self.correspondence_set = correspondence_set if correspondence_set is not None else np.zeros((0, 2), np.int32)
+        self.info = info or {}
+
+    def __repr__(self):
+        return f"RegistrationResult with fitness={self.fitness:e}, inlier_rmse={self.inlier_rmse:e}"
+
+
+def compute_fpfh_feature(pcd, search_param):
+    """``o3d.pipelines.registration.compute_fpfh_feature`` on a ``PointCloud`` record with normals."""
+    if not pcd.has_normals():
+        raise RuntimeError("[Open3D Error] Failed because input point cloud has no normal.")
+    return Feature(_F.fpfh(pcd.xyz32, pcd.normals, search_param.radius, search_param.max_nn, device=pcd.device_index))
+
+
+def _estimation_kind(estimation_method):
+    kind = getattr(estimation_method, "kind", -1)
+    if kind not in (_F.KIND_POINT_TO_POINT, _F.KIND_POINT_TO_PLANE):
+        raise RuntimeError(f"{getattr(estimation_method, 'name', estimation_method)} is not a RANSAC estimation method of this backend "
+                           "(point-to-point or point-to-plane)")
+    return kind
+
+
+def _checker_list(checkers):
+    return [(c.code, c.param) for c in (checkers or [])]
+
+
+def registration_ransac_based_on_correspondence(source, target, corres, max_correspondence_distance, estimation_method=None,
+                                                ransac_n=3, checkers=None, criteria=None, seed=0, batch=8192):
+    """``o3d.pipelines.registration.registration_ransac_based_on_correspondence``, deterministic for a given ``seed``."""
+    estimation_method = estimation_method or TransformationEstimationPointToPoint()
+    kind = _estimation_kind(estimation_method)
+    criteria = criteria or RANSACConvergenceCriteria()
+    if kind == _F.KIND_POINT_TO_PLANE and not target.has_normals():
+        raise RuntimeError("[Open3D Error] TransformationEstimationPointToPlane requires pre-computed normal vectors for target PointCloud.")
+    nrm = source.has_normals() and target.has_normals()
+    r = _F.ransac_correspondence(source.xyz32, target.xyz32, corres, max_correspondence_distance, kind=kind, ransac_n=ransac_n,
+                                 checkers=_checker_list(checkers), max_iteration=criteria.max_iteration, confidence=criteria.confidence,
+                                 seed=seed, batch=batch, src_normals=source.normals if nrm else None,
+                                 tgt_normals=target.normals if (nrm or kind == _F.KIND_POINT_TO_PLANE) else None,
+                                 device=source.device_index)
+    info = {k: r[k] for k in ("best_index", "n_evaluated", "n_valid", "exit_index")}
+    return RegistrationResult(r["transformation"], r["fitness"], r["inlier_rmse"], info=info)
+
+
+def registration_ransac_based_on_feature_matching(source, target, source_feature, target_feature, mutual_filter,
+                                                  max_correspondence_distance, estimation_method=None, ransac_n=3, checkers=None,
+                                                  criteria=None, seed=0, batch=8192):
+    """``o3d.pipelines.registration.registration_ransac_based_on_feature_matching`` (Open3D 0.16): exact feature 1-NN,
+    optional mutual filter (falls back to the one-way set below 3 * ransac_n pairs), then RANSAC over the correspondences."""
+    _estimation_kind(estimation_method or TransformationEstimationPointToPoint())
+    if ransac_n < 3 or not (max_correspondence_distance > 0.0):
+        return RegistrationResult()
+    corres, used_mutual = _F.feature_match(source_feature.rows, target_feature.rows, mutual=bool(mutual_filter), ransac_n=ransac_n,
+                                           device=source.device_index)
+    res = registration_ransac_based_on_correspondence(source, target, corres, max_correspondence_distance, estimation_method, ransac_n,
+                                                      checkers, criteria, seed=seed, batch=batch)
+    res.info["used_mutual"] = used_mutual
+    res.info["n_corres"] = int(corres.shape[0])
+    return res
+
+
+def orient_normals_towards_centroid(pcd):
+    """Flip every normal n of ``pcd`` with n . (centroid - p) < 0 (Open3D's orient_normals_towards_camera_location with the camera at
+    the cloud's centroid).  Keeps the normals' placement."""
+    x, nrm = pcd.xyz32, pcd.normals
+    if torch is not None and isinstance(nrm, torch.Tensor):
+        p = x.detach().double() if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x, np.float64), device=nrm.device)
+        c = p.mean(0)
+        flip = ((c[None] - p) * nrm).sum(1) < 0
+        pcd.normals = torch.where(flip[:, None], -nrm, nrm)
+    else:
+        p = np.asarray(pcd.points, np.float64)
+        c = p.mean(0)
+        nrm = np.asarray(nrm, np.float64)
+        flip = ((c[None] - p) * nrm).sum(1) < 0
+        pcd.normals = np.where(flip[:, None], -nrm, nrm)
+    return pcd
+
+
+def preprocess_point_cloud(pcd, voxel_size):
+    pcd_down = pcd.voxel_down_sample(voxel_size)
+    pcd_down.estimate_normals()
+    orient_normals_towards_centroid(pcd_down)
+    radius_feature = voxel_size * 5
+    pcd_fpfh = compute_fpfh_feature(pcd_down, KDTreeSearchParamHybrid(radius=radius_feature, max_nn=100))
+    return pcd_down, pcd_fpfh
+
+
+def do_ransac_registration(point_cloud_first, point_cloud_second, params):
+    source_down, source_fpfh = preprocess_point_cloud(point_cloud_first, params.voxel_size)
+    target_down, target_fpfh = preprocess_point_cloud(point_cloud_second, params.voxel_size)
+    real_estimation_method = get_estimation_method_from_enum(params.estimation_method)
+    result = registration_ransac_based_on_feature_matching(
+        source_down, target_down, source_fpfh, target_fpfh, params.mutual_filter,
+        params.max_correspondence,
+        real_estimation_method,
+        params.ransac_n,
+        params.checkers,
+        RANSACConvergenceCriteria(params.max_iteration, params.confidence),
+        seed=getattr(params, "seed", 0))
+    return result

@@ -461,6 +461,80 @@ int32_t gsr_voxel_down_sample(int32_t device, void* stream, const float* xyz, co
 int32_t gsr_voxel_fetch(gsr_voxel_result* r, double* xyz, double* cov6, double* color, int32_t on_device);
 int32_t gsr_voxel_free(gsr_voxel_result* r);
 
+/* ------------------------------------------------------------------------------ global registration */
+
+/* The reference's "Global" tab (src/utils/global_registration_util.py: preprocess_point_cloud, do_ransac_registration) through
+ * open3d==0.16.0: compute_fpfh_feature, registration_ransac_based_on_feature_matching and
+ * registration_ransac_based_on_correspondence.  csrc/features.hip; DESIGN.md section 12.
+ *
+ * Neighbourhoods are Open3D's KDTreeSearchParamHybrid(radius, max_nn): the max_nn nearest points of the cloud (the query point
+ * itself included), ordered by (d2, input index), then cut at the radius, where
+ *     d2 = (px - qx)^2 + (py - qy)^2 + (pz - qz)^2     summed left to right in float64 from the float32 coordinates,
+ *     a point is kept iff d2 <= radius * radius.
+ * (= the points with d2 <= radius^2, the max_nn first of them.)  max_nn in [1, 512]. */
+int32_t gsr_hybrid_search(const float* xyz, int64_t n, double radius, int32_t max_nn, int32_t* nbr, int32_t* count, int32_t on_device,
+                          int32_t device, void* stream);
+
+/* Open3D 0.16 ComputeFPFHFeature (Feature.cpp) on the hybrid neighbourhoods above, in float64: SPFH of 11 bins per angle
+ * (increment 100 / (k - 1), entry 0 of the neighbour list skipped, bins clamped to [0, 10]), then the neighbours' SPFH weighted by
+ * 1 / d2 (d2 == 0 skipped), each third normalised to 100, plus the point's own SPFH.  Points with fewer than 2 neighbours get a zero
+ * row.  xyz[n*3] float32, normals[n*3] float64, out[n*33] float64 row-major (Open3D's Feature.data is its transpose); host or
+ * device memory as on_device says. */
+int32_t gsr_fpfh(const float* xyz, const double* normals, int64_t n, double radius, int32_t max_nn, double* out, int32_t on_device,
+                 int32_t device, void* stream);
+
+/* Feature matching of registration_ransac_based_on_feature_matching: nn_st[i] = the exact nearest target row of source row i in
+ * L2 over the 33 float64 features, d = sum over j = 0..32 in order of (s_j - t_j)^2 (no fused multiply-add), ties to the lowest
+ * index (a row whose distances are all NaN or +inf -- NaN features -- gets row 0); with mutual != 0 also nn_ts (target -> source) and the pairs (i, nn_st[i]) with nn_ts[nn_st[i]] == i, in ascending i.
+ * corres[ns*2] int32 receives the mutual set when mutual != 0 and it holds at least 3 * ransac_n pairs, else the one-way set
+ * (i, nn_st[i]) for every i (Open3D 0.16); *n_corres its length, *used_mutual 1 when it is the mutual set.  nn_st[ns] / nn_ts[nt]
+ * may be NULL.  src_feat[ns*33], tgt_feat[nt*33] float64; every array host or device as on_device says, the two counts host. */
+int32_t gsr_feature_match(const double* src_feat, int64_t ns, const double* tgt_feat, int64_t nt, int32_t mutual, int32_t ransac_n,
+                          int32_t* corres, int64_t* n_corres, int32_t* used_mutual, int32_t* nn_st, int32_t* nn_ts, int32_t on_device,
+                          int32_t device, void* stream);
+
+/* Correspondence checkers, applied in the order given to every hypothesis (Open3D CorrespondenceChecker.cpp). */
+#define GSR_CHECK_EDGE_LENGTH 0   /* param = similarity threshold: fail if |ps_i - ps_j| < |pt_i - pt_j| * thr or the reverse */
+#define GSR_CHECK_DISTANCE    1   /* param = distance threshold: fail if |q - T p| > thr */
+#define GSR_CHECK_NORMAL      2   /* param = angle (radians): fail if n_t . (R n_s) < cos(angle); passes when a cloud has no normals */
+#define GSR_RANSAC_MAX_N 16       /* largest ransac_n */
+typedef struct gsr_ransac_params {
+    int32_t kind;              /* GSR_ICP_POINT_TO_POINT (3-pair Umeyama) or GSR_ICP_POINT_TO_PLANE (6x6 solve on ransac_n rows) */
+    int32_t ransac_n;
+    double max_corr;           /* inlier: |T p - q|^2 < max_corr^2 */
+    int64_t max_iteration;
+    double confidence;
+    uint64_t seed;
+    int32_t batch;             /* hypotheses per device batch (B); a speed knob only: the result does not depend on it */
+    int32_t n_checkers;
+    int32_t checker_kind[4];   /* GSR_CHECK_* in the order given */
+    double checker_param[4];
+} gsr_ransac_params;
+typedef struct gsr_ransac_result {
+    double T[16];              /* row-major; identity when no hypothesis won */
+    double fitness;            /* inliers / |corres| */
+    double inlier_rmse;        /* sqrt(sum d2 / inliers); 0 when there are no inliers */
+    int64_t best_index;        /* winning hypothesis, -1 if none */
+    int64_t n_evaluated;       /* hypotheses k visited (k < exit index) */
+    int64_t n_valid;           /* of them: distinct indices and every checker passed */
+    int64_t exit_index;        /* final min(max_iteration, early-exit estimate) */
+} gsr_ransac_result;
+/* Open3D 0.16 RegistrationRANSACBasedOnCorrespondence, deterministic (DESIGN.md 12 lists the deviations):
+ *   sampling    hypothesis k draws corres rows  idx_j = draw(seed, k, j, m), j = 0 .. ransac_n - 1, where
+ *                 splitmix64(x) = { x += 0x9E3779B97F4A7C15; x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9;
+ *                                   x = (x ^ (x >> 27)) * 0x94D049BB133111EB; return x ^ (x >> 31); }   (mod 2^64)
+ *                 draw(seed, k, j, m) = ((splitmix64(seed ^ splitmix64(k * 64 + j)) >> 32) * m) >> 32   (Lemire's reduction)
+ *               the draws are sorted ascending; a hypothesis with a repeated row is invalid;
+ *   estimate    point-to-point: Umeyama of the ransac_n pairs; point-to-plane: Open3D's 6x6 system on the ransac_n rows;
+ *   evaluation  good = #{c : |T p_c - q_c|^2 < max_corr^2}, fitness = good / m, rmse = sqrt(sum d2 / good), in float64;
+ *   selection   Open3D's serial rule in index order: better = higher fitness, or equal fitness and lower rmse; after each new best
+ *               exit = min(exit, ceil(log(1 - confidence) / log(1 - fitness^ransac_n))) when confidence < 1; stop at k >= exit.
+ * corres[m*2] int32 (source row, target row); xyz float32, normals float64 or NULL; host or device as on_device says.  Degenerate
+ * inputs (ransac_n < 3, m < ransac_n, max_corr <= 0) give Open3D's empty result: identity, zeros, best_index -1. */
+int32_t gsr_ransac_correspondence(const float* src_xyz, int64_t ns, const float* tgt_xyz, int64_t nt, const double* src_normals,
+                                  const double* tgt_normals, const int32_t* corres, int64_t m, const gsr_ransac_params* params,
+                                  gsr_ransac_result* out, int32_t on_device, int32_t device, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -29,6 +29,9 @@ def main():
     ap.add_argument("--k", type=float, default=0.0)
     ap.add_argument("--voxel", action="store_true", help="voxel multiscale path instead of HEM mixtures")
     ap.add_argument("--hem", type=float, nargs=4, default=[3.0, 3.0, 2.5, 1.0], metavar=("RHO", "DELTA", "KAPPA", "TAU"))
+    ap.add_argument("--global-ransac", type=float, metavar="VOXEL", help="global registration first (FPFH + RANSAC at this voxel size, the "
+                    "reference's Global tab); its pose is the multiscale ICP's initial transform")
+    ap.add_argument("--ransac-iters", type=int, default=100000, help="RANSAC hypotheses (max_iteration) of --global-ransac")
     ap.add_argument("--out")
     a = ap.parse_args()
 
@@ -66,6 +69,16 @@ def main():
         print("levels:", [len(x) for x in repo.pc_gaussian_list_first], "/", [len(x) for x in repo.pc_gaussian_list_second])
     t2 = time.perf_counter()
     rc = RegistrationController(repo, ui)
+    if a.global_ransac:
+        from gaussiansplattingregistration_amd.params.registration_parameters import RANSACRegistrationParams
+        from gaussiansplattingregistration_amd.utils import global_registration_util as G
+        v = a.global_ransac
+        gp = RANSACRegistrationParams(voxel_size=v, max_correspondence=1.5 * v, max_iteration=a.ransac_iters, confidence=0.999,
+                                      checkers=[G.CorrespondenceCheckerBasedOnEdgeLength(0.9), G.CorrespondenceCheckerBasedOnDistance(1.5 * v)])
+        tg = time.perf_counter()
+        g = rc.execute_ransac_registration_normal(gp)
+        print(f"global RANSAC: fitness {g.fitness:.4f}  rmse {g.inlier_rmse:.6f}  hypotheses {g.info.get('n_evaluated')}  "
+              f"{time.perf_counter() - tg:.3f} s")
     res = rc.execute_multiscale_registration(False, "", "", rtype, 1e-6, 1e-6, a.max_corr, a.iters, loss, a.k, not a.voxel)
     t3 = time.perf_counter()
     if res is None:
