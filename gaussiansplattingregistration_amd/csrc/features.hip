@@ -12,6 +12,7 @@
 //                       the host replays Open3D's serial selection rule over each batch
 #include "gsr_common.h"
 #include "gsr_features.h"
+#include "gsr_oneshot.h"
 #include "gsr_solve.h"
 #include "gsr_test_hooks.h"
 
@@ -21,30 +22,6 @@
 #include <vector>
 
 namespace gsr {
-
-// ---- staging -----------------------------------------------------------------------------------------------------------------
-namespace {
-struct Stage {
-    DevBuf buf;
-    // device view of a caller array of `bytes` bytes: the array itself (on_device) or a staged copy
-    template <typename T> int32_t in(const T* p, size_t bytes, bool on_device, hipStream_t st, const T** out) {
-        if (!p || on_device) { *out = p; return GSR_OK; }
-        GSR_TRY(buf.reserve(bytes));
-        GSR_HIP(hipMemcpyAsync(buf.p, p, bytes, hipMemcpyHostToDevice, st));
-        *out = buf.as<T>();
-        return GSR_OK;
-    }
-};
-
-int32_t open_device(int32_t device, const char* who) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(GSR_E_NO_DEVICE, "%s: no HIP device visible (this backend has no CPU fallback)", who);
-    if (device < 0 || device >= ndev) return fail(GSR_E_INVALID, "%s: device %d out of range", who, device);
-    GSR_HIP(hipSetDevice(device));
-    return GSR_OK;
-}
-}  // namespace
 
 // ---- FPFH --------------------------------------------------------------------------------------------------------------------
 // Open3D 0.16 ComputePairFeatures (Feature.cpp): (phi, alpha, theta) of the Darboux frame, in float64.  Returns false for the zero
@@ -188,7 +165,7 @@ __global__ __launch_bounds__(256) void k_fm_merge(int64_t na, int nchunks, const
 
 namespace {
 // nearest rows of b for every row of a (device arrays), into out[na] (device)
-int32_t nn_rows(const double* a, int64_t na, const double* b, int64_t nb, int* out, hipStream_t st, DevBuf& wi, DevBuf& wd) {
+int32_t nn_rows(OneShot& os, const double* a, int64_t na, const double* b, int64_t nb, int* out) {
     if (na <= 0) return GSR_OK;
     const int64_t gx = (na + FM_BLOCK - 1) / FM_BLOCK;
     // enough workgroups to fill the chip twice over (256 CUs), each chunk at least 512 target rows
@@ -199,10 +176,12 @@ int32_t nn_rows(const double* a, int64_t na, const double* b, int64_t nb, int* o
     if (nch > 65535) nch = 65535;
     const int64_t chunk = (nb + nch - 1) / nch;
     nch = (nb + chunk - 1) / chunk;
-    GSR_TRY(wi.reserve((size_t)(nch * na) * 4));
-    GSR_TRY(wd.reserve((size_t)(nch * na) * 8));
-    hipLaunchKernelGGL(k_fm_nn, dim3((unsigned)gx, (unsigned)nch), dim3(FM_BLOCK), 0, st, na, a, nb, b, chunk, wi.as<int>(), wd.as<double>());
-    hipLaunchKernelGGL(k_fm_merge, dim3(stride_grid(na)), dim3(256), 0, st, na, (int)nch, wi.as<int>(), wd.as<double>(), out);
+    int* wi = nullptr;
+    double* wd = nullptr;
+    GSR_TRY(os.scratch((size_t)(nch * na) * 4, &wi));
+    GSR_TRY(os.scratch((size_t)(nch * na) * 8, &wd));
+    hipLaunchKernelGGL(k_fm_nn, dim3((unsigned)gx, (unsigned)nch), dim3(FM_BLOCK), 0, os.st, na, a, nb, b, chunk, wi, wd);
+    hipLaunchKernelGGL(k_fm_merge, dim3(stride_grid(na)), dim3(256), 0, os.st, na, (int)nch, wi, wd, out);
     GSR_HIP(hipGetLastError());
     return GSR_OK;
 }
@@ -396,28 +375,14 @@ int32_t gsr_hybrid_search(const float* xyz, int64_t n, double radius, int32_t ma
     if (!(radius > 0.0)) return fail(GSR_E_INVALID, "gsr_hybrid_search: radius must be > 0");
     if (n == 0) return GSR_OK;
     GSR_TRY(open_device(device, "gsr_hybrid_search"));
-    hipStream_t st = (hipStream_t)stream;
-    Stage sx;
-    DevBuf dn, dc;
+    OneShot os((hipStream_t)stream, on_device != 0, "gsr_hybrid_search");
     const float* dxyz = nullptr;
-    int32_t r = sx.in(xyz, (size_t)n * 12, on_device != 0, st, &dxyz);
-    int* onbr = on_device ? nbr : nullptr;
-    int* ocnt = on_device ? count : nullptr;
-    if (r == GSR_OK && !on_device) {
-        r = dn.reserve((size_t)n * max_nn * 4);
-        if (r == GSR_OK) r = dc.reserve((size_t)n * 4);
-        onbr = dn.as<int>(); ocnt = dc.as<int>();
-    }
-    if (r == GSR_OK) r = hybrid_search_dev(dxyz, n, radius, max_nn, device, st, onbr, ocnt);
-    if (r == GSR_OK && !on_device) {
-        hipError_t e = hipMemcpyAsync(nbr, onbr, (size_t)n * max_nn * 4, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(count, ocnt, (size_t)n * 4, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) r = fail(GSR_E_HIP, "gsr_hybrid_search: %s", hipGetErrorString(e));
-    }
-    (void)hipStreamSynchronize(st);
-    sx.buf.release(); dn.release(); dc.release();
-    return r;
+    int *dnbr = nullptr, *dcnt = nullptr;
+    GSR_TRY(os.in(xyz, (size_t)n * 12, &dxyz));
+    GSR_TRY(os.out(nbr, (size_t)n * max_nn * 4, &dnbr));
+    GSR_TRY(os.out(count, (size_t)n * 4, &dcnt));
+    GSR_TRY(hybrid_search_dev(dxyz, n, radius, max_nn, device, os.st, dnbr, dcnt));
+    return os.finish();
 }
 
 int32_t gsr_fpfh(const float* xyz, const double* normals, int64_t n, double radius, int32_t max_nn, double* out, int32_t on_device,
@@ -427,31 +392,22 @@ int32_t gsr_fpfh(const float* xyz, const double* normals, int64_t n, double radi
     if (!(radius > 0.0)) return fail(GSR_E_INVALID, "gsr_fpfh: radius must be > 0");
     if (n == 0) return GSR_OK;
     GSR_TRY(open_device(device, "gsr_fpfh"));
-    hipStream_t st = (hipStream_t)stream;
-    Stage sx, sn;
-    DevBuf nbr, cnt, spfh, dout;
+    OneShot os((hipStream_t)stream, on_device != 0, "gsr_fpfh");
     const float* dxyz = nullptr;
     const double* dnrm = nullptr;
-    int32_t r = sx.in(xyz, (size_t)n * 12, on_device != 0, st, &dxyz);
-    if (r == GSR_OK) r = sn.in(normals, (size_t)n * 24, on_device != 0, st, &dnrm);
-    if (r == GSR_OK) r = nbr.reserve((size_t)n * max_nn * 4);
-    if (r == GSR_OK) r = cnt.reserve((size_t)n * 4);
-    if (r == GSR_OK) r = spfh.reserve((size_t)n * 33 * 8);
-    double* o = out;
-    if (r == GSR_OK && !on_device) { r = dout.reserve((size_t)n * 33 * 8); o = dout.as<double>(); }
-    if (r == GSR_OK) r = hybrid_search_dev(dxyz, n, radius, max_nn, device, st, nbr.as<int>(), cnt.as<int>());
-    if (r == GSR_OK) {
-        hipLaunchKernelGGL(k_spfh, dim3(ceil_div(n, SPFH_BLOCK) < 4096 ? ceil_div(n, SPFH_BLOCK) : 4096), dim3(SPFH_BLOCK), 0, st, n, dxyz, dnrm,
-                           nbr.as<int>(), cnt.as<int>(), max_nn, spfh.as<double>());
-        hipLaunchKernelGGL(k_fpfh, dim3(stride_grid(n)), dim3(256), 0, st, n, dxyz, nbr.as<int>(), cnt.as<int>(), max_nn, spfh.as<double>(), o);
-        hipError_t e = hipGetLastError();
-        if (e == hipSuccess && !on_device) e = hipMemcpyAsync(out, o, (size_t)n * 33 * 8, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) r = fail(GSR_E_HIP, "gsr_fpfh: %s", hipGetErrorString(e));
-    }
-    (void)hipStreamSynchronize(st);
-    sx.buf.release(); sn.buf.release(); nbr.release(); cnt.release(); spfh.release(); dout.release();
-    return r;
+    int *nbr = nullptr, *cnt = nullptr;
+    double *spfh = nullptr, *o = nullptr;
+    GSR_TRY(os.in(xyz, (size_t)n * 12, &dxyz));
+    GSR_TRY(os.in(normals, (size_t)n * 24, &dnrm));
+    GSR_TRY(os.scratch((size_t)n * max_nn * 4, &nbr));
+    GSR_TRY(os.scratch((size_t)n * 4, &cnt));
+    GSR_TRY(os.scratch((size_t)n * 33 * 8, &spfh));
+    GSR_TRY(os.out(out, (size_t)n * 33 * 8, &o));
+    GSR_TRY(hybrid_search_dev(dxyz, n, radius, max_nn, device, os.st, nbr, cnt));
+    hipLaunchKernelGGL(k_spfh, dim3(ceil_div(n, SPFH_BLOCK) < 4096 ? ceil_div(n, SPFH_BLOCK) : 4096), dim3(SPFH_BLOCK), 0, os.st, n, dxyz, dnrm, nbr, cnt,
+                       max_nn, spfh);
+    hipLaunchKernelGGL(k_fpfh, dim3(stride_grid(n)), dim3(256), 0, os.st, n, dxyz, nbr, cnt, max_nn, spfh, o);
+    return os.finish();
 }
 
 int32_t gsr_feature_match(const double* src_feat, int64_t ns, const double* tgt_feat, int64_t nt, int32_t mutual, int32_t ransac_n,
@@ -465,52 +421,39 @@ int32_t gsr_feature_match(const double* src_feat, int64_t ns, const double* tgt_
     if (nt == 0) return fail(GSR_E_INVALID, "gsr_feature_match: empty target feature set");
     if (ns >= ((int64_t)1 << 31) || nt >= ((int64_t)1 << 31)) return fail(GSR_E_INVALID, "gsr_feature_match: more than 2^31 rows");
     GSR_TRY(open_device(device, "gsr_feature_match"));
-    hipStream_t st = (hipStream_t)stream;
-    Stage sa, sb;
-    DevBuf dst, dts, wi, wd;
+    std::vector<int32_t> h_st((size_t)ns), h_ts(mutual ? (size_t)nt : 0), pairs;      // before `os`: it waits for the copies into them
+    OneShot os((hipStream_t)stream, on_device != 0, "gsr_feature_match");
     const double *da = nullptr, *db = nullptr;
-    int32_t r = sa.in(src_feat, (size_t)ns * 33 * 8, on_device != 0, st, &da);
-    if (r == GSR_OK) r = sb.in(tgt_feat, (size_t)nt * 33 * 8, on_device != 0, st, &db);
-    if (r == GSR_OK) r = dst.reserve((size_t)ns * 4);
-    if (r == GSR_OK && mutual) r = dts.reserve((size_t)nt * 4);
-    if (r == GSR_OK) r = nn_rows(da, ns, db, nt, dst.as<int>(), st, wi, wd);
-    if (r == GSR_OK && mutual) r = nn_rows(db, nt, da, ns, dts.as<int>(), st, wi, wd);
-    std::vector<int32_t> h_st, h_ts;
-    if (r == GSR_OK) {
-        h_st.resize(ns);
-        hipError_t e = hipMemcpyAsync(h_st.data(), dst.p, (size_t)ns * 4, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess && mutual) { h_ts.resize(nt); e = hipMemcpyAsync(h_ts.data(), dts.p, (size_t)nt * 4, hipMemcpyDeviceToHost, st); }
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) r = fail(GSR_E_HIP, "gsr_feature_match: %s", hipGetErrorString(e));
+    int *dst = nullptr, *dts = nullptr;
+    GSR_TRY(os.in(src_feat, (size_t)ns * 33 * 8, &da));
+    GSR_TRY(os.in(tgt_feat, (size_t)nt * 33 * 8, &db));
+    GSR_TRY(os.scratch((size_t)ns * 4, &dst));
+    if (mutual) GSR_TRY(os.scratch((size_t)nt * 4, &dts));
+    GSR_TRY(nn_rows(os, da, ns, db, nt, dst));
+    if (mutual) GSR_TRY(nn_rows(os, db, nt, da, ns, dts));
+    GSR_HIP(hipMemcpyAsync(h_st.data(), dst, (size_t)ns * 4, hipMemcpyDeviceToHost, os.st));
+    if (mutual) GSR_HIP(hipMemcpyAsync(h_ts.data(), dts, (size_t)nt * 4, hipMemcpyDeviceToHost, os.st));
+    GSR_TRY(os.wait());
+    // the pair list is O(n) host work on the read-back indices
+    pairs.reserve((size_t)ns * 2);
+    bool use_mutual = false;
+    if (mutual) {
+        for (int64_t i = 0; i < ns; ++i)
+            if (h_ts[h_st[i]] == (int32_t)i) { pairs.push_back((int32_t)i); pairs.push_back(h_st[i]); }
+        use_mutual = (int64_t)(pairs.size() / 2) >= 3 * (int64_t)ransac_n;
     }
-    if (r == GSR_OK) {
-        // the pair list is O(n) host work on the read-back indices
-        std::vector<int32_t> pairs;
-        pairs.reserve((size_t)ns * 2);
-        bool use_mutual = false;
-        if (mutual) {
-            for (int64_t i = 0; i < ns; ++i)
-                if (h_ts[h_st[i]] == (int32_t)i) { pairs.push_back((int32_t)i); pairs.push_back(h_st[i]); }
-            use_mutual = (int64_t)(pairs.size() / 2) >= 3 * (int64_t)ransac_n;
-        }
-        if (!use_mutual) {
-            pairs.clear();
-            for (int64_t i = 0; i < ns; ++i) { pairs.push_back((int32_t)i); pairs.push_back(h_st[i]); }
-        }
-        const hipMemcpyKind dk = on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-        hipError_t e = hipSuccess;
-        if (on_device) e = hipMemcpyAsync(corres, pairs.data(), pairs.size() * 4, hipMemcpyHostToDevice, st);
-        else memcpy(corres, pairs.data(), pairs.size() * 4);
-        if (e == hipSuccess && nn_st) e = hipMemcpyAsync(nn_st, dst.p, (size_t)ns * 4, dk, st);
-        if (e == hipSuccess && nn_ts && mutual) e = hipMemcpyAsync(nn_ts, dts.p, (size_t)nt * 4, dk, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) r = fail(GSR_E_HIP, "gsr_feature_match: %s", hipGetErrorString(e));
-        *n_corres = (int64_t)(pairs.size() / 2);
-        if (used_mutual) *used_mutual = use_mutual ? 1 : 0;
+    if (!use_mutual) {
+        pairs.clear();
+        for (int64_t i = 0; i < ns; ++i) { pairs.push_back((int32_t)i); pairs.push_back(h_st[i]); }
     }
-    (void)hipStreamSynchronize(st);
-    sa.buf.release(); sb.buf.release(); dst.release(); dts.release(); wi.release(); wd.release();
-    return r;
+    *n_corres = (int64_t)(pairs.size() / 2);
+    if (used_mutual) *used_mutual = use_mutual ? 1 : 0;
+    const hipMemcpyKind dk = on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    if (on_device) GSR_HIP(hipMemcpyAsync(corres, pairs.data(), pairs.size() * 4, hipMemcpyHostToDevice, os.st));
+    else memcpy(corres, pairs.data(), pairs.size() * 4);
+    if (nn_st) GSR_HIP(hipMemcpyAsync(nn_st, dst, (size_t)ns * 4, dk, os.st));
+    if (nn_ts && mutual) GSR_HIP(hipMemcpyAsync(nn_ts, dts, (size_t)nt * 4, dk, os.st));
+    return os.finish();
 }
 
 int32_t gsr_ransac_correspondence(const float* src_xyz, int64_t ns, const float* tgt_xyz, int64_t nt, const double* src_normals,
@@ -540,82 +483,68 @@ int32_t gsr_ransac_correspondence(const float* src_xyz, int64_t ns, const float*
                 return fail(GSR_E_INVALID, "gsr_ransac_correspondence: correspondence %lld out of range", (long long)c);
     }
     GSR_TRY(open_device(device, "gsr_ransac_correspondence"));
-    hipStream_t st = (hipStream_t)stream;
     const bool has_normals = src_normals && tgt_normals;
     int B = P.batch > 0 ? P.batch : 8192;
     if (B > (1 << 20)) B = 1 << 20;
-    Stage s_sx, s_tx, s_sn, s_tn, s_c;
-    DevBuf dP, dQ, dNS, dNT, dT, dvalid, dfit, drmse;
+    std::vector<double> hfit((size_t)B), hrmse((size_t)B);       // before `os`: it waits for the copies into them
+    double best_T[12];                                           // *out keeps the empty result until the call has succeeded
+    OneShot os((hipStream_t)stream, on_device != 0, "gsr_ransac_correspondence");
     const float *sx = nullptr, *tx = nullptr;
     const double *sn = nullptr, *tn = nullptr;
     const int32_t* dc = nullptr;
-    int32_t r = GSR_OK;
-    std::vector<double> hfit, hrmse;
-    do {
-        if ((r = s_sx.in(src_xyz, (size_t)ns * 12, on_device != 0, st, &sx)) != GSR_OK) break;
-        if ((r = s_tx.in(tgt_xyz, (size_t)nt * 12, on_device != 0, st, &tx)) != GSR_OK) break;
-        if (has_normals && (r = s_sn.in(src_normals, (size_t)ns * 24, on_device != 0, st, &sn)) != GSR_OK) break;
-        if (tgt_normals && (r = s_tn.in(tgt_normals, (size_t)nt * 24, on_device != 0, st, &tn)) != GSR_OK) break;
-        if ((r = s_c.in(corres, (size_t)m * 8, on_device != 0, st, &dc)) != GSR_OK) break;
-        if ((r = dP.reserve((size_t)m * 24)) != GSR_OK || (r = dQ.reserve((size_t)m * 24)) != GSR_OK) break;
-        if (has_normals && (r = dNS.reserve((size_t)m * 24)) != GSR_OK) break;
-        if (tn && (r = dNT.reserve((size_t)m * 24)) != GSR_OK) break;
-        if ((r = dT.reserve((size_t)B * 96)) != GSR_OK || (r = dvalid.reserve((size_t)B * 4)) != GSR_OK) break;
-        if ((r = dfit.reserve((size_t)B * 8)) != GSR_OK || (r = drmse.reserve((size_t)B * 8)) != GSR_OK) break;
-        hipLaunchKernelGGL(k_ransac_gather, dim3(stride_grid(m)), dim3(256), 0, st, m, (const int*)dc, sx, tx, has_normals ? sn : nullptr, tn,
-                           dP.as<double>(), dQ.as<double>(), has_normals ? dNS.as<double>() : (double*)nullptr, tn ? dNT.as<double>() : (double*)nullptr);
-        RansacDev a;
-        a.kind = P.kind; a.n = P.ransac_n; a.n_checkers = P.n_checkers; a.has_normals = has_normals ? 1 : 0;
-        for (int c = 0; c < 4; ++c) { a.ck[c] = c < P.n_checkers ? P.checker_kind[c] : -1; a.cp[c] = c < P.n_checkers ? P.checker_param[c] : 0.0; }
-        a.mc2 = P.max_corr * P.max_corr; a.seed = P.seed; a.m = m;
-        hfit.resize(B); hrmse.resize(B);
-        int64_t exit_k = P.max_iteration, k = 0, best = -1, n_valid = 0;
-        double best_fit = 0.0, best_rmse = 0.0;
-        while (k < exit_k && r == GSR_OK) {
-            const int nb = (int)std::min<int64_t>(B, P.max_iteration - k);
-            hipLaunchKernelGGL(k_ransac_hyp, dim3((nb + 63) / 64), dim3(64), 0, st, k, nb, a, dP.as<double>(), dQ.as<double>(),
-                               has_normals ? dNS.as<double>() : (const double*)nullptr, tn ? dNT.as<double>() : (const double*)nullptr, dT.as<double>(),
-                               dvalid.as<int>());
-            hipLaunchKernelGGL(k_ransac_eval, dim3((nb + RANSAC_HB - 1) / RANSAC_HB), dim3(RANSAC_EVAL_BLOCK), 0, st, nb, m, a.mc2, dP.as<double>(),
-                               dQ.as<double>(), dT.as<double>(), dvalid.as<int>(), dfit.as<double>(), drmse.as<double>());
-            hipError_t e = hipGetLastError();
-            if (e == hipSuccess) e = hipMemcpyAsync(hfit.data(), dfit.p, (size_t)nb * 8, hipMemcpyDeviceToHost, st);
-            if (e == hipSuccess) e = hipMemcpyAsync(hrmse.data(), drmse.p, (size_t)nb * 8, hipMemcpyDeviceToHost, st);
-            if (e == hipSuccess) e = hipStreamSynchronize(st);
-            if (e != hipSuccess) { r = fail(GSR_E_HIP, "gsr_ransac_correspondence: %s", hipGetErrorString(e)); break; }
-            int64_t best_in_batch = -1;
-            // Open3D's serial rule, hypothesis by hypothesis in index order
-            for (int t = 0; t < nb && k < exit_k; ++t, ++k) {
-                const double f = hfit[t], rm = hrmse[t];
-                if (f < 0.0) continue;                                   // repeated row or a checker failed
-                ++n_valid;
-                if (f > best_fit || (f == best_fit && rm < best_rmse)) {
-                    best_fit = f; best_rmse = rm; best = k; best_in_batch = t;
-                    if (P.confidence < 1.0) {
-                        const double est = std::ceil(std::log(1.0 - P.confidence) / std::log(1.0 - std::pow(f, (double)P.ransac_n)));
-                        if (est < (double)exit_k) exit_k = (int64_t)est;
-                    }
+    double *dP = nullptr, *dQ = nullptr, *dNS = nullptr, *dNT = nullptr, *dT = nullptr, *dfit = nullptr, *drmse = nullptr;
+    int* dvalid = nullptr;
+    GSR_TRY(os.in(src_xyz, (size_t)ns * 12, &sx));
+    GSR_TRY(os.in(tgt_xyz, (size_t)nt * 12, &tx));
+    if (has_normals) GSR_TRY(os.in(src_normals, (size_t)ns * 24, &sn));
+    GSR_TRY(os.in(tgt_normals, (size_t)nt * 24, &tn));
+    GSR_TRY(os.in(corres, (size_t)m * 8, &dc));
+    GSR_TRY(os.scratch((size_t)m * 24, &dP));
+    GSR_TRY(os.scratch((size_t)m * 24, &dQ));
+    if (has_normals) GSR_TRY(os.scratch((size_t)m * 24, &dNS));
+    if (tn) GSR_TRY(os.scratch((size_t)m * 24, &dNT));
+    GSR_TRY(os.scratch((size_t)B * 96, &dT));
+    GSR_TRY(os.scratch((size_t)B * 4, &dvalid));
+    GSR_TRY(os.scratch((size_t)B * 8, &dfit));
+    GSR_TRY(os.scratch((size_t)B * 8, &drmse));
+    hipLaunchKernelGGL(k_ransac_gather, dim3(stride_grid(m)), dim3(256), 0, os.st, m, (const int*)dc, sx, tx, sn, tn, dP, dQ, dNS, dNT);
+    RansacDev a;
+    a.kind = P.kind; a.n = P.ransac_n; a.n_checkers = P.n_checkers; a.has_normals = has_normals ? 1 : 0;
+    for (int c = 0; c < 4; ++c) { a.ck[c] = c < P.n_checkers ? P.checker_kind[c] : -1; a.cp[c] = c < P.n_checkers ? P.checker_param[c] : 0.0; }
+    a.mc2 = P.max_corr * P.max_corr; a.seed = P.seed; a.m = m;
+    int64_t exit_k = P.max_iteration, k = 0, best = -1, n_valid = 0;
+    double best_fit = 0.0, best_rmse = 0.0;
+    while (k < exit_k) {
+        const int nb = (int)std::min<int64_t>(B, P.max_iteration - k);
+        hipLaunchKernelGGL(k_ransac_hyp, dim3((nb + 63) / 64), dim3(64), 0, os.st, k, nb, a, dP, dQ, dNS, dNT, dT, dvalid);
+        hipLaunchKernelGGL(k_ransac_eval, dim3((nb + RANSAC_HB - 1) / RANSAC_HB), dim3(RANSAC_EVAL_BLOCK), 0, os.st, nb, m, a.mc2, dP, dQ, dT, dvalid,
+                           dfit, drmse);
+        GSR_HIP(hipMemcpyAsync(hfit.data(), dfit, (size_t)nb * 8, hipMemcpyDeviceToHost, os.st));
+        GSR_HIP(hipMemcpyAsync(hrmse.data(), drmse, (size_t)nb * 8, hipMemcpyDeviceToHost, os.st));
+        GSR_TRY(os.wait());
+        int64_t best_in_batch = -1;
+        // Open3D's serial rule, hypothesis by hypothesis in index order
+        for (int t = 0; t < nb && k < exit_k; ++t, ++k) {
+            const double f = hfit[t], rm = hrmse[t];
+            if (f < 0.0) continue;                                   // repeated row or a checker failed
+            ++n_valid;
+            if (f > best_fit || (f == best_fit && rm < best_rmse)) {
+                best_fit = f; best_rmse = rm; best = k; best_in_batch = t;
+                if (P.confidence < 1.0) {
+                    const double est = std::ceil(std::log(1.0 - P.confidence) / std::log(1.0 - std::pow(f, (double)P.ransac_n)));
+                    if (est < (double)exit_k) exit_k = (int64_t)est;
                 }
             }
-            if (best_in_batch >= 0) {
-                double T12[12];
-                e = hipMemcpyAsync(T12, dT.as<double>() + 12 * best_in_batch, 96, hipMemcpyDeviceToHost, st);
-                if (e == hipSuccess) e = hipStreamSynchronize(st);
-                if (e != hipSuccess) { r = fail(GSR_E_HIP, "gsr_ransac_correspondence: %s", hipGetErrorString(e)); break; }
-                for (int q = 0; q < 12; ++q) out->T[q] = T12[q];
-                out->T[12] = 0.0; out->T[13] = 0.0; out->T[14] = 0.0; out->T[15] = 1.0;
-            }
         }
-        if (r == GSR_OK) {
-            out->fitness = best_fit; out->inlier_rmse = best_rmse; out->best_index = best;
-            out->n_evaluated = k; out->n_valid = n_valid; out->exit_index = exit_k;
+        if (best_in_batch >= 0) {
+            GSR_HIP(hipMemcpyAsync(best_T, dT + 12 * best_in_batch, 96, hipMemcpyDeviceToHost, os.st));
+            GSR_TRY(os.wait());
         }
-    } while (0);
-    (void)hipStreamSynchronize(st);
-    s_sx.buf.release(); s_tx.buf.release(); s_sn.buf.release(); s_tn.buf.release(); s_c.buf.release();
-    dP.release(); dQ.release(); dNS.release(); dNT.release(); dT.release(); dvalid.release(); dfit.release(); drmse.release();
-    if (r != GSR_OK) { mat4_identity(out->T); out->best_index = -1; }
-    return r;
+    }
+    if (best >= 0) memcpy(out->T, best_T, 96);                  // rows 0..2; row 3 is the identity's
+    out->fitness = best_fit; out->inlier_rmse = best_rmse; out->best_index = best;
+    out->n_evaluated = k; out->n_valid = n_valid; out->exit_index = exit_k;
+    return GSR_OK;
 }
 
 // test hook: the sampler's raw draws (host code; the kernels call the same __host__ __device__ function)

@@ -30,6 +30,7 @@
 #include "gsr_normals.h"
 #include "gsr_solve.h"
 #include "gsr_features.h"
+#include "gsr_oneshot.h"
 
 #include <float.h>
 #include <math.h>
@@ -2158,79 +2159,48 @@ int32_t gsr_icp_get_timing(gsr_icp_ctx* c, float* out3) {
 
 int32_t gsr_normals_from_cov(const float* cov6, int64_t n, double* normals, int32_t on_device, int32_t device, void* stream) {
     if (n < 0 || (n > 0 && (!cov6 || !normals))) return fail(GSR_E_INVALID, "gsr_normals_from_cov: bad argument");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(GSR_E_NO_DEVICE, "gsr_normals_from_cov: no HIP device visible (this backend has no CPU fallback)");
+    GSR_TRY(open_device(device, "gsr_normals_from_cov"));
     if (n == 0) return GSR_OK;
-    GSR_HIP(hipSetDevice(device));
-    hipStream_t st = (hipStream_t)stream;
-    if (on_device) {
-        hipLaunchKernelGGL(k_normals_from_cov, dim3(stride_grid(n)), dim3(256), 0, st, n, cov6, normals);
-        GSR_HIP(hipStreamSynchronize(st));
-        return GSR_OK;
-    }
-    DevBuf in, out;
-    int32_t r = in.reserve((size_t)n * 24);
-    if (r == GSR_OK) r = out.reserve((size_t)n * 24);
-    if (r != GSR_OK) { in.release(); out.release(); return r; }
-    hipError_t e = hipMemcpyAsync(in.p, cov6, (size_t)n * 24, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_normals_from_cov, dim3(stride_grid(n)), dim3(256), 0, st, n, in.as<float>(), out.as<double>());
-        e = hipMemcpyAsync(normals, out.p, (size_t)n * 24, hipMemcpyDeviceToHost, st);
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    in.release(); out.release();
-    if (e != hipSuccess) return fail(GSR_E_HIP, "gsr_normals_from_cov: %s", hipGetErrorString(e));
-    return GSR_OK;
+    OneShot os((hipStream_t)stream, on_device != 0, "gsr_normals_from_cov");
+    const float* in = nullptr;
+    double* out = nullptr;
+    GSR_TRY(os.in(cov6, (size_t)n * 24, &in));
+    GSR_TRY(os.out(normals, (size_t)n * 24, &out));
+    hipLaunchKernelGGL(k_normals_from_cov, dim3(stride_grid(n)), dim3(256), 0, os.st, n, in, out);
+    return os.finish();
 }
 
 int32_t gsr_cov_from_normals(const double* normals, int64_t n, double epsilon, double* cov6, int32_t on_device, int32_t device, void* stream) {
     if (n < 0 || (n > 0 && (!normals || !cov6))) return fail(GSR_E_INVALID, "gsr_cov_from_normals: bad argument");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(GSR_E_NO_DEVICE, "gsr_cov_from_normals: no HIP device visible (this backend has no CPU fallback)");
+    GSR_TRY(open_device(device, "gsr_cov_from_normals"));
     if (n == 0) return GSR_OK;
-    GSR_HIP(hipSetDevice(device));
-    hipStream_t st = (hipStream_t)stream;
-    if (on_device) {
-        hipLaunchKernelGGL(k_cov_from_normals, dim3(stride_grid(n)), dim3(256), 0, st, n, normals, epsilon, cov6);
-        GSR_HIP(hipStreamSynchronize(st));
-        return GSR_OK;
-    }
-    DevBuf in, out;
-    int32_t r = in.reserve((size_t)n * 24);
-    if (r == GSR_OK) r = out.reserve((size_t)n * 48);
-    if (r != GSR_OK) { in.release(); out.release(); return r; }
-    hipError_t e = hipMemcpyAsync(in.p, normals, (size_t)n * 24, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_cov_from_normals, dim3(stride_grid(n)), dim3(256), 0, st, n, in.as<double>(), epsilon, out.as<double>());
-        e = hipMemcpyAsync(cov6, out.p, (size_t)n * 48, hipMemcpyDeviceToHost, st);
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    in.release(); out.release();
-    if (e != hipSuccess) return fail(GSR_E_HIP, "gsr_cov_from_normals: %s", hipGetErrorString(e));
-    return GSR_OK;
+    OneShot os((hipStream_t)stream, on_device != 0, "gsr_cov_from_normals");
+    const double* in = nullptr;
+    double* out = nullptr;
+    GSR_TRY(os.in(normals, (size_t)n * 24, &in));
+    GSR_TRY(os.out(cov6, (size_t)n * 48, &out));
+    hipLaunchKernelGGL(k_cov_from_normals, dim3(stride_grid(n)), dim3(256), 0, os.st, n, in, epsilon, out);
+    return os.finish();
 }
 
 int32_t gsr_normals_knn(const float* xyz, int64_t n, int32_t knn, double* normals, int32_t on_device, int32_t device, void* stream) {
     if (n < 0 || (n > 0 && (!xyz || !normals))) return fail(GSR_E_INVALID, "gsr_normals_knn: bad argument");
     if (knn < 1 || knn > ICP_KNN) return fail(GSR_E_INVALID, "gsr_normals_knn: knn must lie in [1, %d] (got %d)", ICP_KNN, knn);
     if (n == 0) return GSR_OK;
+    GSR_TRY(open_device(device, "gsr_normals_knn"));
     gsr_icp_ctx* c = nullptr;
     GSR_TRY(gsr_icp_create(&c, device, stream));
     // the grid of the ICP target index (about two points per cell); the correspondence distance plays no role here
     int32_t r = gsr_icp_set_target(c, xyz, nullptr, n, 1e-300, on_device);
     if (r == GSR_OK) {
-        DevBuf out;
-        r = out.reserve((size_t)n * 24);
+        OneShot os(c->stream, on_device != 0, "gsr_normals_knn");      // in this scope: it waits before the context's buffers are freed
+        double* out = nullptr;
+        r = os.out(normals, (size_t)n * 24, &out);
         if (r == GSR_OK) {
             hipLaunchKernelGGL(k_knn_normals, dim3(stride_grid(n)), dim3(256), 0, c->stream, n, c->grid, c->cellStart.as<int>(), c->Tq.as<float4>(),
-                               c->order.as<unsigned>(), (int)knn, out.as<double>());
-            hipError_t e = hipMemcpyAsync(normals, out.p, (size_t)n * 24, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-            if (e != hipSuccess) r = fail(GSR_E_HIP, "gsr_normals_knn: %s", hipGetErrorString(e));
+                               c->order.as<unsigned>(), (int)knn, out);
+            r = os.finish();
         }
-        out.release();
     }
     (void)gsr_icp_destroy(c);
     return r;

@@ -23,12 +23,11 @@
 // largest magnitude of every eigenvector is positive (first maximum on ties).  Everything the reference path derives from
 // V is invariant under column sign flips except the signs inside the scattered rows; tests compare up to those.
 #include "gsr_common.h"
+#include "gsr_oneshot.h"
 
 #include <float.h>
 #include <math.h>
 #include <string.h>
-
-#include <vector>
 
 namespace gsr {
 
@@ -199,58 +198,34 @@ extern "C" int32_t gsr_plane_score(const float* xyz, const float* normals, int64
                                    int32_t on_device, int32_t device, void* stream) {
     if (n < 0 || n_candidates < 0 || (n > 0 && (!xyz || !normals)) || (n_candidates > 0 && (!candidates || !counts)) || !best)
         return fail(GSR_E_INVALID, "gsr_plane_score: bad argument");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(GSR_E_NO_DEVICE, "gsr_plane_score: no HIP device visible (this backend has no CPU fallback)");
+    GSR_TRY(open_device(device, "gsr_plane_score"));
     *best = -1;
     if (n == 0 || n_candidates == 0) return GSR_OK;
-    GSR_HIP(hipSetDevice(device));
-    hipStream_t st = (hipStream_t)stream;
     static_assert(sizeof(PlaneCand) == 32, "candidates are 8 floats");
-    DevBuf dx, dn, dc, dcnt, dmask;
-    const float* px = xyz;
-    const float* pn = normals;
-    int32_t r = dc.reserve((size_t)n_candidates * 32);
-    if (r == GSR_OK) r = dcnt.reserve((size_t)n_candidates * 4);
-    if (r == GSR_OK && !on_device) { r = dx.reserve((size_t)n * 12); if (r == GSR_OK) r = dn.reserve((size_t)n * 12); }
-    if (r == GSR_OK && best_mask && !on_device) r = dmask.reserve((size_t)n);
-    hipError_t e = hipSuccess;
-    std::vector<uint32_t> hc((size_t)n_candidates);
-    if (r == GSR_OK) {
-        if (!on_device) {
-            e = hipMemcpyAsync(dx.p, xyz, (size_t)n * 12, hipMemcpyHostToDevice, st);
-            if (e == hipSuccess) e = hipMemcpyAsync(dn.p, normals, (size_t)n * 12, hipMemcpyHostToDevice, st);
-            px = dx.as<float>(); pn = dn.as<float>();
-        }
-        if (e == hipSuccess) e = hipMemcpyAsync(dc.p, candidates, (size_t)n_candidates * 32, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipMemsetAsync(dcnt.p, 0, (size_t)n_candidates * 4, st);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(k_plane_score, dim3(stride_grid(n)), dim3(256), 0, st, n, px, pn, (int)n_candidates, dc.as<PlaneCand>(), distance_threshold,
-                               normal_threshold, dcnt.as<unsigned>());
-            e = hipMemcpyAsync(hc.data(), dcnt.p, (size_t)n_candidates * 4, hipMemcpyDeviceToHost, st);
-        }
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-    }
-    if (r == GSR_OK && e == hipSuccess) {
-        // the reference keeps the FIRST candidate with the strictly largest count (plane_fitting_util.py:63-66)
-        uint32_t mx = 0;
-        for (int32_t p = 0; p < n_candidates; ++p) {
-            counts[p] = hc[(size_t)p];
-            if (hc[(size_t)p] > mx) { mx = hc[(size_t)p]; *best = p; }
-        }
-        if (*best >= 0 && best_mask) {
-            PlaneCand c;
-            memcpy(&c, candidates + 8 * (size_t)*best, sizeof(c));
-            uint8_t* dm = on_device ? best_mask : dmask.as<uint8_t>();
-            hipLaunchKernelGGL(k_plane_mask, dim3(stride_grid(n)), dim3(256), 0, st, n, px, pn, c, distance_threshold, normal_threshold, dm);
-            if (!on_device) e = hipMemcpyAsync(best_mask, dm, (size_t)n, hipMemcpyDeviceToHost, st);
-            if (e == hipSuccess) e = hipStreamSynchronize(st);
-        }
-    }
-    dx.release(); dn.release(); dc.release(); dcnt.release(); dmask.release();
-    if (r != GSR_OK) return r;
-    if (e != hipSuccess) return fail(GSR_E_HIP, "gsr_plane_score: %s", hipGetErrorString(e));
-    return GSR_OK;
+    OneShot os((hipStream_t)stream, on_device != 0, "gsr_plane_score");
+    const float *px = nullptr, *pn = nullptr;
+    PlaneCand* dc = nullptr;            // candidates and counts are host arrays in either placement
+    unsigned* dcnt = nullptr;
+    uint8_t* dm = nullptr;
+    GSR_TRY(os.scratch((size_t)n_candidates * 32, &dc));
+    GSR_TRY(os.scratch((size_t)n_candidates * 4, &dcnt));
+    GSR_TRY(os.in(xyz, (size_t)n * 12, &px));
+    GSR_TRY(os.in(normals, (size_t)n * 12, &pn));
+    GSR_TRY(os.out(best_mask, (size_t)n, &dm));
+    GSR_HIP(hipMemcpyAsync(dc, candidates, (size_t)n_candidates * 32, hipMemcpyHostToDevice, os.st));
+    GSR_HIP(hipMemsetAsync(dcnt, 0, (size_t)n_candidates * 4, os.st));
+    hipLaunchKernelGGL(k_plane_score, dim3(stride_grid(n)), dim3(256), 0, os.st, n, px, pn, (int)n_candidates, dc, distance_threshold, normal_threshold, dcnt);
+    GSR_HIP(hipMemcpyAsync(counts, dcnt, (size_t)n_candidates * 4, hipMemcpyDeviceToHost, os.st));
+    GSR_TRY(os.wait());
+    // the reference keeps the FIRST candidate with the strictly largest count (plane_fitting_util.py:63-66)
+    uint32_t mx = 0;
+    for (int32_t p = 0; p < n_candidates; ++p)
+        if (counts[p] > mx) { mx = counts[p]; *best = p; }
+    if (*best < 0 || !best_mask) return GSR_OK;
+    PlaneCand c;
+    memcpy(&c, candidates + 8 * (size_t)*best, sizeof(c));
+    hipLaunchKernelGGL(k_plane_mask, dim3(stride_grid(n)), dim3(256), 0, os.st, n, px, pn, c, distance_threshold, normal_threshold, dm);
+    return os.finish();
 }
 
 // ---- 3DGS .ply rows -> device SoA ------------------------------------------------------------------------
@@ -315,9 +290,7 @@ extern "C" int32_t gsr_ply_unpack(const void* rows_dev, int64_t n, int32_t row_b
                                   float* sh, float* opacity, float* scale, float* rot, float* cov6, int32_t device, void* stream) {
     if (n < 0 || K < 0 || row_bytes <= 0 || !offsets || (n > 0 && (!rows_dev || !xyz || !color || !opacity || !scale || !rot || !cov6 || (K > 0 && !sh))))
         return fail(GSR_E_INVALID, "gsr_ply_unpack: bad argument");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(GSR_E_NO_DEVICE, "gsr_ply_unpack: no HIP device visible (this backend has no CPU fallback)");
+    GSR_TRY(open_device(device, "gsr_ply_unpack"));
     PlyLayout L;
     L.row_bytes = row_bytes; L.K = K;
     for (int i = 0; i < 3; ++i) { L.xyz[i] = offsets[i]; L.dc[i] = offsets[3 + i]; L.scale[i] = offsets[7 + i]; }
@@ -330,7 +303,6 @@ extern "C" int32_t gsr_ply_unpack(const void* rows_dev, int64_t n, int32_t row_b
             return fail(GSR_E_INVALID, "gsr_ply_unpack: property offset %d outside the %d-byte row", offsets[i], row_bytes);
         }
     if (n == 0) return GSR_OK;
-    GSR_HIP(hipSetDevice(device));
     hipLaunchKernelGGL(k_ply_unpack, dim3(stride_grid(n * (K > 0 ? 3 * K : 1))), dim3(256), 0, (hipStream_t)stream, n, (const unsigned char*)rows_dev, L, xyz, color, sh,
                        opacity, scale, rot, cov6);
     GSR_HIP(hipGetLastError());
@@ -341,37 +313,15 @@ extern "C" int32_t gsr_decompose_cov(const float* cov6, int64_t n, int32_t mode,
                                      int32_t on_device, int32_t device, void* stream) {
     if (n < 0 || (n > 0 && (!cov6 || !scaling || !rotation))) return fail(GSR_E_INVALID, "gsr_decompose_cov: bad argument");
     if (mode != GSR_DECOMP_REFERENCE && mode != GSR_DECOMP_EXACT) return fail(GSR_E_INVALID, "gsr_decompose_cov: unknown mode %d", mode);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(GSR_E_NO_DEVICE, "gsr_decompose_cov: no HIP device visible (this backend has no CPU fallback)");
+    GSR_TRY(open_device(device, "gsr_decompose_cov"));
     if (n == 0) return GSR_OK;
-    GSR_HIP(hipSetDevice(device));
-    hipStream_t st = (hipStream_t)stream;
-    if (on_device) {
-        hipLaunchKernelGGL(k_decompose_cov, dim3(stride_grid(n)), dim3(256), 0, st, n, cov6, (int)mode, scaling, rotation, matrix);
-        GSR_HIP(hipGetLastError());
-        GSR_HIP(hipStreamSynchronize(st));
-        return GSR_OK;
-    }
-    DevBuf in, sc, q, m;
-    int32_t r = in.reserve((size_t)n * 24);
-    if (r == GSR_OK) r = sc.reserve((size_t)n * 12);
-    if (r == GSR_OK) r = q.reserve((size_t)n * 16);
-    if (r == GSR_OK && matrix) r = m.reserve((size_t)n * 36);
-    hipError_t e = hipSuccess;
-    if (r == GSR_OK) {
-        e = hipMemcpyAsync(in.p, cov6, (size_t)n * 24, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(k_decompose_cov, dim3(stride_grid(n)), dim3(256), 0, st, n, in.as<float>(), (int)mode, sc.as<float>(), q.as<float>(),
-                               matrix ? m.as<float>() : (float*)nullptr);
-            e = hipMemcpyAsync(scaling, sc.p, (size_t)n * 12, hipMemcpyDeviceToHost, st);
-        }
-        if (e == hipSuccess) e = hipMemcpyAsync(rotation, q.p, (size_t)n * 16, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess && matrix) e = hipMemcpyAsync(matrix, m.p, (size_t)n * 36, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-    }
-    in.release(); sc.release(); q.release(); m.release();
-    if (r != GSR_OK) return r;
-    if (e != hipSuccess) return fail(GSR_E_HIP, "gsr_decompose_cov: %s", hipGetErrorString(e));
-    return GSR_OK;
+    OneShot os((hipStream_t)stream, on_device != 0, "gsr_decompose_cov");
+    const float* in = nullptr;
+    float *sc = nullptr, *q = nullptr, *m = nullptr;
+    GSR_TRY(os.in(cov6, (size_t)n * 24, &in));
+    GSR_TRY(os.out(scaling, (size_t)n * 12, &sc));
+    GSR_TRY(os.out(rotation, (size_t)n * 16, &q));
+    GSR_TRY(os.out(matrix, (size_t)n * 36, &m));
+    hipLaunchKernelGGL(k_decompose_cov, dim3(stride_grid(n)), dim3(256), 0, os.st, n, in, (int)mode, sc, q, m);
+    return os.finish();
 }

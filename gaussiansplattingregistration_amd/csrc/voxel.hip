@@ -18,6 +18,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include "gsr_common.h"
+#include "gsr_oneshot.h"
 
 namespace gsr {
 namespace {
@@ -114,66 +115,64 @@ int32_t gsr_voxel_down_sample(int32_t device, void* stream, const float* xyz, co
     if (!(voxel_size > 0.0)) return fail(GSR_E_PRECONDITION, "[VoxelDownSample] voxel_size <= 0.");
     if (n < 0 || (n > 0 && !xyz)) return fail(GSR_E_INVALID, "gsr_voxel_down_sample: bad input");
     if (n >= ((int64_t)1 << 31) - 1) return fail(GSR_E_INVALID, "gsr_voxel_down_sample: n too large");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(GSR_E_NO_DEVICE, "no HIP device: this library has no CPU fallback");
-    GSR_HIP(hipSetDevice(device));
+    GSR_TRY(open_device(device, "gsr_voxel_down_sample"));
     hipStream_t st = (hipStream_t)stream;
     gsr_voxel_result* r = new gsr_voxel_result();
     r->device = device; r->stream = st; r->has_cov = cov6 != nullptr; r->has_color = color != nullptr;
     *out = r;
     if (n == 0) return GSR_OK;
-    // every failure below returns through GSR_HIP / GSR_TRY: the caller frees *out with gsr_voxel_free
-    DevBuf sx, sc, sk, part, keys, skeys, idx, order, head, rank, start, tmp, bad;
-    struct Guard { DevBuf* b[13]; ~Guard() { for (DevBuf* p : b) p->release(); } } guard{{&sx, &sc, &sk, &part, &keys, &skeys, &idx, &order, &head, &rank, &start, &tmp, &bad}};
-    const float *dx = xyz, *dc = cov6, *dk = color;
-    if (!on_device) {
-        GSR_TRY(sx.reserve((size_t)n * 12));
-        GSR_HIP(hipMemcpyAsync(sx.p, xyz, (size_t)n * 12, hipMemcpyHostToDevice, st));
-        dx = sx.as<float>();
-        if (cov6) { GSR_TRY(sc.reserve((size_t)n * 24)); GSR_HIP(hipMemcpyAsync(sc.p, cov6, (size_t)n * 24, hipMemcpyHostToDevice, st)); dc = sc.as<float>(); }
-        if (color) { GSR_TRY(sk.reserve((size_t)n * 12)); GSR_HIP(hipMemcpyAsync(sk.p, color, (size_t)n * 12, hipMemcpyHostToDevice, st)); dk = sk.as<float>(); }
-    }
+    // every failure below returns through GSR_HIP / GSR_TRY: `os` waits for the stream (the read-backs into hmn, last_rank, ...
+    // included) and frees the scratch; the caller frees *out with gsr_voxel_free
+    OneShot os(st, on_device != 0, "gsr_voxel_down_sample");
+    const float *dx = nullptr, *dc = nullptr, *dk = nullptr;
+    GSR_TRY(os.in(xyz, (size_t)n * 12, &dx));
+    GSR_TRY(os.in(cov6, (size_t)n * 24, &dc));
+    GSR_TRY(os.in(color, (size_t)n * 12, &dk));
     const int nb = stride_grid(n);
-    GSR_TRY(part.reserve((size_t)nb * 12 + 64));
-    hipLaunchKernelGGL(k_vox_min, dim3(nb), dim3(256), 0, st, n, dx, part.as<float>() + 16);
-    hipLaunchKernelGGL(k_vox_min_reduce, dim3(1), dim3(64), 0, st, nb, part.as<float>() + 16, part.as<float>());
+    float* part = nullptr;
+    GSR_TRY(os.scratch((size_t)nb * 12 + 64, &part));
+    hipLaunchKernelGGL(k_vox_min, dim3(nb), dim3(256), 0, st, n, dx, part + 16);
+    hipLaunchKernelGGL(k_vox_min_reduce, dim3(1), dim3(64), 0, st, nb, part + 16, part);
     float hmn[3];
-    GSR_HIP(hipMemcpyAsync(hmn, part.p, 12, hipMemcpyDeviceToHost, st));
+    GSR_HIP(hipMemcpyAsync(hmn, part, 12, hipMemcpyDeviceToHost, st));
     GSR_HIP(hipStreamSynchronize(st));
     VoxGeom g;
     for (int a = 0; a < 3; ++a) g.mn[a] = (double)hmn[a] - voxel_size * 0.5;      // voxel_min_bound
     g.voxel = voxel_size;
-    GSR_TRY(keys.reserve((size_t)n * 8)); GSR_TRY(skeys.reserve((size_t)n * 8)); GSR_TRY(idx.reserve((size_t)n * 4)); GSR_TRY(order.reserve((size_t)n * 4));
-    GSR_TRY(bad.reserve(64));
-    GSR_HIP(hipMemsetAsync(bad.p, 0, 4, st));
-    hipLaunchKernelGGL(k_vox_keys, dim3(nb), dim3(256), 0, st, n, dx, g, keys.as<unsigned long long>(), idx.as<unsigned>(), bad.as<int>());
-    size_t bytes = 0;
-    GSR_HIP(rocprim::radix_sort_pairs(nullptr, bytes, keys.as<unsigned long long>(), skeys.as<unsigned long long>(), idx.as<unsigned>(),
-                                      order.as<unsigned>(), (size_t)n, 0u, 63u, st));
-    GSR_TRY(tmp.reserve(bytes));
-    GSR_HIP(rocprim::radix_sort_pairs(tmp.p, bytes, keys.as<unsigned long long>(), skeys.as<unsigned long long>(), idx.as<unsigned>(),
-                                      order.as<unsigned>(), (size_t)n, 0u, 63u, st));
-    GSR_TRY(head.reserve((size_t)n * 4)); GSR_TRY(rank.reserve((size_t)n * 4));
-    hipLaunchKernelGGL(k_vox_heads, dim3(nb), dim3(256), 0, st, n, skeys.as<unsigned long long>(), head.as<int>());
-    bytes = 0;
-    GSR_HIP(rocprim::exclusive_scan(nullptr, bytes, head.as<int>(), rank.as<int>(), 0, (size_t)n, rocprim::plus<int>(), st));
-    GSR_TRY(tmp.reserve(bytes));
-    GSR_HIP(rocprim::exclusive_scan(tmp.p, bytes, head.as<int>(), rank.as<int>(), 0, (size_t)n, rocprim::plus<int>(), st));
+    unsigned long long *keys = nullptr, *skeys = nullptr;
+    unsigned *idx = nullptr, *order = nullptr;
+    int *bad = nullptr, *head = nullptr, *rank = nullptr;
+    void* tmp = nullptr;
+    GSR_TRY(os.scratch((size_t)n * 8, &keys)); GSR_TRY(os.scratch((size_t)n * 8, &skeys));
+    GSR_TRY(os.scratch((size_t)n * 4, &idx)); GSR_TRY(os.scratch((size_t)n * 4, &order));
+    GSR_TRY(os.scratch(64, &bad));
+    GSR_HIP(hipMemsetAsync(bad, 0, 4, st));
+    hipLaunchKernelGGL(k_vox_keys, dim3(nb), dim3(256), 0, st, n, dx, g, keys, idx, bad);
+    GSR_TRY(os.scratch((size_t)n * 4, &head)); GSR_TRY(os.scratch((size_t)n * 4, &rank));
+    // one temporary for the sort and then the scan (stream order keeps them apart)
+    size_t sort_bytes = 0, scan_bytes = 0;
+    GSR_HIP(rocprim::radix_sort_pairs(nullptr, sort_bytes, keys, skeys, idx, order, (size_t)n, 0u, 63u, st));
+    GSR_HIP(rocprim::exclusive_scan(nullptr, scan_bytes, head, rank, 0, (size_t)n, rocprim::plus<int>(), st));
+    GSR_TRY(os.scratch(sort_bytes > scan_bytes ? sort_bytes : scan_bytes, &tmp));
+    GSR_HIP(rocprim::radix_sort_pairs(tmp, sort_bytes, keys, skeys, idx, order, (size_t)n, 0u, 63u, st));
+    hipLaunchKernelGGL(k_vox_heads, dim3(nb), dim3(256), 0, st, n, skeys, head);
+    GSR_HIP(rocprim::exclusive_scan(tmp, scan_bytes, head, rank, 0, (size_t)n, rocprim::plus<int>(), st));
     int last_rank = 0, last_head = 0, hbad = 0;
-    GSR_HIP(hipMemcpyAsync(&last_rank, rank.as<int>() + (n - 1), 4, hipMemcpyDeviceToHost, st));
-    GSR_HIP(hipMemcpyAsync(&last_head, head.as<int>() + (n - 1), 4, hipMemcpyDeviceToHost, st));
-    GSR_HIP(hipMemcpyAsync(&hbad, bad.p, 4, hipMemcpyDeviceToHost, st));
+    GSR_HIP(hipMemcpyAsync(&last_rank, rank + (n - 1), 4, hipMemcpyDeviceToHost, st));
+    GSR_HIP(hipMemcpyAsync(&last_head, head + (n - 1), 4, hipMemcpyDeviceToHost, st));
+    GSR_HIP(hipMemcpyAsync(&hbad, bad, 4, hipMemcpyDeviceToHost, st));
     GSR_HIP(hipStreamSynchronize(st));
     if (hbad) return fail(GSR_E_PRECONDITION, "[VoxelDownSample] voxel_size is too small (or a coordinate is not finite).");
     const int64_t V = (int64_t)last_rank + last_head;
-    GSR_TRY(start.reserve(((size_t)V + 1) * 8));
-    hipLaunchKernelGGL(k_vox_starts, dim3(nb), dim3(256), 0, st, n, head.as<int>(), rank.as<int>(), V, start.as<int64_t>());
+    int64_t* start = nullptr;
+    GSR_TRY(os.scratch(((size_t)V + 1) * 8, &start));
+    hipLaunchKernelGGL(k_vox_starts, dim3(nb), dim3(256), 0, st, n, head, rank, V, start);
     GSR_TRY(r->xyz.reserve((size_t)V * 24));
     if (cov6) GSR_TRY(r->cov6.reserve((size_t)V * 48));
     if (color) GSR_TRY(r->color.reserve((size_t)V * 24));
-    hipLaunchKernelGGL(k_vox_mean, dim3(stride_grid(V)), dim3(256), 0, st, V, start.as<int64_t>(), order.as<unsigned>(), dx, dc, dk,
+    hipLaunchKernelGGL(k_vox_mean, dim3(stride_grid(V)), dim3(256), 0, st, V, start, order, dx, dc, dk,
                        r->xyz.as<double>(), cov6 ? r->cov6.as<double>() : (double*)nullptr, color ? r->color.as<double>() : (double*)nullptr);
-    GSR_HIP(hipStreamSynchronize(st));
+    GSR_TRY(os.finish());
     r->V = V;
     *n_voxels = V;
     return GSR_OK;

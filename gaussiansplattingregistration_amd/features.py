@@ -12,6 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from . import _marshal as _m
 
 try:
     import torch
@@ -28,52 +29,23 @@ CHECK_DISTANCE = _lib.GSR_CHECK_DISTANCE
 CHECK_NORMAL = _lib.GSR_CHECK_NORMAL
 
 
-def _is_cuda(a):
-    return torch is not None and isinstance(a, torch.Tensor) and a.is_cuda
-
-
-def _prep(a, cols, dtype, device, on_device):
-    """-> (pointer, keep-alive, n) of a contiguous (n, cols) array of `dtype` on the host or on cuda:`device`"""
-    if a is None:
-        return None, None, 0
-    if on_device:
-        if not _is_cuda(a):
-            raise RuntimeError("inputs must be all on the host or all on the device")
-        if a.device.index != device:
-            raise RuntimeError(f"tensor lives on {a.device}, requested cuda:{device}")
-        t = a.detach().to({np.float32: torch.float32, np.float64: torch.float64, np.int32: torch.int32}[dtype]).reshape(-1, cols).contiguous()
-        return t.data_ptr(), t, int(t.shape[0])
-    if _is_cuda(a):
+def _rows(a, cols, dtype, device, on_device):
+    """-> (pointer, keep-alive, n) of a contiguous (n, cols) array of `dtype`, which must lie where `on_device` says"""
+    p, keep, on = _m.prep(a, (-1, cols), dtype, device)
+    if on is not None and on != bool(on_device):
         raise RuntimeError("inputs must be all on the host or all on the device")
-    if torch is not None and isinstance(a, torch.Tensor):
-        a = a.detach().numpy()
-    arr = np.ascontiguousarray(np.asarray(a, dtype=dtype).reshape(-1, cols))
-    return arr.ctypes.data, arr, int(arr.shape[0])
-
-
-def _stream(device, on_device):
-    if on_device:
-        return torch.cuda.current_stream(device).cuda_stream
-    return 0
-
-
-def _out(shape, dtype, device, on_device):
-    if on_device:
-        t = torch.empty(shape, dtype={np.float64: torch.float64, np.int32: torch.int32}[dtype], device=torch.device("cuda", device))
-        return t, t.data_ptr()
-    a = np.empty(shape, dtype)
-    return a, a.ctypes.data
+    return p, keep, 0 if keep is None else int(keep.shape[0])
 
 
 def hybrid_search(xyz, radius, max_nn, device=0):
     """``KDTreeSearchParamHybrid(radius, max_nn)`` of every point against the cloud: ``(nbr (n, max_nn) int32, count (n,) int32)``;
     row i lists ``count[i]`` input indices in (d2, index) order (the rest of the row is unspecified)."""
     L = _lib.load(require_device=True)
-    on = _is_cuda(xyz)
-    px, kx, n = _prep(xyz, 3, np.float32, device, on)
-    nbr, pn = _out((n, int(max_nn)), np.int32, device, on)
-    cnt, pc = _out((n,), np.int32, device, on)
-    _lib.check(L.gsr_hybrid_search(px, n, float(radius), int(max_nn), pn, pc, 1 if on else 0, int(device), C.c_void_p(_stream(device, on))),
+    on = _m.is_cuda(xyz)
+    px, kx, n = _rows(xyz, 3, np.float32, device, on)
+    nbr, pn = _m.out((n, int(max_nn)), np.int32, device, on)
+    cnt, pc = _m.out((n,), np.int32, device, on)
+    _lib.check(L.gsr_hybrid_search(px, n, float(radius), int(max_nn), pn, pc, 1 if on else 0, int(device), C.c_void_p(_m.stream_ptr(device, on))),
                "gsr_hybrid_search")
     return nbr, cnt
 
@@ -82,17 +54,17 @@ def fpfh(xyz, normals, radius, max_nn, device=0, as_torch=False):
     """Open3D ``ComputeFPFHFeature``: float64 (n, 33) rows (numpy, or a cuda tensor when the inputs are on the device or
     ``as_torch``)."""
     L = _lib.load(require_device=True)
-    on = _is_cuda(xyz)
+    on = _m.is_cuda(xyz)
     if as_torch and not on:
         xyz = torch.as_tensor(np.asarray(xyz, np.float32)).to(torch.device("cuda", device))
         normals = torch.as_tensor(np.asarray(normals, np.float64)).to(torch.device("cuda", device))
         on = True
-    px, kx, n = _prep(xyz, 3, np.float32, device, on)
-    pn, kn, nn = _prep(normals, 3, np.float64, device, on)
+    px, kx, n = _rows(xyz, 3, np.float32, device, on)
+    pn, kn, nn = _rows(normals, 3, np.float64, device, on)
     if normals is None or nn != n:
         raise RuntimeError("[Open3D Error] ComputeFPFHFeature needs one normal per point")
-    out, po = _out((n, 33), np.float64, device, on)
-    _lib.check(L.gsr_fpfh(px, pn, n, float(radius), int(max_nn), po, 1 if on else 0, int(device), C.c_void_p(_stream(device, on))), "gsr_fpfh")
+    out, po = _m.out((n, 33), np.float64, device, on)
+    _lib.check(L.gsr_fpfh(px, pn, n, float(radius), int(max_nn), po, 1 if on else 0, int(device), C.c_void_p(_m.stream_ptr(device, on))), "gsr_fpfh")
     return out
 
 
@@ -101,16 +73,16 @@ def feature_match(src_feat, tgt_feat, mutual=False, ransac_n=3, device=0, return
     ``mutual`` and it holds >= 3 * ransac_n pairs, else every (i, nn(i))) and whether the mutual set was used; with ``return_nn``
     also the two nearest-row arrays (``nn_ts`` is None without ``mutual``)."""
     L = _lib.load(require_device=True)
-    on = _is_cuda(src_feat)
-    pa, ka, ns = _prep(src_feat, 33, np.float64, device, on)
-    pb, kb, nt = _prep(tgt_feat, 33, np.float64, device, on)
-    corres, pcor = _out((ns, 2), np.int32, device, on)
-    nst, pst = _out((ns,), np.int32, device, on)
-    nts, pts = _out((nt,), np.int32, device, on) if mutual else (None, None)
+    on = _m.is_cuda(src_feat)
+    pa, ka, ns = _rows(src_feat, 33, np.float64, device, on)
+    pb, kb, nt = _rows(tgt_feat, 33, np.float64, device, on)
+    corres, pcor = _m.out((ns, 2), np.int32, device, on)
+    nst, pst = _m.out((ns,), np.int32, device, on)
+    nts, pts = _m.out((nt,), np.int32, device, on) if mutual else (None, None)
     m = C.c_int64(0)
     um = C.c_int32(0)
     _lib.check(L.gsr_feature_match(pa, ns, pb, nt, 1 if mutual else 0, int(ransac_n), pcor, C.byref(m), C.byref(um), pst, pts,
-                                   1 if on else 0, int(device), C.c_void_p(_stream(device, on))), "gsr_feature_match")
+                                   1 if on else 0, int(device), C.c_void_p(_m.stream_ptr(device, on))), "gsr_feature_match")
     corres = corres[: int(m.value)]
     if return_nn:
         return corres, bool(um.value), nst, nts
@@ -122,12 +94,12 @@ def ransac_correspondence(src_xyz, tgt_xyz, corres, max_corr, kind=KIND_POINT_TO
     """Open3D ``RegistrationRANSACBasedOnCorrespondence``, deterministic (``include/gsr_hip.h``).  ``checkers``: sequence of
     (CHECK_*, parameter).  Returns a dict: transformation, fitness, inlier_rmse, best_index, n_evaluated, n_valid, exit_index."""
     L = _lib.load(require_device=True)
-    on = _is_cuda(src_xyz)
-    ps, ks, ns = _prep(src_xyz, 3, np.float32, device, on)
-    pt, kt, nt = _prep(tgt_xyz, 3, np.float32, device, on)
-    pc, kc, m = _prep(corres, 2, np.int32, device, on)
-    psn, ksn, _ = _prep(src_normals, 3, np.float64, device, on)
-    ptn, ktn, _ = _prep(tgt_normals, 3, np.float64, device, on)
+    on = _m.is_cuda(src_xyz)
+    ps, ks, ns = _rows(src_xyz, 3, np.float32, device, on)
+    pt, kt, nt = _rows(tgt_xyz, 3, np.float32, device, on)
+    pc, kc, m = _rows(corres, 2, np.int32, device, on)
+    psn, ksn, _ = _rows(src_normals, 3, np.float64, device, on)
+    ptn, ktn, _ = _rows(tgt_normals, 3, np.float64, device, on)
     checkers = list(checkers)
     if len(checkers) > 4:
         raise RuntimeError("at most 4 correspondence checkers")
@@ -139,6 +111,6 @@ def ransac_correspondence(src_xyz, tgt_xyz, corres, max_corr, kind=KIND_POINT_TO
         P.checker_param[i] = float(cp)
     R = _lib.RansacResult()
     _lib.check(L.gsr_ransac_correspondence(ps, ns, pt, nt, psn, ptn, pc, m, C.byref(P), C.byref(R), 1 if on else 0, int(device),
-                                           C.c_void_p(_stream(device, on))), "gsr_ransac_correspondence")
+                                           C.c_void_p(_m.stream_ptr(device, on))), "gsr_ransac_correspondence")
     return {"transformation": np.array(R.T[:], dtype=np.float64).reshape(4, 4), "fitness": R.fitness, "inlier_rmse": R.inlier_rmse,
             "best_index": int(R.best_index), "n_evaluated": int(R.n_evaluated), "n_valid": int(R.n_valid), "exit_index": int(R.exit_index)}

@@ -12,6 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from . import _marshal as _m
 
 try:  # torch is optional for host-array use
     import torch
@@ -19,23 +20,6 @@ except Exception:  # pragma: no cover
     torch = None
 
 __all__ = ["HemMixture", "create_mixture"]
-
-
-def _is_tensor(a):
-    return torch is not None and isinstance(a, torch.Tensor)
-
-
-def _prep(a, shape, device_index):
-    """-> (pointer, keepalive, on_device) for a float32 array of the given shape."""
-    if _is_tensor(a):
-        if a.is_cuda:
-            if a.device.index != device_index:
-                raise RuntimeError(f"tensor lives on {a.device}, context on cuda:{device_index}")
-            t = a.detach().to(torch.float32).reshape(shape).contiguous()
-            return t.data_ptr(), t, True
-        a = a.detach().cpu().numpy()
-    arr = np.ascontiguousarray(np.asarray(a, dtype=np.float32).reshape(shape))
-    return arr.ctypes.data, arr, False
 
 
 class HemMixture:
@@ -139,12 +123,12 @@ class HemMixture:
             f = features
             F = int(f.shape[1]) if hasattr(f, "shape") and len(f.shape) == 2 else (len(f[0]) if len(f) else 0)
         self.F = F
-        px, kx, dx = _prep(xyz, (n, 3), self.device)
-        pc, kc, dc = _prep(colors, (n, 3), self.device)
-        pv, kv, dv = _prep(covariance, (n, 6), self.device)
-        po, ko, do = _prep(opacities, (n,), self.device)
+        px, kx, dx = _m.prep(xyz, (n, 3), np.float32, self.device)
+        pc, kc, dc = _m.prep(colors, (n, 3), np.float32, self.device)
+        pv, kv, dv = _m.prep(covariance, (n, 6), np.float32, self.device)
+        po, ko, do = _m.prep(opacities, (n,), np.float32, self.device)
         if F > 0:
-            ps, ks, ds = _prep(features, (n, F), self.device)
+            ps, ks, ds = _m.prep(features, (n, F), np.float32, self.device)
         else:
             ps, ks, ds = 0, None, dx
         if len({dx, dc, dv, do, ds}) != 1:
@@ -169,22 +153,22 @@ class HemMixture:
         f = features
         F = int(f.shape[1]) if hasattr(f, "shape") and len(f.shape) == 2 else 0
         self.F = F
-        px, kx, dx = _prep(xyz, (n, 3), self.device)
-        pc, kc, dc = _prep(colors, (n, 3), self.device)
-        pv, kv, dv = _prep(covariance, (n, 6), self.device)
-        po, ko, do = _prep(opacities, (n,), self.device)
-        ps, ks, ds = _prep(features, (n, F), self.device) if F > 0 else (0, None, dx)
+        px, kx, dx = _m.prep(xyz, (n, 3), np.float32, self.device)
+        pc, kc, dc = _m.prep(colors, (n, 3), np.float32, self.device)
+        pv, kv, dv = _m.prep(covariance, (n, 6), np.float32, self.device)
+        po, ko, do = _m.prep(opacities, (n,), np.float32, self.device)
+        ps, ks, ds = _m.prep(features, (n, F), np.float32, self.device) if F > 0 else (0, None, dx)
         if len({dx, dc, dv, do, ds}) != 1:
             raise RuntimeError("all level-0 arrays must live in the same place (all host or all device)")
-        n_gid = int(gid.numel()) if _is_tensor(gid) else int(np.asarray(gid).size)      # (a plain list of indices is fine too)
+        n_gid = int(gid.numel()) if _m.is_tensor(gid) else int(np.asarray(gid).size)      # (a plain list of indices is fine too)
         if n_gid != n:
             raise RuntimeError(f"gid has {n_gid} entries for {n} components")
         if dx:
-            g = (gid.detach() if _is_tensor(gid) else torch.as_tensor(np.asarray(gid, np.int64))).to(xyz.device, torch.int32).contiguous()
+            g = (gid.detach() if _m.is_tensor(gid) else torch.as_tensor(np.asarray(gid, np.int64))).to(xyz.device, torch.int32).contiguous()
             pg, kg = g.data_ptr(), g
             torch.cuda.current_stream(self.device).synchronize()
         else:
-            kg = np.ascontiguousarray(gid.cpu().numpy() if _is_tensor(gid) else np.asarray(gid), dtype=np.uint32)
+            kg = np.ascontiguousarray(gid.cpu().numpy() if _m.is_tensor(gid) else np.asarray(gid), dtype=np.uint32)
             pg = kg.ctypes.data
         _lib.check(self._L.gsr_hem_set_level0_part(self._h, px, pc, pv, po, ps, pg, n, int(n_global), F, 1 if dx else 0), "gsr_hem_set_level0_part")
         self._out_cur = self._out_prev = None

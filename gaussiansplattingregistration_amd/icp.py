@@ -9,6 +9,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from . import _marshal as _m
 
 try:
     import torch
@@ -37,23 +38,6 @@ class RegistrationResult:
     def __repr__(self):
         return (f"RegistrationResult with fitness={self.fitness:e}, inlier_rmse={self.inlier_rmse:e}, "
                 f"and iterations={self.iterations}")
-
-
-def _is_tensor(a):
-    return torch is not None and isinstance(a, torch.Tensor)
-
-
-def _prep(a, shape, dtype, device_index):
-    tdt = {np.float32: "float32", np.float64: "float64"}[dtype]
-    if _is_tensor(a):
-        if a.is_cuda:
-            if a.device.index != device_index:
-                raise RuntimeError(f"tensor lives on {a.device}, context on cuda:{device_index}")
-            t = a.detach().to(getattr(torch, tdt)).reshape(shape).contiguous()
-            return t.data_ptr(), t, True
-        a = a.detach().cpu().numpy()
-    arr = np.ascontiguousarray(np.asarray(a, dtype=dtype).reshape(shape))
-    return arr.ctypes.data, arr, False
 
 
 class IcpContext:
@@ -95,8 +79,8 @@ class IcpContext:
 
     def set_target(self, xyz, normals, max_corr):
         n = int(xyz.shape[0])
-        px, kx, dx = _prep(xyz, (n, 3), np.float32, self.device)
-        pn, kn, dn = (None, None, dx) if normals is None else _prep(normals, (n, 3), np.float64, self.device)
+        px, kx, dx = _m.prep(xyz, (n, 3), np.float32, self.device)
+        pn, kn, dn = (None, None, dx) if normals is None else _m.prep(normals, (n, 3), np.float64, self.device)
         if dn != dx:
             raise RuntimeError("target points and normals must live in the same place (both host or both device)")
         if dx:
@@ -110,7 +94,7 @@ class IcpContext:
             _lib.check(self._L.gsr_icp_set_source(self._h, None, 0, 0), "gsr_icp_set_source")
             self.n_source = 0
             return
-        px, kx, dx = _prep(xyz, (n, 3), np.float32, self.device)
+        px, kx, dx = _m.prep(xyz, (n, 3), np.float32, self.device)
         if dx:
             self._sync_torch()
         _lib.check(self._L.gsr_icp_set_source(self._h, px, n, 1 if dx else 0), "gsr_icp_set_source")
@@ -119,7 +103,7 @@ class IcpContext:
     @staticmethod
     def _cov6(cov):
         """(N,6) [xx,xy,xz,yy,yz,zz] or (N,3,3) covariances -> contiguous (N,6) float64 (numpy or tensor kept as is)."""
-        if _is_tensor(cov):
+        if _m.is_tensor(cov):
             import torch
             if cov.dim() == 3:
                 cov = torch.stack([cov[:, 0, 0], cov[:, 0, 1], cov[:, 0, 2], cov[:, 1, 1], cov[:, 1, 2], cov[:, 2, 2]], 1)
@@ -132,7 +116,7 @@ class IcpContext:
     def set_target_cov(self, cov):
         """Target covariances for generalized ICP, in the order of the points given to ``set_target``."""
         c6 = self._cov6(cov)
-        p, keep, on_dev = _prep(c6, (self.n_target, 6), np.float64, self.device)
+        p, keep, on_dev = _m.prep(c6, (self.n_target, 6), np.float64, self.device)
         if on_dev:
             self._sync_torch()
         _lib.check(self._L.gsr_icp_set_target_cov(self._h, p, 1 if on_dev else 0), "gsr_icp_set_target_cov")
@@ -140,20 +124,20 @@ class IcpContext:
     def set_source_cov(self, cov):
         """Source covariances (original frame; the library rotates them with the current transform)."""
         c6 = self._cov6(cov)
-        p, keep, on_dev = _prep(c6, (self.n_source, 6), np.float64, self.device)
+        p, keep, on_dev = _m.prep(c6, (self.n_source, 6), np.float64, self.device)
         if on_dev:
             self._sync_torch()
         _lib.check(self._L.gsr_icp_set_source_cov(self._h, p, 1 if on_dev else 0), "gsr_icp_set_source_cov")
 
     def set_target_color(self, rgb):
         """Target colours (N,3) for colored ICP; also prepares the colour gradients (needs target normals)."""
-        p, keep, on_dev = _prep(rgb, (self.n_target, 3), np.float64, self.device)
+        p, keep, on_dev = _m.prep(rgb, (self.n_target, 3), np.float64, self.device)
         if on_dev:
             self._sync_torch()
         _lib.check(self._L.gsr_icp_set_target_color(self._h, p, 1 if on_dev else 0), "gsr_icp_set_target_color")
 
     def set_source_color(self, rgb):
-        p, keep, on_dev = _prep(rgb, (self.n_source, 3), np.float64, self.device)
+        p, keep, on_dev = _m.prep(rgb, (self.n_source, 3), np.float64, self.device)
         if on_dev:
             self._sync_torch()
         _lib.check(self._L.gsr_icp_set_source_color(self._h, p, 1 if on_dev else 0), "gsr_icp_set_source_color")
@@ -246,9 +230,9 @@ class IcpContext:
         synchronisation between them.  Point-to-point / point-to-plane, one process; the same result as ``set_target`` + ``set_source`` +
         ``register``.  All arrays on the host or all on the device."""
         ns, nt = int(src_xyz.shape[0]), int(tgt_xyz.shape[0])
-        ps, ks, ds = _prep(src_xyz, (ns, 3), np.float32, self.device)
-        pt, kt, dt = _prep(tgt_xyz, (nt, 3), np.float32, self.device)
-        pn, kn, dn = (None, None, dt) if tgt_normals is None else _prep(tgt_normals, (nt, 3), np.float64, self.device)
+        ps, ks, ds = _m.prep(src_xyz, (ns, 3), np.float32, self.device)
+        pt, kt, dt = _m.prep(tgt_xyz, (nt, 3), np.float32, self.device)
+        pn, kn, dn = (None, None, dt) if tgt_normals is None else _m.prep(tgt_normals, (nt, 3), np.float64, self.device)
         if not (ds == dt == dn):
             raise RuntimeError("register_clouds: source, target and normals must live in the same place (all host or all device)")
         if dt:
@@ -272,9 +256,9 @@ class IcpContext:
         keep, place = [], set()
         for i, (sx, tx, tn, mc, it) in enumerate(entries):
             ns, nt = int(sx.shape[0]), int(tx.shape[0])
-            ps, ks, ds = _prep(sx, (ns, 3), np.float32, self.device)
-            pt, kt, dt = _prep(tx, (nt, 3), np.float32, self.device)
-            pn, kn, dn = (None, None, dt) if tn is None else _prep(tn, (nt, 3), np.float64, self.device)
+            ps, ks, ds = _m.prep(sx, (ns, 3), np.float32, self.device)
+            pt, kt, dt = _m.prep(tx, (nt, 3), np.float32, self.device)
+            pn, kn, dn = (None, None, dt) if tn is None else _m.prep(tn, (nt, 3), np.float64, self.device)
             keep += [ks, kt, kn]
             place |= {ds, dt, dn}
             ent[i].src_xyz, ent[i].ns, ent[i].tgt_xyz, ent[i].tgt_normals, ent[i].nt = ps, ns, pt, pn, nt
@@ -337,54 +321,32 @@ def registration_icp_arrays(src_xyz, tgt_xyz, tgt_normals, init, kind=0, loss=0,
         return out
 
 
+def _one_shot(fn, a, cols, dtype, out_cols, device, *args):
+    """``fn(a (n, cols) dtype, n, *args, out (n, out_cols) float64, on_device, device, stream)`` where ``a`` lives: -> out"""
+    L = _lib.load(require_device=True)
+    if _m.is_cuda(a):
+        device = a.device.index
+    p, keep, on = _m.prep(a, (int(a.shape[0]), cols), dtype, int(device))
+    n = int(keep.shape[0])
+    out, po = _m.out((n, out_cols), np.float64, int(device), on)
+    if on:
+        torch.cuda.current_stream(device).synchronize()
+    _lib.check(getattr(L, fn)(p, n, *args, po, 1 if on else 0, int(device), C.c_void_p(_m.stream_ptr(device, on))), fn)
+    return out
+
+
 def normals_from_cov(cov6, device=0):
     """float64 unit normals (n,3) = smallest-eigenvalue eigenvector of each splat covariance."""
-    L = _lib.load(require_device=True)
-    n = int(cov6.shape[0])
-    if _is_tensor(cov6) and cov6.is_cuda:
-        t = cov6.detach().to(torch.float32).reshape(n, 6).contiguous()
-        out = torch.empty((n, 3), dtype=torch.float64, device=t.device)
-        torch.cuda.current_stream(t.device.index).synchronize()
-        _lib.check(L.gsr_normals_from_cov(t.data_ptr(), n, out.data_ptr(), 1, t.device.index,
-                                          C.c_void_p(torch.cuda.current_stream(t.device.index).cuda_stream)), "gsr_normals_from_cov")
-        return out
-    a = np.ascontiguousarray(cov6.detach().cpu().numpy() if _is_tensor(cov6) else cov6, dtype=np.float32).reshape(n, 6)
-    out = np.empty((n, 3), np.float64)
-    _lib.check(L.gsr_normals_from_cov(a.ctypes.data, n, out.ctypes.data, 0, int(device), None), "gsr_normals_from_cov")
-    return out
+    return _one_shot("gsr_normals_from_cov", cov6, 6, np.float32, 3, device)
 
 
 def normals_knn(xyz, knn=30, device=0):
     """float64 unit normals (n,3) of a cloud without covariances: Open3D ``estimate_normals()`` with its default
     ``KDTreeSearchParamKNN(30)`` (what the reference does to a sparse input cloud, ``point_cloud_converter.py:9-28``)."""
-    L = _lib.load(require_device=True)
-    n = int(xyz.shape[0])
-    if _is_tensor(xyz) and xyz.is_cuda:
-        t = xyz.detach().to(torch.float32).reshape(n, 3).contiguous()
-        out = torch.empty((n, 3), dtype=torch.float64, device=t.device)
-        torch.cuda.current_stream(t.device.index).synchronize()
-        _lib.check(L.gsr_normals_knn(t.data_ptr(), n, int(knn), out.data_ptr(), 1, t.device.index,
-                                     C.c_void_p(torch.cuda.current_stream(t.device.index).cuda_stream)), "gsr_normals_knn")
-        return out
-    a = np.ascontiguousarray(xyz.detach().cpu().numpy() if _is_tensor(xyz) else xyz, dtype=np.float32).reshape(n, 3)
-    out = np.empty((n, 3), np.float64)
-    _lib.check(L.gsr_normals_knn(a.ctypes.data, n, int(knn), out.ctypes.data, 0, int(device), None), "gsr_normals_knn")
-    return out
+    return _one_shot("gsr_normals_knn", xyz, 3, np.float32, 3, device, int(knn))
 
 
 def cov_from_normals(normals, epsilon=1e-3, device=0):
     """float64 covariances (n,6) [xx,xy,xz,yy,yz,zz] of Open3D's ``InitializePointCloudForGeneralizedICP``: a disc of
     thickness ``epsilon`` perpendicular to each normal -- what generalized ICP uses for a cloud without covariances."""
-    L = _lib.load(require_device=True)
-    n = int(normals.shape[0])
-    if _is_tensor(normals) and normals.is_cuda:
-        t = normals.detach().to(torch.float64).reshape(n, 3).contiguous()
-        out = torch.empty((n, 6), dtype=torch.float64, device=t.device)
-        torch.cuda.current_stream(t.device.index).synchronize()
-        _lib.check(L.gsr_cov_from_normals(t.data_ptr(), n, float(epsilon), out.data_ptr(), 1, t.device.index,
-                                          C.c_void_p(torch.cuda.current_stream(t.device.index).cuda_stream)), "gsr_cov_from_normals")
-        return out
-    a = np.ascontiguousarray(normals.detach().cpu().numpy() if _is_tensor(normals) else normals, dtype=np.float64).reshape(n, 3)
-    out = np.empty((n, 6), np.float64)
-    _lib.check(L.gsr_cov_from_normals(a.ctypes.data, n, float(epsilon), out.ctypes.data, 0, int(device), None), "gsr_cov_from_normals")
-    return out
+    return _one_shot("gsr_cov_from_normals", normals, 3, np.float64, 6, device, float(epsilon))

@@ -24,6 +24,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import hem as _hem
+from ._marshal import is_tensor as _is_tensor
 
 try:
     import torch
@@ -105,10 +106,6 @@ class FeatureVector:
 
     def GetVector(self):
         return list(self._v)
-
-
-def _is_tensor(a):
-    return torch is not None and isinstance(a, torch.Tensor)
 
 
 def _as_array(a, width, what):

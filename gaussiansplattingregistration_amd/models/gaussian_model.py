@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from .. import _lib
+from .. import _marshal as _m
 from .gaussian_mixture_level import GaussianMixtureModel
 
 
@@ -170,20 +171,15 @@ class GaussianModel:
         """-> (scaling (N,3), quaternions (N,4), matrices (N,3,3)) of ``gsr_decompose_cov`` on the model's covariances."""
         import ctypes as C
         L = _lib.load(require_device=True)
-        cov = self._covariance.detach().to(torch.float32).contiguous()
+        cov = self._covariance
         n = int(cov.shape[0])
-        if cov.is_cuda:
-            sc = torch.empty((n, 3), dtype=torch.float32, device=cov.device)
-            q = torch.empty((n, 4), dtype=torch.float32, device=cov.device)
-            mat = torch.empty((n, 3, 3), dtype=torch.float32, device=cov.device)
-            torch.cuda.current_stream(cov.device.index).synchronize()
-            _lib.check(L.gsr_decompose_cov(cov.data_ptr(), n, mode, sc.data_ptr(), q.data_ptr(), mat.data_ptr(), 1, cov.device.index,
-                                           C.c_void_p(torch.cuda.current_stream(cov.device.index).cuda_stream)), "gsr_decompose_cov")
-            return sc, q, mat
-        a = np.ascontiguousarray(cov.numpy())
-        sc, q, mat = np.empty((n, 3), np.float32), np.empty((n, 4), np.float32), np.empty((n, 3, 3), np.float32)
-        _lib.check(L.gsr_decompose_cov(a.ctypes.data, n, mode, sc.ctypes.data, q.ctypes.data, mat.ctypes.data, 0, 0, None), "gsr_decompose_cov")
-        return torch.from_numpy(sc), torch.from_numpy(q), torch.from_numpy(mat)
+        device = cov.device.index if cov.is_cuda else 0
+        p, keep, on = _m.prep(cov, (n, 6), np.float32, device)
+        (sc, psc), (q, pq), (mat, pmat) = (_m.out(s, np.float32, device, on) for s in ((n, 3), (n, 4), (n, 3, 3)))
+        if on:
+            torch.cuda.current_stream(device).synchronize()
+        _lib.check(L.gsr_decompose_cov(p, n, mode, psc, pq, pmat, 1 if on else 0, device, C.c_void_p(_m.stream_ptr(device, on))), "gsr_decompose_cov")
+        return torch.as_tensor(sc), torch.as_tensor(q), torch.as_tensor(mat)
 
     def decompose_covariance_matrix(self):
         """Scaling / rotation of every component from its covariance with the reference's arithmetic

@@ -10,14 +10,12 @@ from __future__ import annotations
 
 import numpy as np
 
+from .._marshal import is_tensor as _is_tensor
+
 try:
     import torch
 except Exception:  # pragma: no cover
     torch = None
-
-
-def _is_tensor(a):
-    return torch is not None and isinstance(a, torch.Tensor)
 
 
 class PointCloud:

@@ -22,6 +22,7 @@ import numpy as np
 import torch
 
 from .. import _lib
+from .. import _marshal as _m
 
 
 def sample_random_points(points: torch.Tensor, min_distance: float) -> torch.Tensor:
@@ -73,22 +74,17 @@ def _fit_single_plane(points_tensor, normal_tensors, iterations, distance_thresh
     counts = np.zeros(iterations, np.uint32)
     best = C.c_int32(-1)
     if points_dev is not None:
-        mask = torch.empty(n, dtype=torch.uint8, device=points_dev.device)
-        torch.cuda.current_stream(points_dev.device.index).synchronize()
-        _lib.check(L.gsr_plane_score(points_dev.data_ptr(), normals_dev.data_ptr(), n, cands.ctypes.data, iterations, float(distance_threshold),
-                                     float(normal_threshold), counts.ctypes.data, mask.data_ptr(), C.byref(best), 1, points_dev.device.index,
-                                     C.c_void_p(torch.cuda.current_stream(points_dev.device.index).cuda_stream)), "gsr_plane_score")
-        mask_t = mask
-    else:
-        pts = np.ascontiguousarray(points_tensor.numpy(), dtype=np.float32)
-        nrm = np.ascontiguousarray(normal_tensors.numpy(), dtype=np.float32)
-        mask = np.empty(n, np.uint8)
-        _lib.check(L.gsr_plane_score(pts.ctypes.data, nrm.ctypes.data, n, cands.ctypes.data, iterations, float(distance_threshold),
-                                     float(normal_threshold), counts.ctypes.data, mask.ctypes.data, C.byref(best), 0, int(device), None), "gsr_plane_score")
-        mask_t = torch.from_numpy(mask)
+        points_tensor, normal_tensors, device = points_dev, normals_dev, points_dev.device.index
+    pp, kp, on = _m.prep(points_tensor, (n, 3), np.float32, int(device))
+    pn, kn, _ = _m.prep(normal_tensors, (n, 3), np.float32, int(device))
+    mask, pm = _m.out((n,), np.uint8, int(device), on)
+    if on:
+        torch.cuda.current_stream(device).synchronize()
+    _lib.check(L.gsr_plane_score(pp, pn, n, cands.ctypes.data, iterations, float(distance_threshold), float(normal_threshold), counts.ctypes.data,
+                                 pm, C.byref(best), 1 if on else 0, int(device), C.c_void_p(_m.stream_ptr(device, on))), "gsr_plane_score")
     if best.value < 0:
         return None, None
-    return planes[best.value], mask_t.nonzero(as_tuple=True)[0].cpu().numpy()
+    return planes[best.value], torch.as_tensor(mask).nonzero(as_tuple=True)[0].cpu().numpy()
 
 
 def fit_planes(point_cloud, plane_count, iterations, threshold, normal_threshold, min_sample_distance, device=None, reference_compat=False):

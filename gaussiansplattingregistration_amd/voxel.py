@@ -11,6 +11,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from . import _marshal as _m
 
 try:
     import torch
@@ -20,36 +21,18 @@ except Exception:  # pragma: no cover
 __all__ = ["voxel_down_sample"]
 
 
-def _is_tensor(a):
-    return torch is not None and isinstance(a, torch.Tensor)
-
-
-def _prep32(a, cols, device):
-    """-> (pointer, keep-alive, on_device, n)"""
-    if a is None:
-        return None, None, None, 0
-    if _is_tensor(a) and a.is_cuda:
-        if a.device.index != device:
-            raise RuntimeError(f"tensor lives on {a.device}, requested cuda:{device}")
-        t = a.detach().to(torch.float32).reshape(-1, cols).contiguous()
-        return t.data_ptr(), t, True, int(t.shape[0])
-    if _is_tensor(a):
-        a = a.detach().cpu().numpy()
-    arr = np.ascontiguousarray(np.asarray(a, dtype=np.float32).reshape(-1, cols))
-    return arr.ctypes.data, arr, False, int(arr.shape[0])
-
-
 def voxel_down_sample(xyz, voxel_size, cov6=None, color=None, device=0, as_torch=False):
     """Means per occupied voxel: ``(xyz (V,3), cov6 (V,6) | None, color (V,3) | None)`` in float64 (numpy, or cuda
     tensors with ``as_torch``).  Inputs: float32 arrays or tensors; all on the host or all on the device."""
     if not (voxel_size > 0.0):
         raise RuntimeError("[Open3D Error] [VoxelDownSample] voxel_size <= 0.")
     L = _lib.load(require_device=True)
-    px, kx, dx, n = _prep32(xyz, 3, device)
-    pc, kc, dc, nc = _prep32(cov6, 6, device)
-    pk, kk, dk, nk = _prep32(color, 3, device)
-    for d, m, name in ((dc, nc, "cov6"), (dk, nk, "color")):
-        if d is not None and (d != dx or m != n):
+    px, kx, dx = _m.prep(xyz, (-1, 3), np.float32, device)
+    pc, kc, dc = _m.prep(cov6, (-1, 6), np.float32, device)
+    pk, kk, dk = _m.prep(color, (-1, 3), np.float32, device)
+    n = 0 if kx is None else int(kx.shape[0])
+    for d, k, name in ((dc, kc, "cov6"), (dk, kk, "color")):
+        if d is not None and (d != dx or int(k.shape[0]) != n):
             raise RuntimeError(f"voxel_down_sample: {name} must match xyz in length and placement")
     if dx and torch is not None:
         torch.cuda.current_stream(device).synchronize()

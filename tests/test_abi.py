@@ -51,6 +51,66 @@ def test_version_and_no_device_behaviour(hip_lib):
         icp.normals_from_cov(np.zeros((3, 6), np.float32))
 
 
+def _one_shot_calls():
+    """name -> call(L) of every stateless entry point, with small valid non-empty host arrays (device 0, null stream)"""
+    from gaussiansplattingregistration_amd import _lib
+    n = 8
+    rng = np.random.default_rng(0)
+    xyz = rng.random((n, 3)).astype(np.float32)
+    nrm32 = np.tile(np.float32([0, 0, 1]), (n, 1))
+    nrm64 = nrm32.astype(np.float64)
+    cov32 = np.tile(np.float32([1, 0, 0, 1, 0, 1]), (n, 1))
+    feat = rng.random((n, 33))
+    p = lambda a: a.ctypes.data
+    keep = []                                   # the output arrays, alive as long as the calls
+
+    def zeros(dtype):
+        def make(*shape):
+            keep.append(np.zeros(shape, dtype))
+            return p(keep[-1])
+        return make
+    f32, f64, i32 = zeros(np.float32), zeros(np.float64), zeros(np.int32)
+    cands = np.tile(np.float32([0, 0, 1, 0, 0, 0, 1, 1]), (2, 1))
+    best, nv, nc, um, h = C.c_int32(-1), C.c_int64(0), C.c_int64(0), C.c_int32(0), C.c_void_p()
+    offsets = (C.c_int32 * 15)(*[4 * i for i in range(15)])
+    corres = np.stack([np.arange(n), np.arange(n)], 1).astype(np.int32)
+    P, R = _lib.RansacParams(), _lib.RansacResult()
+    P.kind, P.ransac_n, P.max_corr, P.max_iteration, P.confidence, P.batch = 0, 3, 0.5, 10, 0.999, 8
+    return {
+        "gsr_plane_score": lambda L: L.gsr_plane_score(p(xyz), p(nrm32), n, p(cands), 2, 0.1, 0.5, i32(2), i32(n), C.byref(best), 0, 0, None),
+        "gsr_decompose_cov": lambda L: L.gsr_decompose_cov(p(cov32), n, _lib.GSR_DECOMP_EXACT, f32(n, 3), f32(n, 4), f32(n, 9), 0, 0, None),
+        "gsr_ply_unpack": lambda L: L.gsr_ply_unpack(f32(n, 15), n, 60, offsets, 0, f32(n, 3), f32(n, 3), None, f32(n), f32(n, 3), f32(n, 4),
+                                                     f32(n, 6), 0, None),
+        "gsr_normals_from_cov": lambda L: L.gsr_normals_from_cov(p(cov32), n, f64(n, 3), 0, 0, None),
+        "gsr_cov_from_normals": lambda L: L.gsr_cov_from_normals(p(nrm64), n, 1e-3, f64(n, 6), 0, 0, None),
+        "gsr_normals_knn": lambda L: L.gsr_normals_knn(p(xyz), n, 5, f64(n, 3), 0, 0, None),
+        "gsr_voxel_down_sample": lambda L: L.gsr_voxel_down_sample(0, None, p(xyz), None, None, n, 0.25, 0, C.byref(h), C.byref(nv)),
+        "gsr_hybrid_search": lambda L: L.gsr_hybrid_search(p(xyz), n, 0.5, 4, i32(n, 4), i32(n), 0, 0, None),
+        "gsr_fpfh": lambda L: L.gsr_fpfh(p(xyz), p(nrm64), n, 0.5, 4, f64(n, 33), 0, 0, None),
+        "gsr_feature_match": lambda L: L.gsr_feature_match(p(feat), n, p(feat), n, 0, 3, i32(n, 2), C.byref(nc), C.byref(um), None, None, 0, 0, None),
+        "gsr_ransac_correspondence": lambda L: L.gsr_ransac_correspondence(p(xyz), n, p(xyz), n, None, None, p(corres), n, C.byref(P), C.byref(R),
+                                                                           0, 0, None),
+    }
+
+
+ONE_SHOT_ENTRY_POINTS = ["gsr_plane_score", "gsr_decompose_cov", "gsr_ply_unpack", "gsr_normals_from_cov", "gsr_cov_from_normals", "gsr_normals_knn",
+                         "gsr_voxel_down_sample", "gsr_hybrid_search", "gsr_fpfh", "gsr_feature_match", "gsr_ransac_correspondence"]
+
+
+@pytest.mark.parametrize("name", ONE_SHOT_ENTRY_POINTS)
+def test_one_shot_entry_points_without_a_device(hip_lib, name):
+    """Every stateless entry point goes through the same device check: valid host arrays and no visible device give
+    GSR_E_NO_DEVICE and a message that names the function."""
+    import torch
+    if torch.cuda.is_available():
+        pytest.skip("a GPU is visible here")
+    calls = _one_shot_calls()
+    assert sorted(calls) == sorted(ONE_SHOT_ENTRY_POINTS)
+    assert calls[name](hip_lib) == -3                                  # GSR_E_NO_DEVICE
+    msg = hip_lib.gsr_last_error()
+    assert b"no HIP device" in msg and name.encode() in msg, msg
+
+
 def test_product_never_imports_the_oracle():
     """oracle/ is test infrastructure: no module of the product package may reference it."""
     pkg = os.path.join(ROOT, "gaussiansplattingregistration_amd")

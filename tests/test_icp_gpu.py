@@ -440,6 +440,9 @@ def test_new_entry_points_error_behaviour():
         assert L.gsr_icp_register_multiscale(c._h, -1, None, 0, T0.ctypes.data, 0, 0, 0.0, 1e-6, 1e-6, None, out.ctypes.data) < 0
         r = c.register_clouds(xyz, xyz, None, 0.3, T0, 0, 0, 0.0, 1e-6, 1e-6, 5)                                                       # ... and a good call
         assert r["fitness"] == 1.0 and np.allclose(r["transformation"], np.eye(4), atol=1e-12)
+    nrm = np.empty((200, 3))
+    assert L.gsr_normals_knn(xyz.ctypes.data, 200, 10, nrm.ctypes.data, 0, 99, None) < 0                                               # a stateless call: no device 99
+    assert b"gsr_normals_knn" in L.gsr_last_error() and b"out of range" in L.gsr_last_error()
     cloud = synth.make_cloud(2000, seed=1, sh_degree=1, h=0.4)
     with hem.HemMixture() as m:
         reports = (_lib.HemLevelReport * 2)()
