@@ -116,6 +116,8 @@ SIGNATURES = {
     "gsr_fpfh": (_i32, [_vp, _vp, _i64, _f64, _i32, _vp, _i32, _i32, _vp]),
     "gsr_feature_match": (_i32, [_vp, _i64, _vp, _i64, _i32, _i32, _vp, C.POINTER(_i64), C.POINTER(_i32), _vp, _vp, _i32, _i32, _vp]),
     "gsr_ransac_correspondence": (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _i32, _i32, _vp]),
+    "gsr_fgr_tuple_test": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, C.POINTER(_i64), C.POINTER(_i64), _i32, _i32, _vp]),
+    "gsr_fgr_optimize": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i32, _i32, _vp]),
 }
 # private test hooks (csrc/gsr_test_hooks.h): exported by the library, not part of the public header
 TEST_HOOKS = {
@@ -158,6 +160,19 @@ class RansacResult(C.Structure):
     """gsr_ransac_result (include/gsr_hip.h)."""
     _fields_ = [("T", C.c_double * 16), ("fitness", C.c_double), ("inlier_rmse", C.c_double), ("best_index", C.c_int64),
                 ("n_evaluated", C.c_int64), ("n_valid", C.c_int64), ("exit_index", C.c_int64)]
+
+
+class FgrOptions(C.Structure):
+    """gsr_fgr_options (include/gsr_hip.h)."""
+    _fields_ = [("division_factor", C.c_double), ("use_absolute_scale", C.c_int32), ("decrease_mu", C.c_int32),
+                ("maximum_correspondence_distance", C.c_double), ("iteration_number", C.c_int32), ("maximum_tuple_count", C.c_int32),
+                ("tuple_scale", C.c_double), ("tuple_test", C.c_int32), ("batch", C.c_int32), ("seed", C.c_uint64)]
+
+
+class FgrResult(C.Structure):
+    """gsr_fgr_result (include/gsr_hip.h)."""
+    _fields_ = [("T", C.c_double * 16), ("n_corres", C.c_int64), ("n_reciprocal", C.c_int64), ("n_trials", C.c_int64),
+                ("n_tuples", C.c_int64), ("iterations", C.c_int32), ("host_waits", C.c_int32), ("scale_global", C.c_double)]
 
 
 GSR_CHECK_EDGE_LENGTH = 0

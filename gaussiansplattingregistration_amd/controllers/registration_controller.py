@@ -1,9 +1,10 @@
-"""Headless ``RegistrationController`` (reference ``src/controllers/registration_controller.py:24-28,47-68,93-120,145-163``)."""
+"""Headless ``RegistrationController`` (reference ``src/controllers/registration_controller.py:24-28,47-91,93-120,145-163``)."""
 from __future__ import annotations
 
 import numpy as np
 
-from ..workers.registrators import LocalRegistrator, MultiScaleRegistratorMixture, MultiScaleRegistratorVoxel, RANSACRegistrator
+from ..workers.registrators import (FGRRegistrator, LocalRegistrator, MultiScaleRegistratorMixture, MultiScaleRegistratorVoxel,
+                                    RANSACRegistrator)
 
 
 class RegistrationController:
@@ -29,6 +30,17 @@ class RegistrationController:
         result = worker.run()
         self.handle_registration_result_global(result)
         return result
+
+    def execute_fgr_registration_normal(self, params):          # :70-74, 84-91
+        repo = self.data_repository
+        pc1 = repo.pc_open3d_list_first[repo.current_index]
+        pc2 = repo.pc_open3d_list_second[repo.current_index]
+        worker = FGRRegistrator(pc1, pc2, self.ui_repository.transformation_matrix, params)
+        result = worker.run()
+        self.handle_registration_result_global(result)
+        return result
+
+    execute_fgr_registration = execute_fgr_registration_normal
 
     def execute_multiscale_registration(self, use_corresponding, sparse_first, sparse_second, registration_type,
                                         relative_fitness, relative_rmse, voxel_values, iter_values, rejection_type, k_value,

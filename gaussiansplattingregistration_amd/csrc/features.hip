@@ -188,18 +188,7 @@ int32_t nn_rows(OneShot& os, const double* a, int64_t na, const double* b, int64
 }  // namespace
 
 // ---- RANSAC ------------------------------------------------------------------------------------------------------------------
-__host__ __device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
-// row j of hypothesis k among m correspondences (the formula of include/gsr_hip.h)
-__host__ __device__ __forceinline__ uint32_t ransac_draw(uint64_t seed, uint64_t k, uint32_t j, uint32_t m) {
-    const uint64_t z = splitmix64(seed ^ splitmix64(k * 64ull + (uint64_t)j));
-    return (uint32_t)(((z >> 32) * (uint64_t)m) >> 32);
-}
-
+// splitmix64 / ransac_draw: gsr_features.h (csrc/fgr.hip draws its triples with the same function)
 struct RansacDev {
     int kind, n, n_checkers, has_normals;
     int ck[4];

@@ -1,8 +1,10 @@
-"""Global registration on the GPU: ctypes front of ``gsr_hybrid_search``, ``gsr_fpfh``, ``gsr_feature_match`` and
-``gsr_ransac_correspondence`` (``include/gsr_hip.h``, ``csrc/features.hip``).
+"""Global registration on the GPU: ctypes front of ``gsr_hybrid_search``, ``gsr_fpfh``, ``gsr_feature_match``,
+``gsr_ransac_correspondence`` (``csrc/features.hip``), ``gsr_fgr_tuple_test`` and ``gsr_fgr_optimize`` (``csrc/fgr.hip``), all
+declared in ``include/gsr_hip.h``.
 
-Reference behaviour: ``compute_fpfh_feature`` and ``registration_ransac_based_on_feature_matching`` of Open3D 0.16.0 as the
-reference's ``src/utils/global_registration_util.py`` calls them.  Inputs are numpy arrays or cuda tensors (all on the host or
+Reference behaviour: ``compute_fpfh_feature``, ``registration_ransac_based_on_feature_matching`` and
+``registration_fgr_based_on_feature_matching`` of Open3D 0.16.0 as the reference's ``src/utils/global_registration_util.py`` calls
+them.  Inputs are numpy arrays or cuda tensors (all on the host or
 all on the device); ``as_torch`` returns cuda tensors the library wrote in place.
 """
 from __future__ import annotations
@@ -19,7 +21,8 @@ try:
 except Exception:  # pragma: no cover
     torch = None
 
-__all__ = ["hybrid_search", "fpfh", "feature_match", "ransac_correspondence", "KIND_POINT_TO_POINT", "KIND_POINT_TO_PLANE",
+__all__ = ["hybrid_search", "fpfh", "feature_match", "ransac_correspondence", "fgr_tuple_test", "fgr_optimize", "KIND_POINT_TO_POINT",
+           "KIND_POINT_TO_PLANE",
            "CHECK_EDGE_LENGTH", "CHECK_DISTANCE", "CHECK_NORMAL"]
 
 KIND_POINT_TO_POINT = 0
@@ -114,3 +117,47 @@ def ransac_correspondence(src_xyz, tgt_xyz, corres, max_corr, kind=KIND_POINT_TO
                                            C.c_void_p(_m.stream_ptr(device, on))), "gsr_ransac_correspondence")
     return {"transformation": np.array(R.T[:], dtype=np.float64).reshape(4, 4), "fitness": R.fitness, "inlier_rmse": R.inlier_rmse,
             "best_index": int(R.best_index), "n_evaluated": int(R.n_evaluated), "n_valid": int(R.n_valid), "exit_index": int(R.exit_index)}
+
+
+def _fgr_options(division_factor=1.4, use_absolute_scale=False, decrease_mu=False, maximum_correspondence_distance=0.025,
+                 iteration_number=64, tuple_scale=0.95, maximum_tuple_count=1000, tuple_test=True, seed=0, batch=0):
+    O = _lib.FgrOptions()
+    O.division_factor, O.use_absolute_scale, O.decrease_mu = float(division_factor), int(bool(use_absolute_scale)), int(bool(decrease_mu))
+    O.maximum_correspondence_distance, O.iteration_number = float(maximum_correspondence_distance), int(iteration_number)
+    O.maximum_tuple_count, O.tuple_scale, O.tuple_test = int(maximum_tuple_count), float(tuple_scale), int(bool(tuple_test))
+    O.batch, O.seed = int(batch), int(seed) & ((1 << 64) - 1)
+    return O
+
+
+def fgr_tuple_test(src_xyz, tgt_xyz, corres, tuple_scale=0.95, maximum_tuple_count=1000, seed=0, batch=0, device=0):
+    """The tuple test of Fast Global Registration over ``corres (m, 2)`` (``gsr_fgr_tuple_test``): ``(pairs (3 * accepted, 2) int32,
+    n_trials)``, the accepted triples in trial order, at most ``maximum_tuple_count`` of them.  ``batch`` (0: the library's default)
+    is a speed knob only."""
+    L = _lib.load(require_device=True)
+    on = _m.is_cuda(src_xyz)
+    ps, ks, ns = _rows(src_xyz, 3, np.float32, device, on)
+    pt, kt, nt = _rows(tgt_xyz, 3, np.float32, device, on)
+    pc, kc, m = _rows(corres, 2, np.int32, device, on)
+    O = _fgr_options(tuple_scale=tuple_scale, maximum_tuple_count=maximum_tuple_count, seed=seed, batch=batch)
+    out, po = _m.out((3 * max(int(maximum_tuple_count), 0), 2), np.int32, device, on)
+    n_out, n_trials = C.c_int64(0), C.c_int64(0)
+    _lib.check(L.gsr_fgr_tuple_test(ps, ns, pt, nt, pc, m, C.byref(O), po, C.byref(n_out), C.byref(n_trials), 1 if on else 0, int(device),
+                                    C.c_void_p(_m.stream_ptr(device, on))), "gsr_fgr_tuple_test")
+    return out[: int(n_out.value)], int(n_trials.value)
+
+
+def fgr_optimize(src_xyz, tgt_xyz, corres, division_factor=1.4, use_absolute_scale=False, decrease_mu=False,
+                 maximum_correspondence_distance=0.025, iteration_number=64, device=0):
+    """Normalisation, graduated-non-convexity optimisation and the way back of Fast Global Registration over ``corres (m, 2)``
+    (``gsr_fgr_optimize``).  Returns a dict: transformation (source -> target), n_corres, iterations, scale_global, host_waits."""
+    L = _lib.load(require_device=True)
+    on = _m.is_cuda(src_xyz)
+    ps, ks, ns = _rows(src_xyz, 3, np.float32, device, on)
+    pt, kt, nt = _rows(tgt_xyz, 3, np.float32, device, on)
+    pc, kc, m = _rows(corres, 2, np.int32, device, on)
+    O = _fgr_options(division_factor, use_absolute_scale, decrease_mu, maximum_correspondence_distance, iteration_number)
+    R = _lib.FgrResult()
+    _lib.check(L.gsr_fgr_optimize(ps, ns, pt, nt, pc, m, C.byref(O), C.byref(R), 1 if on else 0, int(device),
+                                  C.c_void_p(_m.stream_ptr(device, on))), "gsr_fgr_optimize")
+    return {"transformation": np.array(R.T[:], dtype=np.float64).reshape(4, 4), "n_corres": int(R.n_corres), "iterations": int(R.iterations),
+            "scale_global": float(R.scale_global), "host_waits": int(R.host_waits)}

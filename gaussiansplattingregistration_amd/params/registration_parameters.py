@@ -1,4 +1,4 @@
-"""Registration parameters: field names and defaults of the reference's ``src/params/registration_parameters.py:7-15,31-40``."""
+"""Registration parameters: field names and defaults of the reference's ``src/params/registration_parameters.py:7-40``."""
 from dataclasses import dataclass, field
 from typing import List
 
@@ -45,4 +45,19 @@ class RANSACRegistrationParams:
     checkers: list = field(default_factory=list)
     max_iteration: int = 100000
     confidence: float = 0.999
+    seed: int = 0
+
+
+@dataclass
+class FGRRegistrationParams:
+    """The reference's fields and defaults, plus ``seed``: the tuple test draws with the counter-based sampler and is deterministic."""
+    voxel_size: float = 0.05
+    division_factor: float = 1.4
+    use_absolute_scale: bool = False
+    decrease_mu: bool = False
+    maximum_correspondence: float = 0.025
+    max_iterations: int = 64
+    tuple_scale: float = 0.95
+    max_tuple_count: int = 1000
+    tuple_test: bool = True
     seed: int = 0

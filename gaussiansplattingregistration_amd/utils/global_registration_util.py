@@ -1,5 +1,5 @@
 """Global registration: the reference's ``src/utils/global_registration_util.py`` on the GPU (``features.py``,
-``csrc/features.hip``), with Open3D-named shims for what it reaches through open3d==0.16.0.
+``csrc/features.hip``, ``csrc/fgr.hip``), with Open3D-named shims for what it reaches through open3d==0.16.0.
 
 ``preprocess_point_cloud`` follows the project's conventions: ``PointCloud.voxel_down_sample`` then ``estimate_normals()`` (the
 averaged covariances of a splat cloud, KNN-30 without covariances -- so the reference's normal radius ``2 * voxel`` is inert, as
@@ -7,7 +7,8 @@ for the voxel multiscale path), then every normal is turned towards the cloud's 
 orientation is a deviation from the reference, whose normals keep the eigen-solver's arbitrary sign: FPFH is not invariant under a
 normal's sign, and with arbitrary signs only ~7 % of the mutual feature matches of the project's test scene are right (57 % oriented,
 DESIGN.md section 12).  The centroid moves with the cloud, so the orientation is the same for a cloud and its rigidly moved copy.
-FGR (``do_fgr_registration``) is not part of this backend.
+Both methods of the reference's tab are here: ``do_ransac_registration`` and ``do_fgr_registration`` (Fast Global Registration;
+its tuple test draws with the library's counter-based sampler, so it is deterministic for a given ``seed``).
 """
 from __future__ import annotations
 
@@ -16,6 +17,7 @@ from enum import Enum
 import numpy as np
 
 from .. import features as _F
+from .. import icp as _icp
 
 try:
     import torch
@@ -246,4 +248,80 @@ def do_ransac_registration(point_cloud_first, point_cloud_second, params):
         params.checkers,
         RANSACConvergenceCriteria(params.max_iteration, params.confidence),
         seed=getattr(params, "seed", 0))
+    return result
+
+
+class FastGlobalRegistrationOption:
+    """``o3d.pipelines.registration.FastGlobalRegistrationOption`` (Open3D 0.16): its eight fields in its positional order, plus the
+    keywords ``seed`` (of the tuple test's counter-based draws) and ``batch`` (trials per device batch, a speed knob only)."""
+
+    def __init__(self, division_factor=1.4, use_absolute_scale=False, decrease_mu=False, maximum_correspondence_distance=0.025,
+                 iteration_number=64, tuple_scale=0.95, maximum_tuple_count=1000, tuple_test=True, *, seed=0, batch=0):
+        self.division_factor, self.use_absolute_scale, self.decrease_mu = float(division_factor), bool(use_absolute_scale), bool(decrease_mu)
+        self.maximum_correspondence_distance, self.iteration_number = float(maximum_correspondence_distance), int(iteration_number)
+        self.tuple_scale, self.maximum_tuple_count, self.tuple_test = float(tuple_scale), int(maximum_tuple_count), bool(tuple_test)
+        self.seed, self.batch = int(seed), int(batch)
+
+
+def evaluate_registration(source, target, max_correspondence_distance, transformation):
+    """``o3d.pipelines.registration.evaluate_registration``: the nearest target point of every transformed source point through the
+    ICP context's search; a pair is an inlier iff its squared distance is below ``max_correspondence_distance ** 2`` (the ICP's
+    rule).  ``fitness = inliers / |source|``, ``inlier_rmse``, ``correspondence_set`` (source row, target row) in source order."""
+    T = np.asarray(transformation, np.float64).reshape(4, 4)
+    ns = int(source.xyz32.shape[0])
+    if ns == 0 or int(target.xyz32.shape[0]) == 0 or not (max_correspondence_distance > 0.0):
+        return RegistrationResult(T)
+    with _icp.IcpContext(device=source.device_index) as c:
+        c.set_target(target.xyz32, None, max_correspondence_distance)
+        c.set_source(source.xyz32)
+        idx, d2 = c.correspondences(T)
+    inl = idx >= 0
+    good = int(inl.sum())
+    rmse = float(np.sqrt(d2[inl].sum() / good)) if good else 0.0
+    cs = np.stack([np.flatnonzero(inl), idx[inl]], axis=1).astype(np.int32)
+    return RegistrationResult(T, good / ns, rmse, cs)
+
+
+def registration_fgr_based_on_correspondence(source, target, corres, option=None):
+    """Fast Global Registration over given correspondences ``(m, 2)`` (source row, target row): the tuple test (when
+    ``option.tuple_test``), the optimisation, then ``evaluate_registration`` at ``option.maximum_correspondence_distance``."""
+    o = option or FastGlobalRegistrationOption()
+    dev = source.device_index
+    n_trials, n_tuples = 0, 0
+    used = corres
+    if o.tuple_test:
+        used, n_trials = _F.fgr_tuple_test(source.xyz32, target.xyz32, corres, o.tuple_scale, o.maximum_tuple_count, seed=o.seed,
+                                           batch=o.batch, device=dev)
+        n_tuples = int(used.shape[0]) // 3
+    r = _F.fgr_optimize(source.xyz32, target.xyz32, used, o.division_factor, o.use_absolute_scale, o.decrease_mu,
+                        o.maximum_correspondence_distance, o.iteration_number, device=dev)
+    res = evaluate_registration(source, target, o.maximum_correspondence_distance, r["transformation"])
+    res.info = {"n_corres": r["n_corres"], "n_reciprocal": int(corres.shape[0]), "n_trials": n_trials, "n_tuples": n_tuples,
+                "iterations": r["iterations"], "scale_global": r["scale_global"], "host_waits": r["host_waits"]}
+    return res
+
+
+def registration_fgr_based_on_feature_matching(source, target, source_feature, target_feature, option=None):
+    """``o3d.pipelines.registration.registration_fgr_based_on_feature_matching`` (Open3D 0.16): exact feature 1-NN both ways, the
+    reciprocal pairs only (no fall-back to the one-way set), then ``registration_fgr_based_on_correspondence``."""
+    corres, _ = _F.feature_match(source_feature.rows, target_feature.rows, mutual=True, ransac_n=0, device=source.device_index)
+    return registration_fgr_based_on_correspondence(source, target, corres, option)
+
+
+def do_fgr_registration(point_cloud_first, point_cloud_second, registration_params):
+    source_down, source_fpfh = preprocess_point_cloud(point_cloud_first, registration_params.voxel_size)
+    target_down, target_fpfh = preprocess_point_cloud(point_cloud_second, registration_params.voxel_size)
+
+    options = FastGlobalRegistrationOption(registration_params.division_factor,
+                                           registration_params.use_absolute_scale,
+                                           registration_params.decrease_mu,
+                                           registration_params.maximum_correspondence,
+                                           registration_params.max_iterations,
+                                           registration_params.tuple_scale,
+                                           registration_params.max_tuple_count,
+                                           registration_params.tuple_test,
+                                           seed=getattr(registration_params, "seed", 0))
+
+    result = registration_fgr_based_on_feature_matching(source_down, target_down, source_fpfh, target_fpfh, options)
+
     return result

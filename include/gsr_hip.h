@@ -535,6 +535,65 @@ int32_t gsr_ransac_correspondence(const float* src_xyz, int64_t ns, const float*
                                   const double* tgt_normals, const int32_t* corres, int64_t m, const gsr_ransac_params* params,
                                   gsr_ransac_result* out, int32_t on_device, int32_t device, void* stream);
 
+/* Fast Global Registration (Zhou, Park, Koltun 2016) as Open3D 0.16 FastGlobalRegistration.cpp runs it, the second method of the
+ * reference's "Global" tab (do_fgr_registration).  csrc/fgr.hip; DESIGN.md section 12.  The matching in front of it is
+ * gsr_feature_match with mutual = 1 and ransac_n = 0 (the reciprocal pairs, no fall-back to the one-way set); the evaluation behind
+ * it is the ICP context's (gsr_icp_set_target / gsr_icp_set_source / gsr_icp_correspondences).  The fields of gsr_fgr_options are
+ * Open3D's FastGlobalRegistrationOption plus seed and batch. */
+typedef struct gsr_fgr_options {
+    double division_factor;                  /* mu /= division_factor while it is annealed (1.4) */
+    int32_t use_absolute_scale;              /* 0: both clouds are divided by scale_global, mu starts at 1; 1: not divided, mu starts at the scale */
+    int32_t decrease_mu;                     /* anneal mu every 4th iteration while mu > maximum_correspondence_distance */
+    double maximum_correspondence_distance;  /* (0.025) the floor of the annealing; compared with mu as Open3D does: see below */
+    int32_t iteration_number;                /* (64) */
+    int32_t maximum_tuple_count;             /* (1000) accepted triples kept */
+    double tuple_scale;                      /* (0.95) similarity s of the tuple test */
+    int32_t tuple_test;                      /* read by callers only: gsr_fgr_tuple_test always tests, gsr_fgr_optimize never does */
+    int32_t batch;                           /* trials per device batch; <= 0: 65536.  A speed knob only: the result does not depend on it */
+    uint64_t seed;                           /* of draw(seed, k, j, m) */
+} gsr_fgr_options;
+typedef struct gsr_fgr_result {
+    double T[16];              /* row-major, source -> target (what registration_ransac_* returns); identity below 10 pairs */
+    int64_t n_corres;          /* pairs the optimiser ran on (its m) */
+    int64_t n_reciprocal;      /* the caller's bookkeeping of the stages in front: gsr_fgr_optimize leaves these three untouched */
+    int64_t n_trials;
+    int64_t n_tuples;
+    int32_t iterations;        /* iterations that solved (iteration_number unless a solve failed or m < 10) */
+    int32_t host_waits;        /* stream waits of the call: 1 */
+    double scale_global;       /* what the coordinates were divided by */
+} gsr_fgr_result;
+/* The tuple test over m correspondences (source row, target row).  Trial k = 0 .. 100 * m - 1 draws three rows
+ *     r_j = draw(seed, k, j, m), j = 0, 1, 2     (the draw of gsr_ransac_correspondence above; unsorted, repeats allowed)
+ * and with (i_j, t_j) = corres[r_j] forms, in float64 from the float32 coordinates as given (no normalisation),
+ *     li_0 = |P[i_0] - P[i_1]|, li_1 = |P[i_1] - P[i_2]|, li_2 = |P[i_2] - P[i_0]|,  lj_* likewise on Q[t_*],
+ *     |d| = sqrt((dx * dx + dy * dy) + dz * dz)  (no fused multiply-add).
+ * It is accepted iff  li_e * s < lj_e  and  lj_e < li_e / s  for e = 0, 1, 2  (s = tuple_scale; a repeated row gives a zero edge
+ * and fails).  The accepted trials are taken in trial order until maximum_tuple_count of them; each writes its three pairs
+ * (i_j, t_j), j = 0, 1, 2, to corres_out[(3 * a + j) * 2 ..].  *n_out = pairs written (3 * accepted); *n_trials = trials the
+ * serial loop visits: index of the last accepted trial + 1 when the count is reached, else 100 * m.  This is Open3D's loop with
+ * a counter-based generator in place of its random engine; it does not depend on options->batch.
+ * corres_out holds 3 * maximum_tuple_count * 2 int32.  xyz float32; the arrays host or device as on_device says, the two counts
+ * host.  A row outside [0, ns) x [0, nt) is GSR_E_INVALID (device arrays are checked by the kernel: nothing is read out of bounds). */
+int32_t gsr_fgr_tuple_test(const float* src_xyz, int64_t ns, const float* tgt_xyz, int64_t nt, const int32_t* corres, int64_t m,
+                           const gsr_fgr_options* options, int32_t* corres_out, int64_t* n_out, int64_t* n_trials, int32_t on_device,
+                           int32_t device, void* stream);
+/* Normalisation, the graduated-non-convexity optimisation and the way back, all in float64:
+ *   normalise   each cloud minus its own mean; scale = the largest norm of a centred point of either cloud; use_absolute_scale:
+ *               scale_global = 1, mu = scale; else scale_global = scale, mu = 1; points divided by scale_global.
+ *   optimise    m < 10: T = identity.  Else p_c / q_c = normalised source / target point of pair c, trans = I, and
+ *               iteration_number times:  r = p - q,  l = (mu / (r.r + mu))^2,  rows J0 = [0, -qz, qy, -1, 0, 0],
+ *               J1 = [qz, 0, -qx, 0, -1, 0], J2 = [-qy, qx, 0, 0, 0, -1] with residuals rx, ry, rz;  JTJ = sum l J^T J,
+ *               JTr = sum l J^T r;  (-JTJ) x = JTr by LDL^T with diagonal pivoting;  delta = [Rz(x2) Ry(x1) Rx(x0) | x3..5];
+ *               trans = delta trans;  q_c = delta q_c;  then, if decrease_mu and itr % 4 == 0 and
+ *               mu > maximum_correspondence_distance,  mu /= division_factor.  (mu lives in normalised units and is compared with
+ *               a distance in the caller's units: Open3D's behaviour, kept.)  A solve with a non-finite solution (zero or
+ *               non-finite pivot) ends the loop with the transform reached so far.
+ *   way back    R, t of trans:  M = [R | -R mean_t + t scale_global + mean_s]  aligns the target with the source;  T = M^-1.
+ * Every sum is taken in a fixed order without atomics: the same inputs give the same bits.  The iterations are enqueued without
+ * the host: the call waits for the stream once.  Arguments as for gsr_fgr_tuple_test; ns, nt > 0. */
+int32_t gsr_fgr_optimize(const float* src_xyz, int64_t ns, const float* tgt_xyz, int64_t nt, const int32_t* corres, int64_t m,
+                         const gsr_fgr_options* options, gsr_fgr_result* result, int32_t on_device, int32_t device, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

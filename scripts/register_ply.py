@@ -29,8 +29,11 @@ def main():
     ap.add_argument("--k", type=float, default=0.0)
     ap.add_argument("--voxel", action="store_true", help="voxel multiscale path instead of HEM mixtures")
     ap.add_argument("--hem", type=float, nargs=4, default=[3.0, 3.0, 2.5, 1.0], metavar=("RHO", "DELTA", "KAPPA", "TAU"))
-    ap.add_argument("--global-ransac", type=float, metavar="VOXEL", help="global registration first (FPFH + RANSAC at this voxel size, the "
+    method = ap.add_mutually_exclusive_group()
+    method.add_argument("--global-ransac", type=float, metavar="VOXEL", help="global registration first (FPFH + RANSAC at this voxel size, the "
                     "reference's Global tab); its pose is the multiscale ICP's initial transform")
+    method.add_argument("--global-fgr", type=float, metavar="VOXEL", help="global registration first by Fast Global Registration (FPFH + FGR at "
+                    "this voxel size, the tab's other method); its pose is the multiscale ICP's initial transform")
     ap.add_argument("--ransac-iters", type=int, default=100000, help="RANSAC hypotheses (max_iteration) of --global-ransac")
     ap.add_argument("--out")
     a = ap.parse_args()
@@ -79,6 +82,13 @@ def main():
         g = rc.execute_ransac_registration_normal(gp)
         print(f"global RANSAC: fitness {g.fitness:.4f}  rmse {g.inlier_rmse:.6f}  hypotheses {g.info.get('n_evaluated')}  "
               f"{time.perf_counter() - tg:.3f} s")
+    if a.global_fgr:
+        from gaussiansplattingregistration_amd.params.registration_parameters import FGRRegistrationParams
+        v = a.global_fgr
+        tg = time.perf_counter()
+        g = rc.execute_fgr_registration_normal(FGRRegistrationParams(voxel_size=v, maximum_correspondence=1.5 * v))
+        print(f"global FGR: fitness {g.fitness:.4f}  rmse {g.inlier_rmse:.6f}  reciprocal pairs {g.info.get('n_reciprocal')}  "
+              f"tuples {g.info.get('n_tuples')} of {g.info.get('n_trials')} trials  {time.perf_counter() - tg:.3f} s")
     res = rc.execute_multiscale_registration(False, "", "", rtype, 1e-6, 1e-6, a.max_corr, a.iters, loss, a.k, not a.voxel)
     t3 = time.perf_counter()
     if res is None:
