@@ -189,9 +189,358 @@ __global__ __launch_bounds__(256) void k_plane_mask(int64_t n, const float* __re
         mask[i] = plane_inlier(c, xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], nrm[3 * i], nrm[3 * i + 1], nrm[3 * i + 2], dist_thr, nrm_thr) ? 1 : 0;
 }
 
+// ---- rigid motion of a splat model in one pass (gsr_model_transform) ---------------------------------------------------------
+// The last stage of the pipeline (GaussianModel.transform_gaussian_model / get_merged_gaussian_point_clouds): positions,
+// covariances, orientation quaternions and -- what the torch chain never did -- the view-dependent colour, i.e. the SH-rest
+// coefficients, which transform band by band with the matrices D_1 (3x3), D_2 (5x5), D_3 (7x7) of gsr_sh_rotation.
+//
+// SH basis = the one 3DGS evaluates (its published forward pass), coefficient k of _features_rest[n, k, c]:
+//   band 1: -C1 y, C1 z, -C1 x
+//   band 2: C2[0] xy, C2[1] yz, C2[2] (2zz - xx - yy), C2[3] xz, C2[4] (xx - yy)
+//   band 3: C3[0] y(3xx - yy), C3[1] xyz, C3[2] y(4zz - xx - yy), C3[3] z(2zz - 3xx - 3yy), C3[4] x(4zz - xx - yy), C3[5] z(xx - yy),
+//           C3[6] x(xx - 3yy)
+// D_l is defined by  basis_l(R d) . (D_l c) = basis_l(d) . c  for every direction d and coefficient vector c: the rotated splat
+// seen from the rotated direction shows the original colour.  The basis is orthonormal on the sphere, so D_l is orthogonal and
+// basis_l(R d) = D_l basis_l(d); gsr_sh_rotation fits exactly that by least squares over a fixed set of directions (host, float64).
+static const double SH_C1 = 0.4886025119029199;
+static const double SH_C2[5] = {1.0925484305920792, -1.0925484305920792, 0.31539156525252005, -1.0925484305920792, 0.5462742152960396};
+static const double SH_C3[7] = {-0.5900435899266435, 2.890611442640554, -0.4570457994644658, 0.3731763325901154, -0.4570457994644658,
+                                1.445305721320277, -0.5900435899266435};
+
+// the 15 rest basis functions at the unit direction (x, y, z), band after band
+static void sh_basis_rest(double x, double y, double z, double* b) {
+    const double xx = x * x, yy = y * y, zz = z * z;
+    b[0] = -SH_C1 * y; b[1] = SH_C1 * z; b[2] = -SH_C1 * x;
+    b[3] = SH_C2[0] * x * y; b[4] = SH_C2[1] * y * z; b[5] = SH_C2[2] * (2.0 * zz - xx - yy); b[6] = SH_C2[3] * x * z; b[7] = SH_C2[4] * (xx - yy);
+    b[8] = SH_C3[0] * y * (3.0 * xx - yy); b[9] = SH_C3[1] * x * y * z; b[10] = SH_C3[2] * y * (4.0 * zz - xx - yy);
+    b[11] = SH_C3[3] * z * (2.0 * zz - 3.0 * xx - 3.0 * yy); b[12] = SH_C3[4] * x * (4.0 * zz - xx - yy); b[13] = SH_C3[5] * z * (xx - yy);
+    b[14] = SH_C3[6] * x * (xx - 3.0 * yy);
+}
+
+// X <- A^-1 X for a well-conditioned m x m system with m right-hand sides (Gaussian elimination, partial pivoting); false if singular
+static bool solve_in_place(int m, double A[7][7], double X[7][7]) {
+    for (int c = 0; c < m; ++c) {
+        int piv = c;
+        for (int r = c + 1; r < m; ++r) if (fabs(A[r][c]) > fabs(A[piv][c])) piv = r;
+        if (!(fabs(A[piv][c]) > 1e-12)) return false;
+        if (piv != c) for (int k = 0; k < m; ++k) { double t = A[c][k]; A[c][k] = A[piv][k]; A[piv][k] = t; t = X[c][k]; X[c][k] = X[piv][k]; X[piv][k] = t; }
+        for (int r = 0; r < m; ++r) {
+            if (r == c) continue;
+            const double f = A[r][c] / A[c][c];
+            if (f == 0.0) continue;
+            for (int k = 0; k < m; ++k) { A[r][k] -= f * A[c][k]; X[r][k] -= f * X[c][k]; }
+        }
+    }
+    for (int r = 0; r < m; ++r) for (int k = 0; k < m; ++k) X[r][k] /= A[r][r];
+    return true;
+}
+
+// the rotation matrices of the three rest bands in float32, as the kernel takes them BY VALUE (kernel arguments are read with
+// scalar loads: the 83 values are wave-uniform and never cost a per-lane global read)
+struct ShRot { float d1[9], d2[25], d3[49]; };
+struct Rigid { float R[9], t[3], q[4]; };          // rotation, translation, unit quaternion (w, x, y, z) of the rotation
+
+// one channel's band vector of length M = 2l + 1 at s[0], s[3], s[6], ... (coefficient-major, channel-minor) <- D s
+template <int M> __device__ __forceinline__ void sh_band(const float* __restrict__ D, float* s) {
+    float v[M], o[M];
+#pragma unroll
+    for (int j = 0; j < M; ++j) v[j] = s[3 * j];
+#pragma unroll
+    for (int i = 0; i < M; ++i) {
+        float a = D[M * i] * v[0];
+#pragma unroll
+        for (int j = 1; j < M; ++j) a = __builtin_fmaf(D[M * i + j], v[j], a);
+        o[i] = a;
+    }
+#pragma unroll
+    for (int i = 0; i < M; ++i) s[3 * i] = o[i];
+}
+
+// xyz' = R xyz + t;  cov' = R cov R^T on the six-entry form;  q' = normalise(q_R (x) q), a thread per splat
+__device__ __forceinline__ void transform_geometry(int64_t n, const Rigid& G, const float* __restrict__ xyz, const float* __restrict__ cov6,
+                                                   const float* __restrict__ rot, float* __restrict__ xyz_o, float* __restrict__ cov6_o,
+                                                   float* __restrict__ rot_o) {
+    const float* R = G.R;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const float x = xyz[3 * i], y = xyz[3 * i + 1], z = xyz[3 * i + 2];
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+            xyz_o[3 * i + r] = __builtin_fmaf(R[3 * r + 2], z, __builtin_fmaf(R[3 * r + 1], y, R[3 * r] * x)) + G.t[r];
+        const float c00 = cov6[6 * i], c01 = cov6[6 * i + 1], c02 = cov6[6 * i + 2], c11 = cov6[6 * i + 3], c12 = cov6[6 * i + 4], c22 = cov6[6 * i + 5];
+        float M[3][3];                                  // M = R cov
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            M[r][0] = __builtin_fmaf(R[3 * r + 2], c02, __builtin_fmaf(R[3 * r + 1], c01, R[3 * r] * c00));
+            M[r][1] = __builtin_fmaf(R[3 * r + 2], c12, __builtin_fmaf(R[3 * r + 1], c11, R[3 * r] * c01));
+            M[r][2] = __builtin_fmaf(R[3 * r + 2], c22, __builtin_fmaf(R[3 * r + 1], c12, R[3 * r] * c02));
+        }
+        int o = 0;
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+#pragma unroll
+            for (int c = r; c < 3; ++c)                 // (M R^T)[r][c], upper triangle in the order xx xy xz yy yz zz
+                cov6_o[6 * i + o++] = __builtin_fmaf(M[r][2], R[3 * c + 2], __builtin_fmaf(M[r][1], R[3 * c + 1], M[r][0] * R[3 * c]));
+        if (rot) {
+            const float w0 = rot[4 * i], x0 = rot[4 * i + 1], y0 = rot[4 * i + 2], z0 = rot[4 * i + 3];
+            const float w1 = G.q[0], x1 = G.q[1], y1 = G.q[2], z1 = G.q[3];
+            const float qw = w1 * w0 - x1 * x0 - y1 * y0 - z1 * z0;          // Hamilton product, motion on the left (gaussian_model.py)
+            const float qx = w1 * x0 + x1 * w0 + y1 * z0 - z1 * y0;
+            const float qy = w1 * y0 - x1 * z0 + y1 * w0 + z1 * x0;
+            const float qz = w1 * z0 + x1 * y0 - y1 * x0 + z1 * w0;
+            const float nq = sqrtf(qw * qw + qx * qx + qy * qy + qz * qz);
+            rot_o[4 * i] = qw / nq; rot_o[4 * i + 1] = qx / nq; rot_o[4 * i + 2] = qy / nq; rot_o[4 * i + 3] = qz / nq;
+        }
+    }
+}
+
+// Geometry + SH in one launch.  The SH block is the traffic (4 F bytes in and out per splat, F = 3K = 45 floats at degree 3 against 52
+// for everything else): a block's 256 rows are ONE contiguous run of 256 F floats, moved between HBM and LDS with full-width
+// coalesced accesses (dwordx4 when VEC and the arrays are 16-byte aligned, every tile start then is too); in between each lane owns
+// one row of the LDS image.  Row stride FP = F or F + 1, always odd: the 32 lanes of a ds_read_b32 / ds_write_b32 group then fall on
+// 32 different banks.  The row is transformed in place in LDS (a lane reads and writes only its own row), so the image is loaded,
+// rotated and stored with three barriers per tile and no second buffer: 256 x 45 x 4 = 45 KiB at degree 3, three blocks per CU.
+template <int K, bool VEC>
+__global__ __launch_bounds__(256) void k_model_transform(int64_t n, Rigid G, ShRot D, const float* __restrict__ xyz, const float* __restrict__ cov6,
+                                                         const float* __restrict__ rot, const float* __restrict__ sh, float* __restrict__ xyz_o,
+                                                         float* __restrict__ cov6_o, float* __restrict__ rot_o, float* __restrict__ sh_o) {
+    constexpr int F = 3 * K, FP = F | 1, ROWS = 256;
+    __shared__ float s_sh[ROWS * FP];
+    const int tid = threadIdx.x;
+    const int64_t tiles = (n + ROWS - 1) / ROWS;
+    for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {          // uniform over the block: the barriers are legal
+        const int64_t row0 = tile * ROWS;
+        const int rows = n - row0 < ROWS ? (int)(n - row0) : ROWS;
+        const int cnt = rows * F;                                               // floats of this tile, contiguous from row0 * F
+        const float* __restrict__ src = sh + row0 * F;
+        float* __restrict__ dst = sh_o + row0 * F;
+        if (VEC) {
+            const int nv = cnt >> 2;
+            for (int v = tid; v < nv; v += 256) {
+                const float4 q = reinterpret_cast<const float4*>(src)[v];
+                const float e[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+                for (int j = 0; j < 4; ++j) { const int f = 4 * v + j, r = f / F; s_sh[r * FP + (f - r * F)] = e[j]; }
+            }
+            for (int f = 4 * nv + tid; f < cnt; f += 256) { const int r = f / F; s_sh[r * FP + (f - r * F)] = src[f]; }
+        } else {
+            for (int f = tid; f < cnt; f += 256) { const int r = f / F; s_sh[r * FP + (f - r * F)] = src[f]; }
+        }
+        __syncthreads();
+        if (tid < rows) {
+            float* s = s_sh + tid * FP;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                sh_band<3>(D.d1, s + c);
+                if (K >= 8) sh_band<5>(D.d2, s + 9 + c);
+                if (K >= 15) sh_band<7>(D.d3, s + 24 + c);
+            }
+        }
+        __syncthreads();
+        if (VEC) {
+            const int nv = cnt >> 2;
+            for (int v = tid; v < nv; v += 256) {
+                float e[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) { const int f = 4 * v + j, r = f / F; e[j] = s_sh[r * FP + (f - r * F)]; }
+                reinterpret_cast<float4*>(dst)[v] = make_float4(e[0], e[1], e[2], e[3]);
+            }
+            for (int f = 4 * nv + tid; f < cnt; f += 256) { const int r = f / F; dst[f] = s_sh[r * FP + (f - r * F)]; }
+        } else {
+            for (int f = tid; f < cnt; f += 256) { const int r = f / F; dst[f] = s_sh[r * FP + (f - r * F)]; }
+        }
+        __syncthreads();                                                        // the next tile overwrites the image
+    }
+    transform_geometry(n, G, xyz, cov6, rot, xyz_o, cov6_o, rot_o);
+}
+
+// the same without SH rotation: `words` 32-bit words of sh copied bit for bit (as integers: no float ever touches them)
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_model_transform_copy(int64_t n, Rigid G, int64_t words, const float* __restrict__ xyz, const float* __restrict__ cov6,
+                                                              const float* __restrict__ rot, const uint32_t* __restrict__ sh, float* __restrict__ xyz_o,
+                                                              float* __restrict__ cov6_o, float* __restrict__ rot_o, uint32_t* __restrict__ sh_o) {
+    const int64_t t0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, step = (int64_t)gridDim.x * blockDim.x;
+    if (VEC) {
+        const int64_t nv = words >> 2;
+        for (int64_t v = t0; v < nv; v += step) reinterpret_cast<uint4*>(sh_o)[v] = reinterpret_cast<const uint4*>(sh)[v];
+        for (int64_t f = 4 * nv + t0; f < words; f += step) sh_o[f] = sh[f];
+    } else {
+        for (int64_t f = t0; f < words; f += step) sh_o[f] = sh[f];
+    }
+    transform_geometry(n, G, xyz, cov6, rot, xyz_o, cov6_o, rot_o);
+}
+
+// ---- device SoA -> 3DGS .ply rows (gsr_ply_pack), the inverse of k_ply_unpack ------------------------------------------------
+// A thread per output float, consecutive threads on consecutive addresses of the row image: x y z, three zero normals, f_dc_0..2,
+// f_rest channel-major (file f_rest[c * K + k] = sh[i][k][c]), opacity, scale_0..2, rot_0..3 -- 17 + 3K little-endian float32 per row,
+// what save_gaussian_ply writes.  The reads of one row come from six arrays but stay inside that row's own few cache lines.
+__global__ __launch_bounds__(256) void k_ply_pack(int64_t n, int K, const float* __restrict__ xyz, const float* __restrict__ dc, const float* __restrict__ sh,
+                                                  const float* __restrict__ opacity, const float* __restrict__ scale, const float* __restrict__ rot,
+                                                  float* __restrict__ rows) {
+    const int F = 3 * K, W = 17 + F;
+    const int64_t total = n * W;
+    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t i = t / W;
+        const int j = (int)(t - i * W);
+        float v;
+        if (j < 3) v = xyz[3 * i + j];
+        else if (j < 6) v = 0.0f;
+        else if (j < 9) v = dc[3 * i + (j - 6)];
+        else if (j < 9 + F) { const int f = j - 9, c = f / K, k = f - c * K; v = sh[i * F + 3 * k + c]; }
+        else if (j == 9 + F) v = opacity[i];
+        else if (j < 13 + F) v = scale[3 * i + (j - 10 - F)];
+        else v = rot[4 * i + (j - 13 - F)];
+        rows[t] = v;
+    }
+}
+
 }  // namespace gsr
 
 using namespace gsr;
+
+// ---- gsr_sh_rotation: host only ----------------------------------------------------------------------------------------------
+static bool rotation_ok(const double* R) {
+    double worst = 0.0;
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) {
+            double d = i == j ? -1.0 : 0.0;
+            for (int k = 0; k < 3; ++k) d += R[3 * k + i] * R[3 * k + j];
+            if (!(fabs(d) <= worst)) worst = fabs(d);                   // a NaN sticks
+        }
+    const double det = R[0] * (R[4] * R[8] - R[5] * R[7]) - R[1] * (R[3] * R[8] - R[5] * R[6]) + R[2] * (R[3] * R[7] - R[4] * R[6]);
+    return worst <= 1e-3 && det > 0.0;
+}
+
+extern "C" int32_t gsr_sh_rotation(const double* rotation, int32_t degree, double* bands) {
+    if (!rotation || !bands) return fail(GSR_E_INVALID, "gsr_sh_rotation: NULL argument");
+    if (degree < 0 || degree > 3) return fail(GSR_E_INVALID, "gsr_sh_rotation: SH degree %d outside 0..3", degree);
+    if (!rotation_ok(rotation)) return fail(GSR_E_INVALID, "gsr_sh_rotation: the 3x3 is not a rotation (max|R^T R - I| > 1e-3 or det < 0)");
+    // sample directions: a Fibonacci spiral, well spread, so the normal matrix of every band is close to a multiple of the identity
+    const int S = 96;
+    double Y[S][15], Z[S][15];
+    for (int s = 0; s < S; ++s) {
+        const double z = 1.0 - (2.0 * s + 1.0) / S, r = sqrt(1.0 - z * z), phi = 2.399963229728653 * s;
+        const double d[3] = {r * cos(phi), r * sin(phi), z};
+        double e[3];
+        for (int i = 0; i < 3; ++i) e[i] = rotation[3 * i] * d[0] + rotation[3 * i + 1] * d[1] + rotation[3 * i + 2] * d[2];
+        const double ne = sqrt(e[0] * e[0] + e[1] * e[1] + e[2] * e[2]);
+        sh_basis_rest(d[0], d[1], d[2], Y[s]);
+        sh_basis_rest(e[0] / ne, e[1] / ne, e[2] / ne, Z[s]);
+    }
+    const int off[3] = {0, 3, 8}, out[3] = {0, 9, 34};
+    for (int l = 1; l <= 3; ++l) {
+        const int m = 2 * l + 1, o = off[l - 1];
+        double* D = bands + out[l - 1];
+        if (l > degree) {                                               // bands the model does not carry: the identity
+            for (int i = 0; i < m; ++i) for (int j = 0; j < m; ++j) D[m * i + j] = i == j ? 1.0 : 0.0;
+            continue;
+        }
+        // Z = Y D^T in the least-squares sense:  (Y^T Y) D^T = Y^T Z
+        double A[7][7], X[7][7];
+        for (int i = 0; i < m; ++i)
+            for (int j = 0; j < m; ++j) {
+                double a = 0.0, x = 0.0;
+                for (int s = 0; s < S; ++s) { a += Y[s][o + i] * Y[s][o + j]; x += Y[s][o + i] * Z[s][o + j]; }
+                A[i][j] = a; X[i][j] = x;
+            }
+        if (!solve_in_place(m, A, X)) return fail(GSR_E_INVALID, "gsr_sh_rotation: singular fit in band %d", l);
+        for (int i = 0; i < m; ++i) for (int j = 0; j < m; ++j) D[m * i + j] = X[j][i];
+    }
+    return GSR_OK;
+}
+
+// ---- gsr_model_transform -----------------------------------------------------------------------------------------------------
+static bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
+    if (!a || !b || !na || !nb) return false;
+    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+    return pa < pb + nb && pb < pa + na;
+}
+
+template <int K> static void launch_model_transform(bool vec, int grid, hipStream_t st, int64_t n, const Rigid& G, const ShRot& D, const float* xyz,
+                                                    const float* cov6, const float* rot, const float* sh, float* xyz_o, float* cov6_o, float* rot_o, float* sh_o) {
+    if (vec) hipLaunchKernelGGL((k_model_transform<K, true>), dim3(grid), dim3(256), 0, st, n, G, D, xyz, cov6, rot, sh, xyz_o, cov6_o, rot_o, sh_o);
+    else hipLaunchKernelGGL((k_model_transform<K, false>), dim3(grid), dim3(256), 0, st, n, G, D, xyz, cov6, rot, sh, xyz_o, cov6_o, rot_o, sh_o);
+}
+
+extern "C" int32_t gsr_model_transform(const double* transform, int64_t n, int32_t K, int32_t rotate_sh, const float* xyz, const float* cov6,
+                                       const float* rot, const float* sh, float* xyz_out, float* cov6_out, float* rot_out, float* sh_out,
+                                       int32_t on_device, int32_t device, void* stream) {
+    if (!transform || n < 0 || (K != 0 && K != 3 && K != 8 && K != 15)) return fail(GSR_E_INVALID, "gsr_model_transform: bad argument (K must be 0, 3, 8 or 15)");
+    if (n > 0 && (!xyz || !cov6 || !xyz_out || !cov6_out || (rot && !rot_out) || (K > 0 && (!sh || !sh_out))))
+        return fail(GSR_E_INVALID, "gsr_model_transform: NULL array");
+    const double R9[9] = {transform[0], transform[1], transform[2], transform[4], transform[5], transform[6], transform[8], transform[9], transform[10]};
+    if (!rotation_ok(R9)) return fail(GSR_E_INVALID, "gsr_model_transform: the upper 3x3 of the transform is not a rotation");
+    const size_t un = (size_t)n, F = 3 * (size_t)K;
+    const void* ins[4] = {xyz, cov6, rot, K ? sh : nullptr};
+    const void* outs[4] = {xyz_out, cov6_out, rot ? rot_out : nullptr, K ? sh_out : nullptr};
+    const size_t bytes[4] = {un * 12, un * 24, un * 16, un * F * 4};
+    for (int i = 0; i < 4; ++i)
+        for (int j = 0; j < 4; ++j)
+            if (ranges_overlap(outs[i], bytes[i], ins[j], bytes[j]) || (i < j && ranges_overlap(outs[i], bytes[i], outs[j], bytes[j])))
+                return fail(GSR_E_INVALID, "gsr_model_transform: an output array overlaps another array of the call (the transform is not in place)");
+    GSR_TRY(open_device(device, "gsr_model_transform"));
+    if (n == 0) return GSR_OK;
+    // the motion narrowed to float32 once: rotation, translation, the rotation's unit quaternion (Shepperd's branch, w >= 0)
+    Rigid G;
+    for (int i = 0; i < 9; ++i) G.R[i] = (float)R9[i];
+    for (int i = 0; i < 3; ++i) G.t[i] = (float)transform[4 * i + 3];
+    {
+        const double* R = R9;
+        const double tr = R[0] + R[4] + R[8];
+        double w, x, y, z;
+        if (tr > 0.0) { const double s = sqrt(tr + 1.0) * 2.0; w = 0.25 * s; x = (R[7] - R[5]) / s; y = (R[2] - R[6]) / s; z = (R[3] - R[1]) / s; }
+        else if (R[0] > R[4] && R[0] > R[8]) { const double s = sqrt(1.0 + R[0] - R[4] - R[8]) * 2.0; w = (R[7] - R[5]) / s; x = 0.25 * s; y = (R[1] + R[3]) / s; z = (R[2] + R[6]) / s; }
+        else if (R[4] > R[8]) { const double s = sqrt(1.0 + R[4] - R[0] - R[8]) * 2.0; w = (R[2] - R[6]) / s; x = (R[1] + R[3]) / s; y = 0.25 * s; z = (R[5] + R[7]) / s; }
+        else { const double s = sqrt(1.0 + R[8] - R[0] - R[4]) * 2.0; w = (R[3] - R[1]) / s; x = (R[2] + R[6]) / s; y = (R[5] + R[7]) / s; z = 0.25 * s; }
+        const double nq = sqrt(w * w + x * x + y * y + z * z) * (w < 0.0 ? -1.0 : 1.0);
+        G.q[0] = (float)(w / nq); G.q[1] = (float)(x / nq); G.q[2] = (float)(y / nq); G.q[3] = (float)(z / nq);
+    }
+    ShRot D;
+    memset(&D, 0, sizeof(D));
+    const bool rotate = rotate_sh != 0 && K > 0;
+    if (rotate) {
+        double B[83];
+        GSR_TRY(gsr_sh_rotation(R9, K == 3 ? 1 : K == 8 ? 2 : 3, B));
+        for (int i = 0; i < 9; ++i) D.d1[i] = (float)B[i];
+        for (int i = 0; i < 25; ++i) D.d2[i] = (float)B[9 + i];
+        for (int i = 0; i < 49; ++i) D.d3[i] = (float)B[34 + i];
+    }
+    OneShot os((hipStream_t)stream, on_device != 0, "gsr_model_transform");
+    const float *px = nullptr, *pc = nullptr, *pq = nullptr, *ps = nullptr;
+    float *ox = nullptr, *oc = nullptr, *oq = nullptr, *osh = nullptr;
+    GSR_TRY(os.in(xyz, bytes[0], &px));
+    GSR_TRY(os.in(cov6, bytes[1], &pc));
+    GSR_TRY(os.in(rot, bytes[2], &pq));
+    GSR_TRY(os.in(K ? sh : nullptr, bytes[3], &ps));
+    GSR_TRY(os.out(xyz_out, bytes[0], &ox));
+    GSR_TRY(os.out(cov6_out, bytes[1], &oc));
+    GSR_TRY(os.out(rot ? rot_out : nullptr, bytes[2], &oq));
+    GSR_TRY(os.out(K ? sh_out : nullptr, bytes[3], &osh));
+    const bool vec = (((uintptr_t)ps | (uintptr_t)osh) & 15u) == 0u;
+    if (rotate) {
+        const int grid = (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);        // a block per 256-row tile, at most 16 per CU
+        if (K == 3) launch_model_transform<3>(vec, grid, os.st, n, G, D, px, pc, pq, ps, ox, oc, oq, osh);
+        else if (K == 8) launch_model_transform<8>(vec, grid, os.st, n, G, D, px, pc, pq, ps, ox, oc, oq, osh);
+        else launch_model_transform<15>(vec, grid, os.st, n, G, D, px, pc, pq, ps, ox, oc, oq, osh);
+    } else {
+        const int64_t words = n * (int64_t)F;
+        const int grid = stride_grid(words > 4 * n ? words / 4 : n);
+        if (vec) hipLaunchKernelGGL((k_model_transform_copy<true>), dim3(grid), dim3(256), 0, os.st, n, G, words, px, pc, pq, (const uint32_t*)ps, ox, oc, oq, (uint32_t*)osh);
+        else hipLaunchKernelGGL((k_model_transform_copy<false>), dim3(grid), dim3(256), 0, os.st, n, G, words, px, pc, pq, (const uint32_t*)ps, ox, oc, oq, (uint32_t*)osh);
+    }
+    return os.finish();
+}
+
+extern "C" int32_t gsr_ply_pack(const float* xyz, const float* dc, const float* sh, const float* opacity, const float* scale, const float* rot,
+                                int64_t n, int32_t K, void* rows_dev, int32_t device, void* stream) {
+    if (n < 0 || K < 0 || K > 1024 || (n > 0 && (!xyz || !dc || !opacity || !scale || !rot || !rows_dev || (K > 0 && !sh))))
+        return fail(GSR_E_INVALID, "gsr_ply_pack: bad argument");
+    GSR_TRY(open_device(device, "gsr_ply_pack"));
+    if (n == 0) return GSR_OK;
+    hipLaunchKernelGGL(k_ply_pack, dim3(stride_grid(n * (17 + 3 * (int64_t)K))), dim3(256), 0, (hipStream_t)stream, n, (int)K, xyz, dc, sh, opacity, scale, rot,
+                       (float*)rows_dev);
+    GSR_HIP(hipGetLastError());
+    return GSR_OK;
+}
 
 extern "C" int32_t gsr_plane_score(const float* xyz, const float* normals, int64_t n, const float* candidates, int32_t n_candidates,
                                    float distance_threshold, float normal_threshold, uint32_t* counts, uint8_t* best_mask, int32_t* best,

@@ -10,6 +10,9 @@ reader/writer in ``utils/ply_io.py``, ``plyfile`` is not needed).  ``from_arrays
 ``from_mixture`` runs the reference's scaling/rotation rebuild (``:151-153,242-265``: batched ``eigh``, axis matching,
 quaternions; the reference's own comment calls it unused) only when asked (``decompose=True`` / ``"reference"`` /
 ``"exact"``): registration only consumes xyz / covariance.  The rebuild is one device kernel (``csrc/model.hip``).
+
+``transform_gaussian_model`` / ``get_merged_gaussian_point_clouds`` take ``rotate_sh`` (turn the SH coefficients with the cloud) and
+run as one device kernel on CUDA tensors (``gsr_model_transform``); ``save_ply`` of a model on the device packs the rows there.
 """
 from __future__ import annotations
 
@@ -141,6 +144,9 @@ class GaussianModel:
         from ..utils import ply_io
         if self._scaling.numel() == 0:
             raise RuntimeError("save_ply needs scaling/rotation: build the model with from_ply or from_mixture(..., decompose=True)")
+        if self._xyz.is_cuda:          # packed on the device and streamed out through pinned chunks: the same bytes, no full-size host copy
+            ply_io.save_gaussian_device(path, self._xyz, self.get_colors, self.get_spherical_harmonics, self._opacity, self._scaling, self._rotation)
+            return
         c = lambda t: t.detach().cpu().numpy()
         ply_io.save_gaussian_ply(path, c(self._xyz), c(self.get_colors), c(self.get_spherical_harmonics), c(self._opacity),
                                  c(self._scaling), c(self._rotation))
@@ -192,10 +198,64 @@ class GaussianModel:
         self._last_quaternions = q
         return sc, mat
 
+    @staticmethod
+    def rotate_sh_matrices(rotation, sh_degree):
+        """-> (D1 (3,3), D2 (5,5), D3 (7,7)) float64: how the SH-rest coefficients of a splat turn with the rotation ``rotation``
+        (3x3), in the basis 3DGS evaluates and the coefficient order of ``_features_rest[n, k, c]`` (``gsr_sh_rotation``; host
+        only).  For every direction d: ``basis(R d) . (D c) = basis(d) . c``.  Bands above ``sh_degree`` are the identity."""
+        L = _lib.load()
+        R = np.ascontiguousarray(np.asarray(rotation, dtype=np.float64).reshape(3, 3))
+        B = np.empty(83, np.float64)
+        _lib.check(L.gsr_sh_rotation(R.ctypes.data, int(sh_degree), B.ctypes.data), "gsr_sh_rotation")
+        return B[:9].reshape(3, 3).copy(), B[9:34].reshape(5, 5).copy(), B[34:].reshape(7, 7).copy()
+
+    def _transform_kernel(self, transformation_matrix, rotate_sh, into=None):
+        """``gsr_model_transform`` on this model's arrays (one fused kernel; host tensors are staged by the library).  The
+        results go to fresh arrays, or to the first ``len(self)`` rows of the tensors in ``into`` (name -> CUDA tensor).
+        Returns name -> tensor for ``_xyz``, ``_covariance``, ``_rotation``, ``_features_rest``; this model is not modified."""
+        import ctypes as C
+        L = _lib.load(require_device=True)
+        T = np.ascontiguousarray(np.asarray(transformation_matrix, dtype=np.float64).reshape(4, 4))
+        n = len(self)
+        K = int(self._features_rest.shape[1]) if self._features_rest.numel() or self._features_rest.dim() == 3 else 0
+        on = bool(self._xyz.is_cuda)
+        device = self._xyz.device.index if on else 0
+        have_rot = self._rotation.numel() > 0
+        src = {"_xyz": (self._xyz, (n, 3)), "_covariance": (self._covariance, (n, 6)),
+               "_rotation": (self._rotation if have_rot else None, (n, 4)), "_features_rest": (self._features_rest if K else None, (n, K, 3))}
+        ins, outs, ptr = {}, {}, {}
+        for name, (t, shape) in src.items():
+            if t is None:
+                ins[name], ptr[name] = (None, None), None
+                continue
+            p, keep, t_on = _m.prep(t, shape, np.float32, device)
+            if t_on != on:
+                raise RuntimeError("the model's tensors must all live on one device")
+            ins[name] = (p, keep)
+            if into is not None:
+                o = into[name]
+                if not (o.is_cuda and o.is_contiguous() and o.dtype == torch.float32 and o.shape[0] >= n and tuple(o.shape[1:]) == tuple(shape[1:])):
+                    raise RuntimeError(f"bad destination for {name}")
+                outs[name], ptr[name] = o[:n], o.data_ptr()
+            else:
+                outs[name], ptr[name] = _m.out(shape, np.float32, device, on)
+        a = lambda name: ins[name][0]
+        _lib.check(L.gsr_model_transform(T.ctypes.data, n, K, 1 if rotate_sh else 0, a("_xyz"), a("_covariance"), a("_rotation"), a("_features_rest"),
+                                         ptr["_xyz"], ptr["_covariance"], ptr["_rotation"], ptr["_features_rest"], 1 if on else 0, device,
+                                         C.c_void_p(_m.stream_ptr(device, on))), "gsr_model_transform")
+        return {name: torch.as_tensor(o) for name, o in outs.items()}
+
     # -- rigid motion and merge (reference ``gaussian_model.py:198-222,267-290``) ---------------------------------
-    def transform_gaussian_model(self, transformation_matrix):
-        """Apply a rigid 4x4 to positions, covariances and rotation quaternions, in place.  (SH coefficients are left
-        as they are, as in the reference.)"""
+    def transform_gaussian_model(self, transformation_matrix, rotate_sh=False):
+        """Apply a rigid 4x4 to positions, covariances and rotation quaternions, in place.  ``rotate_sh=False``: the SH
+        coefficients are left as they are, as in the reference -- the view-dependent colour then stays behind when the cloud
+        turns.  ``rotate_sh=True`` turns them too (``rotate_sh_matrices``).  With ``rotate_sh=True`` or with CUDA tensors the
+        whole motion is ONE device kernel (``gsr_model_transform``, ``csrc/model.hip``; no GPU: ``RuntimeError``); host tensors
+        with the default keep the torch arithmetic below."""
+        if rotate_sh or self._xyz.is_cuda:
+            for name, t in self._transform_kernel(transformation_matrix, rotate_sh).items():
+                setattr(self, name, t)            # the kernel is not in place: the fresh arrays replace the old ones
+            return self
         T = torch.as_tensor(transformation_matrix, dtype=torch.float32, device=self._xyz.device)
         R, t = T[:3, :3], T[:3, 3]
         self._xyz = self._xyz @ R.T + t
@@ -217,16 +277,45 @@ class GaussianModel:
         return self
 
     @staticmethod
-    def get_merged_gaussian_point_clouds(gaussian1, gaussian2, transformation_matrix):
-        """``gaussian1`` moved by the registration result, concatenated with ``gaussian2`` (the merged-cloud save)."""
-        g1 = gaussian1
-        if transformation_matrix is not None and not np.array_equal(np.asarray(transformation_matrix), np.eye(4)):
-            g1 = gaussian1.clone_gaussian()
-            g1.transform_gaussian_model(np.asarray(transformation_matrix, dtype=np.float32))
+    def get_merged_gaussian_point_clouds(gaussian1, gaussian2, transformation_matrix, rotate_sh=False):
+        """``gaussian1`` moved by the registration result, concatenated with ``gaussian2`` (the merged-cloud save).
+        ``rotate_sh``: turn the SH coefficients of ``gaussian1`` with it (``transform_gaussian_model``).  When both models
+        live on one CUDA device the merged arrays are allocated once, the kernel writes the moved ``gaussian1`` straight into
+        their first rows and ``gaussian2`` is copied behind it: no clone, no ``cat``.  ``gaussian1`` is left as it was."""
         assert gaussian1.sh_degree == gaussian2.sh_degree
+        names = ("_xyz", "_rotation", "_scaling", "_features_dc", "_features_rest", "_opacity", "_covariance")
+        moves = transformation_matrix is not None and not np.array_equal(np.asarray(transformation_matrix), np.eye(4))
+        x1, x2 = gaussian1._xyz, gaussian2._xyz
         m = GaussianModel(gaussian2.device_name)
         m.sh_degree = gaussian1.sh_degree
-        for name in ("_xyz", "_rotation", "_scaling", "_features_dc", "_features_rest", "_opacity", "_covariance"):
+        if moves and x1.is_cuda and x2.is_cuda and x1.device == x2.device:
+            n1, n2 = len(gaussian1), len(gaussian2)
+            for name in names:
+                a, b = getattr(gaussian1, name), getattr(gaussian2, name)
+                if a.numel() == 0 and b.numel() == 0 and a.dim() < 2:          # an array neither model carries (no decompose)
+                    setattr(m, name, torch.empty(0, device=x2.device))
+                    continue
+                if a.shape[0] != n1 or b.shape[0] != n2:
+                    raise RuntimeError(f"{name}: one model carries it, the other does not")
+                setattr(m, name, torch.empty((n1 + n2,) + tuple(b.shape[1:]), dtype=torch.float32, device=x2.device))
+            moved = ("_xyz", "_covariance", "_rotation", "_features_rest")
+            gaussian1._transform_kernel(transformation_matrix, rotate_sh, into={k: getattr(m, k) for k in moved})
+            for name in names:
+                a, b, o = getattr(gaussian1, name), getattr(gaussian2, name), getattr(m, name)
+                if o.shape[0] != n1 + n2 or o.numel() == 0:
+                    continue
+                if name not in moved:
+                    o[:n1].copy_(a)
+                o[n1:].copy_(b)
+            return m
+        g1 = gaussian1
+        if moves:
+            g1 = gaussian1.clone_gaussian()
+            if rotate_sh:
+                g1.transform_gaussian_model(np.asarray(transformation_matrix, dtype=np.float64), rotate_sh=True)
+            else:
+                g1.transform_gaussian_model(np.asarray(transformation_matrix, dtype=np.float32))
+        for name in names:
             setattr(m, name, torch.cat((getattr(g1, name).to(gaussian2.device_name), getattr(gaussian2, name))))
         return m
 

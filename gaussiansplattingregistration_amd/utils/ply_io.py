@@ -6,7 +6,8 @@ element, float32 properties ``x y z nx ny nz f_dc_0..2 f_rest_0..(3K-1) opacity 
 binary little endian.  ``f_rest`` is stored channel-major on disk (``(P, 3, K)``) and transposed to the
 coefficient-major ``(P, K, 3)`` tensors the model keeps (``gaussian_model.py:115-116,131-134``);
 ``opacity`` is the raw logit, ``scale`` the log standard deviations, ``rot`` the (w, x, y, z) quaternion.
-ASCII ply files are read too.
+ASCII ply files are read too.  ``load_gaussian_device`` / ``save_gaussian_device`` are the device-side pair: rows cross PCIe in
+pinned chunks and are scattered / packed by one kernel per chunk.
 """
 from __future__ import annotations
 
@@ -176,6 +177,14 @@ def load_gaussian_device(path, device=0, chunk_rows: int = 1 << 18, timing: dict
     return out
 
 
+def _gaussian_header(P, K, n_scale=3, n_rot=4) -> bytes:
+    """The header of a 3DGS ``.ply`` of ``P`` splats with ``K`` SH-rest coefficients per channel (every property float32)."""
+    names = ["x", "y", "z", "nx", "ny", "nz", "f_dc_0", "f_dc_1", "f_dc_2"] + [f"f_rest_{i}" for i in range(3 * K)] + ["opacity"]
+    names += [f"scale_{i}" for i in range(n_scale)] + [f"rot_{i}" for i in range(n_rot)]
+    return (f"ply\nformat binary_little_endian 1.0\nelement vertex {P}\n" + "".join(f"property float {nme}\n" for nme in names)
+            + "end_header\n").encode()
+
+
 def save_gaussian_ply(path, xyz, colors, sh, opacity, scale, rot):
     """``GaussianModel.save_ply`` (``gaussian_model.py:169-185``): binary little endian, normals zero."""
     xyz = np.asarray(xyz, np.float32)
@@ -186,16 +195,64 @@ def save_gaussian_ply(path, xyz, colors, sh, opacity, scale, rot):
     cols = [xyz, np.zeros((P, 3), np.float32), np.asarray(colors, np.float32).reshape(P, 3), rest,
             np.asarray(opacity, np.float32).reshape(P, 1), np.asarray(scale, np.float32).reshape(P, -1),
             np.asarray(rot, np.float32).reshape(P, -1)]
-    names = ["x", "y", "z", "nx", "ny", "nz", "f_dc_0", "f_dc_1", "f_dc_2"] + [f"f_rest_{i}" for i in range(3 * K)] + ["opacity"]
-    names += [f"scale_{i}" for i in range(cols[5].shape[1])] + [f"rot_{i}" for i in range(cols[6].shape[1])]
     data = np.ascontiguousarray(np.concatenate(cols, 1).astype("<f4"))
     with open(path, "wb") as f:
-        f.write(b"ply\nformat binary_little_endian 1.0\n")
-        f.write(f"element vertex {P}\n".encode())
-        for nme in names:
-            f.write(f"property float {nme}\n".encode())
-        f.write(b"end_header\n")
+        f.write(_gaussian_header(P, K, cols[5].shape[1], cols[6].shape[1]))
         data.tofile(f)
+
+
+def save_gaussian_device(path, xyz, colors, sh, opacity, scale, rot, device=None, chunk_rows: int = 1 << 18, timing: dict | None = None):
+    """``save_gaussian_ply`` for a model that lives on the device -- ``load_gaussian_device`` the other way round: one kernel per
+    chunk (``gsr_ply_pack``) lays ``chunk_rows`` rows out in HBM exactly as they are on disk (normals zero, the SH block transposed
+    to channel-major), an asynchronous copy brings them into one of two PINNED host buffers, and the host writes the previous chunk
+    to the file meanwhile.  No full-size host copy of the cloud, no host-side transpose or concatenation; the file is byte for
+    byte the one ``save_gaussian_ply`` writes from host copies of the same arrays.  CUDA float32 tensors: xyz (P,3), colors (P,3),
+    sh (P,3K) or (P,K,3), opacity (P,) or (P,1), scale (P,3), rot (P,4)."""
+    import time
+    import ctypes as C
+    import torch
+    from .. import _lib
+    L = _lib.load(require_device=True)
+    t0 = time.perf_counter()
+    if not (isinstance(xyz, torch.Tensor) and xyz.is_cuda):
+        raise RuntimeError("save_gaussian_device takes CUDA tensors (save_gaussian_ply is the host writer)")
+    dev = xyz.device
+    if device is not None and int(device) != dev.index:
+        raise RuntimeError(f"tensors live on {dev}, requested cuda:{int(device)}")
+    n = int(xyz.shape[0])
+    c = lambda t, w: t.detach().to(device=dev, dtype=torch.float32).reshape(n, w).contiguous()
+    sh = sh.detach().reshape(n, -1)
+    K = int(sh.shape[1]) // 3
+    if 3 * K != int(sh.shape[1]):
+        raise ValueError("sh must hold 3 K values per splat")
+    xyz, colors, sh, opacity, scale, rot = c(xyz, 3), c(colors, 3), c(sh, 3 * K), c(opacity, 1), c(scale, 3), c(rot, 4)
+    row_bytes = 4 * (17 + 3 * K)
+    rows = max(1, min(int(chunk_rows), n))
+    with torch.cuda.device(dev), open(path, "wb") as f:
+        f.write(_gaussian_header(n, K, 3, 4))
+        pinned = [torch.empty(rows * row_bytes, dtype=torch.uint8).pin_memory() for _ in range(2)]
+        staged = [torch.empty(rows * row_bytes, dtype=torch.uint8, device=dev) for _ in range(2)]
+        arrived = [torch.cuda.Event(), torch.cuda.Event()]       # pinned[b] holds its chunk once its copy has landed
+        stream = torch.cuda.current_stream(dev)
+        done, b, pending = 0, 0, None                            # pending = (buffer, bytes) of the chunk still on its way
+        while done < n:
+            m = min(rows, n - done)
+            o = lambda t, w: C.c_void_p(t.data_ptr() + 4 * w * done)
+            _lib.check(L.gsr_ply_pack(o(xyz, 3), o(colors, 3), o(sh, 3 * K) if K else None, o(opacity, 1), o(scale, 3), o(rot, 4), m, K,
+                                      C.c_void_p(staged[b].data_ptr()), dev.index, C.c_void_p(stream.cuda_stream)), "gsr_ply_pack")
+            pinned[b][: m * row_bytes].copy_(staged[b][: m * row_bytes], non_blocking=True)
+            arrived[b].record(stream)
+            if pending is not None:                              # the previous chunk goes to the file while this one is packed and copied
+                arrived[pending[0]].synchronize()
+                f.write(memoryview(pinned[pending[0]].numpy())[: pending[1]])
+            pending = (b, m * row_bytes)
+            done += m
+            b ^= 1
+        if pending is not None:
+            arrived[pending[0]].synchronize()
+            f.write(memoryview(pinned[pending[0]].numpy())[: pending[1]])
+    if timing is not None:
+        timing.update(seconds=time.perf_counter() - t0, bytes=n * row_bytes, splats=n)
 
 
 def save_input_ply(path, xyz, rgb, normals=None):

@@ -434,6 +434,40 @@ int32_t gsr_decompose_cov(const float* cov6, int64_t n, int32_t mode, float* sca
 int32_t gsr_ply_unpack(const void* rows_dev, int64_t n, int32_t row_bytes, const int32_t* offsets, int32_t K, float* xyz, float* color,
                        float* sh, float* opacity, float* scale, float* rot, float* cov6, int32_t device, void* stream);
 
+/* The opposite direction: device SoA -> n .ply vertex rows in HBM, in the layout GaussianModel.save_ply writes
+ * (src/models/gaussian_model.py:155-185):  x y z  nx ny nz (zero)  f_dc_0..2  f_rest_0..(3K-1) channel-major  opacity  scale_0..2
+ * rot_0..3, 17 + 3K little-endian float32 per row.  Inputs (device, float32) as gsr_ply_unpack produces them: xyz[n*3], dc[n*3],
+ * sh[n*3K] coefficient-major (NULL when K = 0), opacity[n], scale[n*3], rot[n*4]; rows_dev: n * (17 + 3K) * 4 bytes.  The host
+ * copies the rows out through pinned memory chunk by chunk (utils/ply_io.save_gaussian_device).  Enqueued on `stream`; does not
+ * synchronise. */
+int32_t gsr_ply_pack(const float* xyz, const float* dc, const float* sh, const float* opacity, const float* scale, const float* rot,
+                     int64_t n, int32_t K, void* rows_dev, int32_t device, void* stream);
+
+/* ------------------------------------------------------------------------- rigid motion of a splat model */
+
+/* How the SH-rest coefficients of a splat turn with it, on the HOST (no GPU involved).  rotation[9]: a 3x3 rotation, row-major;
+ * degree: 0..3; bands[83]: D_1 (3x3), D_2 (5x5), D_3 (7x7), row-major, band after band (bands above `degree`: the identity).
+ * Basis = the one 3DGS evaluates -- band 1 is (-C1 y, C1 z, -C1 x), then its five degree-2 and seven degree-3 polynomials --,
+ * index = the coefficient index k of _features_rest[n, k, c].  Defining property, for every unit direction d and vector c:
+ *     basis_l(R d) . (D_l c) = basis_l(d) . c
+ * i.e. the rotated splat seen from the rotated direction shows the original colour.  D_l is orthogonal, D(R1 R2) = D(R1) D(R2), and
+ * D_1 = P R P^T with P = [[0,-1,0],[0,0,1],[-1,0,0]] -- NOT R itself.  GSR_E_INVALID for a degree outside 0..3, a NULL pointer, or a
+ * matrix with max|R^T R - I| > 1e-3 or det < 0 (a gate against scales and reflections, not a tolerance). */
+int32_t gsr_sh_rotation(const double* rotation, int32_t degree, double* bands);
+
+/* A rigid motion applied to a splat model in ONE kernel (GaussianModel.transform_gaussian_model, src/models/gaussian_model.py:198-222):
+ *   xyz' = R xyz + t;   cov6' = R cov R^T on the six-entry form (xx,xy,xz,yy,yz,zz);   rot' = normalise(q_R (x) q), quaternions
+ *   (w,x,y,z), the motion on the left;   sh: every channel's band vectors multiplied by D_1 / D_2 / D_3 of gsr_sh_rotation when
+ *   rotate_sh != 0, copied bit for bit otherwise.
+ * transform[16]: row-major 4x4 (float64, narrowed to float32 once; its 3x3 must pass the gate of gsr_sh_rotation); K = SH-rest
+ * coefficients per channel: 0, 3, 8 or 15; sh[n*3K] coefficient-major (NULL when K = 0); rot[n*4] may be NULL (rot_out is then
+ * ignored).  float32 arithmetic, 64-bit indexing.  All arrays on the host or all on the device as on_device says.  NOT in place:
+ * an output that overlaps any other array of the call is GSR_E_INVALID.  Outputs may point into the middle of larger arrays (the
+ * merged cloud's rows). */
+int32_t gsr_model_transform(const double* transform, int64_t n, int32_t K, int32_t rotate_sh, const float* xyz, const float* cov6,
+                            const float* rot, const float* sh, float* xyz_out, float* cov6_out, float* rot_out, float* sh_out,
+                            int32_t on_device, int32_t device, void* stream);
+
 /* RANSAC plane search, the data-parallel part: scores ALL candidate planes of one
  * _fit_single_plane call of the reference (src/utils/plane_fitting_util.py:38-69) in one pass over the points.
  * candidates[n_candidates*8] = {n'_0, n'_1, n'_2, d, m_0, m_1, m_2, |n'|}: the plane normal re-normalised as

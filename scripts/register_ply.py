@@ -3,7 +3,7 @@
 "Multiscale registration" tabs (qt_gaussian_mixture.py, qt_multiscale_registrator.py), as a script.
 
     python scripts/register_ply.py first.ply second.ply --levels 3 --max-corr 0.5 0.3 0.2 0.1 --iters 50 30 20 10 \\
-           [--type plane|point|color|general] [--loss none|tukey|cauchy|gm|huber --k 0.1] [--voxel] [--out merged.ply]
+           [--type plane|point|color|general] [--loss none|tukey|cauchy|gm|huber --k 0.1] [--voxel] [--out merged.ply [--rotate-sh]]
 
 Prints the 4x4 transformation (first -> second), fitness and inlier RMSE; `--out` saves the merged cloud.
 """
@@ -36,6 +36,8 @@ def main():
                     "this voxel size, the tab's other method); its pose is the multiscale ICP's initial transform")
     ap.add_argument("--ransac-iters", type=int, default=100000, help="RANSAC hypotheses (max_iteration) of --global-ransac")
     ap.add_argument("--out")
+    ap.add_argument("--rotate-sh", action="store_true", help="turn the SH coefficients (view-dependent colour) of the moved cloud with it in the "
+                    "merged output")
     a = ap.parse_args()
 
     import __graft_entry__ as g
@@ -99,7 +101,7 @@ def main():
     print(f"load {t1 - t0:.2f} s, mixtures {t2 - t1:.3f} s, registration {t3 - t2:.3f} s")
     if a.out:
         merged = GaussianModel.get_merged_gaussian_point_clouds(repo.pc_gaussian_list_first[0], repo.pc_gaussian_list_second[0],
-                                                                res.result.transformation)
+                                                                res.result.transformation, rotate_sh=a.rotate_sh)
         merged.save_ply(a.out)
         print(f"merged cloud ({len(merged)} splats) -> {a.out}")
 
