@@ -121,6 +121,12 @@ SIGNATURES = {
     "gsr_ransac_correspondence": (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _i32, _i32, _vp]),
     "gsr_fgr_tuple_test": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, C.POINTER(_i64), C.POINTER(_i64), _i32, _i32, _vp]),
     "gsr_fgr_optimize": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i32, _i32, _vp]),
+    "gsr_raster_create": (_i32, [C.POINTER(_vp), _i32, _vp]),
+    "gsr_raster_destroy": (_i32, [_vp]),
+    "gsr_raster_render": (_i32, [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, C.POINTER(_f32), _f32, _f32, _f32, _f32, _i32, _i32, C.POINTER(_f32), _f32,
+                                 _vp, _vp, _vp]),
+    "gsr_raster_get_timing": (_i32, [_vp, C.POINTER(_f32)]),
+    "gsr_image_metrics": (_i32, [_vp, _vp, _i32, _i32, _i32, C.POINTER(_f64), _i32, _vp]),
 }
 # private test hooks (csrc/gsr_test_hooks.h): exported by the library, not part of the public header
 TEST_HOOKS = {

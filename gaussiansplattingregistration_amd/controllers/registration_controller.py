@@ -64,6 +64,17 @@ class RegistrationController:
             self.handle_registration_result_local(result)
         return result
 
+    def evaluate_registration(self, cameras_list, images_path, log_path, color, use_gpu, registration_result=None, rotate_sh=False):
+        """Image-based evaluation of the current transform on the repository's original clouds (reference :122-143): renders of
+        the merged model against the photographs, the JSON log at ``log_path``.  Returns the evaluator's ``EvaluationObject``."""
+        from ..workers.evaluator import RegistrationEvaluator
+        repo = self.data_repository
+        pc1 = repo.pc_gaussian_list_first[repo.current_index]
+        pc2 = repo.pc_gaussian_list_second[repo.current_index]
+        worker = RegistrationEvaluator(pc1, pc2, self.ui_repository.transformation_matrix, cameras_list, images_path, log_path, color,
+                                       registration_result, use_gpu, rotate_sh=rotate_sh)
+        return worker.run()
+
     def handle_registration_result_local(self, result_data):       # :145-163
         self.ui_repository.transformation_matrix = result_data.result.transformation
 

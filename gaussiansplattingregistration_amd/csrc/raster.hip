@@ -1,0 +1,484 @@
+// raster.hip -- forward tile rasteriser of a splat model for one pinhole camera (gsr_raster_*) and the image metrics of the
+// evaluation stage (gsr_image_metrics).  DESIGN.md section 14.
+//
+// Render: k_raster_preprocess (projection, conic, radius, SH colour, tile count) -> exclusive scan of the 64-bit counts -> ONE
+// host read-back of the intersection total -> k_raster_emit (keys (tile id << 32 | depth bits), values = splat index) -> radix
+// sort limited to the bits in use (stable: equal depths keep ascending splat index) -> k_raster_ranges -> k_raster_blend, one
+// 256-thread work-group per 16 x 16 tile.  No float atomics: every pixel sums its splats front to back in the sorted order, so
+// an image is the same bits from run to run.  The two counters (visible splats, non-empty tiles) are integer atomics.
+//
+// The semantics restate the published 3DGS / gsplat forward pass (EWA projection with the clamped perspective Jacobian, 0.3 px
+// dilation, 3-sigma integer radius, alpha clamp 0.999, 1/255 skip, transmittance stop at 1e-4); gsplat itself is not available on
+// ROCm, so parity with it is unpinned.  tests/raster_model.py is the executable restatement the kernels are held to.
+#include <math.h>
+#include <string.h>
+
+#include <rocprim/rocprim.hpp>
+
+#include "gsr_common.h"
+#include "gsr_oneshot.h"
+
+using namespace gsr;
+
+namespace {
+
+constexpr int TILE = 16;
+constexpr int BLEND_THREADS = TILE * TILE;          // four waves
+constexpr int SPLAT_WORDS = 9;                      // mean2d xy, conic A B C, opacity, r g b: 36 bytes
+
+struct RasterCam {
+    float R[9], t[3], cam[3];                       // world -> camera rotation (row-major), translation; camera position in the world
+    float fx, fy, cx, cy;
+    float lim_xp, lim_xn, lim_yp, lim_yn;           // the frustum in x/z, y/z widened by 0.3 tan(fov/2) on each side
+    float near_z, far_z, eps2d, radius_clip;
+    int32_t W, H, tiles_x, tiles_y, degree, K;
+};
+
+// SH colour in the basis 3DGS evaluates; rest[k*3 + c], k = 0 .. K-1 (coefficient-major).  d is a unit vector.
+__device__ __forceinline__ void sh_colour(int degree, const float* __restrict__ dc, const float* __restrict__ rest, float x, float y, float z, float* rgb) {
+    const float C0 = 0.28209479177387814f, C1 = 0.4886025119029199f;
+    const float C2[5] = {1.0925484305920792f, -1.0925484305920792f, 0.31539156525252005f, -1.0925484305920792f, 0.5462742152960396f};
+    const float C3[7] = {-0.5900435899266435f, 2.890611442640554f, -0.4570457994644658f, 0.3731763325901154f, -0.4570457994644658f, 1.445305721320277f,
+                         -0.5900435899266435f};
+    float b[15];
+    int nb = 0;
+    if (degree > 0) {
+        b[0] = -C1 * y; b[1] = C1 * z; b[2] = -C1 * x;
+        nb = 3;
+        if (degree > 1) {
+            const float xx = x * x, yy = y * y, zz = z * z, xy = x * y, yz = y * z, xz = x * z;
+            b[3] = C2[0] * xy; b[4] = C2[1] * yz; b[5] = C2[2] * (2.0f * zz - xx - yy); b[6] = C2[3] * xz; b[7] = C2[4] * (xx - yy);
+            nb = 8;
+            if (degree > 2) {
+                b[8] = C3[0] * y * (3.0f * xx - yy);
+                b[9] = C3[1] * xy * z;
+                b[10] = C3[2] * y * (4.0f * zz - xx - yy);
+                b[11] = C3[3] * z * (2.0f * zz - 3.0f * xx - 3.0f * yy);
+                b[12] = C3[4] * x * (4.0f * zz - xx - yy);
+                b[13] = C3[5] * z * (xx - yy);
+                b[14] = C3[6] * x * (xx - 3.0f * yy);
+                nb = 15;
+            }
+        }
+    }
+    for (int c = 0; c < 3; ++c) {
+        float v = C0 * dc[c];
+        for (int k = 0; k < nb; ++k) v = v + b[k] * rest[3 * k + c];
+        rgb[c] = fmaxf(v + 0.5f, 0.0f);
+    }
+}
+
+// One thread per splat: everything the blend needs (splat[i*9 ..]), its depth, its tile box and the number of tiles it touches
+// (0 = culled).  counters[0] += visible splats (one integer atomic per wave).
+__global__ __launch_bounds__(256) void k_raster_preprocess(int64_t n, RasterCam cam, const float* __restrict__ xyz, const float* __restrict__ cov6,
+                                                           const float* __restrict__ raw_opacity, const float* __restrict__ dc,
+                                                           const float* __restrict__ sh_rest, float* __restrict__ splat, float* __restrict__ depth,
+                                                           ushort4* __restrict__ rect, int64_t* __restrict__ counts, unsigned long long* __restrict__ counters) {
+    for (int64_t base = (int64_t)blockIdx.x * blockDim.x; base < n; base += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t i = base + threadIdx.x;
+        int64_t touched = 0;
+        if (i < n) {
+            const float x = xyz[3 * i], y = xyz[3 * i + 1], z = xyz[3 * i + 2];
+            const float* R = cam.R;
+            const float px = ((R[0] * x + R[1] * y) + R[2] * z) + cam.t[0];
+            const float py = ((R[3] * x + R[4] * y) + R[5] * z) + cam.t[1];
+            const float pz = ((R[6] * x + R[7] * y) + R[8] * z) + cam.t[2];
+            bool ok = pz >= cam.near_z && pz <= cam.far_z;
+            float a = 0.f, b = 0.f, c = 0.f, det = 0.f, mx = 0.f, my = 0.f, rad = 0.f;
+            if (ok) {
+                const float* s = cov6 + 6 * i;
+                const float S[3][3] = {{s[0], s[1], s[2]}, {s[1], s[3], s[4]}, {s[2], s[4], s[5]}};
+                float M[3][3], Sc[3][3];
+                for (int r = 0; r < 3; ++r)
+                    for (int q = 0; q < 3; ++q) M[r][q] = (R[3 * r] * S[0][q] + R[3 * r + 1] * S[1][q]) + R[3 * r + 2] * S[2][q];
+                for (int r = 0; r < 3; ++r)
+                    for (int q = r; q < 3; ++q) Sc[r][q] = Sc[q][r] = (M[r][0] * R[3 * q] + M[r][1] * R[3 * q + 1]) + M[r][2] * R[3 * q + 2];
+                const float rz = 1.0f / pz;
+                const float tx = pz * fminf(cam.lim_xp, fmaxf(-cam.lim_xn, px * rz));
+                const float ty = pz * fminf(cam.lim_yp, fmaxf(-cam.lim_yn, py * rz));
+                const float rz2 = rz * rz;
+                const float j00 = cam.fx * rz, j02 = -(cam.fx * tx) * rz2, j11 = cam.fy * rz, j12 = -(cam.fy * ty) * rz2;
+                const float v00 = Sc[0][0] * j00 + Sc[0][2] * j02, v01 = Sc[1][0] * j00 + Sc[1][2] * j02, v02 = Sc[2][0] * j00 + Sc[2][2] * j02;
+                const float v11 = Sc[1][1] * j11 + Sc[1][2] * j12, v12 = Sc[2][1] * j11 + Sc[2][2] * j12;
+                a = (j00 * v00 + j02 * v02) + cam.eps2d;
+                b = j11 * v01 + j12 * v02;
+                c = (j11 * v11 + j12 * v12) + cam.eps2d;
+                det = a * c - b * b;
+                ok = det > 0.0f;
+                mx = (cam.fx * px) * rz + cam.cx;
+                my = (cam.fy * py) * rz + cam.cy;
+            }
+            if (ok) {
+                const float bm = 0.5f * (a + c);
+                rad = ceilf(3.0f * sqrtf(bm + sqrtf(fmaxf(0.01f, bm * bm - det))));
+                ok = rad > cam.radius_clip && !(mx + rad <= 0.0f || mx - rad >= (float)cam.W || my + rad <= 0.0f || my - rad >= (float)cam.H);
+            }
+            if (ok) {
+                const float inv = 1.0f / (float)TILE;
+                // clamped as floats: a far-off mean or a huge radius must not reach the conversion to int
+                const float fx_t = (float)cam.tiles_x, fy_t = (float)cam.tiles_y;
+                const int x0 = (int)fminf(fmaxf(floorf((mx - rad) * inv), 0.0f), fx_t), x1 = (int)fminf(fmaxf(ceilf((mx + rad) * inv), 0.0f), fx_t);
+                const int y0 = (int)fminf(fmaxf(floorf((my - rad) * inv), 0.0f), fy_t), y1 = (int)fminf(fmaxf(ceilf((my + rad) * inv), 0.0f), fy_t);
+                touched = (int64_t)(x1 - x0) * (int64_t)(y1 - y0);
+                ok = touched > 0;
+                if (ok) {
+                    float dx = x - cam.cam[0], dy = y - cam.cam[1], dz = z - cam.cam[2];
+                    const float il = 1.0f / sqrtf((dx * dx + dy * dy) + dz * dz);
+                    dx *= il; dy *= il; dz *= il;
+                    float rgb[3];
+                    sh_colour(cam.degree, dc + 3 * i, sh_rest ? sh_rest + 3 * (int64_t)cam.K * i : nullptr, dx, dy, dz, rgb);
+                    float* o = splat + SPLAT_WORDS * i;
+                    o[0] = mx; o[1] = my;
+                    o[2] = c / det; o[3] = -b / det; o[4] = a / det;
+                    o[5] = 1.0f / (1.0f + expf(-raw_opacity[i]));
+                    o[6] = rgb[0]; o[7] = rgb[1]; o[8] = rgb[2];
+                    depth[i] = pz;
+                    rect[i] = make_ushort4((unsigned short)x0, (unsigned short)y0, (unsigned short)x1, (unsigned short)y1);
+                } else touched = 0;
+            }
+            counts[i] = touched;
+        }
+        const unsigned long long vis = __ballot(touched > 0);
+        if ((threadIdx.x & 63) == 0 && vis) atomicAdd(&counters[0], (unsigned long long)__popcll(vis));
+    }
+}
+
+// counts[n] is the slot behind the last splat: scanned with the rest, offsets[n] is the intersection total
+__global__ void k_raster_emit(int64_t n, int32_t tiles_x, const float* __restrict__ depth, const ushort4* __restrict__ rect,
+                              const int64_t* __restrict__ counts, const int64_t* __restrict__ offsets, int64_t total, uint64_t* __restrict__ keys,
+                              uint32_t* __restrict__ vals) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        if (counts[i] <= 0) continue;
+        const ushort4 r = rect[i];
+        const uint64_t d = (uint64_t)__float_as_uint(depth[i]);
+        int64_t o = offsets[i];
+        for (int ty = r.y; ty < r.w; ++ty)
+            for (int tx = r.x; tx < r.z; ++tx, ++o)
+                if (o < total) {                                       // cannot fail: the scan of these very counts sized the buffers
+                    keys[o] = ((uint64_t)(uint32_t)(ty * tiles_x + tx) << 32) | d;
+                    vals[o] = (uint32_t)i;
+                }
+    }
+}
+
+// ranges[2 t], ranges[2 t + 1]: first and one-past-last sorted position of tile t (zeroed before: an empty tile is [0, 0))
+__global__ void k_raster_ranges(int64_t total, int32_t n_tiles, const uint64_t* __restrict__ keys, int64_t* __restrict__ ranges,
+                                unsigned long long* __restrict__ counters) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const uint32_t t = (uint32_t)(keys[i] >> 32);
+        if (t >= (uint32_t)n_tiles) continue;
+        if (i == 0 || (uint32_t)(keys[i - 1] >> 32) != t) { ranges[2 * (int64_t)t] = i; atomicAdd(&counters[2], 1ull); }
+        if (i == total - 1 || (uint32_t)(keys[i + 1] >> 32) != t) ranges[2 * (int64_t)t + 1] = i + 1;
+    }
+}
+
+// One work-group per tile, one thread per pixel (wave w holds rows 4 w .. 4 w + 3).  Batches of 256 sorted splats are staged in
+// LDS (stride 9 words: conflict-free writes, broadcast reads); a wave whose ballot shows no live pixel skips the batch, and the
+// group leaves when all four say so.
+__global__ __launch_bounds__(BLEND_THREADS) void k_raster_blend(int32_t W, int32_t H, int32_t tiles_x, float bg0, float bg1, float bg2, int64_t n,
+                                                                const int64_t* __restrict__ ranges, const uint32_t* __restrict__ vals,
+                                                                const float* __restrict__ splat, float* __restrict__ image) {
+    __shared__ float s_splat[BLEND_THREADS * SPLAT_WORDS];
+    __shared__ int s_alive[BLEND_THREADS / 64];
+    const int t = threadIdx.x, wave = t >> 6;
+    const int tile = blockIdx.y * tiles_x + blockIdx.x;
+    const int ix = blockIdx.x * TILE + (t & (TILE - 1)), iy = blockIdx.y * TILE + (t >> 4);
+    const bool inside = ix < W && iy < H;
+    const float px = (float)ix + 0.5f, py = (float)iy + 0.5f;
+    const int64_t first = ranges[2 * (int64_t)tile], last = ranges[2 * (int64_t)tile + 1];
+    float T = 1.0f, r = 0.0f, g = 0.0f, b = 0.0f;
+    bool done = !inside;
+    for (int64_t base = first; base < last; base += BLEND_THREADS) {
+        const bool wave_alive = __ballot(!done) != 0ull;
+        if ((t & 63) == 0) s_alive[wave] = wave_alive ? 1 : 0;
+        const int64_t pos = base + t;
+        if (pos < last) {
+            const uint32_t id = vals[pos];
+            if ((int64_t)id < n) {
+                const float* src = splat + (int64_t)SPLAT_WORDS * id;
+#pragma unroll
+                for (int k = 0; k < SPLAT_WORDS; ++k) s_splat[SPLAT_WORDS * t + k] = src[k];
+            } else {                                               // never: an index the emit kernel did not write
+#pragma unroll
+                for (int k = 0; k < SPLAT_WORDS; ++k) s_splat[SPLAT_WORDS * t + k] = 0.0f;
+            }
+        }
+        __syncthreads();
+        if (!(s_alive[0] | s_alive[1] | s_alive[2] | s_alive[3])) break;
+        if (wave_alive) {
+            const int m = (int)((last - base) < (int64_t)BLEND_THREADS ? (last - base) : (int64_t)BLEND_THREADS);
+            for (int j = 0; j < m && !done; ++j) {
+                const float* s = s_splat + SPLAT_WORDS * j;
+                const float dx = s[0] - px, dy = s[1] - py;
+                const float sigma = 0.5f * (s[2] * dx * dx + s[4] * dy * dy) + s[3] * dx * dy;
+                if (sigma < 0.0f) continue;
+                const float alpha = fminf(0.999f, s[5] * expf(-sigma));
+                if (alpha < 1.0f / 255.0f) continue;
+                const float Tn = T * (1.0f - alpha);
+                if (Tn <= 1e-4f) { done = true; break; }
+                const float vis = alpha * T;
+                r = r + s[6] * vis; g = g + s[7] * vis; b = b + s[8] * vis;
+                T = Tn;
+            }
+        }
+        __syncthreads();
+    }
+    if (inside) {
+        float* o = image + 3 * ((int64_t)iy * W + ix);
+        o[0] = r + T * bg0; o[1] = g + T * bg1; o[2] = b + T * bg2;
+    }
+}
+
+}  // namespace
+
+struct gsr_raster_ctx {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    DevBuf splat, depth, rect, counts, offsets, keys, keys2, vals, vals2, ranges, tmp, counters;
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    bool timed = false;
+};
+
+extern "C" int32_t gsr_raster_create(gsr_raster_ctx** out, int32_t device, void* stream) {
+    if (!out) return fail(GSR_E_INVALID, "gsr_raster_create: out is NULL");
+    *out = nullptr;
+    GSR_TRY(open_device(device, "gsr_raster_create"));
+    gsr_raster_ctx* c = new gsr_raster_ctx();
+    c->device = device;
+    c->stream = (hipStream_t)stream;
+    for (hipEvent_t& e : c->ev)
+        if (hipEventCreate(&e) != hipSuccess) { e = nullptr; (void)gsr_raster_destroy(c); return fail(GSR_E_HIP, "gsr_raster_create: hipEventCreate failed"); }
+    *out = c;
+    return GSR_OK;
+}
+
+extern "C" int32_t gsr_raster_destroy(gsr_raster_ctx* c) {
+    if (!c) return GSR_OK;
+    (void)hipSetDevice(c->device);
+    (void)hipStreamSynchronize(c->stream);
+    DevBuf* all[] = {&c->splat, &c->depth, &c->rect, &c->counts, &c->offsets, &c->keys, &c->keys2, &c->vals, &c->vals2, &c->ranges, &c->tmp, &c->counters};
+    for (DevBuf* b : all) b->release();
+    for (hipEvent_t e : c->ev)
+        if (e) (void)hipEventDestroy(e);
+    delete c;
+    return GSR_OK;
+}
+
+extern "C" int32_t gsr_raster_render(gsr_raster_ctx* c, int64_t n, int32_t K, int32_t sh_degree, const float* xyz, const float* cov6, const float* raw_opacity,
+                                     const float* dc, const float* sh_rest, const float* viewmat, float fx, float fy, float cx, float cy, int32_t width,
+                                     int32_t height, const float* background, float radius_clip, float* image_out, int64_t* stats_out, void* stream) {
+    if (!c) return fail(GSR_E_INVALID, "gsr_raster_render: NULL context");
+    if (n < 0 || n >= ((int64_t)1 << 31) - 1) return fail(GSR_E_INVALID, "gsr_raster_render: n = %lld out of range", (long long)n);
+    if (sh_degree < 0 || sh_degree > 3 || K < (sh_degree + 1) * (sh_degree + 1) - 1)
+        return fail(GSR_E_INVALID, "gsr_raster_render: sh_degree %d needs %d rest coefficients, K = %d", sh_degree, (sh_degree + 1) * (sh_degree + 1) - 1, K);
+    if (width <= 0 || height <= 0 || width > 16 * 65535 || height > 16 * 65535) return fail(GSR_E_INVALID, "gsr_raster_render: bad image size %d x %d", width, height);
+    if (!viewmat || !background || !image_out || !(fx > 0.0f) || !(fy > 0.0f)) return fail(GSR_E_INVALID, "gsr_raster_render: NULL argument or focal length <= 0");
+    if (n > 0 && (!xyz || !cov6 || !raw_opacity || !dc || (sh_degree > 0 && !sh_rest))) return fail(GSR_E_INVALID, "gsr_raster_render: NULL array");
+    GSR_HIP(hipSetDevice(c->device));
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    c->timed = false;
+
+    RasterCam cam;
+    memset(&cam, 0, sizeof(cam));
+    for (int r = 0; r < 3; ++r) {
+        for (int q = 0; q < 3; ++q) cam.R[3 * r + q] = viewmat[4 * r + q];
+        cam.t[r] = viewmat[4 * r + 3];
+    }
+    for (int q = 0; q < 3; ++q)          // camera position = -R^T t, float64 from the float32 matrix, narrowed once
+        cam.cam[q] = (float)-((double)cam.R[q] * cam.t[0] + (double)cam.R[3 + q] * cam.t[1] + (double)cam.R[6 + q] * cam.t[2]);
+    cam.fx = fx; cam.fy = fy; cam.cx = cx; cam.cy = cy;
+    const float tan_x = 0.5f * (float)width / fx, tan_y = 0.5f * (float)height / fy;
+    cam.lim_xp = ((float)width - cx) / fx + 0.3f * tan_x;
+    cam.lim_xn = cx / fx + 0.3f * tan_x;
+    cam.lim_yp = ((float)height - cy) / fy + 0.3f * tan_y;
+    cam.lim_yn = cy / fy + 0.3f * tan_y;
+    cam.near_z = 0.01f; cam.far_z = 1e10f; cam.eps2d = 0.3f; cam.radius_clip = radius_clip;
+    cam.W = width; cam.H = height;
+    cam.tiles_x = (width + TILE - 1) / TILE; cam.tiles_y = (height + TILE - 1) / TILE;
+    cam.degree = sh_degree; cam.K = K;
+    const int64_t n_tiles = (int64_t)cam.tiles_x * cam.tiles_y;
+    if (n_tiles >= ((int64_t)1 << 31)) return fail(GSR_E_INVALID, "gsr_raster_render: %d x %d has %lld tiles, the tile index is 31 bits", width, height, (long long)n_tiles);
+    const size_t un = (size_t)n;
+
+    GSR_TRY(c->counters.reserve(4 * sizeof(unsigned long long)));
+    GSR_TRY(c->splat.reserve(un * SPLAT_WORDS * sizeof(float)));
+    GSR_TRY(c->depth.reserve(un * sizeof(float)));
+    GSR_TRY(c->rect.reserve(un * sizeof(ushort4)));
+    GSR_TRY(c->counts.reserve((un + 1) * sizeof(int64_t)));
+    GSR_TRY(c->offsets.reserve((un + 1) * sizeof(int64_t)));
+    GSR_TRY(c->ranges.reserve((size_t)n_tiles * 2 * sizeof(int64_t)));
+    size_t scan_bytes = 0;
+    GSR_HIP(rocprim::exclusive_scan(nullptr, scan_bytes, c->counts.as<int64_t>(), c->offsets.as<int64_t>(), (int64_t)0, un + 1, rocprim::plus<int64_t>(), st));
+    GSR_TRY(c->tmp.reserve(scan_bytes));
+
+    unsigned long long* counters = c->counters.as<unsigned long long>();
+    GSR_HIP(hipEventRecord(c->ev[0], st));
+    GSR_HIP(hipMemsetAsync(counters, 0, 4 * sizeof(unsigned long long), st));
+    GSR_HIP(hipMemsetAsync(c->counts.as<int64_t>() + n, 0, sizeof(int64_t), st));
+    GSR_HIP(hipMemsetAsync(c->ranges.p, 0, (size_t)n_tiles * 2 * sizeof(int64_t), st));
+    if (n > 0)
+        hipLaunchKernelGGL(k_raster_preprocess, dim3(stride_grid(n)), dim3(256), 0, st, n, cam, xyz, cov6, raw_opacity, dc, sh_rest, c->splat.as<float>(),
+                           c->depth.as<float>(), c->rect.as<ushort4>(), c->counts.as<int64_t>(), counters);
+    GSR_HIP(rocprim::exclusive_scan(c->tmp.p, scan_bytes, c->counts.as<int64_t>(), c->offsets.as<int64_t>(), (int64_t)0, un + 1, rocprim::plus<int64_t>(), st));
+    GSR_HIP(hipEventRecord(c->ev[1], st));
+    // the one host read-back: the total sizes the sort buffers
+    int64_t total = 0;
+    GSR_HIP(hipMemcpyAsync(&total, c->offsets.as<int64_t>() + n, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    GSR_HIP(hipStreamSynchronize(st));
+    if (total < 0) return fail(GSR_E_HIP, "gsr_raster_render: negative intersection count");
+    GSR_HIP(hipMemcpyAsync(counters + 1, &c->offsets.as<int64_t>()[n], sizeof(int64_t), hipMemcpyDeviceToDevice, st));
+
+    if (total > 0) {
+        int tile_bits = 0;
+        while (((int64_t)1 << tile_bits) < n_tiles) ++tile_bits;
+        const unsigned end_bit = 32u + (unsigned)(tile_bits > 0 ? tile_bits : 1);
+        const size_t ut = (size_t)total;
+        size_t sort_bytes = 0;
+        GSR_HIP(rocprim::radix_sort_pairs(nullptr, sort_bytes, c->keys.as<uint64_t>(), c->keys2.as<uint64_t>(), c->vals.as<uint32_t>(), c->vals2.as<uint32_t>(), ut,
+                                          0u, end_bit, st));
+        // what the sort still has to allocate, against what the device has free: an error with the count, not an abort
+        auto grow = [](const DevBuf& b, size_t bytes) { return bytes > b.cap ? bytes + bytes / 8 + 256 : (size_t)0; };
+        const size_t need = grow(c->keys, ut * 8) + grow(c->keys2, ut * 8) + grow(c->vals, ut * 4) + grow(c->vals2, ut * 4) + grow(c->tmp, sort_bytes);
+        const size_t given_back = (ut * 8 > c->keys.cap ? c->keys.cap : 0) + (ut * 8 > c->keys2.cap ? c->keys2.cap : 0) + (ut * 4 > c->vals.cap ? c->vals.cap : 0) +
+                                  (ut * 4 > c->vals2.cap ? c->vals2.cap : 0) + (sort_bytes > c->tmp.cap ? c->tmp.cap : 0);
+        size_t free_b = 0, total_b = 0;
+        GSR_HIP(hipMemGetInfo(&free_b, &total_b));
+        if (need > free_b + given_back)
+            return fail(GSR_E_HIP, "gsr_raster_render: %lld splat-tile intersections need %zu more bytes of sort buffers, the device has %zu free",
+                        (long long)total, need, free_b + given_back);
+        GSR_TRY(c->keys.reserve(ut * 8));
+        GSR_TRY(c->keys2.reserve(ut * 8));
+        GSR_TRY(c->vals.reserve(ut * 4));
+        GSR_TRY(c->vals2.reserve(ut * 4));
+        GSR_TRY(c->tmp.reserve(sort_bytes));
+        hipLaunchKernelGGL(k_raster_emit, dim3(stride_grid(n)), dim3(256), 0, st, n, cam.tiles_x, c->depth.as<float>(), c->rect.as<ushort4>(), c->counts.as<int64_t>(),
+                           c->offsets.as<int64_t>(), total, c->keys.as<uint64_t>(), c->vals.as<uint32_t>());
+        GSR_HIP(rocprim::radix_sort_pairs(c->tmp.p, sort_bytes, c->keys.as<uint64_t>(), c->keys2.as<uint64_t>(), c->vals.as<uint32_t>(), c->vals2.as<uint32_t>(), ut,
+                                          0u, end_bit, st));
+        hipLaunchKernelGGL(k_raster_ranges, dim3(stride_grid(total)), dim3(256), 0, st, total, (int32_t)n_tiles, c->keys2.as<uint64_t>(), c->ranges.as<int64_t>(), counters);
+    }
+    GSR_HIP(hipEventRecord(c->ev[2], st));
+    hipLaunchKernelGGL(k_raster_blend, dim3(cam.tiles_x, cam.tiles_y), dim3(BLEND_THREADS), 0, st, width, height, cam.tiles_x, background[0], background[1],
+                       background[2], n, c->ranges.as<int64_t>(), c->vals2.as<uint32_t>(), c->splat.as<float>(), image_out);
+    GSR_HIP(hipEventRecord(c->ev[3], st));
+    if (stats_out) GSR_HIP(hipMemcpyAsync(stats_out, counters, 3 * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
+    GSR_HIP(hipGetLastError());
+    c->timed = true;
+    return GSR_OK;
+}
+
+extern "C" int32_t gsr_raster_get_timing(gsr_raster_ctx* c, float* ms) {
+    if (!c || !ms) return fail(GSR_E_INVALID, "gsr_raster_get_timing: NULL argument");
+    if (!c->timed) return fail(GSR_E_INVALID, "gsr_raster_get_timing: no completed gsr_raster_render on this context");
+    GSR_HIP(hipSetDevice(c->device));
+    GSR_HIP(hipEventSynchronize(c->ev[3]));
+    for (int i = 0; i < 3; ++i) GSR_HIP(hipEventElapsedTime(&ms[i], c->ev[i], c->ev[i + 1]));
+    return GSR_OK;
+}
+
+// ---- image metrics ---------------------------------------------------------------------------------------------------------------
+namespace {
+
+constexpr int MT = 16, WIN = 11, HALO = 5, MTH = MT + 2 * HALO;       // 16 x 16 pixels per group, 26 x 26 with the halo
+
+struct SsimWindow { double w[WIN]; };
+
+// One group per 16 x 16 tile of one channel.  The halo of both images goes to LDS (zeros outside: the padding of the convolution),
+// a horizontal pass leaves the five moment rows (a, b, a a, b b, a b) in LDS, the vertical pass gives every pixel its SSIM term.
+// float64 throughout; the group's sums are folded in a fixed tree and written to partial[2 g], partial[2 g + 1].
+__global__ __launch_bounds__(MT * MT) void k_metrics_tiles(int32_t H, int32_t W, SsimWindow win, const float* __restrict__ A, const float* __restrict__ B,
+                                                           double* __restrict__ partial) {
+    __shared__ float s_a[MTH][MTH + 1], s_b[MTH][MTH + 1];
+    __shared__ double s_m[5][MTH][MT];
+    __shared__ double s_red[2][MT * MT];
+    const int t = threadIdx.x, lx = t & (MT - 1), ly = t >> 4;
+    const int x0 = blockIdx.x * MT, y0 = blockIdx.y * MT;
+    const int64_t plane = (int64_t)blockIdx.z * H * W;
+    for (int k = t; k < MTH * MTH; k += MT * MT) {
+        const int r = k / MTH, q = k - r * MTH;
+        const int y = y0 + r - HALO, x = x0 + q - HALO;
+        const bool in = y >= 0 && y < H && x >= 0 && x < W;
+        s_a[r][q] = in ? A[plane + (int64_t)y * W + x] : 0.0f;
+        s_b[r][q] = in ? B[plane + (int64_t)y * W + x] : 0.0f;
+    }
+    __syncthreads();
+    for (int k = t; k < MTH * MT; k += MT * MT) {
+        const int r = k / MT, q = k - r * MT;
+        double m0 = 0, m1 = 0, m2 = 0, m3 = 0, m4 = 0;
+        for (int j = 0; j < WIN; ++j) {
+            const double a = (double)s_a[r][q + j], b = (double)s_b[r][q + j], w = win.w[j];
+            m0 += w * a; m1 += w * b; m2 += w * (a * a); m3 += w * (b * b); m4 += w * (a * b);
+        }
+        s_m[0][r][q] = m0; s_m[1][r][q] = m1; s_m[2][r][q] = m2; s_m[3][r][q] = m3; s_m[4][r][q] = m4;
+    }
+    __syncthreads();
+    double ssim = 0.0, se = 0.0;
+    if (x0 + lx < W && y0 + ly < H) {
+        double m[5] = {0, 0, 0, 0, 0};
+        for (int j = 0; j < WIN; ++j)
+            for (int k = 0; k < 5; ++k) m[k] += win.w[j] * s_m[k][ly + j][lx];
+        const double mu1 = m[0], mu2 = m[1], mu1_sq = mu1 * mu1, mu2_sq = mu2 * mu2, mu12 = mu1 * mu2;
+        const double s1 = m[2] - mu1_sq, s2 = m[3] - mu2_sq, s12 = m[4] - mu12;
+        const double C1 = 0.01 * 0.01, C2 = 0.03 * 0.03;
+        ssim = ((2.0 * mu12 + C1) * (2.0 * s12 + C2)) / ((mu1_sq + mu2_sq + C1) * (s1 + s2 + C2));
+        const float d = s_a[ly + HALO][lx + HALO] - s_b[ly + HALO][lx + HALO];      // the difference in float32, as the reference takes it
+        se = (double)d * (double)d;
+    }
+    s_red[0][t] = ssim; s_red[1][t] = se;
+    __syncthreads();
+    for (int s = MT * MT / 2; s > 0; s >>= 1) {
+        if (t < s) { s_red[0][t] += s_red[0][t + s]; s_red[1][t] += s_red[1][t + s]; }
+        __syncthreads();
+    }
+    if (t == 0) {
+        const int64_t g = ((int64_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
+        partial[2 * g] = s_red[0][0]; partial[2 * g + 1] = s_red[1][0];
+    }
+}
+
+// second stage: one group, every thread a strided slice in ascending order, then the same fixed tree.  out = (mse, ssim)
+__global__ __launch_bounds__(256) void k_metrics_final(int64_t groups, double count, const double* __restrict__ partial, double* __restrict__ out) {
+    __shared__ double s_red[2][256];
+    const int t = threadIdx.x;
+    double a = 0.0, b = 0.0;
+    for (int64_t g = t; g < groups; g += 256) { a += partial[2 * g]; b += partial[2 * g + 1]; }
+    s_red[0][t] = a; s_red[1][t] = b;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (t < s) { s_red[0][t] += s_red[0][t + s]; s_red[1][t] += s_red[1][t + s]; }
+        __syncthreads();
+    }
+    if (t == 0) { out[0] = s_red[1][0] / count; out[1] = s_red[0][0] / count; }
+}
+
+}  // namespace
+
+extern "C" int32_t gsr_image_metrics(const float* a, const float* b, int32_t height, int32_t width, int32_t on_device, double* out, int32_t device, void* stream) {
+    if (!a || !b || !out || height <= 0 || width <= 0) return fail(GSR_E_INVALID, "gsr_image_metrics: bad argument");
+    GSR_TRY(open_device(device, "gsr_image_metrics"));
+    SsimWindow win;
+    double sum = 0.0;
+    for (int j = 0; j < WIN; ++j) { win.w[j] = exp(-(double)((j - WIN / 2) * (j - WIN / 2)) / (2.0 * 1.5 * 1.5)); sum += win.w[j]; }
+    for (int j = 0; j < WIN; ++j) win.w[j] /= sum;
+    const size_t bytes = (size_t)3 * (size_t)height * (size_t)width * sizeof(float);
+    const dim3 grid((width + MT - 1) / MT, (height + MT - 1) / MT, 3);
+    if (grid.y > 65535u) return fail(GSR_E_INVALID, "gsr_image_metrics: image too tall");
+    const int64_t groups = (int64_t)grid.x * grid.y * grid.z;
+    double host[2] = {0.0, 0.0};
+    {
+        OneShot os((hipStream_t)stream, on_device != 0, "gsr_image_metrics");
+        const float *da = nullptr, *db = nullptr;
+        double *partial = nullptr, *res = nullptr;
+        GSR_TRY(os.in(a, bytes, &da));
+        GSR_TRY(os.in(b, bytes, &db));
+        GSR_TRY(os.scratch((size_t)groups * 2 * sizeof(double), &partial));
+        GSR_TRY(os.scratch(2 * sizeof(double), &res));
+        hipLaunchKernelGGL(k_metrics_tiles, grid, dim3(MT * MT), 0, os.st, height, width, win, da, db, partial);
+        hipLaunchKernelGGL(k_metrics_final, dim3(1), dim3(256), 0, os.st, groups, 3.0 * (double)height * (double)width, partial, res);
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(host, res, sizeof(host), hipMemcpyDeviceToHost, os.st);
+        GSR_TRY(os.wait(e));
+    }
+    out[0] = host[0]; out[1] = host[1];
+    return GSR_OK;
+}

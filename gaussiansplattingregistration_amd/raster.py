@@ -1,0 +1,103 @@
+"""ctypes front of the splat rasteriser and the image metrics (``csrc/raster.hip``; ``gsr_raster_*``, ``gsr_image_metrics``).
+
+``RasterContext`` owns the library's grow-only workspaces; ``render`` takes the SoA arrays ``GaussianModel`` holds, as CUDA tensors
+(zero-copy) or as host arrays (uploaded through torch first: the library's render entry takes device pointers only).  No GPU:
+``RuntimeError`` -- there is no CPU fallback.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import _lib
+from . import _marshal as _m
+
+
+class RasterContext:
+    def __init__(self, device: int = 0):
+        self._L = _lib.load(require_device=True)
+        self.device = int(device)
+        self._h = C.c_void_p()
+        _lib.check(self._L.gsr_raster_create(C.byref(self._h), self.device, None), "gsr_raster_create")
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            self._L.gsr_raster_destroy(self._h)
+            self._h = C.c_void_p()
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def render(self, xyz, cov6, raw_opacity, dc, sh_rest, sh_degree, viewmat, fx, fy, cx, cy, width, height, background=(0.0, 0.0, 0.0),
+               radius_clip=3.0, with_stats=False):
+        """-> image ``(H, W, 3)`` float32 CUDA tensor [, stats int64 CUDA tensor (visible splats, intersections, non-empty tiles)].
+        ``sh_rest`` is ``(n, K, 3)`` (or ``(n, 3K)`` coefficient-major); ``viewmat`` the 4x4 world -> camera matrix."""
+        dev = torch.device("cuda", self.device)
+
+        def up(a, shape):
+            t = a if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a, dtype=np.float32))
+            return t.detach().to(device=dev, dtype=torch.float32).reshape(shape).contiguous()
+        n = int(xyz.shape[0])
+        sh_degree = int(sh_degree)
+        K = 0 if sh_rest is None else int(np.prod(tuple(sh_rest.shape)[1:])) // 3
+        t_xyz, t_cov, t_op, t_dc = up(xyz, (n, 3)), up(cov6, (n, 6)), up(raw_opacity, (n,)), up(dc, (n, 3))
+        t_sh = up(sh_rest, (n, 3 * K)) if K else None
+        V = (C.c_float * 16)(*np.asarray(viewmat.detach().cpu() if isinstance(viewmat, torch.Tensor) else viewmat, dtype=np.float32).reshape(16))
+        bg = (C.c_float * 3)(*np.asarray(background, dtype=np.float32).reshape(3))
+        image = torch.empty((int(height), int(width), 3), dtype=torch.float32, device=dev)
+        stats = torch.zeros(3, dtype=torch.int64, device=dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(self._L.gsr_raster_render(self._h, n, K, sh_degree, t_xyz.data_ptr(), t_cov.data_ptr(), t_op.data_ptr(), t_dc.data_ptr(),
+                                             t_sh.data_ptr() if K else None, V, float(fx), float(fy), float(cx), float(cy), int(width), int(height), bg,
+                                             float(radius_clip), image.data_ptr(), stats.data_ptr(), C.c_void_p(stream)), "gsr_raster_render")
+        self._keep = (t_xyz, t_cov, t_op, t_dc, t_sh)         # alive until the next render: the blend is still enqueued
+        return (image, stats) if with_stats else image
+
+    def timing(self):
+        """-> {"preprocess", "sort", "blend"} milliseconds of the last render (device events; waits for it)."""
+        ms = (C.c_float * 3)()
+        _lib.check(self._L.gsr_raster_get_timing(self._h, ms), "gsr_raster_get_timing")
+        return {"preprocess": float(ms[0]), "sort": float(ms[1]), "blend": float(ms[2])}
+
+
+_contexts = {}
+
+
+def context(device: int = 0) -> RasterContext:
+    """The process-wide context of a device (workspaces are reused from image to image)."""
+    if device not in _contexts:
+        _contexts[device] = RasterContext(device)
+    return _contexts[device]
+
+
+def render_model(model, viewmat, fx, fy, cx, cy, width, height, background=(0.0, 0.0, 0.0), scale=1.0, radius_clip=3.0, device=0, with_stats=False):
+    """One image of a ``GaussianModel`` (its covariances times ``scale``^2, as ``get_full_covariance(scale)`` gives them)."""
+    full = model.get_full_covariance(scale)
+    cov6 = torch.stack([full[:, 0, 0], full[:, 0, 1], full[:, 0, 2], full[:, 1, 1], full[:, 1, 2], full[:, 2, 2]], dim=1)
+    return context(device).render(model.get_xyz, cov6, model.get_raw_opacity, model.get_colors, model._features_rest, model.sh_degree, viewmat, fx, fy,
+                                  cx, cy, width, height, background, radius_clip, with_stats)
+
+
+def image_metrics(a, b, device=None):
+    """-> (mse, ssim) as Python floats (the kernel's float64 sums) of two ``(3, H, W)`` float32 images, host arrays or CUDA tensors."""
+    L = _lib.load(require_device=True)
+    if tuple(a.shape) != tuple(b.shape) or len(a.shape) != 3 or a.shape[0] != 3:
+        raise ValueError(f"image_metrics takes two (3, H, W) images, got {tuple(a.shape)} and {tuple(b.shape)}")
+    _, H, W = (int(s) for s in a.shape)
+    if device is None:
+        device = a.device.index if _m.is_cuda(a) else b.device.index if _m.is_cuda(b) else 0
+    if _m.is_cuda(a) != _m.is_cuda(b):             # one side on the device: bring the other there
+        dev = torch.device("cuda", device)
+        a, b = (torch.as_tensor(np.asarray(t, dtype=np.float32)).to(dev) if not _m.is_cuda(t) else t for t in (a, b))
+    pa, ka, on = _m.prep(a, (3, H, W), np.float32, device)
+    pb, kb, _ = _m.prep(b, (3, H, W), np.float32, device)
+    out = (C.c_double * 2)()
+    _lib.check(L.gsr_image_metrics(pa, pb, H, W, 1 if on else 0, out, device, C.c_void_p(_m.stream_ptr(device, on))), "gsr_image_metrics")
+    return float(out[0]), float(out[1])

@@ -628,6 +628,38 @@ int32_t gsr_fgr_tuple_test(const float* src_xyz, int64_t ns, const float* tgt_xy
 int32_t gsr_fgr_optimize(const float* src_xyz, int64_t ns, const float* tgt_xyz, int64_t nt, const int32_t* corres, int64_t m,
                          const gsr_fgr_options* options, gsr_fgr_result* result, int32_t on_device, int32_t device, void* stream);
 
+/* ------------------------------------------------------------------- splat rasteriser and image metrics (evaluation) */
+
+/* Forward tile rasteriser of a splat model for one pinhole camera: what the reference's Evaluation tab asks of gsplat's
+ * rasterization(covars=..., render_mode="RGB", packed=True, radius_clip=3) (src/utils/rasterization_util.py:13-29).  csrc/raster.hip;
+ * the semantics are listed in DESIGN.md section 14 and restated in tests/raster_model.py.  gsplat is not available on ROCm: parity
+ * with it is unpinned.  The context owns grow-only workspaces (nothing is allocated in steady state); one render at a time per context. */
+typedef struct gsr_raster_ctx gsr_raster_ctx;
+int32_t gsr_raster_create(gsr_raster_ctx** out, int32_t device, void* stream);
+int32_t gsr_raster_destroy(gsr_raster_ctx* ctx);
+/* One RGB image.  All arrays are DEVICE pointers in the layout GaussianModel holds: xyz[n*3], cov6[n*6] (xx,xy,xz,yy,yz,zz),
+ * raw_opacity[n] (pre-sigmoid), dc[n*3], sh_rest[n*3K] coefficient-major (NULL when sh_degree = 0); K = rest coefficients per channel
+ * stored per splat (>= (sh_degree+1)^2 - 1), sh_degree 0..3 = bands evaluated.  viewmat[16] (world -> camera, row-major), background[3]:
+ * host.  Fixed: near 0.01, far 1e10, 0.3 px dilation, 16 x 16 tiles, classic (not antialiased) mode; radius_clip: splats whose integer
+ * 3-sigma radius is <= it are dropped (the reference passes 3).  image_out[height*width*3] float32 (device), not clamped above.
+ * stats_out (device, 3 x int64, or NULL): visible splats, splat-tile intersections, non-empty tiles.  Enqueued on `stream` (NULL: the
+ * context's); the call waits for the stream ONCE, in the middle, to read the intersection total that sizes the sort buffers, and
+ * returns with the blend enqueued.  If those buffers exceed the device's free memory: GSR_E_HIP with the count in the message.  No
+ * float atomics: the same inputs give the same bits. */
+int32_t gsr_raster_render(gsr_raster_ctx* ctx, int64_t n, int32_t K, int32_t sh_degree, const float* xyz, const float* cov6,
+                          const float* raw_opacity, const float* dc, const float* sh_rest, const float* viewmat, float fx, float fy,
+                          float cx, float cy, int32_t width, int32_t height, const float* background, float radius_clip,
+                          float* image_out, int64_t* stats_out, void* stream);
+/* ms[3]: preprocess + scan, key emission + sort + tile ranges (the host wait included), blend, of the last render; waits for it. */
+int32_t gsr_raster_get_timing(gsr_raster_ctx* ctx, float* ms);
+
+/* MSE and SSIM of two (3, height, width) float32 images as the reference's src/utils/evaluation_utils.py defines them: SSIM with the
+ * 11 x 11 Gaussian window (sigma 1.5, product of the normalised 1-D window), zero padding 5, C1 = 0.01^2, C2 = 0.03^2, mean over all
+ * channels and pixels; MSE the mean of the squared float32 differences.  One fused kernel (separable window through LDS, float64)
+ * and a fixed-order two-stage float64 reduction.  a, b on the host or the device as on_device says; out[2] = (mse, ssim), host. */
+int32_t gsr_image_metrics(const float* a, const float* b, int32_t height, int32_t width, int32_t on_device, double* out, int32_t device,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif

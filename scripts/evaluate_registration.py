@@ -1,0 +1,67 @@
+"""Image-based evaluation of a registration result, headless: the reference's Evaluation tab without the GUI.
+
+    python scripts/evaluate_registration.py a.ply b.ply --transform T.txt --cameras cameras.json --images DIR --log out.json
+                                            [--rotate-sh] [--save-renders DIR] [--background R G B] [--cpu-metrics]
+
+``a.ply`` is moved by the 4x4 in ``T.txt`` (whitespace-separated, row-major) and merged with ``b.ply``; the merged model is rendered
+from every camera of ``cameras.json`` (the file a 3DGS training run writes) and compared with ``DIR/<img_name>.png``.  The log has the
+reference's fields: registration_data, mse, rmse, ssim, psnr, lpips (null: no LPIPS weights here), error_list.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("first")
+    ap.add_argument("second")
+    ap.add_argument("--transform", required=True)
+    ap.add_argument("--cameras", required=True)
+    ap.add_argument("--images", required=True)
+    ap.add_argument("--log", required=True)
+    ap.add_argument("--rotate-sh", action="store_true", help="turn the SH coefficients of the first cloud with it")
+    ap.add_argument("--save-renders", metavar="DIR", help="write every render as DIR/<img_name>.png")
+    ap.add_argument("--background", type=float, nargs=3, default=(0.0, 0.0, 0.0))
+    ap.add_argument("--cpu-metrics", action="store_true", help="use_gpu=False: the metrics in host torch arithmetic")
+    a = ap.parse_args()
+    import __graft_entry__ as g
+    g.build_hip()
+    from gaussiansplattingregistration_amd.controllers.registration_controller import RegistrationController
+    from gaussiansplattingregistration_amd.models.camera import load_cameras
+    from gaussiansplattingregistration_amd.models.data_repository import DataRepository, UIStateRepository
+    from gaussiansplattingregistration_amd.models.gaussian_model import GaussianModel
+    from gaussiansplattingregistration_amd.workers.evaluator import RegistrationEvaluator
+    repo, ui = DataRepository(), UIStateRepository()
+    repo.pc_gaussian_list_first.append(GaussianModel("cuda:0").from_ply(a.first))
+    repo.pc_gaussian_list_second.append(GaussianModel("cuda:0").from_ply(a.second))
+    ui.transformation_matrix = np.loadtxt(a.transform, dtype=np.float64).reshape(4, 4)
+    cameras = load_cameras(a.cameras)
+    if a.save_renders:
+        # the controller's call with a hook on the worker: the same evaluation, the renders kept
+        os.makedirs(a.save_renders, exist_ok=True)
+        from PIL import Image
+
+        def keep(camera, render):
+            img = render[0].clamp(0, 1).mul(255).add(0.5).floor().to("cpu").numpy().astype(np.uint8)
+            Image.fromarray(img).save(os.path.join(a.save_renders, camera.image_name + ".png"))
+        worker = RegistrationEvaluator(repo.pc_gaussian_list_first[0], repo.pc_gaussian_list_second[0], ui.transformation_matrix, cameras, a.images, a.log,
+                                       tuple(a.background), None, not a.cpu_metrics, rotate_sh=a.rotate_sh)
+        worker.on_render = keep
+        result = worker.run()
+    else:
+        result = RegistrationController(repo, ui).evaluate_registration(cameras, a.images, a.log, tuple(a.background), not a.cpu_metrics, rotate_sh=a.rotate_sh)
+    print(json.dumps({"cameras": len(cameras), "mse": result.mse, "rmse": result.rmse, "psnr": result.psnr, "ssim": result.ssim, "lpips": result.lpips,
+                      "errors": len(result.error_list), "log": a.log}))
+
+
+if __name__ == "__main__":
+    main()
