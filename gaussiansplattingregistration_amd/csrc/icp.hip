@@ -21,6 +21,8 @@
 //   estimators              point-to-point (Umeyama), point-to-plane, generalized ICP (W = (Ct + R Cs R^T)^-1/2 per
 //                           pair, float64 Jacobi), colored ICP (k_icp_color_gradient prepares the target: 30 nearest
 //                           neighbours within 2 max_corr, tangent-plane intensity gradient); robust kernel weights
+//   k_icp_accumulate_dev    the same pass for the device-resident loop: T from the device state, the source dealt to the XCDs in
+//                           contiguous eighths; eight instantiations (estimator x 27-cell block search)
 //   k_icp_step              device-resident loop: reduces the partials, tests convergence, solves (3x3 Jacobi SVD /
 //                           6x6 LDL^T) and updates T; the host enqueues chunks of iterations
 //   host (this file)        the same solve for the multi-GPU source split (all-reduce callback of 32 doubles).
@@ -196,18 +198,6 @@ __global__ __launch_bounds__(256) void k_icp_cell_starts(int64_t m, const unsign
         if (j == m - 1)
             for (int64_t c = (int64_t)k + 1; c <= nkeys; ++c) start[c] = (int)m;
     }
-}
-
-// sum over the cells of (points in the cell)^2 = n * (the occupancy of the cell an average POINT sits in): 3 for a uniform cloud at two
-// points per cell, hundreds when most points sit in clumps the box-volume rule does not see
-__global__ __launch_bounds__(256) void k_icp_occupancy(int64_t ncells, const int* __restrict__ cellStart, unsigned long long* __restrict__ out) {
-    unsigned long long acc = 0;
-    for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < ncells; k += (int64_t)gridDim.x * blockDim.x) {
-        const unsigned long long len = (unsigned long long)(cellStart[k + 1] - cellStart[k]);
-        acc += len * len;
-    }
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
-    if ((threadIdx.x & 63) == 0 && acc) atomicAdd(out, acc);
 }
 
 __global__ __launch_bounds__(256) void k_icp_gather_target(int64_t n, const unsigned* __restrict__ order,
@@ -449,8 +439,6 @@ __device__ __forceinline__ IcpRange icp_block_range(int64_t ns, int nb, bool rem
 struct IcpState;
 __device__ __forceinline__ bool icp_state_done(const IcpState* st);
 __device__ __forceinline__ void icp_state_T(const IcpState* st, double T[12]);
-template <int THREADS, bool SC1 = false> __device__ __forceinline__ void icp_fold_partials(int nblocks, const double* partials, const double* __restrict__ reduced, double (*s_x)[32]);
-__device__ __forceinline__ void icp_step_solve(const double* acc32, const IcpState& s_st, IcpState* st);
 
 // nn_j[i] = sorted target position of the accepted nearest neighbour of source point i, or -1.  One thread per source
 // point: a search kernel with few registers (56 VGPRs, 8 waves per SIMD) in front of a streaming accumulate kernel.
@@ -477,133 +465,6 @@ __global__ __launch_bounds__(256) void k_icp_nn(int64_t ns, const float* __restr
         double d2;
         const int j = icp_nearest<BLOCK>(g, cellStart, Tq, px, py, pz, d2, max_corr2);
         nn_j[i] = (j >= 0 && d2 < max_corr2) ? j : -1;
-    }
-}
-
-// The search of a FINE level (rings == 1: the correspondence distance is at most one cell, so the 27 cells around the query's hold every
-// neighbour that can be accepted) over an LDS-staged tile.  k_icp_nn walks the grid per thread: 27 cell spans, two dependent table
-// look-ups and a chain of point loads each, every lane with its own trip counts -- 24 % of the lanes at work, ~3 000 issue slots per
-// query (profiles/archive/r04t_pmc_icp.json).  The source is sorted by the target's cells, so the 256 queries of a workgroup sit in a run of
-// consecutive cells: ONE box of cells [xlo, xhi] x [ylo, yhi] x [zlo, zhi] around their cells (+ 1 ring) holds all their candidates.
-// Its rows are contiguous runs of the cell-sorted target: the workgroup copies them into LDS with coalesced loads (and the rows' cell
-// table with them), and every lane then scans its 3 x 3 spans of three cells from LDS.  Same candidates, same float64 distance, same
-// tie rule (lowest input index): the same neighbour as icp_nearest<0>, whatever the order.  A workgroup whose box does not fit (more
-// than ICP_TILE_ROWS rows or ICP_TILE_PTS points: queries far apart -- the ends of a level's source, a source that moved by cells)
-// searches the old way.
-#define ICP_TILE_ROWS 16
-#define ICP_TILE_PTS 3840
-#define ICP_TILE_XW 256
-#define ICP_TILE_LDS (ICP_TILE_PTS * 16 + ICP_TILE_ROWS * ICP_TILE_XW * 4)
-template <bool FROM_STATE>
-__global__ __launch_bounds__(256) void k_icp_nn_tile(int64_t ns, const float* __restrict__ src, Xform X, const IcpState* __restrict__ st,
-                                                     IcpGrid g, const int* __restrict__ cellStart, const float4* __restrict__ Tq,
-                                                     double max_corr2, int* __restrict__ nn_j, int nb_logical) {
-    extern __shared__ float4 s_dyn[];
-    float4* s_pts = s_dyn;                                             // the staged target points of the box, row after row
-    int* s_cs = reinterpret_cast<int*>(s_dyn + ICP_TILE_PTS);          // [rows][xw + 1]: cell starts as indices into s_pts
-    __shared__ int s_box[6];                                           // min / max cell of the workgroup's queries
-    __shared__ int s_gs[ICP_TILE_ROWS], s_off[ICP_TILE_ROWS + 1];      // a row's first point in Tq / in s_pts
-    __shared__ int s_ok;
-    double T[12];
-    if (FROM_STATE) {
-        if (icp_state_done(st)) return;
-        icp_state_T(st, T);
-    } else {
-#pragma unroll
-        for (int i = 0; i < 12; ++i) T[i] = X.m[i];
-    }
-    const IcpRange rg = icp_block_range(ns, nb_logical < 0 ? -nb_logical : nb_logical, nb_logical > 0);
-    if (rg.row < 0) return;
-    for (int64_t base = rg.lo; base < rg.hi; base += blockDim.x) {
-        const int64_t i = base + threadIdx.x;
-        const bool live = i < rg.hi;
-        double px = 0.0, py = 0.0, pz = 0.0;
-        int cx = 0, cy = 0, cz = 0;
-        bool finite = false;
-        if (live) {
-            const double x = (double)src[3 * i], y = (double)src[3 * i + 1], z = (double)src[3 * i + 2];
-            px = T[0] * x + T[1] * y + T[2] * z + T[3];
-            py = T[4] * x + T[5] * y + T[6] * z + T[7];
-            pz = T[8] * x + T[9] * y + T[10] * z + T[11];
-            finite = px == px && py == py && pz == pz;
-            cx = icp_cell(px, g.ox, g.inv_c, g.gx); cy = icp_cell(py, g.oy, g.inv_c, g.gy); cz = icp_cell(pz, g.oz, g.inv_c, g.gz);
-        }
-        if (threadIdx.x < 3) { s_box[threadIdx.x] = 0x7fffffff; s_box[3 + threadIdx.x] = -1; }
-        __syncthreads();
-        if (live && finite) {
-            atomicMin(&s_box[0], cx); atomicMin(&s_box[1], cy); atomicMin(&s_box[2], cz);
-            atomicMax(&s_box[3], cx); atomicMax(&s_box[4], cy); atomicMax(&s_box[5], cz);
-        }
-        __syncthreads();
-        const int xlo = s_box[0] - 1 > 0 ? s_box[0] - 1 : 0, xhi = s_box[3] + 1 < g.gx - 1 ? s_box[3] + 1 : g.gx - 1;
-        const int ylo = s_box[1] - 1 > 0 ? s_box[1] - 1 : 0, yhi = s_box[4] + 1 < g.gy - 1 ? s_box[4] + 1 : g.gy - 1;
-        const int zlo = s_box[2] - 1 > 0 ? s_box[2] - 1 : 0, zhi = s_box[5] + 1 < g.gz - 1 ? s_box[5] + 1 : g.gz - 1;
-        const int ny = yhi - ylo + 1, nz = zhi - zlo + 1, xw = xhi - xlo + 1;
-        const int rows = s_box[3] < 0 ? 0 : ny * nz;                    // (no finite query at all: nothing to stage)
-        bool ok = rows > 0 && rows <= ICP_TILE_ROWS && xw + 1 <= ICP_TILE_XW;
-        if (ok && (int)threadIdx.x < rows) {
-            const int y = ylo + (int)threadIdx.x % ny, z = zlo + (int)threadIdx.x / ny;
-            const int rowbase = (z * g.gy + y) * g.gx;
-            s_gs[threadIdx.x] = cellStart[rowbase + xlo];
-            s_off[threadIdx.x + 1] = cellStart[rowbase + xhi + 1] - s_gs[threadIdx.x];       // (its length for now)
-        }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            int tot = 0;
-            s_off[0] = 0;
-            if (ok) for (int r = 0; r < rows; ++r) { const int len = s_off[r + 1]; s_off[r + 1] = tot + len; tot += len; }
-            s_ok = ok && tot <= ICP_TILE_PTS ? 1 : 0;
-        }
-        __syncthreads();
-        ok = s_ok != 0;
-        int best = -1;
-        double bd = max_corr2;
-        if (ok) {
-            // the box's points and its cell table into LDS: contiguous runs of Tq / cellStart, consecutive lanes on consecutive addresses
-            const int total = s_off[rows];
-            for (int t = threadIdx.x; t < total; t += blockDim.x) {
-                int r = 0;
-                while (t >= s_off[r + 1]) ++r;
-                s_pts[t] = Tq[s_gs[r] + (t - s_off[r])];
-            }
-            for (int t = threadIdx.x; t < rows * (xw + 1); t += blockDim.x) {
-                const int r = t / (xw + 1), x = t - r * (xw + 1);
-                const int y = ylo + r % ny, z = zlo + r / ny;
-                s_cs[t] = cellStart[(z * g.gy + y) * g.gx + xlo + x] - s_gs[r] + s_off[r];
-            }
-            __syncthreads();
-            if (live && finite) {
-                unsigned best_i = 0xffffffffu;
-                int bk = -1, br = 0;
-                const int xa = (cx - 1 > 0 ? cx - 1 : 0) - xlo, xb = (cx + 1 < g.gx - 1 ? cx + 1 : g.gx - 1) - xlo;
-#pragma unroll 1
-                for (int dz = -1; dz <= 1; ++dz) {
-                    const int z = cz + dz;
-                    if (z < 0 || z >= g.gz) continue;
-#pragma unroll 1
-                    for (int dy = -1; dy <= 1; ++dy) {
-                        const int y = cy + dy;
-                        if (y < 0 || y >= g.gy) continue;
-                        const int r = (z - zlo) * ny + (y - ylo);
-                        const int s = s_cs[r * (xw + 1) + xa], e = s_cs[r * (xw + 1) + xb + 1];
-                        for (int k = s; k < e; ++k) {
-                            const float4 q = s_pts[k];
-                            const double dx = px - (double)q.x, dyy = py - (double)q.y, dzz = pz - (double)q.z;
-                            const double d2 = dx * dx + dyy * dyy + dzz * dzz;
-                            const unsigned qi = __float_as_uint(q.w);
-                            if (d2 < bd || (d2 == bd && qi < best_i)) { bd = d2; bk = k; br = r; best_i = qi; }
-                        }
-                    }
-                }
-                if (bk >= 0) best = s_gs[br] + (bk - s_off[br]);
-            }
-        } else if (live) {
-            double d2;
-            best = icp_nearest<0>(g, cellStart, Tq, px, py, pz, d2, max_corr2);
-            bd = d2;
-        }
-        if (live) nn_j[i] = (best >= 0 && bd < max_corr2) ? best : -1;
-        __syncthreads();
     }
 }
 
@@ -867,9 +728,7 @@ __device__ __forceinline__ double wave_sum_d(double v) {
     return v;
 }
 
-// WT: the partials leave with write-through (sc1) stores -- what a workgroup that hands them to another workgroup of the SAME
-// launch must use (k_icp_accumulate_dev's fused step); plain stores otherwise (the reader is a later kernel)
-template <int NACC, bool WT = false>
+template <int NACC>
 __device__ __forceinline__ void block_reduce_store(double (&acc)[NACC], double* __restrict__ partials, int row = -1) {
     if (row < 0) row = (int)blockIdx.x;
     __shared__ double s_red[4][NACC];
@@ -883,8 +742,7 @@ __device__ __forceinline__ void block_reduce_store(double (&acc)[NACC], double* 
     if (threadIdx.x < NACC) {
         const int k = threadIdx.x;
         const double v = ((s_red[0][k] + s_red[1][k]) + s_red[2][k]) + s_red[3][k];
-        if (WT) __hip_atomic_store(partials + (int64_t)row * GSR_ICP_ACC_LEN + k, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        else partials[(int64_t)row * GSR_ICP_ACC_LEN + k] = v;
+        partials[(int64_t)row * GSR_ICP_ACC_LEN + k] = v;
     }
 }
 
@@ -1129,56 +987,24 @@ __device__ __forceinline__ void icp_state_T(const IcpState* st, double T[12]) {
     for (int i = 0; i < 12; ++i) T[i] = st->T[i];
 }
 
-// FUSE: what the LAST workgroup to finish does with the block partials (it learns that it is the last from a device-scope
-// ticket; release / acquire at agent scope around it as MI355X_MICROARCH.md prescribes for a cross-CU hand-off):
-//   0  nothing (k_icp_reduce / k_icp_step follow as their own launches)
-//   1  the whole step -- fold the partials in k_icp_finalize's order, test convergence, solve, update T: ONE launch per ICP
-//      iteration instead of two (a coarse level's iteration was 36 us + 8.5 us of k_icp_step and its launch gap)
-//   2  fold the partials into acc_out (the rank-local vector of a multi-GPU source split; the all-reduce and k_icp_step follow)
-// (FUSE is a template parameter: the step's code costs the kernel ~24 VGPRs, and with them a wave per SIMD on the levels whose
-// blocks just fill the chip once; the bound of 3 waves per SIMD keeps the fused forms at <= 168 registers -- whatever does not
-// fit spills in the step's code, which one workgroup runs once)
-template <int KIND, int BLOCK, int FUSE>
-__global__ __launch_bounds__(256, (FUSE != 0 && KIND != 2) ? 3 : 1) void k_icp_accumulate_dev(int64_t ns, const float* __restrict__ src, IcpState* st,
+// One evaluation of the device-resident loop: the block partials of this iteration's sums, by logical block.  k_icp_step (single
+// GPU) or k_icp_reduce + the all-reduce + k_icp_step (multi-GPU source split) follow as their own launches.
+template <int KIND, int BLOCK>
+__global__ __launch_bounds__(256, 1) void k_icp_accumulate_dev(int64_t ns, const float* __restrict__ src, IcpState* st,
                                                             IcpGrid g, const int* __restrict__ cellStart, const int* __restrict__ nn_j,
                                                             const float4* __restrict__ Tq, const double* __restrict__ Tn,
                                                             const double* __restrict__ Sc, ColorArgs ca, double max_corr2,
-                                                            int loss, double kparam, double* partials, unsigned* ticket,
-                                                            double* acc_out, int nb_logical) {
-    constexpr int fuse = FUSE;
-    // FUSE == 3: the RESIDENT form (GSR_ICP_PERSISTENT=1, a cooperative launch: every workgroup is on the chip).  The workgroups stay
-    // for the whole registration: evaluate, arrive at a device-scope ticket, the last one folds + solves + publishes a generation
-    // word, the others spin on it (s_sleep, bounded), everybody reads the new transform and goes again.  ticket[0] = arrivals
-    // (monotonic), ticket[1] = generation, ticket[2] = "a spin ran out" (the host reports it).
-    constexpr bool PERSIST = FUSE == 3;
+                                                            int loss, double kparam, double* partials, int nb_logical) {
     constexpr int NACC = KIND == 0 ? 17 : 30;
-    __shared__ int s_last;
-    __shared__ int s_stop;
-    __shared__ double s_x[8][GSR_ICP_ACC_LEN];
-    __shared__ IcpState s_st;
-    const IcpRange rg = icp_block_range(ns, nb_logical < 0 ? -nb_logical : nb_logical, FUSE == 0 && nb_logical > 0);
-    for (unsigned ev = 0;; ++ev) {
+    const IcpRange rg = icp_block_range(ns, nb_logical < 0 ? -nb_logical : nb_logical, nb_logical > 0);
+    if (st->done) return;                           // converged: nothing to search
     double T[12];
-    if constexpr (PERSIST) {
-        // the state another workgroup wrote: agent-scope loads (past the L1 and the scalar cache), behind the acquire of the spin
-        if (threadIdx.x == 0) s_stop = __hip_atomic_load(&st->done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) | (int)__hip_atomic_load(ticket + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __syncthreads();
-        if (s_stop) return;
-#pragma unroll
-        for (int i = 0; i < 12; ++i) T[i] = __hip_atomic_load(&st->T[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    } else {
-    if (st->done) {
-        // converged: nothing to search.  The ranks of a multi-GPU run still meet in the collective: zeros
-        if (fuse == 2 && blockIdx.x == 0 && threadIdx.x < GSR_ICP_ACC_LEN) acc_out[threadIdx.x] = 0.0;
-        return;
-    }
 #pragma unroll
     for (int i = 0; i < 12; ++i) T[i] = st->T[i];
-    }
     double acc[NACC];
 #pragma unroll
     for (int k = 0; k < NACC; ++k) acc[k] = 0.0;
-    if (rg.row < 0) return;                         // (a padding workgroup of the XCD mapping; FUSE != 0 launches none)
+    if (rg.row < 0) return;                         // (a padding workgroup of the XCD mapping)
     for (int64_t i = rg.lo + threadIdx.x; i < rg.hi; i += blockDim.x) {
         const double x = (double)src[3 * i], y = (double)src[3 * i + 1], z = (double)src[3 * i + 2];
         const double px = T[0] * x + T[1] * y + T[2] * z + T[3];
@@ -1226,61 +1052,7 @@ __global__ __launch_bounds__(256, (FUSE != 0 && KIND != 2) ? 3 : 1) void k_icp_a
             acc[29] += r * r;
         }
     }
-    block_reduce_store<NACC, FUSE != 0>(acc, partials, rg.row);
-    if constexpr (FUSE == 0) return;
-    // Hand-off inside one launch (MI355X_MICROARCH.md, "Workgroup dispatch, XCD placement & inter-workgroup visibility"): the
-    // partials were stored by the lanes of wave 0; lane 0 RELEASES them at agent scope and takes a device-scope ticket
-    // (acquire-release); the workgroup whose ticket is the last one ACQUIRES and reads every block's partials.  (Round 3 shipped
-    // this with relaxed atomics and a bare vmcnt(0) -- no release / acquire pair ordered the partials before the ticket across
-    // XCDs; the fences cost ~4 us per iteration, which is one more reason the knob stays off: two launches are faster.)
-    if (threadIdx.x < 64) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (threadIdx.x == 0) {
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-            const unsigned t = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-            s_last = t == (PERSIST ? (ev + 1u) * gridDim.x - 1u : gridDim.x - 1u) ? 1 : 0;
-            if (s_last) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        }
-    }
-    __syncthreads();
-    if (s_last) {
-        if constexpr (PERSIST) {
-            if (threadIdx.x < sizeof(IcpState) / 4)
-                reinterpret_cast<int*>(&s_st)[threadIdx.x] = __hip_atomic_load(reinterpret_cast<const int*>(st) + threadIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        } else {
-            if (threadIdx.x < sizeof(IcpState) / 4) reinterpret_cast<int*>(&s_st)[threadIdx.x] = reinterpret_cast<const int*>(st)[threadIdx.x];
-        }
-        icp_fold_partials<256, true>((int)gridDim.x, partials, nullptr, s_x);
-        if (fuse == 2) {
-            if (threadIdx.x < GSR_ICP_ACC_LEN) acc_out[threadIdx.x] = s_x[0][threadIdx.x];
-        } else if (threadIdx.x == 0) {
-            icp_step_solve(&s_x[0][0], s_st, st);
-        }
-        if constexpr (!PERSIST) {
-            if (threadIdx.x == 0) *ticket = 0u;               // for the next launch (a kernel boundary away)
-        }
-    }
-    if constexpr (!PERSIST) return;
-    if (s_last) {
-        __syncthreads();                                      // (uniform within the workgroup: s_last is shared)
-        if (threadIdx.x == 0) {                               // the new state is out: everybody may go on
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-            __hip_atomic_store(ticket + 1, ev + 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    } else if (threadIdx.x == 0) {
-        unsigned spins = 0;
-        // relaxed polls (a load past the L1, nothing invalidated), ONE acquire when the word has moved
-        while (__hip_atomic_load(ticket + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < ev + 1u) {
-            __builtin_amdgcn_s_sleep(8);
-            if (++spins > (1u << 21)) {                       // ~0.5 s: something is badly wrong
-                __hip_atomic_store(ticket + 2, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                break;
-            }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    }
-    __syncthreads();
-    }
+    block_reduce_store<NACC>(acc, partials, rg.row);
 }
 
 // `reduced` == NULL: fold the block partials here (single GPU).  Multi-GPU source split: k_icp_reduce folds them into a
@@ -1297,8 +1069,7 @@ __global__ __launch_bounds__(256, (FUSE != 0 && KIND != 2) ? 3 : 1) void k_icp_a
 // butterfly s_l + s_(l ^ 32), + (l ^ 16), ... down to lane 0 -- with THREADS = 32 G threads: thread (g = t / 32, k = t % 32) forms
 // the lane sums s_g, s_(g + G), ... of accumulator k (32 threads read one 256-byte row per load, four rounds of loads in flight),
 // folds the butterfly steps it holds both operands of, and an LDS tree over g does the remaining log2 G.  Result: s_x[0][k].
-// SC1: the partials were stored write-through by other workgroups of the SAME launch: read them with sc1 loads (past the L1)
-template <int THREADS, bool SC1>
+template <int THREADS>
 __device__ __forceinline__ void icp_fold_partials(int nblocks, const double* partials, const double* __restrict__ reduced, double (*s_x)[32]) {
     constexpr int G = THREADS / 32, NL = 64 / G;
     const int k = threadIdx.x & 31, g = threadIdx.x >> 5;
@@ -1317,8 +1088,7 @@ __device__ __forceinline__ void icp_fold_partials(int nblocks, const double* par
 #pragma unroll
             for (int j = 0; j < NL; ++j) {
                 const int b = b0 + 64 * u + G * j;
-                if (SC1) v[u][j] = b < nblocks ? __hip_atomic_load(partials + (int64_t)b * GSR_ICP_ACC_LEN + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0;
-                else v[u][j] = b < nblocks ? partials[(int64_t)b * GSR_ICP_ACC_LEN + k] : 0.0;
+                v[u][j] = b < nblocks ? partials[(int64_t)b * GSR_ICP_ACC_LEN + k] : 0.0;
             }
 #pragma unroll
         for (int u = 0; u < 4; ++u)
@@ -1396,20 +1166,13 @@ struct gsr_icp_ctx {
     bool have_target = false, have_normals = false, have_source = false;
     int64_t nt = 0, ns = 0, ns_global = 0;
     double max_corr = 0;
-    DevBuf src_raw, src_order, state, nn_j, Tc, Sc, stage_cov, Ti, Tg, Si, ticket;
+    DevBuf src_raw, src_order, state, nn_j, Tc, Sc, stage_cov, Ti, Tg, Si;
     bool have_tcov = false, have_scov = false, have_tcol = false, have_scol = false;
     double lambda_geometric = 0.968;            // Open3D TransformationEstimationForColoredICP default
     bool src_sorted = false;
     bool device_loop = true;        // GSR_ICP_DEVICE_LOOP=0 selects the host-driven loop
     bool block_search = true;       // GSR_ICP_BLOCK_SEARCH=0: always the ring loop from ring 0
-    int tile_search = 0;            // GSR_ICP_TILE: the search of a fine level (rings == 1) over LDS-staged tiles (k_icp_nn_tile): 0 (default) = never, -1 = where
-                                    // the search has its own kernel (nn_mode), 1 = also for gsr_icp_correspondences on any size (tests).  Built for VERDICT r04
-                                    // item 5 and measured SLOWER on the bench's converged 5 M x 5 M level: 1.21 against 0.39 ms per iteration
-                                    // (profiles/r05g_icp_tile_ab.txt) -- a workgroup stages 3 264 target points (12 rows of the grid) for its 256 queries, of
-                                    // which a converged query needs the six in its own row: the per-thread search reads what it needs, the tile what it might
     bool xcd_ranges = true;         // GSR_ICP_XCD=0: logical block = physical block (every XCD walks the whole source)
-    bool fused_step = false;        // GSR_ICP_FUSED_STEP=1: the accumulate kernel's last workgroup does k_icp_step's (or k_icp_reduce's) work instead of a launch of its own: measured equal (44.8 vs 44.0 us at 185 k), so off
-                                    // accumulate kernel's last workgroup
     gsr_comm* comm = nullptr;       // multi-GPU source split through a communicator (gsr_icp_set_comm)
     unsigned* host_rb = nullptr;    // pinned host memory for small read-backs: 256 words + the sequence flag
     unsigned long long rb_seq = 0;
@@ -1427,9 +1190,6 @@ struct gsr_icp_ctx {
                                     // converged iteration 1.7x faster but a cold start (offsets ~ max_corr) 1.6x slower: keep 2
     DevBuf hist;
     bool robust_box = false;        // the current target's grid lies over the trimmed box (far outliers clamped into the boundary cells)
-    bool persistent = false;        // GSR_ICP_PERSISTENT=1: one RESIDENT kernel per registration on the levels that take the fused search (experiment)
-    bool adapt_cells = false;       // GSR_ICP_ADAPT=1: a finer grid when the points are clumped (experiment)
-    double occupancy = 0.0;         // of the cell an average point sits in (measured when adapt_cells)
     bool robust_allowed = true;     // GSR_ICP_ROBUST_BOX=0: always the box of all points (test knob: results must not change)
     DevBuf bbox, keys, idx, skeys, order, cellStart, Tq, Tn, stage_xyz, stage_nrm, src, partials, acc_dev, rocprim_tmp, corr_idx, corr_d2;
     gsr_allreduce_fn allreduce = nullptr;
@@ -1458,17 +1218,13 @@ inline int icp_blocks(int64_t ns, int cap) {
     return (int)((ns + ppb - 1) / ppb);
 }
 inline int nn_grid1(int64_t ns) { return icp_blocks(ns, 16384); }      // grid of the search kernel: one thread per point, capped
-// the search kernel of one evaluation: over LDS tiles on a fine level (rings == 1), else per thread (27-cell block first where the
-// correspondence distance spans two cells or more: blockf)
+// the search kernel of one evaluation: per thread (27-cell block first where the correspondence distance spans two cells or more: blockf)
 template <bool FROM_STATE>
 void launch_icp_nn(gsr_icp_ctx* c, hipStream_t st, const Xform& X, const IcpState* state, double mc2, bool blockf) {
     const int g1 = nn_grid1(c->ns);
     const dim3 grid(8 * ((g1 + 7) / 8)), blk(256);
     const int nbl = c->xcd_ranges ? g1 : -g1;
-    if (c->tile_search != 0 && c->grid.rings == 1)
-        hipLaunchKernelGGL((k_icp_nn_tile<FROM_STATE>), grid, blk, ICP_TILE_LDS, st, c->ns, c->src.as<float>(), X, state, c->grid, c->cellStart.as<int>(), c->Tq.as<float4>(),
-                           mc2, c->nn_j.as<int>(), nbl);
-    else if (blockf)
+    if (blockf)
         hipLaunchKernelGGL((k_icp_nn<FROM_STATE, 1>), grid, blk, 0, st, c->ns, c->src.as<float>(), X, state, c->grid, c->cellStart.as<int>(), c->Tq.as<float4>(), mc2,
                            c->nn_j.as<int>(), nbl);
     else
@@ -1476,7 +1232,8 @@ void launch_icp_nn(gsr_icp_ctx* c, hipStream_t st, const Xform& X, const IcpStat
                            c->nn_j.as<int>(), nbl);
 }
 
-int32_t run_accumulate(gsr_icp_ctx* c, const double* T, int kind, int loss, double k, double* acc, bool timed) {
+// what an evaluation with estimator `kind` needs of the context
+int32_t icp_check_kind(const gsr_icp_ctx* c, int kind) {
     if (!c->have_target || !c->have_source) return fail(GSR_E_INVALID, "icp: target and source must be set first");
     if (kind < GSR_ICP_POINT_TO_POINT || kind > GSR_ICP_COLORED) return fail(GSR_E_INVALID, "icp: unknown estimation kind %d", kind);
     if (kind == GSR_ICP_POINT_TO_PLANE && !c->have_normals)
@@ -1485,6 +1242,30 @@ int32_t run_accumulate(gsr_icp_ctx* c, const double* T, int kind, int loss, doub
         return fail(GSR_E_PRECONDITION, "ColoredICP requires target normals and the colours of both clouds");
     if (kind == GSR_ICP_GENERALIZED && (!c->have_tcov || !c->have_scov))
         return fail(GSR_E_PRECONDITION, "TransformationEstimationForGeneralizedICP requires source and target covariances");
+    return GSR_OK;
+}
+
+// one evaluation of the device-resident loop: 8 * ceil(nb / 8) workgroups, the padding ones get nothing (icp_block_range)
+void launch_accumulate_dev(gsr_icp_ctx* c, hipStream_t st, int kind, bool blockf, int nb, const int* nnj, const ColorArgs& cargs, double mc2, int loss, double k) {
+    const double* tn = kind == GSR_ICP_POINT_TO_POINT ? nullptr : (kind == GSR_ICP_GENERALIZED ? c->Tc.as<double>() : c->Tn.as<double>());
+    const double* sc = kind == GSR_ICP_GENERALIZED ? c->Sc.as<double>() : nullptr;
+    decltype(&k_icp_accumulate_dev<0, 0>) kernel = nullptr;
+    switch (2 * kind + (blockf ? 1 : 0)) {
+        case 0: kernel = k_icp_accumulate_dev<0, 0>; break;
+        case 1: kernel = k_icp_accumulate_dev<0, 1>; break;
+        case 2: kernel = k_icp_accumulate_dev<1, 0>; break;
+        case 3: kernel = k_icp_accumulate_dev<1, 1>; break;
+        case 4: kernel = k_icp_accumulate_dev<2, 0>; break;
+        case 5: kernel = k_icp_accumulate_dev<2, 1>; break;
+        case 6: kernel = k_icp_accumulate_dev<3, 0>; break;
+        default: kernel = k_icp_accumulate_dev<3, 1>; break;
+    }
+    hipLaunchKernelGGL(kernel, dim3(8 * ((nb + 7) / 8)), dim3(256), 0, st, c->ns, c->src.as<float>(), c->state.as<IcpState>(), c->grid, c->cellStart.as<int>(), nnj,
+                       c->Tq.as<float4>(), tn, sc, cargs, mc2, loss, k, c->partials.as<double>(), c->xcd_ranges ? nb : -nb);
+}
+
+int32_t run_accumulate(gsr_icp_ctx* c, const double* T, int kind, int loss, double k, double* acc, bool timed) {
+    GSR_TRY(icp_check_kind(c, kind));
     hipStream_t st = c->stream;
     Xform X;
     for (int i = 0; i < 12; ++i) X.m[i] = T[i];
@@ -1528,34 +1309,6 @@ int32_t run_accumulate(gsr_icp_ctx* c, const double* T, int kind, int loss, doub
         if (r != 0) return fail(GSR_E_INVALID, "icp: all-reduce callback returned %d", r);
     }
     return GSR_OK;
-}
-
-// The resident form of one registration (k_icp_accumulate_dev<KIND, BLOCK, 3>): a cooperative launch -- every workgroup must be on the
-// chip, they wait for one another --, so it is taken only when the occupancy query says all nb workgroups fit.  Returns 1 when it
-// was launched, 0 when the caller should take the launch-per-iteration loop, < 0 on error.
-template <int KIND, int BLOCK>
-int32_t launch_persistent(gsr_icp_ctx* c, int nb, const double* TN, const double* SC, ColorArgs cargs, double mc2, int loss, double k) {
-    const void* fn = (const void*)k_icp_accumulate_dev<KIND, BLOCK, 3>;
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 256, 0) != hipSuccess) { (void)hipGetLastError(); return 0; }
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, c->device) != hipSuccess) { (void)hipGetLastError(); return 0; }
-    if (!prop.cooperativeLaunch || (int64_t)per_cu * prop.multiProcessorCount < nb) return 0;
-    int64_t ns = c->ns;
-    const float* src = c->src.as<float>();
-    IcpState* st = c->state.as<IcpState>();
-    IcpGrid g = c->grid;
-    const int* cellStart = c->cellStart.as<int>();
-    const int* nnj = nullptr;
-    const float4* Tq = c->Tq.as<float4>();
-    double* partials = c->partials.as<double>();
-    unsigned* ticket = c->ticket.as<unsigned>();
-    double* acc_out = c->acc_dev.as<double>();
-    int nb_logical = -nb;                    // (logical block = physical block: the resident form launches exactly nb workgroups)
-    void* args[] = {&ns, &src, &st, &g, &cellStart, &nnj, &Tq, &TN, &SC, &cargs, &mc2, &loss, &k, &partials, &ticket, &acc_out, &nb_logical};
-    const hipError_t e = hipLaunchCooperativeKernel(fn, dim3(nb), dim3(256), args, 0, c->stream);
-    if (e != hipSuccess) { (void)hipGetLastError(); return 0; }
-    return 1;
 }
 
 }  // namespace
@@ -1613,14 +1366,8 @@ int32_t gsr_icp_create(gsr_icp_ctx** out, int32_t device, void* stream) {
     // Environment knobs (all of them): none changes a result, tests/test_icp_gpu.py::test_icp_knobs_change_nothing
     if (const char* e = getenv("GSR_ICP_DEVICE_LOOP")) c->device_loop = atoi(e) != 0;
     if (const char* e = getenv("GSR_ICP_BLOCK_SEARCH")) c->block_search = atoi(e) != 0;
-    if (const char* e = getenv("GSR_ICP_TILE")) c->tile_search = atoi(e);
-    (void)hipFuncSetAttribute((const void*)k_icp_nn_tile<true>, hipFuncAttributeMaxDynamicSharedMemorySize, ICP_TILE_LDS);
-    (void)hipFuncSetAttribute((const void*)k_icp_nn_tile<false>, hipFuncAttributeMaxDynamicSharedMemorySize, ICP_TILE_LDS);
     if (const char* e = getenv("GSR_ICP_XCD")) c->xcd_ranges = atoi(e) != 0;
     if (const char* e = getenv("GSR_ICP_ROBUST_BOX")) c->robust_allowed = atoi(e) != 0;
-    if (const char* e = getenv("GSR_ICP_ADAPT")) c->adapt_cells = atoi(e) != 0;
-    if (const char* e = getenv("GSR_ICP_PERSISTENT")) c->persistent = atoi(e) != 0;
-    if (const char* e = getenv("GSR_ICP_FUSED_STEP")) c->fused_step = atoi(e) != 0;
     if (const char* e = getenv("GSR_ICP_BLOCKS")) { int v = atoi(e); if (v >= 1 && v <= 65536) c->nblocks = v; }
     // pinned, device-mapped, COHERENT host memory: the device's system-scope stores must reach the host while the stream is still
     // running (a non-coherent mapping would only show them at the end of the kernel).  GSR_ICP_RB_POLL=0: no polling at all
@@ -1638,7 +1385,7 @@ int32_t gsr_icp_create(gsr_icp_ctx** out, int32_t device, void* stream) {
 int32_t gsr_icp_destroy(gsr_icp_ctx* c) {
     if (!c) return GSR_OK;
     (void)hipSetDevice(c->device);
-    DevBuf* all[] = {&c->hist, &c->ticket, &c->src_raw, &c->src_order, &c->state, &c->nn_j, &c->Tc, &c->Sc, &c->stage_cov, &c->Ti, &c->Tg, &c->Si, &c->bbox, &c->keys, &c->idx, &c->skeys, &c->order, &c->cellStart, &c->Tq, &c->Tn, &c->stage_xyz, &c->stage_nrm,
+    DevBuf* all[] = {&c->hist, &c->src_raw, &c->src_order, &c->state, &c->nn_j, &c->Tc, &c->Sc, &c->stage_cov, &c->Ti, &c->Tg, &c->Si, &c->bbox, &c->keys, &c->idx, &c->skeys, &c->order, &c->cellStart, &c->Tq, &c->Tn, &c->stage_xyz, &c->stage_nrm,
                      &c->src, &c->partials, &c->acc_dev, &c->rocprim_tmp, &c->corr_idx, &c->corr_d2};
     for (DevBuf* b : all) b->release();
     if (c->e0) (void)hipEventDestroy(c->e0);
@@ -1707,47 +1454,30 @@ int32_t gsr_icp_set_target(gsr_icp_ctx* c, const float* xyz, const double* norma
         if (cell < max_corr / ICP_CELL_FLOOR_DIV) cell = max_corr / ICP_CELL_FLOOR_DIV;
     }
     GSR_TRY(c->keys.reserve(n * 4)); GSR_TRY(c->idx.reserve(n * 4)); GSR_TRY(c->skeys.reserve(n * 4)); GSR_TRY(c->order.reserve(n * 4));
-    c->occupancy = 0.0;
-    for (int attempt = 0;; ++attempt) {
-        for (;;) {
-            double fx = floor((mx[0] - mn[0]) / cell) + 1, fy = floor((mx[1] - mn[1]) / cell) + 1, fz = floor((mx[2] - mn[2]) / cell) + 1;
-            if (fx * fy * fz <= (double)c->max_cells) { g.gx = (int)fx; g.gy = (int)fy; g.gz = (int)fz; break; }
-            cell *= 1.2599210498948732;
-        }
-        g.ox = mn[0]; g.oy = mn[1]; g.oz = mn[2];
-        g.c = cell; g.inv_c = 1.0 / cell;
-        g.cx = 0.5 * (mn[0] + mx[0]); g.cy = 0.5 * (mn[1] + mx[1]); g.cz = 0.5 * (mn[2] + mx[2]);
-        g.ncells = g.gx * g.gy * g.gz;
-        g.rings = (int)ceil(max_corr / cell);
-        if (g.rings < 1) g.rings = 1;
-        g.bx0 = raw_box[0]; g.by0 = raw_box[1]; g.bz0 = raw_box[2]; g.bx1 = raw_box[3]; g.by1 = raw_box[4]; g.bz1 = raw_box[5];
-        if (!(raw_box[3] >= raw_box[0])) { g.bx0 = g.by0 = g.bz0 = -1.0 / 0.0; g.bx1 = g.by1 = g.bz1 = 1.0 / 0.0; }      // (no finite point: no box, no early leave)
-        hipLaunchKernelGGL(k_icp_keys, dim3(stride_grid(n)), dim3(256), 0, st, n, dxyz, g, c->keys.as<unsigned>(), c->idx.as<unsigned>());
-        int bits = 1;
-        while (bits < 32 && ((int64_t)1 << bits) < g.ncells) ++bits;
-        size_t bytes = 0;
-        GSR_HIP(rocprim::radix_sort_pairs<icp_sort_cfg>(nullptr, bytes, c->keys.as<unsigned>(), c->skeys.as<unsigned>(), c->idx.as<unsigned>(),
-                                          c->order.as<unsigned>(), (size_t)n, 0u, (unsigned)bits, st));
-        GSR_TRY(c->rocprim_tmp.reserve(bytes));
-        GSR_HIP(rocprim::radix_sort_pairs<icp_sort_cfg>(c->rocprim_tmp.p, bytes, c->keys.as<unsigned>(), c->skeys.as<unsigned>(), c->idx.as<unsigned>(),
-                                          c->order.as<unsigned>(), (size_t)n, 0u, (unsigned)bits, st));
-        GSR_TRY(c->cellStart.reserve(((size_t)g.ncells + 1) * 4));
-        hipLaunchKernelGGL(k_icp_cell_starts, dim3(stride_grid(n)), dim3(256), 0, st, n, c->skeys.as<unsigned>(), (int64_t)g.ncells, c->cellStart.as<int>());
-        if (!c->adapt_cells || attempt >= 2) break;
-        // Clustered clouds: the box-volume rule gives two points per cell ON AVERAGE OVER THE BOX, and a scene whose points sit in
-        // clumps has hundreds in the cells that matter.  When the average point shares its cell with more than ICP_OCC_MAX others the
-        // grid is rebuilt finer (GSR_ICP_ADAPT=1; measured).
-        GSR_HIP(hipMemsetAsync(c->hist.p, 0, 8, st));
-        hipLaunchKernelGGL(k_icp_occupancy, dim3(stride_grid(g.ncells)), dim3(256), 0, st, (int64_t)g.ncells, c->cellStart.as<int>(), c->hist.as<unsigned long long>());
-        unsigned long long sumsq = 0;
-        GSR_TRY(icp_fetch(c, c->hist.p, &sumsq, 8));
-        c->occupancy = (double)sumsq / (double)n;
-        const double floor_cell = max_corr / ICP_CELL_FLOOR_DIV;
-        if (!(c->occupancy > 12.0) || cell <= floor_cell * 1.0001 || (double)g.ncells * 1.9 > (double)c->max_cells) break;
-        double f = cbrt(4.0 / c->occupancy);
-        f = f < 0.4 ? 0.4 : f;
-        cell = fmax(cell * f, floor_cell);
+    for (;;) {
+        double fx = floor((mx[0] - mn[0]) / cell) + 1, fy = floor((mx[1] - mn[1]) / cell) + 1, fz = floor((mx[2] - mn[2]) / cell) + 1;
+        if (fx * fy * fz <= (double)c->max_cells) { g.gx = (int)fx; g.gy = (int)fy; g.gz = (int)fz; break; }
+        cell *= 1.2599210498948732;
     }
+    g.ox = mn[0]; g.oy = mn[1]; g.oz = mn[2];
+    g.c = cell; g.inv_c = 1.0 / cell;
+    g.cx = 0.5 * (mn[0] + mx[0]); g.cy = 0.5 * (mn[1] + mx[1]); g.cz = 0.5 * (mn[2] + mx[2]);
+    g.ncells = g.gx * g.gy * g.gz;
+    g.rings = (int)ceil(max_corr / cell);
+    if (g.rings < 1) g.rings = 1;
+    g.bx0 = raw_box[0]; g.by0 = raw_box[1]; g.bz0 = raw_box[2]; g.bx1 = raw_box[3]; g.by1 = raw_box[4]; g.bz1 = raw_box[5];
+    if (!(raw_box[3] >= raw_box[0])) { g.bx0 = g.by0 = g.bz0 = -1.0 / 0.0; g.bx1 = g.by1 = g.bz1 = 1.0 / 0.0; }      // (no finite point: no box, no early leave)
+    hipLaunchKernelGGL(k_icp_keys, dim3(stride_grid(n)), dim3(256), 0, st, n, dxyz, g, c->keys.as<unsigned>(), c->idx.as<unsigned>());
+    int bits = 1;
+    while (bits < 32 && ((int64_t)1 << bits) < g.ncells) ++bits;
+    size_t bytes = 0;
+    GSR_HIP(rocprim::radix_sort_pairs<icp_sort_cfg>(nullptr, bytes, c->keys.as<unsigned>(), c->skeys.as<unsigned>(), c->idx.as<unsigned>(),
+                                      c->order.as<unsigned>(), (size_t)n, 0u, (unsigned)bits, st));
+    GSR_TRY(c->rocprim_tmp.reserve(bytes));
+    GSR_HIP(rocprim::radix_sort_pairs<icp_sort_cfg>(c->rocprim_tmp.p, bytes, c->keys.as<unsigned>(), c->skeys.as<unsigned>(), c->idx.as<unsigned>(),
+                                      c->order.as<unsigned>(), (size_t)n, 0u, (unsigned)bits, st));
+    GSR_TRY(c->cellStart.reserve(((size_t)g.ncells + 1) * 4));
+    hipLaunchKernelGGL(k_icp_cell_starts, dim3(stride_grid(n)), dim3(256), 0, st, n, c->skeys.as<unsigned>(), (int64_t)g.ncells, c->cellStart.as<int>());
     c->grid = g;
     GSR_TRY(c->Tq.reserve((size_t)n * 16));
     if (normals) GSR_TRY(c->Tn.reserve((size_t)n * 24));
@@ -1939,14 +1669,7 @@ int32_t gsr_icp_register(gsr_icp_ctx* c, const double* init_T, int32_t kind, int
     if (!c->allreduce && (c->device_loop || multi)) {
         // device-resident loop: no per-iteration host round trip.  With a device all-reduce (multi-GPU source split) the
         // only addition per iteration is one stream-ordered collective on 32 doubles between the reduction and the solve.
-        if (!c->have_target || !c->have_source) return fail(GSR_E_INVALID, "icp: target and source must be set first");
-        if (kind < GSR_ICP_POINT_TO_POINT || kind > GSR_ICP_COLORED) return fail(GSR_E_INVALID, "icp: unknown estimation kind %d", kind);
-        if (kind == GSR_ICP_POINT_TO_PLANE && !c->have_normals)
-            return fail(GSR_E_PRECONDITION, "TransformationEstimationPointToPlane requires target normals");
-        if (kind == GSR_ICP_COLORED && (!c->have_normals || !c->have_tcol || !c->have_scol))
-            return fail(GSR_E_PRECONDITION, "ColoredICP requires target normals and the colours of both clouds");
-        if (kind == GSR_ICP_GENERALIZED && (!c->have_tcov || !c->have_scov))
-            return fail(GSR_E_PRECONDITION, "TransformationEstimationForGeneralizedICP requires source and target covariances");
+        GSR_TRY(icp_check_kind(c, kind));
         hipStream_t st = c->stream;
         IcpState hs;
         memset(&hs, 0, sizeof(hs));
@@ -1960,11 +1683,7 @@ int32_t gsr_icp_register(gsr_icp_ctx* c, const double* init_T, int32_t kind, int
         GSR_TRY(c->partials.reserve((size_t)nb * GSR_ICP_ACC_LEN * 8));
         GSR_TRY(c->nn_j.reserve((size_t)(c->ns > 0 ? c->ns : 1) * 4));
         GSR_TRY(c->acc_dev.reserve(GSR_ICP_ACC_LEN * 8));
-        GSR_TRY(c->ticket.reserve(64));
         GSR_HIP(hipMemsetAsync(c->partials.p, 0, (size_t)nb * GSR_ICP_ACC_LEN * 8, st));
-        GSR_HIP(hipMemsetAsync(c->ticket.p, 0, 64, st));
-        // what the accumulate kernel's last workgroup does: the whole step (single GPU), the rank-local fold (multi-GPU), nothing
-        const int fuse = !c->fused_step ? 0 : (multi ? 2 : 1);
         const double mc2 = c->max_corr * c->max_corr;
         const ColorArgs cargs = {c->Ti.as<double>(), c->Tg.as<double>(), c->Si.as<double>(), sqrt(c->lambda_geometric), sqrt(1.0 - c->lambda_geometric)};
         const int total_evals = hs.max_iter + 1;
@@ -1972,45 +1691,14 @@ int32_t gsr_icp_register(gsr_icp_ctx* c, const double* init_T, int32_t kind, int
         const bool blockf = c->block_search && c->grid.rings >= 2;
         int issued = 0;
         GSR_HIP(hipEventRecord(c->e0, st));
-        // GSR_ICP_PERSISTENT=1: single GPU, fused search (the levels below 4 * 10^5 source points): ONE resident kernel runs the whole loop
-        if (c->persistent && !multi && c->nn_mode() == 0 && c->ns > 0) {
-            int32_t pr = 0;
-            const double* tn = c->Tn.as<double>();
-            const double* nul = nullptr;
-            if (kind == GSR_ICP_POINT_TO_POINT) pr = blockf ? launch_persistent<0, 1>(c, nb, nul, nul, cargs, mc2, loss, k) : launch_persistent<0, 0>(c, nb, nul, nul, cargs, mc2, loss, k);
-            else if (kind == GSR_ICP_POINT_TO_PLANE) pr = blockf ? launch_persistent<1, 1>(c, nb, tn, nul, cargs, mc2, loss, k) : launch_persistent<1, 0>(c, nb, tn, nul, cargs, mc2, loss, k);
-            if (pr < 0) return pr;
-            if (pr == 1) {
-                GSR_TRY(icp_fetch(c, c->state.p, &hs, sizeof(hs)));
-                unsigned tk[4] = {0, 0, 0, 0};
-                GSR_TRY(icp_fetch(c, c->ticket.p, tk, sizeof(tk)));
-                if (tk[2]) return fail(GSR_E_HIP, "gsr_icp_register: the resident kernel's barrier ran out of patience (GSR_ICP_PERSISTENT=0 takes the launch-per-iteration loop)");
-                issued = total_evals;
-            }
-        }
         while (issued < total_evals) {
             const int chunk = total_evals - issued < 8 ? total_evals - issued : 8;
             const int* nnj = c->nn_mode() ? c->nn_j.as<int>() : (const int*)nullptr;
             for (int i = 0; i < chunk; ++i) {
-#define GSR_ICP_ACC1(KIND, BLK, FUSE, TN, SC)                                                                                        \
-    hipLaunchKernelGGL((k_icp_accumulate_dev<KIND, BLK, FUSE>), dim3(FUSE == 0 ? 8 * ((nb + 7) / 8) : nb), dim3(256), 0, st, c->ns, c->src.as<float>(), \
-                       c->state.as<IcpState>(), c->grid, c->cellStart.as<int>(), nnj, c->Tq.as<float4>(), TN, SC, cargs, mc2, loss, k,          \
-                       c->partials.as<double>(), c->ticket.as<unsigned>(), c->acc_dev.as<double>(), c->xcd_ranges ? nb : -nb)
-#define GSR_ICP_ACC(KIND, TN, SC)                                                                                                    \
-    do {                                                                                                                             \
-        if (blockf) { if (fuse == 0) GSR_ICP_ACC1(KIND, 1, 0, TN, SC); else if (fuse == 1) GSR_ICP_ACC1(KIND, 1, 1, TN, SC); else GSR_ICP_ACC1(KIND, 1, 2, TN, SC); } \
-        else { if (fuse == 0) GSR_ICP_ACC1(KIND, 0, 0, TN, SC); else if (fuse == 1) GSR_ICP_ACC1(KIND, 0, 1, TN, SC); else GSR_ICP_ACC1(KIND, 0, 2, TN, SC); } \
-    } while (0)
                 if (c->nn_mode()) launch_icp_nn<true>(c, st, Xform(), c->state.as<IcpState>(), mc2, blockf);
-                if (kind == GSR_ICP_COLORED) GSR_ICP_ACC(3, c->Tn.as<double>(), (const double*)nullptr);
-                else if (kind == GSR_ICP_POINT_TO_POINT) GSR_ICP_ACC(0, (const double*)nullptr, (const double*)nullptr);
-                else if (kind == GSR_ICP_POINT_TO_PLANE) GSR_ICP_ACC(1, c->Tn.as<double>(), (const double*)nullptr);
-                else GSR_ICP_ACC(2, c->Tc.as<double>(), c->Sc.as<double>());
-#undef GSR_ICP_ACC
-#undef GSR_ICP_ACC1
+                launch_accumulate_dev(c, st, kind, blockf, nb, nnj, cargs, mc2, loss, k);
                 if (multi) {
-                    if (fuse == 0)
-                        hipLaunchKernelGGL(k_icp_reduce, dim3(1), dim3(1024), 0, st, nb, c->partials.as<double>(), c->state.as<IcpState>(), c->acc_dev.as<double>());
+                    hipLaunchKernelGGL(k_icp_reduce, dim3(1), dim3(1024), 0, st, nb, c->partials.as<double>(), c->state.as<IcpState>(), c->acc_dev.as<double>());
                     if (c->comm) {                            // RCCL enqueued on this stream: no host involvement
                         GSR_TRY(gsr_comm_allreduce(c->comm, c->acc_dev.p, GSR_ICP_ACC_LEN, GSR_DT_F64, GSR_OP_SUM, (void*)st));
                     } else {
@@ -2018,7 +1706,7 @@ int32_t gsr_icp_register(gsr_icp_ctx* c, const double* init_T, int32_t kind, int
                         if (rc != 0) return fail(GSR_E_INVALID, "icp: device all-reduce callback returned %d", rc);
                     }
                     hipLaunchKernelGGL(k_icp_step, dim3(1), dim3(ICP_STEP_THREADS), 0, st, nb, c->partials.as<double>(), c->acc_dev.as<double>(), c->state.as<IcpState>());
-                } else if (fuse == 0) {
+                } else {
                     hipLaunchKernelGGL(k_icp_step, dim3(1), dim3(ICP_STEP_THREADS), 0, st, nb, c->partials.as<double>(), (const double*)nullptr, c->state.as<IcpState>());
                 }
             }
@@ -2068,12 +1756,7 @@ int32_t gsr_icp_correspondences(gsr_icp_ctx* c, const double* T, int64_t* idx, d
     Xform X;
     for (int i = 0; i < 12; ++i) X.m[i] = T[i];
     GSR_TRY(c->nn_j.reserve((size_t)c->ns * 4));
-    {   // (the ring loop per thread -- or, GSR_ICP_TILE=1 and a fine level, the tile search: the tests compare both with the oracle's KD-tree)
-        const int keep = c->tile_search;
-        if (keep != 1) c->tile_search = 0;
-        launch_icp_nn<false>(c, c->stream, X, (const IcpState*)nullptr, c->max_corr * c->max_corr, false);
-        c->tile_search = keep;
-    }
+    launch_icp_nn<false>(c, c->stream, X, (const IcpState*)nullptr, c->max_corr * c->max_corr, false);
     hipLaunchKernelGGL(k_icp_correspond, dim3(stride_grid(c->ns)), dim3(256), 0, c->stream, c->ns, c->src.as<float>(), X, c->nn_j.as<int>(),
                        c->Tq.as<float4>(), c->src_sorted ? c->src_order.as<unsigned>() : (const unsigned*)nullptr, c->corr_idx.as<int64_t>(),
                        c->corr_d2.as<double>());

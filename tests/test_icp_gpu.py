@@ -96,15 +96,12 @@ def test_correspondences_exact_adversarial(oracle, case):
 
 
 @pytest.mark.parametrize("case", ["plain", "offset", "ties", "lattice", "outside", "clustered", "moved"])
-def test_tile_search_of_a_fine_level_is_exact(monkeypatch, oracle, case):
-    """k_icp_nn_tile: on a fine level (the correspondence distance is at most one grid cell: rings == 1) a workgroup stages the target
-    points of the box around its 256 queries in LDS and every lane scans its 27 cells from there.  GSR_ICP_TILE=1 routes
-    gsr_icp_correspondences through it: the indices must be the oracle's KD-tree neighbours bit for bit -- duplicated target points
-    (ties to the lowest index), coordinates around 2000, queries on cell faces, queries far outside the target's box (clamped cells),
-    a clustered target (boxes that do not fit the tile fall back to the per-thread search), a source that moved by several cells since
-    it was sorted (boxes too large: fallback again)."""
+def test_per_thread_search_of_a_fine_level_is_exact(oracle, case):
+    """k_icp_nn on a fine level (the correspondence distance is at most one grid cell: rings == 1, the 27 cells around a query hold every
+    neighbour that can be accepted): the indices of gsr_icp_correspondences must be the oracle's KD-tree neighbours bit for bit --
+    duplicated target points (ties to the lowest index), coordinates around 2000, queries on cell faces, queries far outside the
+    target's box (clamped cells), a clustered target, a source that moved by several cells since it was sorted."""
     from gaussiansplattingregistration_amd import icp
-    monkeypatch.setenv("GSR_ICP_TILE", "1")
     rng = np.random.default_rng(23)
     n = 60000
     tgt = rng.uniform(-1.6, 1.6, (n, 3)).astype(np.float32)
@@ -137,24 +134,25 @@ def test_tile_search_of_a_fine_level_is_exact(monkeypatch, oracle, case):
     assert (idx >= 0).any() or (idx0 >= 0).any()
 
 
-def test_tile_search_changes_no_registration(monkeypatch):
-    """A registration whose finest schedule entry searches over LDS tiles (the default from 400 k source points on when max_corr is at
-    most a cell) against the same with GSR_ICP_TILE=0 (every level searched per thread): transform, fitness, RMSE and iteration count
-    equal -- the neighbours are the same, the accumulate kernel does not know who found them."""
+def test_split_search_changes_no_registration(monkeypatch):
+    """A registration above the 400 k source points from which on the search runs as its own kernel (k_icp_nn in front of a streaming
+    accumulate: the default at this size) against the same with GSR_ICP_NN_KERNEL=0 (search and accumulate in one kernel): transform,
+    fitness, RMSE and iteration count equal -- the neighbours are the same, the accumulate kernel does not know who found them."""
     from gaussiansplattingregistration_amd import icp, synth
     src, tgt, _ = synth.make_pair(450000, seed=14, sh_degree=0)
     nrm = icp.normals_from_cov(tgt["cov6"])
     res = {}
-    for tile in ("0", "-1"):
-        monkeypatch.setenv("GSR_ICP_TILE", tile)
+    for nn_kernel in ("default", "0"):
+        if nn_kernel == "default": monkeypatch.delenv("GSR_ICP_NN_KERNEL", raising=False)
+        else: monkeypatch.setenv("GSR_ICP_NN_KERNEL", nn_kernel)
         out = []
         for kind, nn in ((0, None), (1, nrm)):
             r = icp.registration_icp_arrays(src["xyz"], tgt["xyz"], nn, np.eye(4), kind=kind, max_corr=0.07, max_iter=12)
             out.append((r["transformation"], r["fitness"], r["inlier_rmse"], r["iterations"]))
-        res[tile] = out
-    for a, b in zip(res["0"], res["-1"]):
+        res[nn_kernel] = out
+    for a, b in zip(res["default"], res["0"]):
         assert np.abs(a[0] - b[0]).max() < 1e-12 and a[3] == b[3] and abs(a[1] - b[1]) < 1e-15 and abs(a[2] - b[2]) < 1e-12
-    assert res["0"][0][1] > 0.5
+    assert res["default"][0][1] > 0.5
 
 
 def test_accumulators_match_numpy():
@@ -465,8 +463,8 @@ def test_icp_knobs_change_nothing(monkeypatch):
     other grid resolutions (GSR_ICP_CELL_TARGET, GSR_ICP_MAX_CELLS), the ring loop from ring 0 against the 27-cell block of
     batched loads the coarse levels start with (GSR_ICP_BLOCK_SEARCH; max_corr = 0.3 spans several cells here, and the
     split-kernel case runs it in k_icp_nn too), another number of workgroups -- another association of the points with the partial
-    sums (GSR_ICP_BLOCKS) --, workgroups without the XCD-contiguous mapping of the source ranges (GSR_ICP_XCD=0), k_icp_step as its own launch against the accumulate kernel's last workgroup doing
-    its work (GSR_ICP_FUSED_STEP: one launch per iteration instead of two)."""
+    sums (GSR_ICP_BLOCKS) --, workgroups without the XCD-contiguous mapping of the source ranges (GSR_ICP_XCD=0), the read-back by
+    stream synchronisation instead of the polled host word (GSR_ICP_RB_POLL=0), the grid over the box of all points (GSR_ICP_ROBUST_BOX=0)."""
     from gaussiansplattingregistration_amd import icp, synth
     src, tgt, _ = synth.make_pair(50000, seed=13, sh_degree=0)
     C = tgt["cov6"]
@@ -487,9 +485,7 @@ def test_icp_knobs_change_nothing(monkeypatch):
     for env in ({"GSR_ICP_NN_KERNEL": "0"}, {"GSR_ICP_NN_KERNEL": "2"}, {"GSR_ICP_DEVICE_LOOP": "0"}, {"GSR_ICP_CELL_TARGET": "0.5"},
                 {"GSR_ICP_CELL_TARGET": "16"}, {"GSR_ICP_MAX_CELLS": "4096"}, {"GSR_ICP_BLOCK_SEARCH": "0"},
                 {"GSR_ICP_BLOCKS": "100"}, {"GSR_ICP_RB_POLL": "0"}, {"GSR_ICP_XCD": "0"},
-                {"GSR_ICP_BLOCK_SEARCH": "0", "GSR_ICP_NN_KERNEL": "2"}, {"GSR_ICP_FUSED_STEP": "1"}, {"GSR_ICP_FUSED_STEP": "1", "GSR_ICP_NN_KERNEL": "2"},
-                {"GSR_ICP_ADAPT": "1"}, {"GSR_ICP_ADAPT": "1", "GSR_ICP_CELL_TARGET": "64"}, {"GSR_ICP_ROBUST_BOX": "0"},
-                {"GSR_ICP_PERSISTENT": "1"}, {"GSR_ICP_PERSISTENT": "1", "GSR_ICP_BLOCK_SEARCH": "0"}, {"GSR_ICP_PERSISTENT": "1", "GSR_ICP_BLOCKS": "100"}):
+                {"GSR_ICP_BLOCK_SEARCH": "0", "GSR_ICP_NN_KERNEL": "2"}, {"GSR_ICP_ROBUST_BOX": "0"}):
         for k, v in env.items():
             monkeypatch.setenv(k, v)
         got = run()
