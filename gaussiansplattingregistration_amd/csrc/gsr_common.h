@@ -4,6 +4,7 @@
 #include <sched.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <string.h>
 #include <string>
 
 #include "../../include/gsr_hip.h"
@@ -29,10 +30,19 @@ int32_t fail(int32_t code, const char* fmt, ...);
     } while (0)
 
 // Grow-only device buffer: the library owns its workspace and performs no allocation in steady
-// state (a second level or ICP call of the same size reuses everything).
+// state (a second level or ICP call of the same size reuses everything).  It frees its memory when it goes out of scope, so a
+// context or a function that holds one keeps no release list.  borrow() makes it stand for memory of the CALLER instead: reserve()
+// is then a no-op and nothing here ever frees that pointer.  Only this struct writes `p` and `cap`; everything else reads them.
 struct DevBuf {
     void* p = nullptr;
     size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    DevBuf(DevBuf&& o) noexcept { swap(o); }
+    DevBuf& operator=(DevBuf&& o) noexcept { swap(o); return *this; }      // (what this one held goes with `o`)
+    ~DevBuf() { release(); }
+    void borrow(void* caller_ptr) { release(); p = caller_ptr; cap = BORROWED; }
     int32_t reserve(size_t bytes) {
         if (bytes <= cap) return GSR_OK;
         if (p) { hipError_t e = hipFree(p); p = nullptr; cap = 0; if (e != hipSuccess) return fail(GSR_E_HIP, "hipFree: %s", hipGetErrorString(e)); }
@@ -42,9 +52,57 @@ struct DevBuf {
         cap = want;
         return GSR_OK;
     }
-    void release() { if (p) { (void)hipFree(p); p = nullptr; cap = 0; } }
+    void release() { if (p && cap != BORROWED) (void)hipFree(p); p = nullptr; cap = 0; }      // an early free; a borrowed pointer is only let go
     template <typename T> T* as() const { return reinterpret_cast<T*>(p); }
     void swap(DevBuf& o) { void* tp = p; p = o.p; o.p = tp; size_t tc = cap; cap = o.cap; o.cap = tc; }
+
+private:
+    static constexpr size_t BORROWED = (size_t)-1;      // as a capacity: larger than any request
+};
+
+// The other things the library creates on a device, each destroyed by its holder.  A stream the CALLER passed in (gsr_hem_ctx::stream,
+// gsr_icp_ctx::stream) is not one of them and stays a raw hipStream_t.  All three are empty until created and convert to the raw handle.
+struct Event {
+    Event() = default;
+    Event(Event&& o) noexcept : e(o.e) { o.e = nullptr; }
+    Event& operator=(Event&& o) noexcept { hipEvent_t t = e; e = o.e; o.e = t; return *this; }
+    ~Event() { if (e) (void)hipEventDestroy(e); }
+    hipError_t create() { return hipEventCreate(&e); }                                               // timed
+    hipError_t create_untimed() { return hipEventCreateWithFlags(&e, hipEventDisableTiming); }      // ordering only
+    operator hipEvent_t() const { return e; }
+
+private:
+    hipEvent_t e = nullptr;
+};
+
+struct Stream {     // non-blocking
+    Stream() = default;
+    Stream(Stream&& o) noexcept : s(o.s) { o.s = nullptr; }
+    Stream& operator=(Stream&& o) noexcept { hipStream_t t = s; s = o.s; o.s = t; return *this; }
+    ~Stream() { if (s) (void)hipStreamDestroy(s); }
+    hipError_t create() { return hipStreamCreateWithFlags(&s, hipStreamNonBlocking); }
+    operator hipStream_t() const { return s; }
+
+private:
+    hipStream_t s = nullptr;
+};
+
+// pinned host memory, device-mapped and COHERENT (the device's system-scope stores reach the host while the stream is still running:
+// the read-backs the host polls for), zeroed
+struct PinnedBlock {
+    PinnedBlock() = default;
+    PinnedBlock(PinnedBlock&& o) noexcept : p(o.p) { o.p = nullptr; }
+    PinnedBlock& operator=(PinnedBlock&& o) noexcept { void* t = p; p = o.p; o.p = t; return *this; }
+    ~PinnedBlock() { if (p) (void)hipHostFree(p); }
+    hipError_t alloc(size_t bytes) {
+        hipError_t e = hipHostMalloc(&p, bytes, hipHostMallocMapped | hipHostMallocCoherent);
+        if (e == hipSuccess) memset(p, 0, bytes); else p = nullptr;
+        return e;
+    }
+    template <typename T> T* as() const { return reinterpret_cast<T*>(p); }
+
+private:
+    void* p = nullptr;
 };
 
 // one step of a host spin loop on device-written pinned memory: a pause instruction on x86, a yield elsewhere; after ~20 us of

@@ -1,6 +1,7 @@
 // gsr_oneshot.h -- the device memory of a stateless one-shot entry point (gsr_plane_score, gsr_fpfh, gsr_voxel_down_sample, ...):
 // caller arrays that are all on the host or all on the device, scratch, results copied back for host callers, one wait, everything
-// freed.  The contexts (gsr_hem_*, gsr_icp_*) own grow-only DevBuf workspaces with a manual lifetime and do not use this.
+// freed.  The contexts (gsr_hem_*, gsr_icp_*, gsr_raster_*) keep grow-only DevBuf workspaces as members, which live as long as the
+// context does, and do not use this.
 #pragma once
 #include <vector>
 
@@ -21,14 +22,13 @@ inline int32_t open_device(int32_t device, const char* who) {
 // Owner of everything one call allocates on the device.  The destructor WAITS FOR THE STREAM AND THEN FREES, on every exit, the
 // early returns of GSR_HIP / GSR_TRY included: that wait is what makes an asynchronous copy into the caller's frame (a local, a
 // std::vector declared before the OneShot) or out of a staged buffer safe when the function leaves before its own wait.  There is
-// no release without the wait.
+// no release without the wait: the wait is the destructor's body and the buffers are members, which C++ destroys after the body.
 struct OneShot {
     OneShot(hipStream_t stream, bool on_device, const char* who) : st(stream), on_device(on_device), who(who) {}
     OneShot(const OneShot&) = delete;
     OneShot& operator=(const OneShot&) = delete;
     ~OneShot() {
         (void)hipStreamSynchronize(st);
-        for (DevBuf& b : owned) b.release();
     }
 
     // plain device scratch of `bytes` bytes

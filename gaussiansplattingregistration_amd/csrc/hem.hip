@@ -51,6 +51,7 @@
 #include "gsr_common.h"
 #include "gsr_math.h"
 #include "gsr_normals.h"
+#include "gsr_oneshot.h"
 #include "gsr_test_hooks.h"
 #include "hem_device.h"
 #include "hem_select.h"
@@ -2473,7 +2474,6 @@ struct Level {
         GSR_TRY(sh.reserve(mm * (size_t)(f > 0 ? f : 1) * 4)); GSR_TRY(is_parent.reserve(mm));
         return GSR_OK;
     }
-    void release() { xyz.release(); color.release(); cov6.release(); opacity.release(); weight.release(); sh.release(); is_parent.release(); }
     void swap(Level& o) {
         std::swap(n, o.n); std::swap(F, o.F);
         xyz.swap(o.xyz); color.swap(o.color); cov6.swap(o.cov6); opacity.swap(o.opacity);
@@ -2488,13 +2488,13 @@ using namespace gsr;
 struct gsr_hem_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
-    hipStream_t aux = nullptr;      // second stream: the queue of heavy work items runs beside the light parents
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    hipEvent_t ev_pre = nullptr;    // the parents' output ranks (flags in input order + their scan), computed beside the grid phase
-    hipStream_t aux2 = nullptr;     // third stream: the SH rows are gathered into cell order (an HBM stream only the M-step needs)
-    hipEvent_t ev_sh_fork = nullptr, ev_sh_join = nullptr;      // beside the selection (VALU / latency bound)
-    hipEvent_t ev_halo = nullptr;   // partitioned level: the ghosts' SH rows have arrived (their exchange runs on aux2 beside the grid phase and the selection)
-    hipEvent_t evp[4] = {nullptr, nullptr, nullptr, nullptr};   // brackets of the two halo exchanges (records on the main stream, SH rows on aux2)
+    Stream aux;                     // second stream: the queue of heavy work items runs beside the light parents
+    Event ev_fork, ev_join;
+    Event ev_pre;                   // the parents' output ranks (flags in input order + their scan), computed beside the grid phase
+    Stream aux2;                    // third stream: the SH rows are gathered into cell order (an HBM stream only the M-step needs)
+    Event ev_sh_fork, ev_sh_join;   // beside the selection (VALU / latency bound)
+    Event ev_halo;                  // partitioned level: the ghosts' SH rows have arrived (their exchange runs on aux2 beside the grid phase and the selection)
+    Event evp[4];                   // brackets of the two halo exchanges (records on the main stream, SH rows on aux2)
     float part_ms[4] = {0, 0, 0, 0};                            // their durations (gsr_hem_get_part_ms)
     DevBuf sh_send;
     float rho = 3.0f, delta = 3.0f, kappa = 2.5f, tau = 1.0f;
@@ -2529,7 +2529,7 @@ struct gsr_hem_ctx {
     bool partition_fixed = true;    // bucket regions of fixed capacity filled straight from the segments (GSR_HEM_PARTITION=exact: histogram + scan)
     bool partition_overflowed = false;      // a region overflowed once: this context uses the exact partition from then on
     double partition_factor = 0.0;  // GSR_HEM_PARTITION_FACTOR: region capacity in multiples of the mean (test knob: < 1 forces the overflow path)
-    unsigned long long* host_rb = nullptr;      // pinned host memory the device writes read-backs into (16 words; [15] = sequence number)
+    PinnedBlock host_rb;            // unsigned long long[64], the device writes read-backs into it: [0..14] k_collect, [15] sequence number, [16..31] k_level_collect
     unsigned long long rb_seq = 0;
     bool rb_poll = true;            // the host polls the sequence word (GSR_HEM_RB_POLL=0: hipStreamSynchronize)
     DevBuf rec, bbox, bbox_part, gparams, keys, idx, skeys, order, cellStart, A, geo, shs, Rs, pflag, ppos, plist;
@@ -2547,7 +2547,7 @@ struct gsr_hem_ctx {
     int select_np = 0;              // GSR_HEM_SELECT_NP=1|2|4: light parents per selection wave (the rings are kept across them, see SEL_NP); 0 = by level size
     bool mstep_split = true;        // GSR_HEM_MSTEP_SPLIT=0: a parent of more than MSTEP_SEG pairs keeps ONE wave for all its segments (the schedule of rounds 1-3)
     DevBuf mh_list, mh_items, mh_scratch;
-    hipEvent_t ev_mfork = nullptr, ev_mjoin = nullptr;          // the heavy parents' segments run on the second stream beside k_mstep
+    Event ev_mfork, ev_mjoin;       // the heavy parents' segments run on the second stream beside k_mstep
     bool mstep_small = true;        // GSR_HEM_MSTEP_SMALL=0: no four-at-a-time path for the parents of <= 16 pairs (test knob: nothing may change)
     bool use_ell = true;            // GSR_HEM_ELL=0: no ellipsoid row clipping (test knob: the pair set must not change)
     int shard_rank = 0, shard_world = 1;      // work-sharded level: parents split over ranks, data replicated
@@ -2562,27 +2562,28 @@ struct gsr_hem_ctx {
     int64_t stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     int64_t stats_ex[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     float phase_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    hipEvent_t ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    hipEvent_t evk[4] = {nullptr, nullptr, nullptr, nullptr};   // brackets of k_select<COUNT> and k_select<FILL>
-    hipEvent_t evm[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // brackets of k_mstep, k_partition, k_bucket_sum
+    Event ev[8];
+    Event evk[4];                   // brackets of k_select<COUNT> and k_select<FILL>
+    Event evm[6];                   // brackets of k_mstep, k_partition, k_bucket_sum
     float kernel_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     // The PROLOGUE of a level -- packed records, bounding box, axis histograms, grid geometry, the counts of parents and irregular
     // components: everything the host needs before it can size and launch the level -- is computed when the level's INPUT comes into
     // being (gsr_hem_set_level0, the end of the level before), and its answer rides in that moment's round trip.  pro.valid: `rec`,
     // `gparams` and the counter block pro.cblock hold it for the current level of pro.n components.
     struct Prologue { bool valid = false; GridParams gp; int P = 0, n_irr = 0, cblock = 0; int64_t n = 0; float ms = 0.0f; } pro;
-    hipEvent_t ev_pro[2] = {nullptr, nullptr};      // brackets of a prologue: its time counts for the level that consumes it (pro.ms)
+    Event ev_pro[2];                // brackets of a prologue: its time counts for the level that consumes it (pro.ms)
     int cblock = 0;                 // which of the two counter blocks the running level uses (the next level's prologue clears the other)
     DevBuf lvl;                     // long long[8]: device-resident counts of an asynchronous level (k_level_tail); [2] = work-item size (k_heavy_items)
     bool async_ok = true;           // GSR_HEM_ASYNC=0: every level sizes its buffers from counts read back on the way (five round trips, the rounds 1-4 schedule)
     bool last_level = false;        // gsr_hem_run_levels: the level being run is the last of its hierarchy -- no prologue of a next level behind it
-    hipStream_t side = nullptr;     // gsr_hem_run_levels: the levels' normals beside the next level
-    hipEvent_t ev_side = nullptr, ev_side_fork = nullptr;
+    Stream side;                    // gsr_hem_run_levels: the levels' normals beside the next level (created on first use, with its events)
+    Event ev_side, ev_side_fork;
     int round_trips = 0;            // host round trips of the last gsr_hem_run_level (statistic: gsr_hem_get_stats_ex [6])
     int was_async = 0;              // the last level ran without a round trip between its first and its last kernel ([7])
     float cell_target = 16.0f;      // components per grid cell (GSR_HEM_CELL_TARGET; the result does not depend on it).  Swept at 5 M after the parents left
                                     // the candidate stream: 5 -> 13.15 ms per level, 8 -> 12.87, 12 -> 12.70, 16 -> 12.61, 24 -> 12.60, 32 -> 12.68 (fewer, longer rows)
     int max_cells = 1 << 24;
+    ~gsr_hem_ctx();
 };
 
 namespace {
@@ -2692,7 +2693,7 @@ int32_t wait_round_trip(gsr_hem_ctx* c, unsigned long long seq) {
     if (c->rb_poll) {
         (void)hipStreamQuery(c->stream);                        // makes sure the queue is submitted
         (void)hipGetLastError();                                // (hipErrorNotReady is not an error here)
-        volatile unsigned long long* flag = c->host_rb + 15;
+        volatile unsigned long long* flag = c->host_rb.as<unsigned long long>() + 15;
         const auto t0 = std::chrono::steady_clock::now();
         for (unsigned spins = 1; !(seen = __atomic_load_n(flag, __ATOMIC_ACQUIRE) == seq); ++spins) {
             if ((spins & 0x3ffu) == 0u && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(200)) break;   // a fault upstream: let the
@@ -2704,19 +2705,19 @@ int32_t wait_round_trip(gsr_hem_ctx* c, unsigned long long seq) {
 }
 int32_t read_back(gsr_hem_ctx* c, const Collect& q, unsigned long long* out) {
     const unsigned long long seq = ++c->rb_seq;
-    hipLaunchKernelGGL(k_collect, dim3(1), dim3(8), 0, c->stream, q, c->host_rb, seq);
+    hipLaunchKernelGGL(k_collect, dim3(1), dim3(8), 0, c->stream, q, c->host_rb.as<unsigned long long>(), seq);
     GSR_HIP(hipGetLastError());
     GSR_TRY(wait_round_trip(c, seq));
-    for (int i = 0; i < q.n; ++i) out[i] = __atomic_load_n(c->host_rb + i, __ATOMIC_RELAXED);
+    for (int i = 0; i < q.n; ++i) out[i] = __atomic_load_n(c->host_rb.as<unsigned long long>() + i, __ATOMIC_RELAXED);
     return GSR_OK;
 }
 // the level-wide answer (k_level_collect): LC_WORDS words
 int32_t read_back_level(gsr_hem_ctx* c, const LevelCollect& q, unsigned long long* out) {
     const unsigned long long seq = ++c->rb_seq;
-    hipLaunchKernelGGL(k_level_collect, dim3(1), dim3(64), 0, c->stream, q, c->host_rb, seq);
+    hipLaunchKernelGGL(k_level_collect, dim3(1), dim3(64), 0, c->stream, q, c->host_rb.as<unsigned long long>(), seq);
     GSR_HIP(hipGetLastError());
     GSR_TRY(wait_round_trip(c, seq));
-    for (int i = 0; i < LC_WORDS; ++i) out[i] = __atomic_load_n(c->host_rb + 16 + i, __ATOMIC_RELAXED);
+    for (int i = 0; i < LC_WORDS; ++i) out[i] = __atomic_load_n(c->host_rb.as<unsigned long long>() + 16 + i, __ATOMIC_RELAXED);
     return GSR_OK;
 }
 
@@ -2811,11 +2812,18 @@ void unborrow_level0(gsr_hem_ctx* c) {
     if (!c->cur_borrowed) return;
     for (int i = 0; i < 5; ++i) {
         DevBuf* b = level_big(c->cur, i);
-        b->p = nullptr; b->cap = 0;                 // the caller's memory: never freed here
+        b->release();                               // the caller's memory: let go, never freed
         b->swap(c->spare[i]);
     }
     c->cur_borrowed = false;
 }
+}  // namespace
+// the members free themselves (on the context's device); a borrowed level 0 goes back to the caller first, cur gets its own buffers again
+gsr_hem_ctx::~gsr_hem_ctx() {
+    (void)hipSetDevice(device);
+    unborrow_level0(this);
+}
+namespace {
 
 // The prologue of the level whose input is L (gsr_hem_ctx::Prologue): k_prep (the packed records, box partials, the counts of parents
 // and irregular components), their fold (which also clears the level's counter block and the histograms), the axis histograms, the grid
@@ -2886,38 +2894,26 @@ int32_t gsr_hem_create(gsr_hem_ctx** out, int32_t device, void* stream) {
     gsr_hem_ctx* c = new gsr_hem_ctx();
     c->device = device;
     c->stream = (hipStream_t)stream;
-    for (int i = 0; i < 8; ++i) {
-        hipError_t e = hipEventCreate(&c->ev[i]);
-        if (e != hipSuccess) { delete c; return fail(GSR_E_HIP, "hipEventCreate: %s", hipGetErrorString(e)); }
-    }
-    for (int i = 0; i < 4; ++i) {
-        hipError_t e = hipEventCreate(&c->evk[i]);
-        if (e != hipSuccess) { delete c; return fail(GSR_E_HIP, "hipEventCreate: %s", hipGetErrorString(e)); }
-    }
-    for (int i = 0; i < 6; ++i) {
-        hipError_t e = hipEventCreate(&c->evm[i]);
+    {
+        hipError_t e = hipSuccess;
+        for (Event& ev : c->ev) if (e == hipSuccess) e = ev.create();
+        for (Event& ev : c->evk) if (e == hipSuccess) e = ev.create();
+        for (Event& ev : c->evm) if (e == hipSuccess) e = ev.create();
         if (e != hipSuccess) { delete c; return fail(GSR_E_HIP, "hipEventCreate: %s", hipGetErrorString(e)); }
     }
     {
-        hipError_t e = hipStreamCreateWithFlags(&c->aux, hipStreamNonBlocking);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_pre, hipEventDisableTiming);
-        if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->aux2, hipStreamNonBlocking);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_sh_fork, hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_sh_join, hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_halo, hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_mfork, hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_mjoin, hipEventDisableTiming);
-        for (int i = 0; i < 4 && e == hipSuccess; ++i) e = hipEventCreate(&c->evp[i]);
-        for (int i = 0; i < 2 && e == hipSuccess; ++i) e = hipEventCreate(&c->ev_pro[i]);
+        hipError_t e = c->aux.create();
+        for (Event* ev : {&c->ev_fork, &c->ev_join, &c->ev_pre}) if (e == hipSuccess) e = ev->create_untimed();
+        if (e == hipSuccess) e = c->aux2.create();
+        for (Event* ev : {&c->ev_sh_fork, &c->ev_sh_join, &c->ev_halo, &c->ev_mfork, &c->ev_mjoin}) if (e == hipSuccess) e = ev->create_untimed();
+        for (Event& ev : c->evp) if (e == hipSuccess) e = ev.create();
+        for (Event& ev : c->ev_pro) if (e == hipSuccess) e = ev.create();
         if (e != hipSuccess) { delete c; return fail(GSR_E_HIP, "second stream: %s", hipGetErrorString(e)); }
     }
     {
-        // pinned, device-mapped, COHERENT: the read-back kernel's system-scope stores must reach the host while the stream is running
-        hipError_t e = hipHostMalloc((void**)&c->host_rb, 512, hipHostMallocMapped | hipHostMallocCoherent);      // [0..14] k_collect, [15] sequence, [16..31] k_level_collect
-        if (e != hipSuccess) { c->host_rb = nullptr; delete c; return fail(GSR_E_HIP, "hipHostMalloc: %s", hipGetErrorString(e)); }
-        memset(c->host_rb, 0, 512);
+        // the read-back kernel's system-scope stores must reach the host while the stream is running
+        hipError_t e = c->host_rb.alloc(512);
+        if (e != hipSuccess) { delete c; return fail(GSR_E_HIP, "hipHostMalloc: %s", hipGetErrorString(e)); }
     }
     // Environment knobs (all of them): none changes a result, each is exercised by a test.
     if (const char* s = getenv("GSR_HEM_ELL")) c->use_ell = atoi(s) != 0;
@@ -2952,43 +2948,7 @@ int32_t gsr_hem_create(gsr_hem_ctx** out, int32_t device, void* stream) {
 }
 
 int32_t gsr_hem_destroy(gsr_hem_ctx* c) {
-    if (!c) return GSR_OK;
-    (void)hipSetDevice(c->device);
-    unborrow_level0(c);
-    for (DevBuf& b : c->spare) b.release();
-    for (DevBuf& b : c->spare_out) b.release();
-    c->cur.release(); c->nxt.release(); c->tmp.release();
-    DevBuf* part_bufs[] = {&c->gid, &c->gid_next, &c->rec_loc, &c->gid_loc, &c->ghost_sh, &c->ghost_src, &c->perm, &c->pown, &c->ppos_own, &c->inv, &c->gmax, &c->gacc,
-                           &c->cmask, &c->dflag, &c->dpos, &c->sent_idx, &c->rows_send, &c->rows_recv, &c->sh_send, &c->xsend, &c->xrecv, &c->gbits, &c->wcnt, &c->wpre,
-                           &c->grank, &c->allflags, &c->pcounts, &c->pmatrix};
-    for (DevBuf* b : part_bufs) b->release();
-    DevBuf* all[] = {&c->rec, &c->bbox, &c->bbox_part, &c->gparams, &c->keys, &c->idx, &c->skeys, &c->order, &c->cellStart, &c->A, &c->geo, &c->shs,
-                     &c->Rs, &c->pflag, &c->ppos, &c->plist, &c->hitem, &c->hfirst, &c->part_cnt, &c->Ac, &c->cellStartC, &c->cellStartI, &c->pcnt, &c->poff, &c->pair_child, &c->pair_wl,
-                     &c->spair_child, &c->spair_wl, &c->cstart, &c->sumLw, &c->oflag, &c->pflag_in, &c->oflag_in, &c->prank_in,
-                     &c->orank_in, &c->hist, &c->iflag, &c->irank, &c->ipos, &c->rng_blocks, &c->bhist, &c->bstart, &c->bcursor,
-                     &c->porder, &c->pkeys, &c->pkeys2, &c->pidx, &c->mhdr, &c->prec, &c->rowlist, &c->shard_send, &c->shard_recv, &c->pcap, &c->coff, &c->sp_child, &c->sp_wl,
-                     &c->keep, &c->kpos, &c->scratch, &c->draws, &c->counters, &c->rocprim_tmp, &c->rocprim_tmp2, &c->mh_list, &c->mh_items, &c->mh_scratch, &c->lvl, &c->sh_tail, &c->holes, &c->erase_halo};
-    for (DevBuf* b : all) b->release();
-    if (c->host_rb) (void)hipHostFree(c->host_rb);
-    for (int i = 0; i < 8; ++i) if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
-    for (int i = 0; i < 4; ++i) if (c->evk[i]) (void)hipEventDestroy(c->evk[i]);
-    for (int i = 0; i < 6; ++i) if (c->evm[i]) (void)hipEventDestroy(c->evm[i]);
-    if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
-    if (c->ev_pre) (void)hipEventDestroy(c->ev_pre);
-    if (c->ev_join) (void)hipEventDestroy(c->ev_join);
-    if (c->ev_sh_fork) (void)hipEventDestroy(c->ev_sh_fork);
-    if (c->ev_sh_join) (void)hipEventDestroy(c->ev_sh_join);
-    if (c->ev_halo) (void)hipEventDestroy(c->ev_halo);
-    if (c->ev_mfork) (void)hipEventDestroy(c->ev_mfork);
-    if (c->ev_mjoin) (void)hipEventDestroy(c->ev_mjoin);
-    for (int i = 0; i < 4; ++i) if (c->evp[i]) (void)hipEventDestroy(c->evp[i]);
-    for (int i = 0; i < 2; ++i) if (c->ev_pro[i]) (void)hipEventDestroy(c->ev_pro[i]);
-    if (c->aux) (void)hipStreamDestroy(c->aux);
-    if (c->aux2) (void)hipStreamDestroy(c->aux2);
-    if (c->side) (void)hipStreamDestroy(c->side);
-    if (c->ev_side) (void)hipEventDestroy(c->ev_side);
-    if (c->ev_side_fork) (void)hipEventDestroy(c->ev_side_fork);
-    delete c;
+    delete c;       // (NULL: nothing)
     return GSR_OK;
 }
 
@@ -3031,12 +2991,12 @@ int32_t gsr_hem_set_level0(gsr_hem_ctx* c, const float* xyz, const float* color,
     Level& L = c->cur;
     if (on_device == 2 && n > 0) {
         // borrow: no copy of the five big arrays (1.19 GB at 5 M splats); they must stay valid and unchanged until the
-        // next gsr_hem_run_level returns.  cap = SIZE_MAX makes every later reserve() on them a no-op.
+        // next gsr_hem_run_level returns.  Every later reserve() on a borrowed buffer is a no-op.
         const void* src[5] = {xyz, color, cov6, opacity, F > 0 ? sh : xyz};
         for (int i = 0; i < 5; ++i) {
             DevBuf* b = level_big(L, i);
             b->swap(c->spare[i]);
-            b->p = const_cast<void*>(src[i]); b->cap = (size_t)-1;
+            b->borrow(const_cast<void*>(src[i]));
         }
         c->cur_borrowed = true;
         const size_t mm = (size_t)n;
@@ -3558,7 +3518,7 @@ struct LevelRun {
         memset(&sa, 0, sizeof(sa));
     }
     ~LevelRun() {       // an error return hands nxt its own buffers back
-        if (out_active) for (int i = 0; i < 5; ++i) { DevBuf* b = level_big(c->nxt, i); b->p = nullptr; b->cap = 0; b->swap(c->spare_out[i]); }
+        if (out_active) for (int i = 0; i < 5; ++i) { DevBuf* b = level_big(c->nxt, i); b->release(); b->swap(c->spare_out[i]); }
     }
 
     int32_t run(int64_t* n_out, int64_t* n_dropped);
@@ -4097,7 +4057,7 @@ int32_t LevelRun::open_output() {
             for (int i = 0; i < 5; ++i) {
                 DevBuf* b = level_big(O, i);
                 b->swap(c->spare_out[i]);
-                b->p = c->out_ptr[i] ? c->out_ptr[i] : c->out_ptr[0]; b->cap = (size_t)-1;       // reserve() on them is a no-op
+                b->borrow(c->out_ptr[i] ? c->out_ptr[i] : c->out_ptr[0]);       // reserve() on them is a no-op
             }
             out_active = true;
         }
@@ -4515,9 +4475,9 @@ int32_t gsr_hem_run_levels(gsr_hem_ctx* c, int32_t n_levels, float* xyz, float* 
     const int F = c->cur.F;
     const bool want_normals = normals != nullptr || normals0 != nullptr;
     if (want_normals && !c->side) {
-        GSR_HIP(hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking));
-        GSR_HIP(hipEventCreateWithFlags(&c->ev_side, hipEventDisableTiming));
-        GSR_HIP(hipEventCreateWithFlags(&c->ev_side_fork, hipEventDisableTiming));
+        GSR_HIP(c->side.create());
+        GSR_HIP(c->ev_side.create_untimed());
+        GSR_HIP(c->ev_side_fork.create_untimed());
     }
     bool side_used = false;
     // the side stream starts behind whatever the caller has enqueued on the context's stream (the arrays of level 0 may still be written)
@@ -4570,27 +4530,20 @@ int32_t gsr_hem_run_levels(gsr_hem_ctx* c, int32_t n_levels, float* xyz, float* 
 int32_t gsr_debug_select_profile(unsigned long long* out16, int32_t reset) { return select_profile(out16, reset); }
 #endif
 
+// The test hooks: host arrays in, one kernel on the null stream, host arrays out (OneShot stages, copies back, waits and frees).
 int32_t gsr_debug_logf(const float* x, int64_t n, float* out, int32_t device) {
     if (n < 0 || (n > 0 && (!x || !out))) return fail(GSR_E_INVALID, "gsr_debug_logf: bad argument");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(GSR_E_NO_DEVICE, "gsr_debug_logf: no HIP device visible");
     if (n == 0) return GSR_OK;
     GSR_HIP(hipSetDevice(device));
-    DevBuf a, b;
-    int32_t r = a.reserve((size_t)n * 4);
-    if (r == GSR_OK) r = b.reserve((size_t)n * 4);
-    hipError_t e = hipSuccess;
-    if (r == GSR_OK) {
-        e = hipMemcpy(a.p, x, (size_t)n * 4, hipMemcpyHostToDevice);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(k_debug_logf, dim3(stride_grid(n)), dim3(256), 0, nullptr, n, a.as<float>(), b.as<float>());
-            e = hipMemcpy(out, b.p, (size_t)n * 4, hipMemcpyDeviceToHost);
-        }
-    }
-    a.release(); b.release();
-    if (r != GSR_OK) return r;
-    if (e != hipSuccess) return fail(GSR_E_HIP, "gsr_debug_logf: %s", hipGetErrorString(e));
-    return GSR_OK;
+    OneShot os(nullptr, false, "gsr_debug_logf");
+    const float* dx = nullptr;
+    float* dout = nullptr;
+    GSR_TRY(os.in(x, (size_t)n * 4, &dx));
+    GSR_TRY(os.out(out, (size_t)n * 4, &dout));
+    hipLaunchKernelGGL(k_debug_logf, dim3(stride_grid(n)), dim3(256), 0, os.st, n, dx, dout);
+    return os.finish();
 }
 
 int32_t gsr_debug_kld(const float* cm, const float* cc, const float* pm, const float* pc, int64_t n, float* out, int32_t device) {
@@ -4599,22 +4552,14 @@ int32_t gsr_debug_kld(const float* cm, const float* cc, const float* pm, const f
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(GSR_E_NO_DEVICE, "gsr_debug_kld: no HIP device visible");
     if (n == 0) return GSR_OK;
     GSR_HIP(hipSetDevice(device));
-    DevBuf b[5];
-    const size_t sz[5] = {(size_t)n * 12, (size_t)n * 24, (size_t)n * 12, (size_t)n * 24, (size_t)n * 4};
-    const float* src[4] = {cm, cc, pm, pc};
-    int32_t r = GSR_OK;
-    hipError_t e = hipSuccess;
-    for (int i = 0; i < 5 && r == GSR_OK; ++i) r = b[i].reserve(sz[i]);
-    for (int i = 0; i < 4 && r == GSR_OK && e == hipSuccess; ++i) e = hipMemcpy(b[i].p, src[i], sz[i], hipMemcpyHostToDevice);
-    if (r == GSR_OK && e == hipSuccess) {
-        hipLaunchKernelGGL(k_debug_kld, dim3(stride_grid(n)), dim3(256), 0, nullptr, n, b[0].as<float>(), b[1].as<float>(), b[2].as<float>(),
-                           b[3].as<float>(), b[4].as<float>());
-        e = hipMemcpy(out, b[4].p, sz[4], hipMemcpyDeviceToHost);
-    }
-    for (int i = 0; i < 5; ++i) b[i].release();
-    if (r != GSR_OK) return r;
-    if (e != hipSuccess) return fail(GSR_E_HIP, "gsr_debug_kld: %s", hipGetErrorString(e));
-    return GSR_OK;
+    OneShot os(nullptr, false, "gsr_debug_kld");
+    const float *dcm = nullptr, *dcc = nullptr, *dpm = nullptr, *dpc = nullptr;
+    float* dout = nullptr;
+    GSR_TRY(os.in(cm, (size_t)n * 12, &dcm)); GSR_TRY(os.in(cc, (size_t)n * 24, &dcc));
+    GSR_TRY(os.in(pm, (size_t)n * 12, &dpm)); GSR_TRY(os.in(pc, (size_t)n * 24, &dpc));
+    GSR_TRY(os.out(out, (size_t)n * 4, &dout));
+    hipLaunchKernelGGL(k_debug_kld, dim3(stride_grid(n)), dim3(256), 0, os.st, n, dcm, dcc, dpm, dpc, dout);
+    return os.finish();
 }
 
 int32_t gsr_debug_stage1(const float* parent_mean, const float* parent_cov6, const float* child_mean, const float* child_cov6, int64_t n,
@@ -4626,23 +4571,17 @@ int32_t gsr_debug_stage1(const float* parent_mean, const float* parent_cov6, con
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(GSR_E_NO_DEVICE, "gsr_debug_stage1: no HIP device visible");
     if (n == 0) return GSR_OK;
     GSR_HIP(hipSetDevice(device));
-    DevBuf b[10];
-    const size_t sz[10] = {(size_t)n * 12, (size_t)n * 24, (size_t)n * 12, (size_t)n * 24, (size_t)n, (size_t)n, (size_t)n, (size_t)n, (size_t)n * 4, (size_t)n};
-    const float* src[4] = {parent_mean, parent_cov6, child_mean, child_cov6};
-    void* dst[6] = {parent_regular, child_regular, white, reject, T1, clip_on};
-    int32_t r = GSR_OK;
-    hipError_t e = hipSuccess;
-    for (int i = 0; i < 10 && r == GSR_OK; ++i) r = b[i].reserve(sz[i]);
-    for (int i = 0; i < 4 && r == GSR_OK && e == hipSuccess; ++i) e = hipMemcpy(b[i].p, src[i], sz[i], hipMemcpyHostToDevice);
-    if (r == GSR_OK && e == hipSuccess) {
-        hipLaunchKernelGGL(k_debug_stage1, dim3(stride_grid(n)), dim3(256), 0, nullptr, n, b[0].as<float>(), b[1].as<float>(), b[2].as<float>(), b[3].as<float>(),
-                           kld_thr, b[4].as<uint8_t>(), b[5].as<uint8_t>(), b[6].as<uint8_t>(), b[7].as<uint8_t>(), b[8].as<float>(), b[9].as<uint8_t>());
-        for (int i = 0; i < 6 && e == hipSuccess; ++i) e = hipMemcpy(dst[i], b[4 + i].p, sz[4 + i], hipMemcpyDeviceToHost);
-    }
-    for (int i = 0; i < 10; ++i) b[i].release();
-    if (r != GSR_OK) return r;
-    if (e != hipSuccess) return fail(GSR_E_HIP, "gsr_debug_stage1: %s", hipGetErrorString(e));
-    return GSR_OK;
+    OneShot os(nullptr, false, "gsr_debug_stage1");
+    const float *dpm = nullptr, *dpc = nullptr, *dcm = nullptr, *dcc = nullptr;
+    uint8_t *dpr = nullptr, *dcr = nullptr, *dwhite = nullptr, *dreject = nullptr, *dclip = nullptr;
+    float* dT1 = nullptr;
+    GSR_TRY(os.in(parent_mean, (size_t)n * 12, &dpm)); GSR_TRY(os.in(parent_cov6, (size_t)n * 24, &dpc));
+    GSR_TRY(os.in(child_mean, (size_t)n * 12, &dcm)); GSR_TRY(os.in(child_cov6, (size_t)n * 24, &dcc));
+    GSR_TRY(os.out(parent_regular, (size_t)n, &dpr)); GSR_TRY(os.out(child_regular, (size_t)n, &dcr));
+    GSR_TRY(os.out(white, (size_t)n, &dwhite)); GSR_TRY(os.out(reject, (size_t)n, &dreject));
+    GSR_TRY(os.out(T1, (size_t)n * 4, &dT1)); GSR_TRY(os.out(clip_on, (size_t)n, &dclip));
+    hipLaunchKernelGGL(k_debug_stage1, dim3(stride_grid(n)), dim3(256), 0, os.st, n, dpm, dpc, dcm, dcc, kld_thr, dpr, dcr, dwhite, dreject, dT1, dclip);
+    return os.finish();
 }
 
 int32_t gsr_debug_kl_gate(const float* s2, const float* det_c, const float* det_p, int64_t n, float thr, uint8_t* reject, float* fast_log,
@@ -4652,24 +4591,14 @@ int32_t gsr_debug_kl_gate(const float* s2, const float* det_c, const float* det_
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(GSR_E_NO_DEVICE, "gsr_debug_kl_gate: no HIP device visible");
     if (n == 0) return GSR_OK;
     GSR_HIP(hipSetDevice(device));
-    DevBuf b[6];
-    const size_t sz[6] = {(size_t)n * 4, (size_t)n * 4, (size_t)n * 4, (size_t)n, (size_t)n * 4, (size_t)n};
-    const float* src[3] = {s2, det_c, det_p};
-    int32_t r = GSR_OK;
-    hipError_t e = hipSuccess;
-    for (int i = 0; i < 6 && r == GSR_OK; ++i) r = b[i].reserve(sz[i]);
-    for (int i = 0; i < 3 && r == GSR_OK && e == hipSuccess; ++i) e = hipMemcpy(b[i].p, src[i], sz[i], hipMemcpyHostToDevice);
-    if (r == GSR_OK && e == hipSuccess) {
-        hipLaunchKernelGGL(k_debug_kl_gate, dim3(stride_grid(n)), dim3(256), 0, nullptr, n, b[0].as<float>(), b[1].as<float>(), b[2].as<float>(), thr,
-                           b[3].as<uint8_t>(), b[4].as<float>(), b[5].as<uint8_t>());
-        e = hipMemcpy(reject, b[3].p, sz[3], hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(fast_log, b[4].p, sz[4], hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(need_exact, b[5].p, sz[5], hipMemcpyDeviceToHost);
-    }
-    for (int i = 0; i < 6; ++i) b[i].release();
-    if (r != GSR_OK) return r;
-    if (e != hipSuccess) return fail(GSR_E_HIP, "gsr_debug_kl_gate: %s", hipGetErrorString(e));
-    return GSR_OK;
+    OneShot os(nullptr, false, "gsr_debug_kl_gate");
+    const float *ds2 = nullptr, *ddc = nullptr, *ddp = nullptr;
+    uint8_t *dreject = nullptr, *dexact = nullptr;
+    float* dlog = nullptr;
+    GSR_TRY(os.in(s2, (size_t)n * 4, &ds2)); GSR_TRY(os.in(det_c, (size_t)n * 4, &ddc)); GSR_TRY(os.in(det_p, (size_t)n * 4, &ddp));
+    GSR_TRY(os.out(reject, (size_t)n, &dreject)); GSR_TRY(os.out(fast_log, (size_t)n * 4, &dlog)); GSR_TRY(os.out(need_exact, (size_t)n, &dexact));
+    hipLaunchKernelGGL(k_debug_kl_gate, dim3(stride_grid(n)), dim3(256), 0, os.st, n, ds2, ddc, ddp, thr, dreject, dlog, dexact);
+    return os.finish();
 }
 
 }  // extern "C"

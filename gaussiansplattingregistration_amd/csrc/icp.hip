@@ -1174,7 +1174,7 @@ struct gsr_icp_ctx {
     bool block_search = true;       // GSR_ICP_BLOCK_SEARCH=0: always the ring loop from ring 0
     bool xcd_ranges = true;         // GSR_ICP_XCD=0: logical block = physical block (every XCD walks the whole source)
     gsr_comm* comm = nullptr;       // multi-GPU source split through a communicator (gsr_icp_set_comm)
-    unsigned* host_rb = nullptr;    // pinned host memory for small read-backs: 256 words + the sequence flag
+    PinnedBlock host_rb;            // small read-backs: unsigned[256] + the sequence flag; empty = no polling (icp_fetch)
     unsigned long long rb_seq = 0;
     // Search / accumulate split (GSR_ICP_NN_KERNEL): 0 = one fused kernel (120 VGPRs with the 30 float64 accumulators:
     // 4 waves per SIMD); 2 = a thread-per-point search kernel (56 VGPRs, 8 waves per SIMD) writes nn_j and a streaming
@@ -1196,7 +1196,7 @@ struct gsr_icp_ctx {
     void* allreduce_user = nullptr;
     gsr_allreduce_dev64_fn allreduce_dev = nullptr;      // device-resident loop with a stream-ordered collective per iteration
     void* allreduce_dev_user = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr, eb0 = nullptr, eb1 = nullptr;      // e0 / e1: the iteration loop; eb0 / eb1: the target index build
+    Event e0, e1, eb0, eb1;         // e0 / e1: the iteration loop; eb0 / eb1: the target index build
     bool defer_sync = false;        // gsr_icp_register_clouds: set_target / set_source do not wait for the stream (the registration behind them does)
     bool build_pending = false;     // ms_build has not been read from eb0 / eb1 yet
     float ms_build = 0, ms_iter = 0;
@@ -1205,6 +1205,7 @@ struct gsr_icp_ctx {
     // workgroups of the search + accumulate kernel: three fit a CU (141 VGPRs), 768 are ONE round on the chip.  With 1 024 the last
     // 256 ran as a second, quarter-full round: 108 -> 95 us per iteration at 556 k source points (GSR_ICP_BLOCKS)
     int nblocks = 768;
+    ~gsr_icp_ctx() { (void)hipSetDevice(device); }     // the members free themselves, on the context's device
 };
 
 namespace {
@@ -1327,14 +1328,15 @@ __global__ void k_icp_publish(const unsigned* __restrict__ src, int nwords, unsi
 }
 static int32_t icp_fetch(gsr_icp_ctx* c, const void* dev, void* out, size_t bytes) {
     hipStream_t st = c->stream;
-    if (!c->host_rb || bytes > 1024 || (bytes & 3)) {
+    unsigned* const host_rb = c->host_rb.as<unsigned>();
+    if (!host_rb || bytes > 1024 || (bytes & 3)) {
         GSR_HIP(hipMemcpyAsync(out, dev, bytes, hipMemcpyDeviceToHost, st));
         GSR_HIP(hipStreamSynchronize(st));
         return GSR_OK;
     }
     const unsigned long long seq = ++c->rb_seq;
-    unsigned long long* flag = reinterpret_cast<unsigned long long*>(c->host_rb + 256);
-    hipLaunchKernelGGL(k_icp_publish, dim3(1), dim3(64), 0, st, (const unsigned*)dev, (int)(bytes >> 2), c->host_rb, flag, seq);
+    unsigned long long* flag = reinterpret_cast<unsigned long long*>(host_rb + 256);
+    hipLaunchKernelGGL(k_icp_publish, dim3(1), dim3(64), 0, st, (const unsigned*)dev, (int)(bytes >> 2), host_rb, flag, seq);
     GSR_HIP(hipGetLastError());
     (void)hipStreamQuery(st);
     (void)hipGetLastError();
@@ -1345,7 +1347,7 @@ static int32_t icp_fetch(gsr_icp_ctx* c, const void* dev, void* out, size_t byte
         gsr::cpu_relax(spins);
     }
     if (!seen) GSR_HIP(hipStreamSynchronize(st));
-    memcpy(out, (const void*)c->host_rb, bytes);
+    memcpy(out, (const void*)host_rb, bytes);
     return GSR_OK;
 }
 
@@ -1360,7 +1362,7 @@ int32_t gsr_icp_create(gsr_icp_ctx** out, int32_t device, void* stream) {
     gsr_icp_ctx* c = new gsr_icp_ctx();
     c->device = device;
     c->stream = (hipStream_t)stream;
-    if (hipEventCreate(&c->e0) != hipSuccess || hipEventCreate(&c->e1) != hipSuccess || hipEventCreate(&c->eb0) != hipSuccess || hipEventCreate(&c->eb1) != hipSuccess) {
+    if (c->e0.create() != hipSuccess || c->e1.create() != hipSuccess || c->eb0.create() != hipSuccess || c->eb1.create() != hipSuccess) {
         delete c; return fail(GSR_E_HIP, "hipEventCreate failed");
     }
     // Environment knobs (all of them): none changes a result, tests/test_icp_gpu.py::test_icp_knobs_change_nothing
@@ -1373,8 +1375,7 @@ int32_t gsr_icp_create(gsr_icp_ctx** out, int32_t device, void* stream) {
     // running (a non-coherent mapping would only show them at the end of the kernel).  GSR_ICP_RB_POLL=0: no polling at all
     bool poll = true;
     if (const char* e = getenv("GSR_ICP_RB_POLL")) poll = atoi(e) != 0;
-    if (poll && hipHostMalloc((void**)&c->host_rb, 1024 + 64, hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess) memset(c->host_rb, 0, 1024 + 64);
-    else { c->host_rb = nullptr; (void)hipGetLastError(); }
+    if (!poll || c->host_rb.alloc(1024 + 64) != hipSuccess) (void)hipGetLastError();
     if (const char* e = getenv("GSR_ICP_NN_KERNEL")) c->nn_kernel = atoi(e);
     if (const char* e = getenv("GSR_ICP_CELL_TARGET")) { double v = atof(e); if (v > 0.01 && v < 1000) c->cell_target = v; }
     if (const char* e = getenv("GSR_ICP_MAX_CELLS")) { int v = atoi(e); if (v >= 1024) c->max_cells = v; }
@@ -1383,17 +1384,7 @@ int32_t gsr_icp_create(gsr_icp_ctx** out, int32_t device, void* stream) {
 }
 
 int32_t gsr_icp_destroy(gsr_icp_ctx* c) {
-    if (!c) return GSR_OK;
-    (void)hipSetDevice(c->device);
-    DevBuf* all[] = {&c->hist, &c->src_raw, &c->src_order, &c->state, &c->nn_j, &c->Tc, &c->Sc, &c->stage_cov, &c->Ti, &c->Tg, &c->Si, &c->bbox, &c->keys, &c->idx, &c->skeys, &c->order, &c->cellStart, &c->Tq, &c->Tn, &c->stage_xyz, &c->stage_nrm,
-                     &c->src, &c->partials, &c->acc_dev, &c->rocprim_tmp, &c->corr_idx, &c->corr_d2};
-    for (DevBuf* b : all) b->release();
-    if (c->e0) (void)hipEventDestroy(c->e0);
-    if (c->e1) (void)hipEventDestroy(c->e1);
-    if (c->eb0) (void)hipEventDestroy(c->eb0);
-    if (c->eb1) (void)hipEventDestroy(c->eb1);
-    if (c->host_rb) (void)hipHostFree(c->host_rb);
-    delete c;
+    delete c;       // (NULL: nothing)
     return GSR_OK;
 }
 

@@ -235,8 +235,12 @@ struct gsr_raster_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
     DevBuf splat, depth, rect, counts, offsets, keys, keys2, vals, vals2, ranges, tmp, counters;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    Event ev[4];
     bool timed = false;
+    ~gsr_raster_ctx() {     // waits for the stream, then the members free themselves (on the context's device)
+        (void)hipSetDevice(device);
+        (void)hipStreamSynchronize(stream);
+    }
 };
 
 extern "C" int32_t gsr_raster_create(gsr_raster_ctx** out, int32_t device, void* stream) {
@@ -246,21 +250,14 @@ extern "C" int32_t gsr_raster_create(gsr_raster_ctx** out, int32_t device, void*
     gsr_raster_ctx* c = new gsr_raster_ctx();
     c->device = device;
     c->stream = (hipStream_t)stream;
-    for (hipEvent_t& e : c->ev)
-        if (hipEventCreate(&e) != hipSuccess) { e = nullptr; (void)gsr_raster_destroy(c); return fail(GSR_E_HIP, "gsr_raster_create: hipEventCreate failed"); }
+    for (Event& e : c->ev)
+        if (e.create() != hipSuccess) { delete c; return fail(GSR_E_HIP, "gsr_raster_create: hipEventCreate failed"); }
     *out = c;
     return GSR_OK;
 }
 
 extern "C" int32_t gsr_raster_destroy(gsr_raster_ctx* c) {
-    if (!c) return GSR_OK;
-    (void)hipSetDevice(c->device);
-    (void)hipStreamSynchronize(c->stream);
-    DevBuf* all[] = {&c->splat, &c->depth, &c->rect, &c->counts, &c->offsets, &c->keys, &c->keys2, &c->vals, &c->vals2, &c->ranges, &c->tmp, &c->counters};
-    for (DevBuf* b : all) b->release();
-    for (hipEvent_t e : c->ev)
-        if (e) (void)hipEventDestroy(e);
-    delete c;
+    delete c;       // (NULL: nothing)
     return GSR_OK;
 }
 

@@ -104,6 +104,7 @@ struct gsr_voxel_result {
     int64_t V = 0;
     bool has_cov = false, has_color = false;
     DevBuf xyz, cov6, color;
+    ~gsr_voxel_result() { (void)hipSetDevice(device); }     // the members free themselves, on the result's device
 };
 
 extern "C" {
@@ -198,10 +199,7 @@ int32_t gsr_voxel_fetch(gsr_voxel_result* r, double* xyz, double* cov6, double* 
 }
 
 int32_t gsr_voxel_free(gsr_voxel_result* r) {
-    if (!r) return GSR_OK;
-    (void)hipSetDevice(r->device);
-    r->xyz.release(); r->cov6.release(); r->color.release();
-    delete r;
+    delete r;       // (NULL: nothing)
     return GSR_OK;
 }
 
