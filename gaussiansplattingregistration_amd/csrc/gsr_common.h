@@ -5,6 +5,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
+#include <chrono>
 #include <string>
 
 #include "../../include/gsr_hip.h"
@@ -114,6 +115,24 @@ inline void cpu_relax(unsigned spins) {
     asm volatile("" ::: "memory");
 #endif
     if (spins > 4096u && (spins & 63u) == 0u) sched_yield();
+}
+
+// The host's wait for the sequence number `seq` that a kernel already enqueued on `st` publishes in pinned memory behind its payload
+// (k_collect, k_level_collect, k_icp_publish).  poll: the host does not call hipStreamSynchronize (20-75 us until the thread is awake
+// again) but looks at that word in its own memory (~5 us); after 200 ms, or without polling, the synchronisation waits and reports.
+inline int32_t wait_host_flag(hipStream_t st, const volatile unsigned long long* flag, unsigned long long seq, bool poll) {
+    bool seen = false;
+    if (poll) {
+        (void)hipStreamQuery(st);                               // makes sure the queue is submitted
+        (void)hipGetLastError();                                // (hipErrorNotReady is not an error here)
+        const auto t0 = std::chrono::steady_clock::now();
+        for (unsigned spins = 1; !(seen = __atomic_load_n(flag, __ATOMIC_ACQUIRE) == seq); ++spins) {
+            if ((spins & 0x3ffu) == 0u && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(200)) break;   // a fault upstream: let the
+            cpu_relax(spins);                                                                                             // synchronisation report it
+        }
+    }
+    if (!seen) GSR_HIP(hipStreamSynchronize(st));
+    return GSR_OK;
 }
 
 inline int ceil_div(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }

@@ -1,4 +1,4 @@
-// hem_select.h -- what the child selection (hem_select.hip: k_parent_prep, k_spans, k_select) shares with the rest of the level (hem.hip):
+// hem_select.h -- what the child selection (hem_select.hip: k_parent_prep, k_spans, k_select) shares with the rest of the level (hem.hip and its host headers):
 // the argument block, the per-parent record, the row-span and filter geometry (also used by the partitioned level's halo marking and
 // by the test hooks), and the launchers.  hem_select.hip is the one translation unit built without MachineLICM.
 #pragma once

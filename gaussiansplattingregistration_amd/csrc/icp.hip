@@ -33,15 +33,13 @@
 #include "gsr_solve.h"
 #include "gsr_features.h"
 #include "gsr_oneshot.h"
+#include "gsr_prims.h"
 
 #include <float.h>
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
-#include <chrono>
 #include <vector>
-
-#include <rocprim/rocprim.hpp>
 
 namespace gsr {
 // rocPRIM's Onesweep with its gfx950 kernel shapes but 11 bits per pass: the 22-bit cell keys of a 5 M-point grid take two passes
@@ -1318,7 +1316,7 @@ extern "C" {
 
 // Small device results the host waits for (the bounding box, the loop state) are copied by one tiny kernel into pinned host
 // memory, the sequence number of the round trip last, and the host polls that word: a hipMemcpyAsync into pageable memory
-// plus hipStreamSynchronize costs 30-50 us per round trip (hem.hip does the same).
+// plus hipStreamSynchronize costs 30-50 us per round trip (wait_host_flag, gsr_common.h: the HEM read-backs wait the same way).
 __global__ void k_icp_publish(const unsigned* __restrict__ src, int nwords, unsigned* __restrict__ host, unsigned long long* __restrict__ flag,
                               unsigned long long seq) {
     for (int t = threadIdx.x; t < nwords; t += blockDim.x) __hip_atomic_store(host + t, src[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -1338,15 +1336,7 @@ static int32_t icp_fetch(gsr_icp_ctx* c, const void* dev, void* out, size_t byte
     unsigned long long* flag = reinterpret_cast<unsigned long long*>(host_rb + 256);
     hipLaunchKernelGGL(k_icp_publish, dim3(1), dim3(64), 0, st, (const unsigned*)dev, (int)(bytes >> 2), host_rb, flag, seq);
     GSR_HIP(hipGetLastError());
-    (void)hipStreamQuery(st);
-    (void)hipGetLastError();
-    bool seen = false;
-    const auto t0 = std::chrono::steady_clock::now();
-    for (unsigned spins = 1; !(seen = __atomic_load_n(flag, __ATOMIC_ACQUIRE) == seq); ++spins) {
-        if ((spins & 0x3ffu) == 0u && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(200)) break;
-        gsr::cpu_relax(spins);
-    }
-    if (!seen) GSR_HIP(hipStreamSynchronize(st));
+    GSR_TRY(wait_host_flag(st, flag, seq, true));       // (GSR_ICP_RB_POLL=0 left host_rb empty: the copy above)
     memcpy(out, (const void*)host_rb, bytes);
     return GSR_OK;
 }
@@ -1461,12 +1451,8 @@ int32_t gsr_icp_set_target(gsr_icp_ctx* c, const float* xyz, const double* norma
     hipLaunchKernelGGL(k_icp_keys, dim3(stride_grid(n)), dim3(256), 0, st, n, dxyz, g, c->keys.as<unsigned>(), c->idx.as<unsigned>());
     int bits = 1;
     while (bits < 32 && ((int64_t)1 << bits) < g.ncells) ++bits;
-    size_t bytes = 0;
-    GSR_HIP(rocprim::radix_sort_pairs<icp_sort_cfg>(nullptr, bytes, c->keys.as<unsigned>(), c->skeys.as<unsigned>(), c->idx.as<unsigned>(),
-                                      c->order.as<unsigned>(), (size_t)n, 0u, (unsigned)bits, st));
-    GSR_TRY(c->rocprim_tmp.reserve(bytes));
-    GSR_HIP(rocprim::radix_sort_pairs<icp_sort_cfg>(c->rocprim_tmp.p, bytes, c->keys.as<unsigned>(), c->skeys.as<unsigned>(), c->idx.as<unsigned>(),
-                                      c->order.as<unsigned>(), (size_t)n, 0u, (unsigned)bits, st));
+    GSR_TRY(sort_pairs_by_key<icp_sort_cfg>(c->rocprim_tmp, st, c->keys.as<unsigned>(), c->skeys.as<unsigned>(), c->idx.as<unsigned>(),
+                                            c->order.as<unsigned>(), (size_t)n, 0u, (unsigned)bits));
     GSR_TRY(c->cellStart.reserve(((size_t)g.ncells + 1) * 4));
     hipLaunchKernelGGL(k_icp_cell_starts, dim3(stride_grid(n)), dim3(256), 0, st, n, c->skeys.as<unsigned>(), (int64_t)g.ncells, c->cellStart.as<int>());
     c->grid = g;
@@ -1512,12 +1498,8 @@ int32_t gsr_icp_set_source(gsr_icp_ctx* c, const float* xyz, int64_t n, int32_t 
         hipLaunchKernelGGL(k_icp_keys, dim3(stride_grid(n)), dim3(256), 0, st, n, raw, c->grid, c->keys.as<unsigned>(), c->idx.as<unsigned>());
         int bits = 1;
         while (bits < 32 && ((int64_t)1 << bits) < c->grid.ncells) ++bits;
-        size_t bytes = 0;
-        GSR_HIP(rocprim::radix_sort_pairs<icp_sort_cfg>(nullptr, bytes, c->keys.as<unsigned>(), c->skeys.as<unsigned>(), c->idx.as<unsigned>(),
-                                          c->src_order.as<unsigned>(), (size_t)n, 0u, (unsigned)bits, st));
-        GSR_TRY(c->rocprim_tmp.reserve(bytes));
-        GSR_HIP(rocprim::radix_sort_pairs<icp_sort_cfg>(c->rocprim_tmp.p, bytes, c->keys.as<unsigned>(), c->skeys.as<unsigned>(), c->idx.as<unsigned>(),
-                                          c->src_order.as<unsigned>(), (size_t)n, 0u, (unsigned)bits, st));
+        GSR_TRY(sort_pairs_by_key<icp_sort_cfg>(c->rocprim_tmp, st, c->keys.as<unsigned>(), c->skeys.as<unsigned>(), c->idx.as<unsigned>(),
+                                                c->src_order.as<unsigned>(), (size_t)n, 0u, (unsigned)bits));
         hipLaunchKernelGGL(k_icp_gather_source, dim3(stride_grid(n)), dim3(256), 0, st, n, c->src_order.as<unsigned>(), raw, c->src.as<float>());
         c->src_sorted = true;
     } else {
