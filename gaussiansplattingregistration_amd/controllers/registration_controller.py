@@ -13,11 +13,11 @@ class RegistrationController:
         self.ui_repository = ui_repository
         self.errors = []
 
-    def execute_local_registration_normal(self, params):
+    def execute_local_registration_normal(self, params, with_scaling=False):
         repo = self.data_repository
         pc1 = repo.pc_open3d_list_first[repo.current_index]
         pc2 = repo.pc_open3d_list_second[repo.current_index]
-        worker = LocalRegistrator(pc1, pc2, self.ui_repository.transformation_matrix, params)
+        worker = LocalRegistrator(pc1, pc2, self.ui_repository.transformation_matrix, params, with_scaling=with_scaling)
         result = worker.run()
         self.handle_registration_result_local(result)
         return result
@@ -44,35 +44,36 @@ class RegistrationController:
 
     def execute_multiscale_registration(self, use_corresponding, sparse_first, sparse_second, registration_type,
                                         relative_fitness, relative_rmse, voxel_values, iter_values, rejection_type, k_value,
-                                        use_mixture=True):
+                                        use_mixture=True, with_scaling=False):
         repo = self.data_repository
         if use_mixture:
             worker = MultiScaleRegistratorMixture(repo.pc_open3d_list_first, repo.pc_open3d_list_second,
                                                   self.ui_repository.transformation_matrix, use_corresponding, sparse_first,
                                                   sparse_second, registration_type, relative_fitness, relative_rmse,
-                                                  voxel_values, iter_values, rejection_type, k_value)
+                                                  voxel_values, iter_values, rejection_type, k_value, with_scaling=with_scaling)
         else:
             # the original clouds (the reference indexes the second list with [1], registration_controller.py:108 --
             # an IndexError without mixtures and the wrong cloud with them; the original cloud [0] is what is meant)
             worker = MultiScaleRegistratorVoxel(repo.pc_open3d_list_first[0], repo.pc_open3d_list_second[0],
                                                 self.ui_repository.transformation_matrix, use_corresponding, sparse_first,
                                                 sparse_second, registration_type, relative_fitness, relative_rmse,
-                                                voxel_values, iter_values, rejection_type, k_value)
+                                                voxel_values, iter_values, rejection_type, k_value, with_scaling=with_scaling)
         result = worker.run()
         self.errors = worker.errors
         if result is not None:
             self.handle_registration_result_local(result)
         return result
 
-    def evaluate_registration(self, cameras_list, images_path, log_path, color, use_gpu, registration_result=None, rotate_sh=False):
-        """Image-based evaluation of the current transform on the repository's original clouds (reference :122-143): renders of
+    def evaluate_registration(self, cameras_list, images_path, log_path, color, use_gpu, registration_result=None, rotate_sh=False, with_scaling=False):
+        """``with_scaling``: the current transform is a similarity (a registration with scaling); the merge before rendering applies it as one.
+        Image-based evaluation of the current transform on the repository's original clouds (reference :122-143): renders of
         the merged model against the photographs, the JSON log at ``log_path``.  Returns the evaluator's ``EvaluationObject``."""
         from ..workers.evaluator import RegistrationEvaluator
         repo = self.data_repository
         pc1 = repo.pc_gaussian_list_first[repo.current_index]
         pc2 = repo.pc_gaussian_list_second[repo.current_index]
         worker = RegistrationEvaluator(pc1, pc2, self.ui_repository.transformation_matrix, cameras_list, images_path, log_path, color,
-                                       registration_result, use_gpu, rotate_sh=rotate_sh)
+                                       registration_result, use_gpu, rotate_sh=rotate_sh, with_scaling=with_scaling)
         return worker.run()
 
     def handle_registration_result_local(self, result_data):       # :145-163

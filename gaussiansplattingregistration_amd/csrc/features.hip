@@ -225,9 +225,10 @@ __global__ __launch_bounds__(64) void k_ransac_hyp(int64_t k0, int nb, RansacDev
         for (int j = 0; j < n; ++j) {
             const int64_t c = idx[j];
             const double p[3] = {P[3 * c], P[3 * c + 1], P[3 * c + 2]}, q[3] = {Q[3 * c], Q[3 * c + 1], Q[3 * c + 2]};
-            if (a.kind == GSR_ICP_POINT_TO_POINT) {
+            if (a.kind == GSR_ICP_POINT_TO_POINT || a.kind == GSR_ICP_POINT_TO_POINT_SCALED) {
                 for (int r = 0; r < 3; ++r) { acc[2 + r] += p[r]; acc[5 + r] += q[r]; }
                 for (int r = 0; r < 3; ++r) for (int s = 0; s < 3; ++s) acc[8 + 3 * r + s] += p[r] * q[s];
+                if (a.kind == GSR_ICP_POINT_TO_POINT_SCALED) acc[17] += p[0] * p[0] + p[1] * p[1] + p[2] * p[2];
             } else {
                 const double nt[3] = {NT[3 * c], NT[3 * c + 1], NT[3 * c + 2]};
                 const double rr = (p[0] - q[0]) * nt[0] + (p[1] - q[1]) * nt[1] + (p[2] - q[2]) * nt[2];
@@ -264,12 +265,18 @@ __global__ __launch_bounds__(64) void k_ransac_hyp(int64_t k0, int nb, RansacDev
                 }
             } else if (a.ck[ci] == GSR_CHECK_NORMAL && a.has_normals) {
                 const double cth = cos(thr);
+                // a scaled hypothesis is A = c R: normals turn by R = A / c (c = cbrt(det A) > 0 by construction)
+                double ic = 1.0;
+                if (a.kind == GSR_ICP_POINT_TO_POINT_SCALED) {
+                    const double A3[3][3] = {{update[0], update[1], update[2]}, {update[4], update[5], update[6]}, {update[8], update[9], update[10]}};
+                    ic = 1.0 / cbrt(det3(A3));
+                }
                 for (int j = 0; j < n && ok; ++j) {
                     const int64_t c = idx[j];
                     double dot = 0.0;
                     for (int r = 0; r < 3; ++r)
                         dot += NT[3 * c + r] * (update[4 * r] * NS[3 * c] + update[4 * r + 1] * NS[3 * c + 1] + update[4 * r + 2] * NS[3 * c + 2]);
-                    if (dot < cth) ok = false;
+                    if (dot * ic < cth) ok = false;
                 }
             }
         }
@@ -453,8 +460,8 @@ int32_t gsr_ransac_correspondence(const float* src_xyz, int64_t ns, const float*
     memset(out, 0, sizeof(*out));
     mat4_identity(out->T);
     out->best_index = -1;
-    if (P.kind != GSR_ICP_POINT_TO_POINT && P.kind != GSR_ICP_POINT_TO_PLANE)
-        return fail(GSR_E_INVALID, "gsr_ransac_correspondence: estimation kind %d is not supported (point-to-point or point-to-plane)", P.kind);
+    if (P.kind != GSR_ICP_POINT_TO_POINT && P.kind != GSR_ICP_POINT_TO_PLANE && P.kind != GSR_ICP_POINT_TO_POINT_SCALED)
+        return fail(GSR_E_INVALID, "gsr_ransac_correspondence: estimation kind %d is not supported (point-to-point, plain or scaled, or point-to-plane)", P.kind);
     if (P.n_checkers < 0 || P.n_checkers > 4) return fail(GSR_E_INVALID, "gsr_ransac_correspondence: at most 4 checkers");
     for (int c = 0; c < P.n_checkers; ++c)
         if (P.checker_kind[c] < GSR_CHECK_EDGE_LENGTH || P.checker_kind[c] > GSR_CHECK_NORMAL)

@@ -132,11 +132,15 @@ __host__ __device__ static void mat4_mul(const double A[16], const double B[16],
 }
 
 // estimator update from the reduced accumulators (Open3D TransformationEstimation*.ComputeTransformation)
+// GSR_ICP_POINT_TO_POINT_SCALED is Eigen::umeyama(src, dst, true): mp, mq, sigma, the SVD and the sign matrix S as for kind 0, then
+//     var = acc[17] / n - |mp|^2,   c = (s0 S0 + s1 S1 + s2 S2) / var,   update = [c R | (mq + ctr) - c R (mp + ctr)].
+// DEVIATION from Eigen: when !(var > 0) or !(c > 0) -- one correspondence, coincident sources, a rank-0 sigma -- Eigen divides by
+// zero (a NaN / inf transform); here the update is the identity, as for no correspondences at all.
 __host__ __device__ static void estimate_update(const double ctr[3], int kind, const double* acc, double update[16]) {
     mat4_identity(update);
     const double n = acc[0];
     if (!(n > 0)) return;                                   // no correspondences -> identity
-    if (kind == GSR_ICP_POINT_TO_POINT) {                   // Eigen::umeyama(src, dst, false)
+    if (kind == GSR_ICP_POINT_TO_POINT || kind == GSR_ICP_POINT_TO_POINT_SCALED) {      // Eigen::umeyama(src, dst, with_scaling)
         const double mp[3] = {acc[2] / n, acc[3] / n, acc[4] / n}, mq[3] = {acc[5] / n, acc[6] / n, acc[7] / n};
         double sigma[3][3], U[3][3], V[3][3], s[3];
         for (int r = 0; r < 3; ++r)
@@ -147,6 +151,12 @@ __host__ __device__ static void estimate_update(const double ctr[3], int kind, c
         double R[3][3];
         for (int r = 0; r < 3; ++r)
             for (int col = 0; col < 3; ++col) { double v = 0; for (int k = 0; k < 3; ++k) v += U[r][k] * S[k] * V[col][k]; R[r][col] = v; }
+        if (kind == GSR_ICP_POINT_TO_POINT_SCALED) {
+            const double var = acc[17] / n - (mp[0] * mp[0] + mp[1] * mp[1] + mp[2] * mp[2]);
+            const double c = (s[0] * S[0] + s[1] * S[1] + s[2] * S[2]) / var;
+            if (!(var > 0) || !(c > 0)) return;             // degenerate: the identity (see above)
+            for (int r = 0; r < 3; ++r) for (int col = 0; col < 3; ++col) R[r][col] *= c;
+        }
         for (int r = 0; r < 3; ++r) {
             for (int col = 0; col < 3; ++col) update[4 * r + col] = R[r][col];
             double Rp = 0;

@@ -744,14 +744,15 @@ __device__ __forceinline__ void block_reduce_store(double (&acc)[NACC], double* 
     }
 }
 
-// KIND 0: point-to-point sums (17 values); KIND 1: point-to-plane normal equations (30 values)
+// KIND 0: point-to-point sums (17 values); KIND 1: point-to-plane normal equations (30 values); KIND 4: kind 0's 17 sums in the same
+// order plus slot 17 = sum |a|^2 (18 values) -- an instantiation of its own: the kind-0 kernels carry no trace of it
 template <int KIND>
 __global__ __launch_bounds__(256) void k_icp_accumulate(int64_t ns, const float* __restrict__ src, Xform T, IcpGrid g,
                                                         const int* __restrict__ cellStart, const int* __restrict__ nn_j,
                                                         const float4* __restrict__ Tq, const double* __restrict__ Tn,
                                                         const double* __restrict__ Sc, ColorArgs ca, double max_corr2,
                                                         int loss, double kparam, double* __restrict__ partials) {
-    constexpr int NACC = KIND == 0 ? 17 : 30;
+    constexpr int NACC = KIND == 0 ? 17 : (KIND == 4 ? 18 : 30);
     double acc[NACC];
 #pragma unroll
     for (int k = 0; k < NACC; ++k) acc[k] = 0.0;
@@ -775,7 +776,7 @@ __global__ __launch_bounds__(256) void k_icp_accumulate(int64_t ns, const float*
         const double d2 = ddx * ddx + ddy * ddy + ddz * ddz;
         acc[0] += 1.0;
         acc[1] += d2;
-        if constexpr (KIND == 0) {
+        if constexpr (KIND == 0 || KIND == 4) {
             const double ax = px - g.cx, ay = py - g.cy, az = pz - g.cz;
             const double bx = qx - g.cx, by = qy - g.cy, bz = qz - g.cz;
             acc[2] += ax; acc[3] += ay; acc[4] += az;
@@ -783,6 +784,7 @@ __global__ __launch_bounds__(256) void k_icp_accumulate(int64_t ns, const float*
             acc[8] += ax * bx; acc[9] += ax * by; acc[10] += ax * bz;
             acc[11] += ay * bx; acc[12] += ay * by; acc[13] += ay * bz;
             acc[14] += az * bx; acc[15] += az * by; acc[16] += az * bz;
+            if constexpr (KIND == 4) acc[17] += ax * ax + ay * ay + az * az;        // Umeyama's source variance (with_scaling)
         } else if constexpr (KIND == 2) {
             icp_gicp_rows<NACC>(acc, T.m, px, py, pz, qx, qy, qz, Sc + 6 * i, Tn + 6 * (int64_t)j, loss, kparam);
         } else if constexpr (KIND == 3) {
@@ -993,7 +995,7 @@ __global__ __launch_bounds__(256, 1) void k_icp_accumulate_dev(int64_t ns, const
                                                             const float4* __restrict__ Tq, const double* __restrict__ Tn,
                                                             const double* __restrict__ Sc, ColorArgs ca, double max_corr2,
                                                             int loss, double kparam, double* partials, int nb_logical) {
-    constexpr int NACC = KIND == 0 ? 17 : 30;
+    constexpr int NACC = KIND == 0 ? 17 : (KIND == 4 ? 18 : 30);
     const IcpRange rg = icp_block_range(ns, nb_logical < 0 ? -nb_logical : nb_logical, nb_logical > 0);
     if (st->done) return;                           // converged: nothing to search
     double T[12];
@@ -1023,7 +1025,7 @@ __global__ __launch_bounds__(256, 1) void k_icp_accumulate_dev(int64_t ns, const
         const double d2 = ddx * ddx + ddy * ddy + ddz * ddz;
         acc[0] += 1.0;
         acc[1] += d2;
-        if constexpr (KIND == 0) {
+        if constexpr (KIND == 0 || KIND == 4) {
             const double ax = px - g.cx, ay = py - g.cy, az = pz - g.cz;
             const double bx = qx - g.cx, by = qy - g.cy, bz = qz - g.cz;
             acc[2] += ax; acc[3] += ay; acc[4] += az;
@@ -1031,6 +1033,7 @@ __global__ __launch_bounds__(256, 1) void k_icp_accumulate_dev(int64_t ns, const
             acc[8] += ax * bx; acc[9] += ax * by; acc[10] += ax * bz;
             acc[11] += ay * bx; acc[12] += ay * by; acc[13] += ay * bz;
             acc[14] += az * bx; acc[15] += az * by; acc[16] += az * bz;
+            if constexpr (KIND == 4) acc[17] += ax * ax + ay * ay + az * az;        // Umeyama's source variance (with_scaling)
         } else if constexpr (KIND == 2) {
             icp_gicp_rows<NACC>(acc, T, px, py, pz, qx, qy, qz, Sc + 6 * i, Tn + 6 * (int64_t)j, loss, kparam);
         } else if constexpr (KIND == 3) {
@@ -1231,10 +1234,23 @@ void launch_icp_nn(gsr_icp_ctx* c, hipStream_t st, const Xform& X, const IcpStat
                            c->nn_j.as<int>(), nbl);
 }
 
+// The scaled estimator, checked on the arguments alone (before any context is looked at): with_scaling exists for point-to-point
+// only (Open3D offers it nowhere else), and a robust loss does not apply to it -- kind 0 ignores the loss argument, the new kind
+// says so.  Every other kind passes: what it needs is icp_check_kind's business.
+int32_t icp_check_scaled(int kind, int loss, const char* who) {
+    if (kind > GSR_ICP_POINT_TO_POINT_SCALED && kind <= (GSR_ICP_COLORED | GSR_ICP_WITH_SCALING))
+        return fail(GSR_E_INVALID, "%s: with_scaling is offered for point-to-point estimation only (kind %d asks for it with kind %d)", who, kind,
+                    kind & ~GSR_ICP_WITH_SCALING);
+    if (kind == GSR_ICP_POINT_TO_POINT_SCALED && loss != GSR_LOSS_L2)
+        return fail(GSR_E_INVALID, "%s: TransformationEstimationPointToPoint(with_scaling) takes no robust loss (loss %d)", who, loss);
+    return GSR_OK;
+}
+
 // what an evaluation with estimator `kind` needs of the context
 int32_t icp_check_kind(const gsr_icp_ctx* c, int kind) {
     if (!c->have_target || !c->have_source) return fail(GSR_E_INVALID, "icp: target and source must be set first");
-    if (kind < GSR_ICP_POINT_TO_POINT || kind > GSR_ICP_COLORED) return fail(GSR_E_INVALID, "icp: unknown estimation kind %d", kind);
+    GSR_TRY(icp_check_scaled(kind, GSR_LOSS_L2, "icp"));
+    if (kind < GSR_ICP_POINT_TO_POINT || kind > GSR_ICP_POINT_TO_POINT_SCALED) return fail(GSR_E_INVALID, "icp: unknown estimation kind %d", kind);
     if (kind == GSR_ICP_POINT_TO_PLANE && !c->have_normals)
         return fail(GSR_E_PRECONDITION, "TransformationEstimationPointToPlane requires target normals");
     if (kind == GSR_ICP_COLORED && (!c->have_normals || !c->have_tcol || !c->have_scol))
@@ -1246,7 +1262,8 @@ int32_t icp_check_kind(const gsr_icp_ctx* c, int kind) {
 
 // one evaluation of the device-resident loop: 8 * ceil(nb / 8) workgroups, the padding ones get nothing (icp_block_range)
 void launch_accumulate_dev(gsr_icp_ctx* c, hipStream_t st, int kind, bool blockf, int nb, const int* nnj, const ColorArgs& cargs, double mc2, int loss, double k) {
-    const double* tn = kind == GSR_ICP_POINT_TO_POINT ? nullptr : (kind == GSR_ICP_GENERALIZED ? c->Tc.as<double>() : c->Tn.as<double>());
+    const bool p2p = kind == GSR_ICP_POINT_TO_POINT || kind == GSR_ICP_POINT_TO_POINT_SCALED;
+    const double* tn = p2p ? nullptr : (kind == GSR_ICP_GENERALIZED ? c->Tc.as<double>() : c->Tn.as<double>());
     const double* sc = kind == GSR_ICP_GENERALIZED ? c->Sc.as<double>() : nullptr;
     decltype(&k_icp_accumulate_dev<0, 0>) kernel = nullptr;
     switch (2 * kind + (blockf ? 1 : 0)) {
@@ -1257,7 +1274,9 @@ void launch_accumulate_dev(gsr_icp_ctx* c, hipStream_t st, int kind, bool blockf
         case 4: kernel = k_icp_accumulate_dev<2, 0>; break;
         case 5: kernel = k_icp_accumulate_dev<2, 1>; break;
         case 6: kernel = k_icp_accumulate_dev<3, 0>; break;
-        default: kernel = k_icp_accumulate_dev<3, 1>; break;
+        case 7: kernel = k_icp_accumulate_dev<3, 1>; break;
+        case 8: kernel = k_icp_accumulate_dev<4, 0>; break;
+        default: kernel = k_icp_accumulate_dev<4, 1>; break;
     }
     hipLaunchKernelGGL(kernel, dim3(8 * ((nb + 7) / 8)), dim3(256), 0, st, c->ns, c->src.as<float>(), c->state.as<IcpState>(), c->grid, c->cellStart.as<int>(), nnj,
                        c->Tq.as<float4>(), tn, sc, cargs, mc2, loss, k, c->partials.as<double>(), c->xcd_ranges ? nb : -nb);
@@ -1286,6 +1305,9 @@ int32_t run_accumulate(gsr_icp_ctx* c, const double* T, int kind, int loss, doub
                            c->Tq.as<float4>(), c->Tn.as<double>(), (const double*)nullptr, cargs, mc2, loss, k, c->partials.as<double>());
     else if (kind == GSR_ICP_POINT_TO_POINT)
         hipLaunchKernelGGL(k_icp_accumulate<0>, dim3(nb), dim3(256), 0, st, c->ns, c->src.as<float>(), X, c->grid, c->cellStart.as<int>(), nnj,
+                           c->Tq.as<float4>(), (const double*)nullptr, (const double*)nullptr, cargs, mc2, loss, k, c->partials.as<double>());
+    else if (kind == GSR_ICP_POINT_TO_POINT_SCALED)
+        hipLaunchKernelGGL(k_icp_accumulate<4>, dim3(nb), dim3(256), 0, st, c->ns, c->src.as<float>(), X, c->grid, c->cellStart.as<int>(), nnj,
                            c->Tq.as<float4>(), (const double*)nullptr, (const double*)nullptr, cargs, mc2, loss, k, c->partials.as<double>());
     else if (kind == GSR_ICP_POINT_TO_PLANE)
         hipLaunchKernelGGL(k_icp_accumulate<1>, dim3(nb), dim3(256), 0, st, c->ns, c->src.as<float>(), X, c->grid, c->cellStart.as<int>(), nnj,
@@ -1626,6 +1648,7 @@ int32_t gsr_icp_set_allreduce(gsr_icp_ctx* c, gsr_allreduce_fn fn, void* user, i
 }
 
 int32_t gsr_icp_accumulate(gsr_icp_ctx* c, const double* T, int32_t kind, int32_t loss, double k, double* acc) {
+    GSR_TRY(icp_check_scaled(kind, loss, "gsr_icp_accumulate"));
     if (!c || !T || !acc) return fail(GSR_E_INVALID, "gsr_icp_accumulate: NULL argument");
     GSR_HIP(hipSetDevice(c->device));
     return run_accumulate(c, T, kind, loss, k, acc, false);
@@ -1633,6 +1656,7 @@ int32_t gsr_icp_accumulate(gsr_icp_ctx* c, const double* T, int32_t kind, int32_
 
 int32_t gsr_icp_register(gsr_icp_ctx* c, const double* init_T, int32_t kind, int32_t loss, double k, double rel_fitness,
                          double rel_rmse, int32_t max_iter, double* out_T, double* fitness, double* inlier_rmse, int32_t* iterations) {
+    GSR_TRY(icp_check_scaled(kind, loss, "gsr_icp_register"));
     if (!c || !init_T || !out_T) return fail(GSR_E_INVALID, "gsr_icp_register: NULL argument");
     GSR_HIP(hipSetDevice(c->device));
     c->ms_iter = 0; c->n_iter_kernels = 0;
@@ -1741,7 +1765,8 @@ int32_t gsr_icp_correspondences(gsr_icp_ctx* c, const double* T, int64_t* idx, d
 
 int32_t gsr_icp_solve(const double* acc, int32_t kind, const double* centre, double* update) {
     if (!acc || !update) return fail(GSR_E_INVALID, "gsr_icp_solve: NULL argument");
-    if (kind < GSR_ICP_POINT_TO_POINT || kind > GSR_ICP_COLORED) return fail(GSR_E_INVALID, "gsr_icp_solve: unknown kind %d", kind);
+    GSR_TRY(icp_check_scaled(kind, GSR_LOSS_L2, "gsr_icp_solve"));
+    if (kind < GSR_ICP_POINT_TO_POINT || kind > GSR_ICP_POINT_TO_POINT_SCALED) return fail(GSR_E_INVALID, "gsr_icp_solve: unknown kind %d", kind);
     const double zero[3] = {0, 0, 0};
     estimate_update(centre ? centre : zero, kind, acc, update);
     return GSR_OK;
@@ -1766,8 +1791,9 @@ static void icp_read_build_ms(gsr_icp_ctx* c) {
 int32_t gsr_icp_register_clouds(gsr_icp_ctx* c, const float* src_xyz, int64_t ns, const float* tgt_xyz, const double* tgt_normals, int64_t nt,
                                 int32_t on_device, double max_corr, const double* init_T, int32_t kind, int32_t loss, double k, double rel_fitness,
                                 double rel_rmse, int32_t max_iter, double* out_T, double* fitness, double* inlier_rmse, int32_t* iterations) {
+    GSR_TRY(icp_check_scaled(kind, loss, "gsr_icp_register_clouds"));
     if (!c) return fail(GSR_E_INVALID, "gsr_icp_register_clouds: NULL context");
-    if (kind != GSR_ICP_POINT_TO_POINT && kind != GSR_ICP_POINT_TO_PLANE)
+    if (kind != GSR_ICP_POINT_TO_POINT && kind != GSR_ICP_POINT_TO_PLANE && kind != GSR_ICP_POINT_TO_POINT_SCALED)
         return fail(GSR_E_INVALID, "gsr_icp_register_clouds: point-to-point and point-to-plane only (covariances / colours: the step-by-step entry points)");
     if (kind == GSR_ICP_POINT_TO_PLANE && !tgt_normals) return fail(GSR_E_PRECONDITION, "TransformationEstimationPointToPlane requires target normals");
     // one process, one GPU: a communicator or an all-reduce callback of an earlier sharded call must not stay behind
@@ -1787,6 +1813,7 @@ int32_t gsr_icp_register_clouds(gsr_icp_ctx* c, const float* src_xyz, int64_t ns
 // the entries.  entries[k] describes entry k (coarsest first); results[k] receives its outcome; out_T the last entry's transform.
 int32_t gsr_icp_register_multiscale(gsr_icp_ctx* c, int32_t n_entries, const gsr_icp_entry* entries, int32_t on_device, const double* init_T, int32_t kind,
                                     int32_t loss, double k, double rel_fitness, double rel_rmse, gsr_icp_entry_result* results, double* out_T) {
+    GSR_TRY(icp_check_scaled(kind, loss, "gsr_icp_register_multiscale"));
     if (!c || !init_T || !out_T || n_entries < 0 || (n_entries > 0 && (!entries || !results)))
         return fail(GSR_E_INVALID, "gsr_icp_register_multiscale: bad argument");
     double T[16];

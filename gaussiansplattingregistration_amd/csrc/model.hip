@@ -238,7 +238,9 @@ static bool solve_in_place(int m, double A[7][7], double X[7][7]) {
 // the rotation matrices of the three rest bands in float32, as the kernel takes them BY VALUE (kernel arguments are read with
 // scalar loads: the 83 values are wave-uniform and never cost a per-lane global read)
 struct ShRot { float d1[9], d2[25], d3[49]; };
-struct Rigid { float R[9], t[3], q[4]; };          // rotation, translation, unit quaternion (w, x, y, z) of the rotation
+// rotation, translation, unit quaternion (w, x, y, z) of the rotation; c, c2 = c^2, lnc = ln c: the factor of a similarity, read by
+// the SIM instantiations only (gsr_model_similarity) -- the rigid ones never touch them
+struct Rigid { float R[9], t[3], q[4], c, c2, lnc; };
 
 // one channel's band vector of length M = 2l + 1 at s[0], s[3], s[6], ... (coefficient-major, channel-minor) <- D s
 template <int M> __device__ __forceinline__ void sh_band(const float* __restrict__ D, float* s) {
@@ -256,16 +258,21 @@ template <int M> __device__ __forceinline__ void sh_band(const float* __restrict
     for (int i = 0; i < M; ++i) s[3 * i] = o[i];
 }
 
-// xyz' = R xyz + t;  cov' = R cov R^T on the six-entry form;  q' = normalise(q_R (x) q), a thread per splat
+// xyz' = R xyz + t;  cov' = R cov R^T on the six-entry form;  q' = normalise(q_R (x) q), a thread per splat.
+// SIM: xyz' = c (R xyz) + t, cov' = c^2 (R cov R^T) -- one more float32 multiply each, behind the rigid expression -- and the
+// log-scales scl' = scl + ln c (scl may be NULL).
+template <bool SIM>
 __device__ __forceinline__ void transform_geometry(int64_t n, const Rigid& G, const float* __restrict__ xyz, const float* __restrict__ cov6,
                                                    const float* __restrict__ rot, float* __restrict__ xyz_o, float* __restrict__ cov6_o,
-                                                   float* __restrict__ rot_o) {
+                                                   float* __restrict__ rot_o, const float* __restrict__ scl = nullptr, float* __restrict__ scl_o = nullptr) {
     const float* R = G.R;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         const float x = xyz[3 * i], y = xyz[3 * i + 1], z = xyz[3 * i + 2];
 #pragma unroll
-        for (int r = 0; r < 3; ++r)
-            xyz_o[3 * i + r] = __builtin_fmaf(R[3 * r + 2], z, __builtin_fmaf(R[3 * r + 1], y, R[3 * r] * x)) + G.t[r];
+        for (int r = 0; r < 3; ++r) {
+            const float m = __builtin_fmaf(R[3 * r + 2], z, __builtin_fmaf(R[3 * r + 1], y, R[3 * r] * x));
+            xyz_o[3 * i + r] = (SIM ? G.c * m : m) + G.t[r];
+        }
         const float c00 = cov6[6 * i], c01 = cov6[6 * i + 1], c02 = cov6[6 * i + 2], c11 = cov6[6 * i + 3], c12 = cov6[6 * i + 4], c22 = cov6[6 * i + 5];
         float M[3][3];                                  // M = R cov
 #pragma unroll
@@ -278,8 +285,14 @@ __device__ __forceinline__ void transform_geometry(int64_t n, const Rigid& G, co
 #pragma unroll
         for (int r = 0; r < 3; ++r)
 #pragma unroll
-            for (int c = r; c < 3; ++c)                 // (M R^T)[r][c], upper triangle in the order xx xy xz yy yz zz
-                cov6_o[6 * i + o++] = __builtin_fmaf(M[r][2], R[3 * c + 2], __builtin_fmaf(M[r][1], R[3 * c + 1], M[r][0] * R[3 * c]));
+            for (int c = r; c < 3; ++c) {               // (M R^T)[r][c], upper triangle in the order xx xy xz yy yz zz
+                const float v = __builtin_fmaf(M[r][2], R[3 * c + 2], __builtin_fmaf(M[r][1], R[3 * c + 1], M[r][0] * R[3 * c]));
+                cov6_o[6 * i + o++] = SIM ? G.c2 * v : v;
+            }
+        if (SIM && scl) {
+#pragma unroll
+            for (int r = 0; r < 3; ++r) scl_o[3 * i + r] = scl[3 * i + r] + G.lnc;
+        }
         if (rot) {
             const float w0 = rot[4 * i], x0 = rot[4 * i + 1], y0 = rot[4 * i + 2], z0 = rot[4 * i + 3];
             const float w1 = G.q[0], x1 = G.q[1], y1 = G.q[2], z1 = G.q[3];
@@ -299,10 +312,11 @@ __device__ __forceinline__ void transform_geometry(int64_t n, const Rigid& G, co
 // one row of the LDS image.  Row stride FP = F or F + 1, always odd: the 32 lanes of a ds_read_b32 / ds_write_b32 group then fall on
 // 32 different banks.  The row is transformed in place in LDS (a lane reads and writes only its own row), so the image is loaded,
 // rotated and stored with three barriers per tile and no second buffer: 256 x 45 x 4 = 45 KiB at degree 3, three blocks per CU.
-template <int K, bool VEC>
+template <int K, bool VEC, bool SIM>
 __global__ __launch_bounds__(256) void k_model_transform(int64_t n, Rigid G, ShRot D, const float* __restrict__ xyz, const float* __restrict__ cov6,
                                                          const float* __restrict__ rot, const float* __restrict__ sh, float* __restrict__ xyz_o,
-                                                         float* __restrict__ cov6_o, float* __restrict__ rot_o, float* __restrict__ sh_o) {
+                                                         float* __restrict__ cov6_o, float* __restrict__ rot_o, float* __restrict__ sh_o,
+                                                         const float* __restrict__ scl, float* __restrict__ scl_o) {
     constexpr int F = 3 * K, FP = F | 1, ROWS = 256;
     __shared__ float s_sh[ROWS * FP];
     const int tid = threadIdx.x;
@@ -350,14 +364,15 @@ __global__ __launch_bounds__(256) void k_model_transform(int64_t n, Rigid G, ShR
         }
         __syncthreads();                                                        // the next tile overwrites the image
     }
-    transform_geometry(n, G, xyz, cov6, rot, xyz_o, cov6_o, rot_o);
+    transform_geometry<SIM>(n, G, xyz, cov6, rot, xyz_o, cov6_o, rot_o, scl, scl_o);
 }
 
 // the same without SH rotation: `words` 32-bit words of sh copied bit for bit (as integers: no float ever touches them)
-template <bool VEC>
+template <bool VEC, bool SIM>
 __global__ __launch_bounds__(256) void k_model_transform_copy(int64_t n, Rigid G, int64_t words, const float* __restrict__ xyz, const float* __restrict__ cov6,
                                                               const float* __restrict__ rot, const uint32_t* __restrict__ sh, float* __restrict__ xyz_o,
-                                                              float* __restrict__ cov6_o, float* __restrict__ rot_o, uint32_t* __restrict__ sh_o) {
+                                                              float* __restrict__ cov6_o, float* __restrict__ rot_o, uint32_t* __restrict__ sh_o,
+                                                              const float* __restrict__ scl, float* __restrict__ scl_o) {
     const int64_t t0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, step = (int64_t)gridDim.x * blockDim.x;
     if (VEC) {
         const int64_t nv = words >> 2;
@@ -366,7 +381,7 @@ __global__ __launch_bounds__(256) void k_model_transform_copy(int64_t n, Rigid G
     } else {
         for (int64_t f = t0; f < words; f += step) sh_o[f] = sh[f];
     }
-    transform_geometry(n, G, xyz, cov6, rot, xyz_o, cov6_o, rot_o);
+    transform_geometry<SIM>(n, G, xyz, cov6, rot, xyz_o, cov6_o, rot_o, scl, scl_o);
 }
 
 // ---- device SoA -> 3DGS .ply rows (gsr_ply_pack), the inverse of k_ply_unpack ------------------------------------------------
@@ -455,34 +470,44 @@ static bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
     return pa < pb + nb && pb < pa + na;
 }
 
-template <int K> static void launch_model_transform(bool vec, int grid, hipStream_t st, int64_t n, const Rigid& G, const ShRot& D, const float* xyz,
-                                                    const float* cov6, const float* rot, const float* sh, float* xyz_o, float* cov6_o, float* rot_o, float* sh_o) {
-    if (vec) hipLaunchKernelGGL((k_model_transform<K, true>), dim3(grid), dim3(256), 0, st, n, G, D, xyz, cov6, rot, sh, xyz_o, cov6_o, rot_o, sh_o);
-    else hipLaunchKernelGGL((k_model_transform<K, false>), dim3(grid), dim3(256), 0, st, n, G, D, xyz, cov6, rot, sh, xyz_o, cov6_o, rot_o, sh_o);
+template <int K, bool SIM> static void launch_model_transform(bool vec, int grid, hipStream_t st, int64_t n, const Rigid& G, const ShRot& D, const float* xyz,
+                                                              const float* cov6, const float* rot, const float* sh, float* xyz_o, float* cov6_o, float* rot_o, float* sh_o,
+                                                              const float* scl, float* scl_o) {
+    if (vec) hipLaunchKernelGGL((k_model_transform<K, true, SIM>), dim3(grid), dim3(256), 0, st, n, G, D, xyz, cov6, rot, sh, xyz_o, cov6_o, rot_o, sh_o, scl, scl_o);
+    else hipLaunchKernelGGL((k_model_transform<K, false, SIM>), dim3(grid), dim3(256), 0, st, n, G, D, xyz, cov6, rot, sh, xyz_o, cov6_o, rot_o, sh_o, scl, scl_o);
 }
 
-extern "C" int32_t gsr_model_transform(const double* transform, int64_t n, int32_t K, int32_t rotate_sh, const float* xyz, const float* cov6,
-                                       const float* rot, const float* sh, float* xyz_out, float* cov6_out, float* rot_out, float* sh_out,
-                                       int32_t on_device, int32_t device, void* stream) {
-    if (!transform || n < 0 || (K != 0 && K != 3 && K != 8 && K != 15)) return fail(GSR_E_INVALID, "gsr_model_transform: bad argument (K must be 0, 3, 8 or 15)");
-    if (n > 0 && (!xyz || !cov6 || !xyz_out || !cov6_out || (rot && !rot_out) || (K > 0 && (!sh || !sh_out))))
-        return fail(GSR_E_INVALID, "gsr_model_transform: NULL array");
-    const double R9[9] = {transform[0], transform[1], transform[2], transform[4], transform[5], transform[6], transform[8], transform[9], transform[10]};
-    if (!rotation_ok(R9)) return fail(GSR_E_INVALID, "gsr_model_transform: the upper 3x3 of the transform is not a rotation");
+// The similarity gate: det A > 0, c = cbrt(det A) in [1e-6, 1e6], max|A^T A / c^2 - I| <= 1e-3.  R9 = A / c (float64).
+static bool similarity_ok(const double* A, double* c_out, double* R9) {
+    const double det = A[0] * (A[4] * A[8] - A[5] * A[7]) - A[1] * (A[3] * A[8] - A[5] * A[6]) + A[2] * (A[3] * A[7] - A[4] * A[6]);
+    if (!(det > 0.0)) return false;
+    const double c = cbrt(det);
+    if (!(c >= 1e-6 && c <= 1e6)) return false;
+    for (int i = 0; i < 9; ++i) R9[i] = A[i] / c;
+    *c_out = c;
+    return rotation_ok(R9);
+}
+
+// gsr_model_transform (SIM = false: c = 1, no scaling arrays) and gsr_model_similarity (SIM = true) behind their gates
+template <bool SIM>
+static int32_t model_move(const char* who, const double* transform, const double* R9, double c, int64_t n, int32_t K, int32_t rotate_sh, const float* xyz,
+                          const float* cov6, const float* rot, const float* sh, const float* scaling, float* xyz_out, float* cov6_out, float* rot_out,
+                          float* sh_out, float* scaling_out, int32_t on_device, int32_t device, void* stream) {
     const size_t un = (size_t)n, F = 3 * (size_t)K;
-    const void* ins[4] = {xyz, cov6, rot, K ? sh : nullptr};
-    const void* outs[4] = {xyz_out, cov6_out, rot ? rot_out : nullptr, K ? sh_out : nullptr};
-    const size_t bytes[4] = {un * 12, un * 24, un * 16, un * F * 4};
-    for (int i = 0; i < 4; ++i)
-        for (int j = 0; j < 4; ++j)
+    const void* ins[5] = {xyz, cov6, rot, K ? sh : nullptr, scaling};
+    const void* outs[5] = {xyz_out, cov6_out, rot ? rot_out : nullptr, K ? sh_out : nullptr, scaling ? scaling_out : nullptr};
+    const size_t bytes[5] = {un * 12, un * 24, un * 16, un * F * 4, un * 12};
+    for (int i = 0; i < 5; ++i)
+        for (int j = 0; j < 5; ++j)
             if (ranges_overlap(outs[i], bytes[i], ins[j], bytes[j]) || (i < j && ranges_overlap(outs[i], bytes[i], outs[j], bytes[j])))
-                return fail(GSR_E_INVALID, "gsr_model_transform: an output array overlaps another array of the call (the transform is not in place)");
-    GSR_TRY(open_device(device, "gsr_model_transform"));
+                return fail(GSR_E_INVALID, "%s: an output array overlaps another array of the call (the transform is not in place)", who);
+    GSR_TRY(open_device(device, who));
     if (n == 0) return GSR_OK;
     // the motion narrowed to float32 once: rotation, translation, the rotation's unit quaternion (Shepperd's branch, w >= 0)
     Rigid G;
     for (int i = 0; i < 9; ++i) G.R[i] = (float)R9[i];
     for (int i = 0; i < 3; ++i) G.t[i] = (float)transform[4 * i + 3];
+    G.c = (float)c; G.c2 = (float)(c * c); G.lnc = (float)log(c);
     {
         const double* R = R9;
         const double tr = R[0] + R[4] + R[8];
@@ -504,30 +529,58 @@ extern "C" int32_t gsr_model_transform(const double* transform, int64_t n, int32
         for (int i = 0; i < 25; ++i) D.d2[i] = (float)B[9 + i];
         for (int i = 0; i < 49; ++i) D.d3[i] = (float)B[34 + i];
     }
-    OneShot os((hipStream_t)stream, on_device != 0, "gsr_model_transform");
-    const float *px = nullptr, *pc = nullptr, *pq = nullptr, *ps = nullptr;
-    float *ox = nullptr, *oc = nullptr, *oq = nullptr, *osh = nullptr;
+    OneShot os((hipStream_t)stream, on_device != 0, who);
+    const float *px = nullptr, *pc = nullptr, *pq = nullptr, *ps = nullptr, *pl = nullptr;
+    float *ox = nullptr, *oc = nullptr, *oq = nullptr, *osh = nullptr, *ol = nullptr;
     GSR_TRY(os.in(xyz, bytes[0], &px));
     GSR_TRY(os.in(cov6, bytes[1], &pc));
     GSR_TRY(os.in(rot, bytes[2], &pq));
     GSR_TRY(os.in(K ? sh : nullptr, bytes[3], &ps));
+    if (SIM) GSR_TRY(os.in(scaling, bytes[4], &pl));
     GSR_TRY(os.out(xyz_out, bytes[0], &ox));
     GSR_TRY(os.out(cov6_out, bytes[1], &oc));
     GSR_TRY(os.out(rot ? rot_out : nullptr, bytes[2], &oq));
     GSR_TRY(os.out(K ? sh_out : nullptr, bytes[3], &osh));
+    if (SIM) GSR_TRY(os.out(scaling ? scaling_out : nullptr, bytes[4], &ol));
     const bool vec = (((uintptr_t)ps | (uintptr_t)osh) & 15u) == 0u;
     if (rotate) {
         const int grid = (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);        // a block per 256-row tile, at most 16 per CU
-        if (K == 3) launch_model_transform<3>(vec, grid, os.st, n, G, D, px, pc, pq, ps, ox, oc, oq, osh);
-        else if (K == 8) launch_model_transform<8>(vec, grid, os.st, n, G, D, px, pc, pq, ps, ox, oc, oq, osh);
-        else launch_model_transform<15>(vec, grid, os.st, n, G, D, px, pc, pq, ps, ox, oc, oq, osh);
+        if (K == 3) launch_model_transform<3, SIM>(vec, grid, os.st, n, G, D, px, pc, pq, ps, ox, oc, oq, osh, pl, ol);
+        else if (K == 8) launch_model_transform<8, SIM>(vec, grid, os.st, n, G, D, px, pc, pq, ps, ox, oc, oq, osh, pl, ol);
+        else launch_model_transform<15, SIM>(vec, grid, os.st, n, G, D, px, pc, pq, ps, ox, oc, oq, osh, pl, ol);
     } else {
         const int64_t words = n * (int64_t)F;
         const int grid = stride_grid(words > 4 * n ? words / 4 : n);
-        if (vec) hipLaunchKernelGGL((k_model_transform_copy<true>), dim3(grid), dim3(256), 0, os.st, n, G, words, px, pc, pq, (const uint32_t*)ps, ox, oc, oq, (uint32_t*)osh);
-        else hipLaunchKernelGGL((k_model_transform_copy<false>), dim3(grid), dim3(256), 0, os.st, n, G, words, px, pc, pq, (const uint32_t*)ps, ox, oc, oq, (uint32_t*)osh);
+        if (vec) hipLaunchKernelGGL((k_model_transform_copy<true, SIM>), dim3(grid), dim3(256), 0, os.st, n, G, words, px, pc, pq, (const uint32_t*)ps, ox, oc, oq, (uint32_t*)osh, pl, ol);
+        else hipLaunchKernelGGL((k_model_transform_copy<false, SIM>), dim3(grid), dim3(256), 0, os.st, n, G, words, px, pc, pq, (const uint32_t*)ps, ox, oc, oq, (uint32_t*)osh, pl, ol);
     }
     return os.finish();
+}
+
+extern "C" int32_t gsr_model_transform(const double* transform, int64_t n, int32_t K, int32_t rotate_sh, const float* xyz, const float* cov6,
+                                       const float* rot, const float* sh, float* xyz_out, float* cov6_out, float* rot_out, float* sh_out,
+                                       int32_t on_device, int32_t device, void* stream) {
+    if (!transform || n < 0 || (K != 0 && K != 3 && K != 8 && K != 15)) return fail(GSR_E_INVALID, "gsr_model_transform: bad argument (K must be 0, 3, 8 or 15)");
+    if (n > 0 && (!xyz || !cov6 || !xyz_out || !cov6_out || (rot && !rot_out) || (K > 0 && (!sh || !sh_out))))
+        return fail(GSR_E_INVALID, "gsr_model_transform: NULL array");
+    const double R9[9] = {transform[0], transform[1], transform[2], transform[4], transform[5], transform[6], transform[8], transform[9], transform[10]};
+    if (!rotation_ok(R9)) return fail(GSR_E_INVALID, "gsr_model_transform: the upper 3x3 of the transform is not a rotation");
+    return model_move<false>("gsr_model_transform", transform, R9, 1.0, n, K, rotate_sh, xyz, cov6, rot, sh, nullptr, xyz_out, cov6_out, rot_out, sh_out, nullptr,
+                             on_device, device, stream);
+}
+
+extern "C" int32_t gsr_model_similarity(const double* transform, int64_t n, int32_t K, int32_t rotate_sh, const float* xyz, const float* cov6,
+                                        const float* rot, const float* sh, const float* scaling, float* xyz_out, float* cov6_out, float* rot_out,
+                                        float* sh_out, float* scaling_out, int32_t on_device, int32_t device, void* stream) {
+    if (!transform || n < 0 || (K != 0 && K != 3 && K != 8 && K != 15)) return fail(GSR_E_INVALID, "gsr_model_similarity: bad argument (K must be 0, 3, 8 or 15)");
+    if (n > 0 && (!xyz || !cov6 || !xyz_out || !cov6_out || (rot && !rot_out) || (scaling && !scaling_out) || (K > 0 && (!sh || !sh_out))))
+        return fail(GSR_E_INVALID, "gsr_model_similarity: NULL array");
+    const double A9[9] = {transform[0], transform[1], transform[2], transform[4], transform[5], transform[6], transform[8], transform[9], transform[10]};
+    double c = 1.0, R9[9];
+    if (!similarity_ok(A9, &c, R9))
+        return fail(GSR_E_INVALID, "gsr_model_similarity: the upper 3x3 of the transform is not c R (det > 0, 1e-6 <= c <= 1e6, max|A^T A / c^2 - I| <= 1e-3)");
+    return model_move<true>("gsr_model_similarity", transform, R9, c, n, K, rotate_sh, xyz, cov6, rot, sh, scaling, xyz_out, cov6_out, rot_out, sh_out, scaling_out,
+                            on_device, device, stream);
 }
 
 extern "C" int32_t gsr_ply_pack(const float* xyz, const float* dc, const float* sh, const float* opacity, const float* scale, const float* rot,

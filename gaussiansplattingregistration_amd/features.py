@@ -27,6 +27,7 @@ __all__ = ["hybrid_search", "fpfh", "feature_match", "ransac_correspondence", "f
 
 KIND_POINT_TO_POINT = 0
 KIND_POINT_TO_PLANE = 1
+KIND_POINT_TO_POINT_SCALED = 4          # Umeyama with scaling: the hypotheses are similarities
 CHECK_EDGE_LENGTH = _lib.GSR_CHECK_EDGE_LENGTH
 CHECK_DISTANCE = _lib.GSR_CHECK_DISTANCE
 CHECK_NORMAL = _lib.GSR_CHECK_NORMAL

@@ -22,6 +22,8 @@ KIND_POINT_TO_POINT = 0
 KIND_POINT_TO_PLANE = 1
 KIND_GENERALIZED = 2
 KIND_COLORED = 3
+KIND_WITH_SCALING = 4                   # the with_scaling bit: valid on point-to-point only
+KIND_POINT_TO_POINT_SCALED = KIND_POINT_TO_POINT | KIND_WITH_SCALING       # TransformationEstimationPointToPoint(with_scaling=True)
 LOSS_L2, LOSS_TUKEY, LOSS_CAUCHY, LOSS_GM, LOSS_HUBER = 0, 1, 2, 3, 4
 
 

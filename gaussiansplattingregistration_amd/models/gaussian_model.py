@@ -209,10 +209,12 @@ class GaussianModel:
         _lib.check(L.gsr_sh_rotation(R.ctypes.data, int(sh_degree), B.ctypes.data), "gsr_sh_rotation")
         return B[:9].reshape(3, 3).copy(), B[9:34].reshape(5, 5).copy(), B[34:].reshape(7, 7).copy()
 
-    def _transform_kernel(self, transformation_matrix, rotate_sh, into=None):
+    def _transform_kernel(self, transformation_matrix, rotate_sh, into=None, similarity=False):
         """``gsr_model_transform`` on this model's arrays (one fused kernel; host tensors are staged by the library).  The
         results go to fresh arrays, or to the first ``len(self)`` rows of the tensors in ``into`` (name -> CUDA tensor).
-        Returns name -> tensor for ``_xyz``, ``_covariance``, ``_rotation``, ``_features_rest``; this model is not modified."""
+        Returns name -> tensor for ``_xyz``, ``_covariance``, ``_rotation``, ``_features_rest``; this model is not modified.
+        ``similarity``: ``gsr_model_similarity`` instead -- the matrix is ``[c R | t]`` -- and ``_scaling`` (log-scales, shifted by
+        ``ln c``) joins the moved arrays when the model carries it."""
         import ctypes as C
         L = _lib.load(require_device=True)
         T = np.ascontiguousarray(np.asarray(transformation_matrix, dtype=np.float64).reshape(4, 4))
@@ -223,6 +225,8 @@ class GaussianModel:
         have_rot = self._rotation.numel() > 0
         src = {"_xyz": (self._xyz, (n, 3)), "_covariance": (self._covariance, (n, 6)),
                "_rotation": (self._rotation if have_rot else None, (n, 4)), "_features_rest": (self._features_rest if K else None, (n, K, 3))}
+        if similarity:
+            src["_scaling"] = (self._scaling if self._scaling.numel() > 0 else None, (n, 3))
         ins, outs, ptr = {}, {}, {}
         for name, (t, shape) in src.items():
             if t is None:
@@ -240,6 +244,11 @@ class GaussianModel:
             else:
                 outs[name], ptr[name] = _m.out(shape, np.float32, device, on)
         a = lambda name: ins[name][0]
+        if similarity:
+            _lib.check(L.gsr_model_similarity(T.ctypes.data, n, K, 1 if rotate_sh else 0, a("_xyz"), a("_covariance"), a("_rotation"), a("_features_rest"),
+                                              a("_scaling"), ptr["_xyz"], ptr["_covariance"], ptr["_rotation"], ptr["_features_rest"], ptr["_scaling"],
+                                              1 if on else 0, device, C.c_void_p(_m.stream_ptr(device, on))), "gsr_model_similarity")
+            return {name: torch.as_tensor(o) for name, o in outs.items()}
         _lib.check(L.gsr_model_transform(T.ctypes.data, n, K, 1 if rotate_sh else 0, a("_xyz"), a("_covariance"), a("_rotation"), a("_features_rest"),
                                          ptr["_xyz"], ptr["_covariance"], ptr["_rotation"], ptr["_features_rest"], 1 if on else 0, device,
                                          C.c_void_p(_m.stream_ptr(device, on))), "gsr_model_transform")
@@ -276,9 +285,19 @@ class GaussianModel:
             self._rotation = q / torch.linalg.vector_norm(q, dim=-1, keepdim=True)
         return self
 
+    def similarity_transform_gaussian_model(self, transformation_matrix, rotate_sh=False):
+        """Apply a similarity ``[c R | t]`` -- the result of a registration with scaling -- in place: positions ``c R x + t``,
+        covariances ``c^2 R C R^T``, rotation quaternions by ``R``, the log-scales ``_scaling`` shifted by ``ln c``, the SH
+        coefficients by ``R`` when ``rotate_sh``; opacity and DC colour stay.  Always ONE device kernel (``gsr_model_similarity``;
+        host tensors are staged by the library, no GPU: ``RuntimeError``).  A matrix that is not ``c R`` with ``c > 0`` is refused."""
+        for name, t in self._transform_kernel(transformation_matrix, rotate_sh, similarity=True).items():
+            setattr(self, name, t)
+        return self
+
     @staticmethod
-    def get_merged_gaussian_point_clouds(gaussian1, gaussian2, transformation_matrix, rotate_sh=False):
+    def get_merged_gaussian_point_clouds(gaussian1, gaussian2, transformation_matrix, rotate_sh=False, with_scaling=False):
         """``gaussian1`` moved by the registration result, concatenated with ``gaussian2`` (the merged-cloud save).
+        ``with_scaling``: the matrix is a similarity (``similarity_transform_gaussian_model``); ``_scaling`` moves too.
         ``rotate_sh``: turn the SH coefficients of ``gaussian1`` with it (``transform_gaussian_model``).  When both models
         live on one CUDA device the merged arrays are allocated once, the kernel writes the moved ``gaussian1`` straight into
         their first rows and ``gaussian2`` is copied behind it: no clone, no ``cat``.  ``gaussian1`` is left as it was."""
@@ -299,7 +318,9 @@ class GaussianModel:
                     raise RuntimeError(f"{name}: one model carries it, the other does not")
                 setattr(m, name, torch.empty((n1 + n2,) + tuple(b.shape[1:]), dtype=torch.float32, device=x2.device))
             moved = ("_xyz", "_covariance", "_rotation", "_features_rest")
-            gaussian1._transform_kernel(transformation_matrix, rotate_sh, into={k: getattr(m, k) for k in moved})
+            if with_scaling:
+                moved += ("_scaling",)
+            gaussian1._transform_kernel(transformation_matrix, rotate_sh, into={k: getattr(m, k) for k in moved}, similarity=with_scaling)
             for name in names:
                 a, b, o = getattr(gaussian1, name), getattr(gaussian2, name), getattr(m, name)
                 if o.shape[0] != n1 + n2 or o.numel() == 0:
@@ -311,7 +332,9 @@ class GaussianModel:
         g1 = gaussian1
         if moves:
             g1 = gaussian1.clone_gaussian()
-            if rotate_sh:
+            if with_scaling:
+                g1.similarity_transform_gaussian_model(np.asarray(transformation_matrix, dtype=np.float64), rotate_sh=rotate_sh)
+            elif rotate_sh:
                 g1.transform_gaussian_model(np.asarray(transformation_matrix, dtype=np.float64), rotate_sh=True)
             else:
                 g1.transform_gaussian_model(np.asarray(transformation_matrix, dtype=np.float32))

@@ -114,3 +114,18 @@ class PointCloud:
         if self.cov6 is not None:
             self.cov6 = _cov(self.cov6)
         return self
+
+    def transform_similarity(self, T):
+        """``transform`` for a similarity ``T = [c R | t]`` (a registration with scaling): points p -> c R p + t, normals
+        n -> R n (they stay unit vectors), covariances C -> c^2 R C R^T.  ``T`` must pass ``similarity_util.split_similarity``."""
+        from ..utils.similarity_util import split_similarity
+        c, R, _ = split_similarity(T)
+        normals, self.normals = self.normals, None
+        self.transform(T)                       # points by A = c R, covariances by A C A^T = c^2 R C R^T
+        if normals is not None:
+            if _is_tensor(normals):
+                normals = (normals.detach().double() @ torch.as_tensor(R, device=normals.device).T).to(normals.dtype)
+            else:
+                normals = (np.asarray(normals, np.float64) @ R.T).astype(np.asarray(normals).dtype)
+        self.normals = normals
+        return self

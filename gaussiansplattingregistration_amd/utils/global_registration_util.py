@@ -56,7 +56,14 @@ class RANSACEstimationMethod(Enum):
 
 
 class TransformationEstimationPointToPoint:
+    """``with_scaling=True``: Umeyama with scaling, the hypotheses are similarities ``[c R | t]``.  The edge-length checker compares
+    lengths of the two clouds as they are (Open3D's behaviour, kept): leave it out when the clouds' relative scale is unknown."""
+
     kind = _F.KIND_POINT_TO_POINT
+
+    def __init__(self, with_scaling=False):
+        self.with_scaling = bool(with_scaling)
+        self.kind = _F.KIND_POINT_TO_POINT_SCALED if self.with_scaling else _F.KIND_POINT_TO_POINT
 
 
 class TransformationEstimationPointToPlane:
@@ -164,7 +171,7 @@ def compute_fpfh_feature(pcd, search_param):
 
 def _estimation_kind(estimation_method):
     kind = getattr(estimation_method, "kind", -1)
-    if kind not in (_F.KIND_POINT_TO_POINT, _F.KIND_POINT_TO_PLANE):
+    if kind not in (_F.KIND_POINT_TO_POINT, _F.KIND_POINT_TO_PLANE, _F.KIND_POINT_TO_POINT_SCALED):
         raise RuntimeError(f"{getattr(estimation_method, 'name', estimation_method)} is not a RANSAC estimation method of this backend "
                            "(point-to-point or point-to-plane)")
     return kind

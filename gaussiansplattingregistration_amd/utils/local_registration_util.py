@@ -87,7 +87,14 @@ class ConvergenceCriteria:
         self.relative_fitness, self.relative_rmse, self.max_iteration = relative_fitness, relative_rmse, max_iteration
 
 
-def get_estimation(registration_type, loss_function):
+def get_estimation(registration_type, loss_function, with_scaling=False):
+    """``with_scaling=True``: ``TransformationEstimationPointToPoint(with_scaling=True)`` -- the registration's transform is a
+    similarity ``[c R | t]``.  Open3D offers it for point-to-point only; any other type is a ``RuntimeError``."""
+    if with_scaling:
+        if registration_type is not LocalRegistrationType.ICP_Point_To_Point:
+            raise RuntimeError("[Open3D Error] with_scaling is an option of TransformationEstimationPointToPoint only; "
+                               f"it cannot be combined with {getattr(registration_type, 'instance_name', registration_type)}.")
+        return Estimation(_icp.KIND_POINT_TO_POINT_SCALED, None, "TransformationEstimationPointToPoint(with_scaling=True)")
     if loss_function is None:
         return Estimation(_icp.KIND_POINT_TO_POINT, None, "TransformationEstimationPointToPoint")
     if registration_type is LocalRegistrationType.ICP_Point_To_Point:
@@ -158,7 +165,7 @@ def registration_icp(source, target, max_correspondence_distance, init, estimati
     if own:
         ctx = _icp.IcpContext(device=dev)
     try:
-        if (estimation_method.kind in (_icp.KIND_POINT_TO_POINT, _icp.KIND_POINT_TO_PLANE) and not target_prepared and comm is None
+        if (estimation_method.kind in (_icp.KIND_POINT_TO_POINT, _icp.KIND_POINT_TO_PLANE, _icp.KIND_POINT_TO_POINT_SCALED) and not target_prepared and comm is None
                 and allreduce_device is None and allreduce is None and len(source) > 0
                 and len({bool(getattr(a, "is_cuda", False)) for a in (source.xyz32, target.xyz32, target.normals) if a is not None}) == 1):
             # the plain single-process call: the two clouds go to the library in ONE call (gsr_icp_register_clouds), like Open3D's own
@@ -219,10 +226,11 @@ def registration_generalized_icp(source, target, max_correspondence_distance, in
     return registration_icp(source, target, max_correspondence_distance, init, estimation_method, criteria, **kw)
 
 
-def do_icp_registration(point_cloud_first, point_cloud_second, init_transform, registration_params, *extra, **kw):
+def do_icp_registration(point_cloud_first, point_cloud_second, init_transform, registration_params, *extra, with_scaling=False, **kw):
     """Reference signature (4 arguments) or the multiscale worker's intended 10-positional form:
     ``(pc1, pc2, T, registration_type, max_correspondence, relative_fitness, relative_rmse, max_iteration,
-    rejection_type, k_value)``."""
+    rejection_type, k_value)``.  ``with_scaling=True`` (keyword, both forms): point-to-point with scaling -- the result is a
+    similarity; with any other registration type a ``RuntimeError``."""
     if extra:
         if len(extra) != 6:
             raise TypeError(f"do_icp_registration() takes 4 or 10 positional arguments but {4 + len(extra)} were given")
@@ -232,7 +240,7 @@ def do_icp_registration(point_cloud_first, point_cloud_second, init_transform, r
                                                       rejection_type=extra[4], k_value=extra[5])
     loss_function = get_rejection_loss(registration_params.rejection_type, registration_params.k_value,
                                        registration_params.registration_type)
-    estimation_method = get_estimation(registration_params.registration_type, loss_function)
+    estimation_method = get_estimation(registration_params.registration_type, loss_function, with_scaling=with_scaling)
     convergence_criteria = get_convergence_criteria(registration_params.relative_fitness,
                                                     registration_params.relative_rmse,
                                                     registration_params.max_iteration)

@@ -3,6 +3,8 @@
 HEM levels.  The multiscale worker reproduces the *intended* behaviour: the reference calls
 ``do_icp_registration`` with ten positional arguments (``:218-220``) although it takes four at HEAD.
 Errors are returned as a list of strings where the reference emits ``signal_error``.
+``with_scaling=True`` (a keyword of the local and multiscale workers) is handed to ``do_icp_registration``: point-to-point with
+scaling, the transforms are similarities.  The ``params`` dataclasses keep their fields.
 """
 from __future__ import annotations
 
@@ -19,12 +21,13 @@ class LocalRegistrator:
             self.result = result
             self.registration_data = registration_data
 
-    def __init__(self, pc1, pc2, init_trans, registration_params):
+    def __init__(self, pc1, pc2, init_trans, registration_params, with_scaling=False):
         self.pc1, self.pc2, self.init_trans, self.params = pc1, pc2, init_trans, registration_params
+        self.with_scaling = bool(with_scaling)
 
     def run(self):
         p = self.params
-        results = do_icp_registration(self.pc1, self.pc2, self.init_trans, p)
+        results = do_icp_registration(self.pc1, self.pc2, self.init_trans, p, with_scaling=self.with_scaling)
         data = LocalRegistrationData(registration_type=p.registration_type.instance_name,
                                      initial_transformation=self.init_trans, relative_fitness=p.relative_fitness,
                                      relative_rmse=p.relative_rmse, result_fitness=results.fitness,
@@ -40,7 +43,8 @@ class MultiScaleRegistratorMixture:
             self.registration_data = registration_data
 
     def __init__(self, pc1_list, pc2_list, init_trans, use_corresponding, sparse_first, sparse_second, registration_type,
-                 relative_fitness, relative_rmse, voxel_values, iter_values, rejection_type, k_value, progress=None):
+                 relative_fitness, relative_rmse, voxel_values, iter_values, rejection_type, k_value, progress=None, with_scaling=False):
+        self.with_scaling = bool(with_scaling)
         self.pc1_list, self.pc2_list = pc1_list, pc2_list
         self.init_trans = init_trans
         self.use_corresponding = use_corresponding
@@ -82,7 +86,7 @@ class MultiScaleRegistratorMixture:
         try:
             sparse_result = do_icp_registration(sparse_pc1, sparse_pc2, self.init_trans, self.registration_type,
                                                 self.voxel_values[0], self.relative_fitness, self.relative_rmse,
-                                                self.iter_values[0], self.rejection_type, self.k_value)
+                                                self.iter_values[0], self.rejection_type, self.k_value, with_scaling=self.with_scaling)
         except RuntimeError as e:
             self.errors.append(f"{e}\nSource: \"{sparse_pc1}\"\nTarget: \"{sparse_pc2}\"")
             return None
@@ -104,7 +108,7 @@ class MultiScaleRegistratorMixture:
             try:
                 results = do_icp_registration(pc1, pc2, current_trans, self.registration_type, max_correspondence,
                                               self.relative_fitness, self.relative_rmse, max_iter, self.rejection_type,
-                                              self.k_value)
+                                              self.k_value, with_scaling=self.with_scaling)
             except RuntimeError as e:
                 self.errors.append(f"{e}\nSource: \"{pc1}\"\nTarget: \"{pc2}\"")
                 return None
@@ -147,9 +151,9 @@ class MultiScaleRegistratorVoxel(MultiScaleRegistratorMixture):
     call is inert), and ICP runs with ``max_correspondence = voxel_values[scale]``."""
 
     def __init__(self, pc1, pc2, init_trans, use_corresponding, sparse_first, sparse_second, registration_type,
-                 relative_fitness, relative_rmse, voxel_values, iter_values, rejection_type, k_value, progress=None):
+                 relative_fitness, relative_rmse, voxel_values, iter_values, rejection_type, k_value, progress=None, with_scaling=False):
         super().__init__([pc1], [pc2], init_trans, use_corresponding, sparse_first, sparse_second, registration_type,
-                         relative_fitness, relative_rmse, voxel_values, iter_values, rejection_type, k_value, progress)
+                         relative_fitness, relative_rmse, voxel_values, iter_values, rejection_type, k_value, progress, with_scaling=with_scaling)
         self.pc1, self.pc2 = pc1, pc2
 
     def _check_valid_data(self):            # :116-122
@@ -173,7 +177,7 @@ class MultiScaleRegistratorVoxel(MultiScaleRegistratorMixture):
                 target_down.estimate_normals()
                 results = do_icp_registration(source_down, target_down, current_trans, self.registration_type, radius,
                                               self.relative_fitness, self.relative_rmse, max_iter, self.rejection_type,
-                                              self.k_value)
+                                              self.k_value, with_scaling=self.with_scaling)
             except RuntimeError as e:
                 self.errors.append(f"{e}\nSource: \"{source_down}\"\nTarget: \"{target_down}\"")
                 return None

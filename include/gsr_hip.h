@@ -273,6 +273,16 @@ typedef struct gsr_icp_ctx gsr_icp_ctx;
 #define GSR_ICP_POINT_TO_PLANE 1   /* LocalRegistrationType.ICP_Point_To_Plane, :34 */
 #define GSR_ICP_GENERALIZED    2   /* LocalRegistrationType.ICP_General, :36 (registration_generalized_icp, :96-98) */
 #define GSR_ICP_COLORED        3   /* LocalRegistrationType.ICP_Color, :35 (registration_colored_icp, :92-94) */
+/* TransformationEstimationPointToPoint(with_scaling=True), i.e. Eigen::umeyama(src, dst, true): the update is a SIMILARITY
+ * [c R | t] and so is the registration's transform (two splat scenes from separate structure-from-motion runs share no unit of
+ * length).  The value is the point-to-point kind with the GSR_ICP_WITH_SCALING bit; that bit on any other kind (5, 6, 7) is
+ * GSR_E_INVALID with a message -- Open3D offers scaling for point-to-point only -- and so is the scaled kind with a loss other than
+ * GSR_LOSS_L2 (kind 0 ignores the loss argument).  Fitness, RMSE and max_corr are measured in the target's frame after T, as for
+ * every kind.  Where Eigen would divide by zero (one correspondence, coincident source points: var = 0 or c = 0) the update is
+ * the identity.  Open3D is absent from the test machines: like the rest of the ICP half this is checked against a float64
+ * restatement of the definition (tests/sim3_model.py), parity with Open3D itself is unpinned. */
+#define GSR_ICP_WITH_SCALING   4
+#define GSR_ICP_POINT_TO_POINT_SCALED (GSR_ICP_POINT_TO_POINT | GSR_ICP_WITH_SCALING)   /* = 4 */
 
 #define GSR_LOSS_L2     0          /* KernelLossFunctionType.Loss_None or k == 0, :63-64 */
 #define GSR_LOSS_TUKEY  1
@@ -326,7 +336,8 @@ int32_t gsr_icp_set_comm(gsr_icp_ctx* ctx, gsr_comm* comm, int64_t n_source_glob
 
 /* One correspondence evaluation + accumulator reduction at transform T (row-major 4x4 float64):
  * acc[0]=count, acc[1]=sum d^2, then for point-to-point acc[2..4]=sum p, [5..7]=sum q, [8..16]=sum p q^T
- * (p = transformed source, q = matched target, both relative to the target-bbox centre);
+ * (p = transformed source, q = matched target, both relative to the target-bbox centre); the scaled point-to-point kind has the
+ * same seventeen and acc[17]=sum |p|^2;
  * for point-to-plane and generalized ICP acc[2..22]=upper triangle of J^T w J (row-major), [23..28]=J^T w r,
  * [29]=sum r^2 (generalized: three residual rows per pair, J = W [-skew(p) | I], W = (Ct + R Cs R^T)^-1/2;
  * colored: a geometric and a photometric row per pair).
@@ -343,7 +354,7 @@ int32_t gsr_icp_register(gsr_icp_ctx* ctx, const double* init_T, int32_t kind, i
 /* The same with the two CLOUDS as arguments -- Open3D's own signature, registration_icp(source, target, max_correspondence_distance,
  * init, estimation_method, criteria) (local_registration_util.py:88-90): gsr_icp_set_target + gsr_icp_set_source + gsr_icp_register in
  * one call, without a return to the host language or a stream synchronisation between them; same result, bit for bit.  Point-to-point
- * and point-to-plane (tgt_normals[nt*3] float64, required for the latter; ignored for the former); one process, one GPU (an installed
+ * (plain or scaled) and point-to-plane (tgt_normals[nt*3] float64, required for the latter; ignored for the former); one process, one GPU (an installed
  * communicator / all-reduce callback is removed).  on_device: 0 = host arrays, 1 = device arrays (read in place). */
 int32_t gsr_icp_register_clouds(gsr_icp_ctx* ctx, const float* src_xyz, int64_t ns, const float* tgt_xyz, const double* tgt_normals,
                                 int64_t nt, int32_t on_device, double max_corr, const double* init_T, int32_t kind, int32_t loss,
@@ -381,7 +392,7 @@ int32_t gsr_normals_from_cov(const float* cov6, int64_t n, double* normals, int3
                              int32_t device, void* stream);
 
 /* Estimator solve on the HOST from a reduced accumulator vector (no GPU involved): the 3x3 Jacobi
- * SVD of Eigen::umeyama (point-to-point) or the 6x6 LDL^T solve + Rz*Ry*Rx of Open3D's point-to-plane
+ * SVD of Eigen::umeyama (point-to-point, plain or scaled) or the 6x6 LDL^T solve + Rz*Ry*Rx of Open3D's point-to-plane
  * estimator.  centre[3] = the point the point-to-point sums are relative to (ignored for
  * point-to-plane).  update = row-major 4x4.  Every rank of a multi-GPU run calls this on the same
  * all-reduced vector and so gets the identical update. */
@@ -468,6 +479,17 @@ int32_t gsr_model_transform(const double* transform, int64_t n, int32_t K, int32
                             const float* rot, const float* sh, float* xyz_out, float* cov6_out, float* rot_out, float* sh_out,
                             int32_t on_device, int32_t device, void* stream);
 
+/* The same for a SIMILARITY A = c R (a registration with GSR_ICP_POINT_TO_POINT_SCALED; gsr_model_transform keeps refusing it).
+ * Gate on the upper 3x3: det A > 0, c = cbrt(det A), 1e-6 <= c <= 1e6, max|A^T A / c^2 - I| <= 1e-3, else GSR_E_INVALID;
+ * R = A / c in float64, narrowed to float32 once.  Per splat, in ONE kernel (the rigid kernel's code, instantiated with a factor):
+ *   xyz' = c (R xyz) + t;   cov6' = c^2 (R cov R^T);   rot' = normalise(q_R (x) q);   scaling' = scaling + ln c, the LOG-scales
+ *   (n, 3) with ln c computed in float64 and narrowed once;   sh by D_l(R) when rotate_sh != 0, copied bit for bit otherwise.
+ * Opacity and the DC colour do not change and are not arguments.  scaling / scaling_out may be NULL together, like rot / rot_out.
+ * Everything else -- K, placement, NOT in place, outputs into the middle of larger arrays -- as for gsr_model_transform. */
+int32_t gsr_model_similarity(const double* transform, int64_t n, int32_t K, int32_t rotate_sh, const float* xyz, const float* cov6,
+                             const float* rot, const float* sh, const float* scaling, float* xyz_out, float* cov6_out, float* rot_out,
+                             float* sh_out, float* scaling_out, int32_t on_device, int32_t device, void* stream);
+
 /* RANSAC plane search, the data-parallel part: scores ALL candidate planes of one
  * _fit_single_plane call of the reference (src/utils/plane_fitting_util.py:38-69) in one pass over the points.
  * candidates[n_candidates*8] = {n'_0, n'_1, n'_2, d, m_0, m_1, m_2, |n'|}: the plane normal re-normalised as
@@ -533,7 +555,8 @@ int32_t gsr_feature_match(const double* src_feat, int64_t ns, const double* tgt_
 #define GSR_CHECK_NORMAL      2   /* param = angle (radians): fail if n_t . (R n_s) < cos(angle); passes when a cloud has no normals */
 #define GSR_RANSAC_MAX_N 16       /* largest ransac_n */
 typedef struct gsr_ransac_params {
-    int32_t kind;              /* GSR_ICP_POINT_TO_POINT (3-pair Umeyama) or GSR_ICP_POINT_TO_PLANE (6x6 solve on ransac_n rows) */
+    int32_t kind;              /* GSR_ICP_POINT_TO_POINT (3-pair Umeyama), GSR_ICP_POINT_TO_POINT_SCALED (the same with scaling) or
+                                  GSR_ICP_POINT_TO_PLANE (6x6 solve on ransac_n rows) */
     int32_t ransac_n;
     double max_corr;           /* inlier: |T p - q|^2 < max_corr^2 */
     int64_t max_iteration;
@@ -563,6 +586,11 @@ typedef struct gsr_ransac_result {
  *   evaluation  good = #{c : |T p_c - q_c|^2 < max_corr^2}, fitness = good / m, rmse = sqrt(sum d2 / good), in float64;
  *   selection   Open3D's serial rule in index order: better = higher fitness, or equal fitness and lower rmse; after each new best
  *               exit = min(exit, ceil(log(1 - confidence) / log(1 - fitness^ransac_n))) when confidence < 1; stop at k >= exit.
+ * With GSR_ICP_POINT_TO_POINT_SCALED every hypothesis is a similarity A = c R: the distance checker and the evaluation use all of
+ * it, the normal checker turns the normals by R = A / c (c = cbrt(det A)), and the edge-length checker is applied as written, as
+ * Open3D does -- it compares lengths of the two clouds directly, so it is SCALE-SENSITIVE: callers who register clouds of unknown
+ * relative scale should leave it out.  Sampling, selection and early exit are the same.  (gsr_fgr_* stay rigid: Open3D's FGR has
+ * no scale.)
  * corres[m*2] int32 (source row, target row); xyz float32, normals float64 or NULL; host or device as on_device says.  Degenerate
  * inputs (ransac_n < 3, m < ransac_n, max_corr <= 0) give Open3D's empty result: identity, zeros, best_index -1. */
 int32_t gsr_ransac_correspondence(const float* src_xyz, int64_t ns, const float* tgt_xyz, int64_t nt, const double* src_normals,

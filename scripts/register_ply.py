@@ -4,6 +4,11 @@
 
     python scripts/register_ply.py first.ply second.ply --levels 3 --max-corr 0.5 0.3 0.2 0.1 --iters 50 30 20 10 \\
            [--type plane|point|color|general] [--loss none|tukey|cauchy|gm|huber --k 0.1] [--voxel] [--out merged.ply [--rotate-sh]]
+           [--with-scaling]
+
+`--with-scaling`: the two scenes do not share a unit of length (separate structure-from-motion runs).  Point-to-point ICP with scaling
+(`--type point` is implied, any other type is refused); without a global method the start is `initial_similarity` (centroids and RMS
+radii aligned); the result is a similarity [c R | t], and the merged .ply has the moved cloud's scale_* columns shifted by ln c.
 
 Prints the 4x4 transformation (first -> second), fitness and inlier RMSE; `--out` saves the merged cloud.
 """
@@ -24,7 +29,8 @@ def main():
     ap.add_argument("--levels", type=int, default=3, help="HEM mixture levels per cloud (ignored with --voxel)")
     ap.add_argument("--max-corr", type=float, nargs="+", default=[0.5, 0.3, 0.2, 0.1], help="coarse -> fine (voxel sizes with --voxel)")
     ap.add_argument("--iters", type=int, nargs="+", default=[50, 30, 20, 10])
-    ap.add_argument("--type", choices=["point", "plane", "color", "general"], default="plane")
+    ap.add_argument("--type", choices=["point", "plane", "color", "general"], default=None, help="default: plane (point with --with-scaling)")
+    ap.add_argument("--with-scaling", action="store_true", help="estimate a similarity (scale, rotation, translation): point-to-point only")
     ap.add_argument("--loss", choices=["none", "tukey", "cauchy", "gm", "huber"], default="none")
     ap.add_argument("--k", type=float, default=0.0)
     ap.add_argument("--voxel", action="store_true", help="voxel multiscale path instead of HEM mixtures")
@@ -39,6 +45,9 @@ def main():
     ap.add_argument("--rotate-sh", action="store_true", help="turn the SH coefficients (view-dependent colour) of the moved cloud with it in the "
                     "merged output")
     a = ap.parse_args()
+    if a.with_scaling and a.type not in (None, "point"):
+        raise SystemExit(f"--with-scaling is point-to-point only (Open3D offers scaling for no other estimator): --type {a.type} refused")
+    a.type = a.type or ("point" if a.with_scaling else "plane")
 
     import __graft_entry__ as g
     g.build_hip()
@@ -74,6 +83,10 @@ def main():
         print("levels:", [len(x) for x in repo.pc_gaussian_list_first], "/", [len(x) for x in repo.pc_gaussian_list_second])
     t2 = time.perf_counter()
     rc = RegistrationController(repo, ui)
+    if a.with_scaling and not (a.global_ransac or a.global_fgr):
+        from gaussiansplattingregistration_amd.utils.similarity_util import initial_similarity, split_similarity
+        ui.transformation_matrix = initial_similarity(repo.pc_gaussian_list_first[0].get_xyz, repo.pc_gaussian_list_second[0].get_xyz)
+        print(f"initial similarity: scale {split_similarity(ui.transformation_matrix)[0]:.6f}")
     if a.global_ransac:
         from gaussiansplattingregistration_amd.params.registration_parameters import RANSACRegistrationParams
         from gaussiansplattingregistration_amd.utils import global_registration_util as G
@@ -91,17 +104,21 @@ def main():
         g = rc.execute_fgr_registration_normal(FGRRegistrationParams(voxel_size=v, maximum_correspondence=1.5 * v))
         print(f"global FGR: fitness {g.fitness:.4f}  rmse {g.inlier_rmse:.6f}  reciprocal pairs {g.info.get('n_reciprocal')}  "
               f"tuples {g.info.get('n_tuples')} of {g.info.get('n_trials')} trials  {time.perf_counter() - tg:.3f} s")
-    res = rc.execute_multiscale_registration(False, "", "", rtype, 1e-6, 1e-6, a.max_corr, a.iters, loss, a.k, not a.voxel)
+    res = rc.execute_multiscale_registration(False, "", "", rtype, 1e-6, 1e-6, a.max_corr, a.iters, loss, a.k, not a.voxel, with_scaling=a.with_scaling)
     t3 = time.perf_counter()
     if res is None:
         raise SystemExit("registration failed: " + "; ".join(rc.errors))
     np.set_printoptions(precision=6, suppress=True)
     print("transformation (first -> second):\n", res.result.transformation)
+    if a.with_scaling:
+        from gaussiansplattingregistration_amd.utils.similarity_util import split_similarity
+        print(f"scale {split_similarity(res.result.transformation)[0]:.9f}")
     print(f"fitness {res.result.fitness:.4f}  inlier RMSE {res.result.inlier_rmse:.6f}")
     print(f"load {t1 - t0:.2f} s, mixtures {t2 - t1:.3f} s, registration {t3 - t2:.3f} s")
     if a.out:
         merged = GaussianModel.get_merged_gaussian_point_clouds(repo.pc_gaussian_list_first[0], repo.pc_gaussian_list_second[0],
-                                                                res.result.transformation, rotate_sh=a.rotate_sh)
+                                                                res.result.transformation, rotate_sh=a.rotate_sh,
+                                                                with_scaling=a.with_scaling)
         merged.save_ply(a.out)
         print(f"merged cloud ({len(merged)} splats) -> {a.out}")
 
