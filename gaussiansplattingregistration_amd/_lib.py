@@ -113,6 +113,7 @@ SIGNATURES = {
     "gsr_sh_rotation": (_i32, [_vp, _i32, _vp]),
     "gsr_model_transform": (_i32, [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp]),
     "gsr_model_similarity": (_i32, [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp]),
+    "gsr_model_fuse": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _vp]),
     "gsr_plane_score": (_i32, [_vp, _vp, _i64, _vp, _i32, _f32, _f32, _vp, _vp, C.POINTER(_i32), _i32, _i32, _vp]),
     "gsr_icp_solve": (_i32, [_vp, _i32, _vp, _vp]),
     "gsr_icp_get_centre": (_i32, [_vp, _vp]),
@@ -183,6 +184,23 @@ class FgrResult(C.Structure):
     """gsr_fgr_result (include/gsr_hip.h)."""
     _fields_ = [("T", C.c_double * 16), ("n_corres", C.c_int64), ("n_reciprocal", C.c_int64), ("n_trials", C.c_int64),
                 ("n_tuples", C.c_int64), ("iterations", C.c_int32), ("host_waits", C.c_int32), ("scale_global", C.c_double)]
+
+
+class ModelView(C.Structure):
+    """gsr_model_view (include/gsr_hip.h): the arrays of one splat model."""
+    _fields_ = [("n", C.c_int64), ("xyz", C.c_void_p), ("cov6", C.c_void_p), ("dc", C.c_void_p), ("sh", C.c_void_p), ("opacity", C.c_void_p),
+                ("scaling", C.c_void_p), ("rot", C.c_void_p)]
+
+
+class FuseParams(C.Structure):
+    """gsr_fuse_params (include/gsr_hip.h)."""
+    _fields_ = [("max_distance", C.c_double), ("kld_max", C.c_double), ("color_delta", C.c_double)]
+
+
+class FuseReport(C.Structure):
+    """gsr_fuse_report (include/gsr_hip.h)."""
+    _fields_ = [("n_out", C.c_int64), ("n_pairs", C.c_int64), ("n_a_only", C.c_int64), ("n_b_only", C.c_int64), ("n_invalid_a", C.c_int64),
+                ("n_invalid_b", C.c_int64), ("gated_pairs", C.c_int64), ("workspace_bytes", C.c_int64), ("phase_ms", C.c_float * 4)]
 
 
 GSR_CHECK_EDGE_LENGTH = 0

@@ -64,8 +64,10 @@ class RegistrationController:
             self.handle_registration_result_local(result)
         return result
 
-    def evaluate_registration(self, cameras_list, images_path, log_path, color, use_gpu, registration_result=None, rotate_sh=False, with_scaling=False):
+    def evaluate_registration(self, cameras_list, images_path, log_path, color, use_gpu, registration_result=None, rotate_sh=False, with_scaling=False,
+                              fuse=None):
         """``with_scaling``: the current transform is a similarity (a registration with scaling); the merge before rendering applies it as one.
+        ``fuse`` (``FuseOverlapParams``): the merge fuses the splats the two clouds share (``GaussianModel.fuse_overlap``).
         Image-based evaluation of the current transform on the repository's original clouds (reference :122-143): renders of
         the merged model against the photographs, the JSON log at ``log_path``.  Returns the evaluator's ``EvaluationObject``."""
         from ..workers.evaluator import RegistrationEvaluator
@@ -73,7 +75,7 @@ class RegistrationController:
         pc1 = repo.pc_gaussian_list_first[repo.current_index]
         pc2 = repo.pc_gaussian_list_second[repo.current_index]
         worker = RegistrationEvaluator(pc1, pc2, self.ui_repository.transformation_matrix, cameras_list, images_path, log_path, color,
-                                       registration_result, use_gpu, rotate_sh=rotate_sh, with_scaling=with_scaling)
+                                       registration_result, use_gpu, rotate_sh=rotate_sh, with_scaling=with_scaling, fuse=fuse)
         return worker.run()
 
     def handle_registration_result_local(self, result_data):       # :145-163

@@ -1,0 +1,461 @@
+// fuse.hip -- overlap-aware merge of two registered splat models (gsr_model_fuse, include/gsr_hip.h).
+//
+// A splat of model A and a splat of model B that are each other's best match under a distance gate, a colour gate and a gate on the
+// symmetrised KL divergence J are replaced by their moment-matched union (the operation of HEM's M-step, across two models);
+// everything else is copied bit for bit.  The definition is restated in float64 NumPy in tests/fuse_model.py.
+//
+//   k_fuse_prep        per splat of both models: validity, w = sigmoid(opacity) sqrt(det), the float64 inverse covariance
+//   k_fuse_moments /   the box of the grid over A without the host: moments of the valid centres, then of those within 3 sigma of the
+//   k_fuse_box         first pass (far outliers leave), box = mean +- 4 sigma cut to the extremes; edge >= max_distance, enlarged
+//                      until the table has at most `cap` = max(na, 1024) cells.  Coordinates outside the box clamp into boundary
+//                      cells: clamping is monotone, so two centres within one edge of each other stay in adjacent cells.
+//   k_fuse_keys, sort, k_fuse_cell_starts, k_fuse_gather_a    A in cell order: a cell is a contiguous span of the search arrays
+//   k_fuse_search      a thread per splat of B in the order of A's cell key: 9 spans (3 x-adjacent cells each), gates cheapest first,
+//                      its own best (J32, a) in registers, one no-return 64-bit atomicMin of (J32 bits << 32 | b) into best_a[a] per
+//                      GATED pair.  J >= 0, so the float bits order like the value; min is exact and order-free: deterministic.
+//   k_fuse_pair        mutual test (best_a is complete here: the kernel boundary is the only synchronisation), flags, the pair list
+//   scan_exclusive x2, k_fuse_rows    a lane per output FLOAT: unpaired rows are copied as 32-bit words, fused rows are computed in
+//                      float64 and narrowed once.  Output: A-only rows, fused rows (ascending a), B-only rows.
+// The host reads the counts back once; scaling / rot of the fused rows are then gsr_decompose_cov (GSR_DECOMP_EXACT) of the fused
+// covariances, which lie in one contiguous block of the output.
+#include "gsr_common.h"
+#include "gsr_oneshot.h"
+#include "gsr_prims.h"
+
+#include <float.h>
+#include <math.h>
+#include <string.h>
+
+namespace gsr {
+
+struct FuseGrid {
+    double ox, oy, oz, inv_c;
+    int gx, gy, gz, ncells;
+};
+#define FUSE_MOM 13      // count, sum x y z, sum xx yy zz, min x y z, max x y z
+
+__device__ __forceinline__ int fuse_cell(double v, double o, double inv_c, int g) {
+    double t = (v - o) * inv_c;
+    t = fmin(fmax(t, 0.0), (double)(g - 1));      // NaN -> 0
+    return (int)t;
+}
+
+// validity, weight and inverse covariance of every splat; counts the invalid ones (one atomic per wave that has any)
+__global__ __launch_bounds__(256) void k_fuse_prep(int64_t n, const float* __restrict__ xyz, const float* __restrict__ cov6, const float* __restrict__ opacity,
+                                                   double* __restrict__ w, double* __restrict__ inv, unsigned long long* __restrict__ n_invalid) {
+    const int lane = threadIdx.x & 63;
+    for (int64_t i0 = (int64_t)blockIdx.x * blockDim.x; i0 < n; i0 += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t i = i0 + threadIdx.x;
+        const bool live = i < n;
+        bool valid = false;
+        if (live) {
+            const double x = xyz[3 * i], y = xyz[3 * i + 1], z = xyz[3 * i + 2], op = opacity[i];
+            const double c00 = cov6[6 * i], c01 = cov6[6 * i + 1], c02 = cov6[6 * i + 2], c11 = cov6[6 * i + 3], c12 = cov6[6 * i + 4], c22 = cov6[6 * i + 5];
+            const double m00 = c11 * c22 - c12 * c12, m01 = c02 * c12 - c01 * c22, m02 = c01 * c12 - c02 * c11;
+            const double det = c00 * m00 + c01 * m01 + c02 * m02;
+            double wi = 0.0;
+            if (fabs(x) <= DBL_MAX && fabs(y) <= DBL_MAX && fabs(z) <= DBL_MAX && fabs(op) <= DBL_MAX && fabs(c00) <= DBL_MAX && fabs(c01) <= DBL_MAX &&
+                fabs(c02) <= DBL_MAX && fabs(c11) <= DBL_MAX && fabs(c12) <= DBL_MAX && fabs(c22) <= DBL_MAX && det > 0.0) {      // (NaN fails every test)
+                wi = (1.0 / (1.0 + exp(-op))) * sqrt(det);
+                if (!(wi > 0.0 && wi <= DBL_MAX)) wi = 0.0;
+            }
+            valid = wi > 0.0;
+            w[i] = wi;
+            const double m11 = c00 * c22 - c02 * c02, m12 = c01 * c02 - c00 * c12, m22 = c00 * c11 - c01 * c01;
+            double* o = inv + 6 * i;
+            if (valid) { o[0] = m00 / det; o[1] = m01 / det; o[2] = m02 / det; o[3] = m11 / det; o[4] = m12 / det; o[5] = m22 / det; }
+            else { o[0] = o[1] = o[2] = o[3] = o[4] = o[5] = 0.0; }
+        }
+        const unsigned long long m = __ballot(live && !valid);
+        if (m != 0ull && lane == 0) atomicAdd(n_invalid, (unsigned long long)__popcll(m));
+    }
+}
+
+// per-block moments of the valid centres (inside `box` when given): FUSE_MOM doubles per block, fixed order, no atomics
+__global__ __launch_bounds__(256) void k_fuse_moments(int64_t n, const float* __restrict__ xyz, const double* __restrict__ w, const double* __restrict__ box,
+                                                      double* __restrict__ part) {
+    double a[FUSE_MOM];
+    for (int k = 0; k < 7; ++k) a[k] = 0.0;
+    for (int k = 0; k < 3; ++k) { a[7 + k] = DBL_MAX; a[10 + k] = -DBL_MAX; }
+    double lo[3] = {-DBL_MAX, -DBL_MAX, -DBL_MAX}, hi[3] = {DBL_MAX, DBL_MAX, DBL_MAX};
+    if (box) for (int k = 0; k < 3; ++k) { lo[k] = box[k]; hi[k] = box[3 + k]; }
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        if (!(w[i] > 0.0)) continue;
+        const double p[3] = {(double)xyz[3 * i], (double)xyz[3 * i + 1], (double)xyz[3 * i + 2]};
+        if (!(p[0] >= lo[0] && p[0] <= hi[0] && p[1] >= lo[1] && p[1] <= hi[1] && p[2] >= lo[2] && p[2] <= hi[2])) continue;
+        a[0] += 1.0;
+        for (int k = 0; k < 3; ++k) { a[1 + k] += p[k]; a[4 + k] += p[k] * p[k]; a[7 + k] = fmin(a[7 + k], p[k]); a[10 + k] = fmax(a[10 + k], p[k]); }
+    }
+    __shared__ double s[4][FUSE_MOM];
+    for (int k = 0; k < FUSE_MOM; ++k)
+        for (int o = 32; o > 0; o >>= 1) {
+            const double v = __shfl_xor(a[k], o);
+            a[k] = k < 7 ? a[k] + v : k < 10 ? fmin(a[k], v) : fmax(a[k], v);
+        }
+    if ((threadIdx.x & 63) == 0) for (int k = 0; k < FUSE_MOM; ++k) s[threadIdx.x >> 6][k] = a[k];
+    __syncthreads();
+    if (threadIdx.x < FUSE_MOM) {
+        const int k = threadIdx.x;
+        double v = s[0][k];
+        for (int j = 1; j < 4; ++j) v = k < 7 ? v + s[j][k] : k < 10 ? fmin(v, s[j][k]) : fmax(v, s[j][k]);
+        part[(int64_t)blockIdx.x * FUSE_MOM + k] = v;
+    }
+}
+
+// one block: the partial moments summed in block order; stage 0 writes the 3-sigma box of the first pass to box[0..5], stage 1
+// the grid.  Edge = max_distance (1 + 1e-6) -- the margin keeps the rounding of (v - o) * inv_c from separating two centres that
+// are exactly max_distance apart by two cells -- times 2^(1/3) until gx gy gz <= cap.
+__global__ __launch_bounds__(64) void k_fuse_box(int nblocks, const double* __restrict__ part, int stage, double max_distance, int64_t cap,
+                                                 double* __restrict__ box, FuseGrid* __restrict__ grid) {
+    __shared__ double m[FUSE_MOM];
+    if (threadIdx.x < FUSE_MOM) {
+        const int k = threadIdx.x;
+        double v = part[k];
+        for (int b = 1; b < nblocks; ++b) { const double u = part[(int64_t)b * FUSE_MOM + k]; v = k < 7 ? v + u : k < 10 ? fmin(v, u) : fmax(v, u); }
+        m[k] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    double lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
+    if (m[0] > 0.0) {
+        const double f = stage == 0 ? 3.0 : 4.0;
+        for (int k = 0; k < 3; ++k) {
+            const double mean = m[1 + k] / m[0];
+            double var = m[4 + k] / m[0] - mean * mean;
+            if (!(var > 0.0)) var = 0.0;
+            const double sd = sqrt(var);
+            lo[k] = fmax(mean - f * sd, m[7 + k]);
+            hi[k] = fmin(mean + f * sd, m[10 + k]);
+            if (!(hi[k] >= lo[k])) { lo[k] = m[7 + k]; hi[k] = m[10 + k]; }
+        }
+    }
+    if (stage == 0) {
+        for (int k = 0; k < 3; ++k) { box[k] = lo[k]; box[3 + k] = hi[k]; }
+        return;
+    }
+    FuseGrid g;
+    g.ox = lo[0]; g.oy = lo[1]; g.oz = lo[2];
+    double cell = max_distance * (1.0 + 1e-6);
+    g.gx = g.gy = g.gz = 1;
+    g.inv_c = 0.0;
+    for (int it = 0; it < 8192; ++it) {
+        const double fx = floor((hi[0] - lo[0]) / cell) + 1.0, fy = floor((hi[1] - lo[1]) / cell) + 1.0, fz = floor((hi[2] - lo[2]) / cell) + 1.0;
+        if (fx * fy * fz <= (double)cap) { g.gx = (int)fx; g.gy = (int)fy; g.gz = (int)fz; g.inv_c = 1.0 / cell; break; }
+        cell *= 1.2599210498948732;
+    }
+    g.ncells = g.gx * g.gy * g.gz;
+    *grid = g;
+}
+
+__global__ __launch_bounds__(256) void k_fuse_keys(int64_t n, const float* __restrict__ xyz, const FuseGrid* __restrict__ G, unsigned* __restrict__ keys,
+                                                   unsigned* __restrict__ idx) {
+    const FuseGrid g = *G;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const int cx = fuse_cell(xyz[3 * i], g.ox, g.inv_c, g.gx), cy = fuse_cell(xyz[3 * i + 1], g.oy, g.inv_c, g.gy), cz = fuse_cell(xyz[3 * i + 2], g.oz, g.inv_c, g.gz);
+        keys[i] = (unsigned)((cz * g.gy + cy) * g.gx + cx);
+        idx[i] = (unsigned)i;
+    }
+}
+
+// start[c] = the first position of the sorted keys that is >= c, for c = 0 .. cap (every entry is written: the cell count lives on the device)
+__global__ __launch_bounds__(256) void k_fuse_cell_starts(int64_t n, const unsigned* __restrict__ skeys, int64_t cap, int* __restrict__ start) {
+    for (int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; c <= cap; c += (int64_t)gridDim.x * blockDim.x) {
+        int64_t lo = 0, hi = n;
+        while (lo < hi) {
+            const int64_t mid = (lo + hi) >> 1;
+            if ((int64_t)skeys[mid] < c) lo = mid + 1; else hi = mid;
+        }
+        start[c] = (int)lo;
+    }
+}
+
+// A's search arrays in cell order; an invalid splat gets NaN centres, which fail the distance gate
+__global__ __launch_bounds__(256) void k_fuse_gather_a(int64_t n, const unsigned* __restrict__ order, const float* __restrict__ xyz, const float* __restrict__ dc,
+                                                       const float* __restrict__ cov6, const double* __restrict__ w, const double* __restrict__ inv,
+                                                       float* __restrict__ sxyz, float* __restrict__ sdc, float* __restrict__ scov, double* __restrict__ sinv) {
+    for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < n; p += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t a = order[p];
+        const bool valid = w[a] > 0.0;
+        const float nan = __builtin_nanf("");
+        for (int k = 0; k < 3; ++k) { sxyz[3 * p + k] = valid ? xyz[3 * a + k] : nan; sdc[3 * p + k] = dc[3 * a + k]; }
+        for (int k = 0; k < 6; ++k) { scov[6 * p + k] = cov6[6 * a + k]; sinv[6 * p + k] = inv[6 * a + k]; }
+    }
+}
+
+// tr(P Q) of two symmetric 3x3 in the six-entry form (xx, xy, xz, yy, yz, zz)
+__device__ __forceinline__ double sym_trace(const double* P, const double* Q) {
+    return ((P[0] * Q[0] + P[3] * Q[3]) + P[5] * Q[5]) + 2.0 * ((P[1] * Q[1] + P[2] * Q[2]) + P[4] * Q[4]);
+}
+__device__ __forceinline__ double sym_quad(const double* P, double x, double y, double z) {
+    return ((P[0] * x * x + P[3] * y * y) + P[5] * z * z) + 2.0 * ((P[1] * x * y + P[2] * x * z) + P[4] * y * z);
+}
+
+__global__ __launch_bounds__(256) void k_fuse_search(int64_t nb, const unsigned* __restrict__ orderB, const float* __restrict__ xyzB, const float* __restrict__ dcB,
+                                                     const float* __restrict__ covB, const double* __restrict__ wB, const double* __restrict__ invB,
+                                                     const FuseGrid* __restrict__ G, const int* __restrict__ cellStart, const float* __restrict__ sxyz,
+                                                     const float* __restrict__ sdc, const float* __restrict__ scov, const double* __restrict__ sinv,
+                                                     const unsigned* __restrict__ orderA, double r2, double kld_max, double cd2,
+                                                     unsigned long long* __restrict__ best_a, int* __restrict__ best_b, unsigned long long* __restrict__ n_gated) {
+    const FuseGrid g = *G;
+    unsigned gated = 0;
+    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < nb; t += (int64_t)gridDim.x * blockDim.x) {
+        const unsigned b = orderB[t];
+        int best = -1;
+        if (wB[b] > 0.0) {
+            const double bx = xyzB[3 * (int64_t)b], by = xyzB[3 * (int64_t)b + 1], bz = xyzB[3 * (int64_t)b + 2];
+            const double e0 = dcB[3 * (int64_t)b], e1 = dcB[3 * (int64_t)b + 1], e2 = dcB[3 * (int64_t)b + 2];
+            double Bc[6], Bi[6];
+            for (int k = 0; k < 6; ++k) { Bc[k] = covB[6 * (int64_t)b + k]; Bi[k] = invB[6 * (int64_t)b + k]; }
+            const int cx = fuse_cell(bx, g.ox, g.inv_c, g.gx), cy = fuse_cell(by, g.oy, g.inv_c, g.gy), cz = fuse_cell(bz, g.oz, g.inv_c, g.gz);
+            const int x0 = cx > 0 ? cx - 1 : 0, x1 = cx < g.gx - 1 ? cx + 1 : g.gx - 1;
+            const int y0 = cy > 0 ? cy - 1 : 0, y1 = cy < g.gy - 1 ? cy + 1 : g.gy - 1;
+            const int z0 = cz > 0 ? cz - 1 : 0, z1 = cz < g.gz - 1 ? cz + 1 : g.gz - 1;
+            unsigned long long mine = ~0ull;                    // (J32 bits << 32) | a
+            for (int z = z0; z <= z1; ++z)
+                for (int y = y0; y <= y1; ++y) {
+                    const int row = (z * g.gy + y) * g.gx;
+                    const int p1 = cellStart[row + x1 + 1];
+                    for (int p = cellStart[row + x0]; p < p1; ++p) {
+                        const double dx = (double)sxyz[3 * (int64_t)p] - bx, dy = (double)sxyz[3 * (int64_t)p + 1] - by, dz = (double)sxyz[3 * (int64_t)p + 2] - bz;
+                        if (!((dx * dx + dy * dy) + dz * dz <= r2)) continue;
+                        const double f0 = (double)sdc[3 * (int64_t)p] - e0, f1 = (double)sdc[3 * (int64_t)p + 1] - e1, f2 = (double)sdc[3 * (int64_t)p + 2] - e2;
+                        if (!((f0 * f0 + f1 * f1) + f2 * f2 <= cd2)) continue;
+                        double Ac[6], Ai[6];
+                        for (int k = 0; k < 6; ++k) { Ac[k] = scov[6 * (int64_t)p + k]; Ai[k] = sinv[6 * (int64_t)p + k]; }
+                        double J = 0.25 * (((sym_trace(Bi, Ac) + sym_trace(Ai, Bc)) - 6.0) + (sym_quad(Ai, dx, dy, dz) + sym_quad(Bi, dx, dy, dz)));
+                        if (J < 0.0) J = 0.0;                   // rounding only: J >= 0 in exact arithmetic
+                        if (!(J <= kld_max)) continue;
+                        const unsigned long long jb = (unsigned long long)__float_as_uint((float)J) << 32;
+                        const unsigned a = orderA[p];
+                        const unsigned long long k = jb | a;
+                        if (k < mine) mine = k;
+                        atomicMin(&best_a[a], jb | b);
+                        ++gated;
+                    }
+                }
+            if (mine != ~0ull) best = (int)(unsigned)(mine & 0xffffffffull);
+        }
+        best_b[b] = best;
+    }
+    for (int o = 32; o > 0; o >>= 1) gated += __shfl_xor(gated, o);
+    if ((threadIdx.x & 63) == 0 && gated) atomicAdd(n_gated, (unsigned long long)gated);
+}
+
+// the mutual test: a and b pair iff each is the other's best
+__global__ __launch_bounds__(256) void k_fuse_pair(int64_t na, const unsigned long long* __restrict__ best_a, const int* __restrict__ best_b,
+                                                   int* __restrict__ flagA, int* __restrict__ flagB, int* __restrict__ mate) {
+    for (int64_t a = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; a < na; a += (int64_t)gridDim.x * blockDim.x) {
+        const unsigned long long k = best_a[a];
+        int b = -1;
+        if (k != ~0ull) {
+            const unsigned c = (unsigned)(k & 0xffffffffull);
+            if (best_b[c] == (int)a) b = (int)c;
+        }
+        mate[a] = b;
+        if (b >= 0) { flagA[a] = 1; flagB[b] = 1; }
+    }
+}
+
+__global__ __launch_bounds__(256) void k_fuse_pairs_out(int64_t na, const int* __restrict__ mate, const int* __restrict__ scanA, int32_t* __restrict__ pairs) {
+    for (int64_t a = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; a < na; a += (int64_t)gridDim.x * blockDim.x)
+        if (mate[a] >= 0) { pairs[2 * (int64_t)scanA[a]] = (int32_t)a; pairs[2 * (int64_t)scanA[a] + 1] = mate[a]; }
+}
+
+// One array of the output, a lane per float of the two inputs laid end to end (consecutive lanes on consecutive addresses of a row).
+//   an unpaired row        its W words, copied as integers
+//   a paired row of A      MODE 1: the w-weighted mean of the two rows' floats (xyz, dc, sh, opacity), MODE 2 (W = 6): the moment-
+//                          matched covariance [wa (Ca + da da^T) + wb (Cb + db db^T)] / (wa + wb), d = the centre minus the fused
+//                          centre -- a sum of PSD terms -- both in float64, narrowed once; MODE 0: left for gsr_decompose_cov
+//   a paired row of B      nothing
+#define FUSE_COPY 0
+#define FUSE_MEAN 1
+#define FUSE_COV 2
+__global__ __launch_bounds__(256) void k_fuse_rows(int64_t na, int64_t nb, int W, int mode, const float* __restrict__ A, const float* __restrict__ B,
+                                                   float* __restrict__ O, const int* __restrict__ mate, const int* __restrict__ scanA,
+                                                   const int* __restrict__ flagB, const int* __restrict__ scanB, const double* __restrict__ wA,
+                                                   const double* __restrict__ wB, const float* __restrict__ xyzA, const float* __restrict__ xyzB) {
+    const int64_t total = (na + nb) * W;
+    const int64_t a_only = na - scanA[na];                       // scanA[na] = the number of pairs
+    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t i = t / W;
+        const int j = (int)(t - i * W);
+        if (i >= na) {
+            const int64_t b = i - na;
+            if (!flagB[b]) reinterpret_cast<uint32_t*>(O)[(na + b - scanB[b]) * W + j] = reinterpret_cast<const uint32_t*>(B)[b * W + j];
+            continue;
+        }
+        const int64_t b = mate[i];
+        if (b < 0) { reinterpret_cast<uint32_t*>(O)[(i - scanA[i]) * W + j] = reinterpret_cast<const uint32_t*>(A)[t]; continue; }
+        if (mode == FUSE_COPY) continue;
+        const double wa = wA[i], wb = wB[b], ws = wa + wb;
+        double v;
+        if (mode == FUSE_MEAN) v = (wa * (double)A[t] + wb * (double)B[b * W + j]) / ws;
+        else {
+            const int r = j < 3 ? 0 : j < 5 ? 1 : 2, c = j < 3 ? j : j < 5 ? j - 2 : 2;      // (xx, xy, xz, yy, yz, zz)
+            const double ar = xyzA[3 * i + r], ac = xyzA[3 * i + c], br = xyzB[3 * b + r], bc = xyzB[3 * b + c];
+            const double mr = (wa * ar + wb * br) / ws, mc = (wa * ac + wb * bc) / ws;
+            v = (wa * ((double)A[t] + (ar - mr) * (ac - mc)) + wb * ((double)B[b * W + j] + (br - mr) * (bc - mc))) / ws;
+        }
+        O[(a_only + scanA[i]) * W + j] = (float)v;
+    }
+}
+
+static bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
+    if (!a || !b || !na || !nb) return false;
+    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+    return pa < pb + nb && pb < pa + na;
+}
+
+}  // namespace gsr
+
+using namespace gsr;
+
+extern "C" int32_t gsr_model_fuse(const gsr_model_view* a, const gsr_model_view* b, int32_t K, const gsr_fuse_params* params, gsr_model_view* out,
+                                  int32_t* pairs, gsr_fuse_report* report, int32_t on_device, int32_t device, void* stream) {
+    const char* who = "gsr_model_fuse";
+    if (!a || !b || !params || !out || !report) return fail(GSR_E_INVALID, "gsr_model_fuse: NULL argument");
+    if (K != 0 && K != 3 && K != 8 && K != 15) return fail(GSR_E_INVALID, "gsr_model_fuse: K = %d (must be 0, 3, 8 or 15)", K);
+    if (!(params->max_distance > 0.0 && params->max_distance <= DBL_MAX)) return fail(GSR_E_INVALID, "gsr_model_fuse: max_distance must be positive and finite");
+    if (!(params->kld_max >= 0.0) || !(params->color_delta >= 0.0)) return fail(GSR_E_INVALID, "gsr_model_fuse: kld_max and color_delta must be >= 0");
+    const int64_t na = a->n, nb = b->n;
+    if (na < 0 || nb < 0 || na >= ((int64_t)1 << 31) || nb >= ((int64_t)1 << 31)) return fail(GSR_E_INVALID, "gsr_model_fuse: row counts must be in [0, 2^31)");
+    const bool sr_a = a->scaling && a->rot, sr_b = b->scaling && b->rot;
+    for (const gsr_model_view* v : {a, b}) {
+        if ((v->scaling != nullptr) != (v->rot != nullptr)) return fail(GSR_E_INVALID, "gsr_model_fuse: scaling and rot come together");
+        if (v->n > 0 && (!v->xyz || !v->cov6 || !v->dc || !v->opacity || (K > 0 && !v->sh))) return fail(GSR_E_INVALID, "gsr_model_fuse: NULL array in an input model");
+    }
+    // an empty model has no arrays to carry: the other one decides
+    const bool with_sr = na > 0 ? sr_a : sr_b;
+    if (na > 0 && nb > 0 && sr_a != sr_b) return fail(GSR_E_INVALID, "gsr_model_fuse: scaling / rot present in one model only");
+    const int64_t cap_rows = na + nb;
+    if (out->n < cap_rows) return fail(GSR_E_INVALID, "gsr_model_fuse: the output holds %lld rows, %lld are needed", (long long)out->n, (long long)cap_rows);
+    if (cap_rows > 0 && (!out->xyz || !out->cov6 || !out->dc || !out->opacity || (K > 0 && !out->sh) || (with_sr && (!out->scaling || !out->rot))))
+        return fail(GSR_E_INVALID, "gsr_model_fuse: NULL array in the output model");
+    const size_t F = 3 * (size_t)K;
+    const int NARR = 7;
+    const size_t width[NARR] = {3, 6, 3, F, 1, 3, 4};
+    const int modes[NARR] = {FUSE_MEAN, FUSE_COV, FUSE_MEAN, FUSE_MEAN, FUSE_MEAN, FUSE_COPY, FUSE_COPY};
+    const float* pa[NARR] = {a->xyz, a->cov6, a->dc, a->sh, a->opacity, a->scaling, a->rot};
+    const float* pb[NARR] = {b->xyz, b->cov6, b->dc, b->sh, b->opacity, b->scaling, b->rot};
+    float* po[NARR] = {out->xyz, out->cov6, out->dc, out->sh, out->opacity, out->scaling, out->rot};
+    bool used[NARR];
+    for (int k = 0; k < NARR; ++k) used[k] = k == 3 ? K > 0 : k >= 5 ? with_sr : true;
+    const size_t npair_cap = (size_t)(na < nb ? na : nb);
+    for (int i = 0; i < NARR; ++i) {
+        if (!used[i]) continue;
+        const size_t bo = (size_t)cap_rows * width[i] * 4;
+        if (ranges_overlap(po[i], bo, pairs, npair_cap * 8)) return fail(GSR_E_INVALID, "gsr_model_fuse: an output array overlaps another array of the call (the fusion is not in place)");
+        for (int j = 0; j < NARR; ++j) {
+            if (!used[j]) continue;
+            if (ranges_overlap(po[i], bo, pa[j], (size_t)na * width[j] * 4) || ranges_overlap(po[i], bo, pb[j], (size_t)nb * width[j] * 4) ||
+                (i < j && ranges_overlap(po[i], bo, po[j], (size_t)cap_rows * width[j] * 4)))
+                return fail(GSR_E_INVALID, "gsr_model_fuse: an output array overlaps another array of the call (the fusion is not in place)");
+        }
+    }
+    GSR_TRY(open_device(device, who));
+    memset(report, 0, sizeof(*report));
+    if (cap_rows == 0) { out->n = 0; return GSR_OK; }
+
+    const bool dev = on_device != 0;
+    DevBuf tmp_sort_a, tmp_sort_b, tmp_scan_a, tmp_scan_b;      // rocPRIM's temporaries: declared before the OneShot, freed after its wait
+    Event ev[5];
+    for (Event& e : ev) GSR_HIP(e.create());
+    OneShot os((hipStream_t)stream, dev, who);
+    hipStream_t st = os.st;
+    size_t workspace = 0;                                       // device bytes this call asks for beyond the caller's arrays (rocPRIM's temporaries are added at the end)
+    auto ws = [&](size_t bytes, auto** p) { workspace += bytes; return os.scratch(bytes, p); };
+    const float *da[NARR], *db[NARR];
+    float* dout[NARR];
+    for (int k = 0; k < NARR; ++k) {
+        da[k] = db[k] = nullptr; dout[k] = nullptr;
+        if (!used[k]) continue;
+        GSR_TRY(os.in(na > 0 ? pa[k] : nullptr, (size_t)na * width[k] * 4, &da[k]));
+        GSR_TRY(os.in(nb > 0 ? pb[k] : nullptr, (size_t)nb * width[k] * 4, &db[k]));
+        if (dev) dout[k] = po[k];
+        else GSR_TRY(os.scratch((size_t)cap_rows * width[k] * 4, &dout[k]));      // copied back below: n_out rows, not the capacity
+    }
+    int32_t* dpairs = nullptr;
+    if (pairs && npair_cap) { if (dev) dpairs = pairs; else GSR_TRY(os.scratch(npair_cap * 8, &dpairs)); }
+
+    const int64_t cap = na > 1024 ? na : 1024;                  // cells of the table
+    double *wA, *wB, *invA, *invB, *part, *box, *sinv;
+    float *sxyz, *sdc, *scov;
+    unsigned *keysA, *idxA, *skeysA, *orderA, *keysB, *idxB, *skeysB, *orderB;
+    int *cellStart, *best_b, *flagA, *flagB, *scanA, *scanB, *mate;
+    unsigned long long *best_a, *counters;                      // counters: invalid A, invalid B, gated pairs
+    FuseGrid* grid;
+    const size_t ua = (size_t)na, ub = (size_t)nb;
+    const int nblk = stride_grid(na);
+    GSR_TRY(ws(ua * 8 + 8, &wA)); GSR_TRY(ws(ub * 8 + 8, &wB));
+    GSR_TRY(ws(ua * 48 + 8, &invA)); GSR_TRY(ws(ub * 48 + 8, &invB));
+    GSR_TRY(ws((size_t)nblk * FUSE_MOM * 8, &part)); GSR_TRY(ws(6 * 8, &box)); GSR_TRY(ws(sizeof(FuseGrid), &grid));
+    GSR_TRY(ws(ua * 48 + 8, &sinv)); GSR_TRY(ws(ua * 12 + 8, &sxyz)); GSR_TRY(ws(ua * 12 + 8, &sdc)); GSR_TRY(ws(ua * 24 + 8, &scov));
+    GSR_TRY(ws(ua * 4 + 8, &keysA)); GSR_TRY(ws(ua * 4 + 8, &idxA)); GSR_TRY(ws(ua * 4 + 8, &skeysA)); GSR_TRY(ws(ua * 4 + 8, &orderA));
+    GSR_TRY(ws(ub * 4 + 8, &keysB)); GSR_TRY(ws(ub * 4 + 8, &idxB)); GSR_TRY(ws(ub * 4 + 8, &skeysB)); GSR_TRY(ws(ub * 4 + 8, &orderB));
+    GSR_TRY(ws(((size_t)cap + 2) * 4, &cellStart));
+    GSR_TRY(ws(ua * 8 + 8, &best_a)); GSR_TRY(ws(ub * 4 + 8, &best_b)); GSR_TRY(ws(ua * 4 + 8, &mate));
+    GSR_TRY(ws((ua + 1) * 4, &flagA)); GSR_TRY(ws((ub + 1) * 4, &flagB)); GSR_TRY(ws((ua + 1) * 4, &scanA)); GSR_TRY(ws((ub + 1) * 4, &scanB));
+    GSR_TRY(ws(3 * 8, &counters));
+    GSR_HIP(hipMemsetAsync(counters, 0, 3 * 8, st));
+    GSR_HIP(hipMemsetAsync(flagA, 0, (ua + 1) * 4, st));
+    GSR_HIP(hipMemsetAsync(flagB, 0, (ub + 1) * 4, st));
+    GSR_HIP(hipMemsetAsync(best_a, 0xff, ua * 8 + 8, st));
+
+    // ---- pre-pass and grid
+    GSR_HIP(hipEventRecord(ev[0], st));
+    hipLaunchKernelGGL(k_fuse_prep, dim3(stride_grid(na)), dim3(256), 0, st, na, da[0], da[1], da[4], wA, invA, counters);
+    hipLaunchKernelGGL(k_fuse_prep, dim3(stride_grid(nb)), dim3(256), 0, st, nb, db[0], db[1], db[4], wB, invB, counters + 1);
+    hipLaunchKernelGGL(k_fuse_moments, dim3(nblk), dim3(256), 0, st, na, da[0], wA, (const double*)nullptr, part);
+    hipLaunchKernelGGL(k_fuse_box, dim3(1), dim3(64), 0, st, nblk, part, 0, params->max_distance, cap, box, grid);
+    hipLaunchKernelGGL(k_fuse_moments, dim3(nblk), dim3(256), 0, st, na, da[0], wA, (const double*)box, part);
+    hipLaunchKernelGGL(k_fuse_box, dim3(1), dim3(64), 0, st, nblk, part, 1, params->max_distance, cap, box, grid);
+    hipLaunchKernelGGL(k_fuse_keys, dim3(stride_grid(na)), dim3(256), 0, st, na, da[0], grid, keysA, idxA);
+    hipLaunchKernelGGL(k_fuse_keys, dim3(stride_grid(nb)), dim3(256), 0, st, nb, db[0], grid, keysB, idxB);
+    unsigned bits = 1;
+    while (bits < 32 && ((int64_t)1 << bits) < cap) ++bits;
+    if (na > 0) GSR_TRY(sort_pairs_by_key<rocprim::default_config>(tmp_sort_a, st, (const unsigned*)keysA, skeysA, (const unsigned*)idxA, orderA, ua, 0u, bits));
+    if (nb > 0) GSR_TRY(sort_pairs_by_key<rocprim::default_config>(tmp_sort_b, st, (const unsigned*)keysB, skeysB, (const unsigned*)idxB, orderB, ub, 0u, bits));
+    hipLaunchKernelGGL(k_fuse_cell_starts, dim3(stride_grid(cap + 1)), dim3(256), 0, st, na, skeysA, cap, cellStart);
+    hipLaunchKernelGGL(k_fuse_gather_a, dim3(stride_grid(na)), dim3(256), 0, st, na, orderA, da[0], da[2], da[1], wA, invA, sxyz, sdc, scov, sinv);
+    // ---- search
+    GSR_HIP(hipEventRecord(ev[1], st));
+    const double r2 = params->max_distance * params->max_distance, cd2 = params->color_delta * params->color_delta;
+    hipLaunchKernelGGL(k_fuse_search, dim3(stride_grid(nb)), dim3(256), 0, st, nb, orderB, db[0], db[2], db[1], wB, invB, grid, cellStart, sxyz, sdc, scov, sinv,
+                       orderA, r2, params->kld_max, cd2, best_a, best_b, counters + 2);
+    // ---- pairs and scans
+    GSR_HIP(hipEventRecord(ev[2], st));
+    hipLaunchKernelGGL(k_fuse_pair, dim3(stride_grid(na)), dim3(256), 0, st, na, best_a, best_b, flagA, flagB, mate);
+    GSR_TRY(scan_exclusive<rocprim::default_config>(tmp_scan_a, st, (const int*)flagA, scanA, ua + 1));
+    GSR_TRY(scan_exclusive<rocprim::default_config>(tmp_scan_b, st, (const int*)flagB, scanB, ub + 1));
+    if (dpairs) hipLaunchKernelGGL(k_fuse_pairs_out, dim3(stride_grid(na)), dim3(256), 0, st, na, mate, scanA, dpairs);
+    // ---- writer
+    GSR_HIP(hipEventRecord(ev[3], st));
+    for (int k = 0; k < NARR; ++k)
+        if (used[k])
+            hipLaunchKernelGGL(k_fuse_rows, dim3(stride_grid(cap_rows * (int64_t)width[k])), dim3(256), 0, st, na, nb, (int)width[k], modes[k], da[k], db[k], dout[k],
+                               mate, scanA, flagB, scanB, wA, wB, da[0], db[0]);
+    GSR_HIP(hipEventRecord(ev[4], st));
+    // ---- the one read-back: the counts
+    unsigned long long hc[3] = {0, 0, 0};
+    int hp = 0;
+    GSR_HIP(hipMemcpyAsync(hc, counters, sizeof(hc), hipMemcpyDeviceToHost, st));
+    GSR_HIP(hipMemcpyAsync(&hp, scanA + na, 4, hipMemcpyDeviceToHost, st));
+    GSR_TRY(os.wait());
+    const int64_t np = hp, n_out = cap_rows - np;
+    report->n_pairs = np; report->n_out = n_out; report->n_a_only = na - np; report->n_b_only = nb - np;
+    report->n_invalid_a = (int64_t)hc[0]; report->n_invalid_b = (int64_t)hc[1];
+    for (int k = 0; k < 4; ++k) (void)hipEventElapsedTime(&report->phase_ms[k], ev[k], ev[k + 1]);
+    report->gated_pairs = (int64_t)hc[2];
+    report->workspace_bytes = (int64_t)(workspace + tmp_sort_a.cap + tmp_sort_b.cap + tmp_scan_a.cap + tmp_scan_b.cap);
+    if (with_sr && np > 0) {
+        const int64_t off = na - np;
+        GSR_TRY(gsr_decompose_cov(dout[1] + 6 * off, np, GSR_DECOMP_EXACT, dout[5] + 3 * off, dout[6] + 4 * off, nullptr, 1, device, stream));
+    }
+    if (!dev) {
+        for (int k = 0; k < NARR; ++k)
+            if (used[k] && n_out > 0) GSR_HIP(hipMemcpyAsync(po[k], dout[k], (size_t)n_out * width[k] * 4, hipMemcpyDeviceToHost, st));
+        if (dpairs && np > 0) GSR_HIP(hipMemcpyAsync(pairs, dpairs, (size_t)np * 8, hipMemcpyDeviceToHost, st));
+    }
+    out->n = n_out;
+    return os.finish();
+}

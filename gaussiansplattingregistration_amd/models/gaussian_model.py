@@ -294,14 +294,89 @@ class GaussianModel:
             setattr(self, name, t)
         return self
 
+    _FUSE_ARRAYS = (("_xyz", 3), ("_covariance", 6), ("_features_dc", 3), ("_features_rest", None), ("_opacity", 1), ("_scaling", 3), ("_rotation", 4))
+
     @staticmethod
-    def get_merged_gaussian_point_clouds(gaussian1, gaussian2, transformation_matrix, rotate_sh=False, with_scaling=False):
+    def fuse_overlap(gaussian1, gaussian2, params):
+        """Overlap-aware merge of two models that are ALREADY IN ONE FRAME (``gsr_model_fuse``, ``csrc/fuse.hip``): a splat of
+        ``gaussian1`` and a splat of ``gaussian2`` that are each other's best match under the gates of ``params``
+        (``FuseOverlapParams``) are replaced by their moment-matched union; every other row is kept bit for bit.  Returns
+        ``(model, info)``: the rows of ``gaussian1`` not in a pair, the fused rows, the rows of ``gaussian2`` not in a pair;
+        ``info`` holds the report (``n_out``, ``n_pairs``, ``n_a_only``, ``n_b_only``, ``n_invalid_a``, ``n_invalid_b``) and
+        ``pairs`` ((n_pairs, 2) int32: row of ``gaussian1``, row of ``gaussian2``), ``gated_pairs`` (the (a, b) that passed all gates),
+        ``workspace_bytes`` (device memory the call allocated) and ``phase_ms`` (device events).  The result tensors are views ``[:n_out]`` of
+        arrays allocated for ``n1 + n2`` rows.  Host tensors are staged by the library; no GPU: ``RuntimeError``."""
+        import ctypes as C
+        assert gaussian1.sh_degree == gaussian2.sh_degree
+        L = _lib.load(require_device=True)
+        n1, n2 = len(gaussian1), len(gaussian2)
+        K = int(gaussian1._features_rest.shape[1]) if gaussian1._features_rest.dim() == 3 else 0
+        K2 = int(gaussian2._features_rest.shape[1]) if gaussian2._features_rest.dim() == 3 else 0
+        if K != K2:
+            raise RuntimeError("the two models carry different numbers of SH coefficients")
+        on = bool(gaussian1._xyz.is_cuda)
+        if bool(gaussian2._xyz.is_cuda) != on or (on and gaussian1._xyz.device != gaussian2._xyz.device):
+            raise RuntimeError("the two models must live on one device")
+        device = gaussian1._xyz.device.index if on else 0
+        have = [g._scaling.numel() > 0 and g._rotation.numel() > 0 for g in (gaussian1, gaussian2)]
+        if have[0] != have[1] and n1 > 0 and n2 > 0:
+            raise RuntimeError("_scaling / _rotation: one model carries them, the other does not")
+        with_sr = have[0] if n1 > 0 else have[1]
+        views, keep, outs = [_lib.ModelView(), _lib.ModelView(), _lib.ModelView()], [], {}
+        views[0].n, views[1].n, views[2].n = n1, n2, n1 + n2
+        field = {"_xyz": "xyz", "_covariance": "cov6", "_features_dc": "dc", "_features_rest": "sh", "_opacity": "opacity", "_scaling": "scaling",
+                 "_rotation": "rot"}
+        for name, width in GaussianModel._FUSE_ARRAYS:
+            width = 3 * K if width is None else width
+            if width == 0 or (name in ("_scaling", "_rotation") and not with_sr):
+                continue
+            for v, g, n in ((views[0], gaussian1, n1), (views[1], gaussian2, n2)):
+                if n == 0:
+                    continue
+                p, k, t_on = _m.prep(getattr(g, name), (n, width), np.float32, device)
+                if t_on != on:
+                    raise RuntimeError("the model's tensors must all live on one device")
+                keep.append(k)
+                setattr(v, field[name], p)
+            outs[name], p = _m.out((n1 + n2, width), np.float32, device, on)
+            setattr(views[2], field[name], p)
+        pairs, ppairs = _m.out((min(n1, n2), 2), np.int32, device, on)
+        P = _lib.FuseParams(float(params.max_distance), float(params.kld_max), float(params.color_delta))
+        R = _lib.FuseReport()
+        if on:
+            torch.cuda.current_stream(device).synchronize()
+        _lib.check(L.gsr_model_fuse(C.addressof(views[0]), C.addressof(views[1]), K, C.addressof(P), C.addressof(views[2]), ppairs, C.addressof(R),
+                                    1 if on else 0, device, C.c_void_p(_m.stream_ptr(device, on))), "gsr_model_fuse")
+        n_out = int(R.n_out)
+        m = GaussianModel(gaussian2.device_name)
+        m.sh_degree = gaussian1.sh_degree
+        shapes = {"_features_dc": (1, 3), "_features_rest": (K, 3)}
+        for name, _ in GaussianModel._FUSE_ARRAYS:
+            if name in outs:
+                t = torch.as_tensor(outs[name])[:n_out]
+                setattr(m, name, t.view((n_out,) + shapes[name]) if name in shapes else t)
+            elif name == "_features_rest":
+                setattr(m, name, torch.empty((n_out, 0, 3), dtype=torch.float32, device=m._xyz.device))
+        info = {k: int(getattr(R, k)) for k in ("n_out", "n_pairs", "n_a_only", "n_b_only", "n_invalid_a", "n_invalid_b")}
+        info["pairs"] = torch.as_tensor(pairs)[:info["n_pairs"]]
+        info["gated_pairs"], info["workspace_bytes"] = int(R.gated_pairs), int(R.workspace_bytes)
+        info["phase_ms"] = dict(zip(("prepass_grid", "search", "pair_scan", "write"), (float(x) for x in R.phase_ms)))      # device events of the call
+        return m, info
+
+    @staticmethod
+    def get_merged_gaussian_point_clouds(gaussian1, gaussian2, transformation_matrix, rotate_sh=False, with_scaling=False, fuse=None):
         """``gaussian1`` moved by the registration result, concatenated with ``gaussian2`` (the merged-cloud save).
         ``with_scaling``: the matrix is a similarity (``similarity_transform_gaussian_model``); ``_scaling`` moves too.
         ``rotate_sh``: turn the SH coefficients of ``gaussian1`` with it (``transform_gaussian_model``).  When both models
         live on one CUDA device the merged arrays are allocated once, the kernel writes the moved ``gaussian1`` straight into
-        their first rows and ``gaussian2`` is copied behind it: no clone, no ``cat``.  ``gaussian1`` is left as it was."""
+        their first rows and ``gaussian2`` is copied behind it: no clone, no ``cat``.  ``gaussian1`` is left as it was.
+        ``fuse`` (``FuseOverlapParams``; default ``None``: the plain concatenation above): move, then ``fuse_overlap`` -- the splats
+        the two models share are stored once.  Refused (``RuntimeError``) when the model has SH coefficients, the matrix rotates
+        and ``rotate_sh`` is false."""
         assert gaussian1.sh_degree == gaussian2.sh_degree
+        if fuse is not None:
+            return GaussianModel.get_fused_gaussian_point_clouds(gaussian1, gaussian2, transformation_matrix, fuse, rotate_sh=rotate_sh,
+                                                                 with_scaling=with_scaling)[0]
         names = ("_xyz", "_rotation", "_scaling", "_features_dc", "_features_rest", "_opacity", "_covariance")
         moves = transformation_matrix is not None and not np.array_equal(np.asarray(transformation_matrix), np.eye(4))
         x1, x2 = gaussian1._xyz, gaussian2._xyz
@@ -341,6 +416,32 @@ class GaussianModel:
         for name in names:
             setattr(m, name, torch.cat((getattr(g1, name).to(gaussian2.device_name), getattr(gaussian2, name))))
         return m
+
+    @staticmethod
+    def get_fused_gaussian_point_clouds(gaussian1, gaussian2, transformation_matrix, fuse, rotate_sh=False, with_scaling=False):
+        """``gaussian1`` moved by the matrix, then ``fuse_overlap`` with ``gaussian2`` -> ``(model, info)``: what
+        ``get_merged_gaussian_point_clouds(..., fuse=params)`` returns the model of, with the report.  As in the plain merge,
+        ``gaussian1`` is left as it was and may live on another device than ``gaussian2``: its moved copy goes to ``gaussian2``'s."""
+        g1 = gaussian1
+        moves = transformation_matrix is not None and not np.array_equal(np.asarray(transformation_matrix), np.eye(4))
+        if moves:
+            T = np.asarray(transformation_matrix, dtype=np.float64).reshape(4, 4)
+            A = T[:3, :3]
+            rotates = not (np.count_nonzero(A - np.diag(np.diag(A))) == 0 and A[0, 0] == A[1, 1] == A[2, 2] and A[0, 0] > 0)
+            K = int(gaussian1._features_rest.shape[1]) if gaussian1._features_rest.dim() == 3 else 0
+            if K > 0 and rotates and not rotate_sh:
+                raise RuntimeError("fuse needs rotate_sh=True when the matrix rotates a model with SH coefficients: an average of SH rows "
+                                   "in two frames means nothing")
+            g1 = gaussian1.clone_gaussian()
+            if with_scaling:
+                g1.similarity_transform_gaussian_model(T, rotate_sh=rotate_sh)
+            else:
+                g1.transform_gaussian_model(T, rotate_sh=rotate_sh)
+        if g1._xyz.device != gaussian2._xyz.device:
+            if g1 is gaussian1:
+                g1 = gaussian1.clone_gaussian()
+            g1.move_to_device(str(gaussian2._xyz.device))
+        return GaussianModel.fuse_overlap(g1, gaussian2, fuse)
 
     def clone_gaussian(self):
         m = GaussianModel(self.device_name)

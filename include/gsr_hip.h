@@ -656,6 +656,56 @@ int32_t gsr_fgr_tuple_test(const float* src_xyz, int64_t ns, const float* tgt_xy
 int32_t gsr_fgr_optimize(const float* src_xyz, int64_t ns, const float* tgt_xyz, int64_t nt, const int32_t* corres, int64_t m,
                          const gsr_fgr_options* options, gsr_fgr_result* result, int32_t on_device, int32_t device, void* stream);
 
+/* ------------------------------------------------------------------- overlap-aware merge */
+
+/* Fuse two splat models that are ALREADY IN ONE FRAME (move one first: gsr_model_transform / gsr_model_similarity): a splat of A
+ * and a splat of B that are each other's best match are replaced by their moment-matched union, everything else is kept bit for
+ * bit.  csrc/fuse.hip; restated in float64 NumPy in tests/fuse_model.py.  Every quantity is computed in
+ * float64 from the float32 inputs and every comparison is written so that NaN fails it.
+ *   valid      all of xyz, cov6, opacity finite, det C > 0 (cofactor expansion along the first row) and
+ *              w = sigmoid(opacity) sqrt(det C) finite and > 0.  Invalid splats never pair.
+ *   candidate  both valid, |ma - mb|^2 <= max_distance^2, |dc_a - dc_b|_2 <= color_delta (inf: no colour gate), J <= kld_max with
+ *              J = 1/4 [tr(Cb^-1 Ca) + tr(Ca^-1 Cb) - 6 + d^T (Ca^-1 + Cb^-1) d], d = ma - mb (a negative J, which only rounding
+ *              can give, counts as 0).
+ *   best       J32 = float32(J); best_b[b] = the candidate a with the smallest (J32, a), best_a[a] the candidate b with the smallest
+ *              (J32, b): ties go to the lowest index.  (a, b) is a PAIR iff best_b[b] = a and best_a[a] = b.
+ *   fusion     W = wa + wb;  m = (wa ma + wb mb) / W;  C = [wa (Ca + (ma - m)(ma - m)^T) + wb (Cb + (mb - m)(mb - m)^T)] / W;
+ *              dc, every sh coefficient and the RAW opacity: the w-weighted mean; narrowed to float32 once.  With scaling / rot the
+ *              fused row gets the GSR_DECOMP_EXACT decomposition of its (float32) fused covariance.
+ *   output     rows of A not in a pair (ascending a, bit for bit), fused rows (ascending a), rows of B not in a pair (ascending b,
+ *              bit for bit): n_out = na + nb - n_pairs.
+ * A view: n rows; xyz[n*3], cov6[n*6] (xx,xy,xz,yy,yz,zz), dc[n*3], sh[n*3K] coefficient-major (ignored when K = 0), opacity[n] RAW,
+ * scaling[n*3] (log) and rot[n*4] (w,x,y,z): both or neither, and in both input models or in neither; float32.  `out`: the caller's
+ * buffers, out->n = their capacity in rows (>= a->n + b->n) on entry and n_out on return; rows behind n_out are not defined.
+ * pairs: int32 (min(na, nb), 2) receiving (a, b) in ascending a, or NULL.  All arrays on the host or all on the device as on_device
+ * says; the structs themselves on the host.  NOT in place: an output that overlaps another array of the call is GSR_E_INVALID, as
+ * are K outside {0, 3, 8, 15}, max_distance <= 0 or not finite, a negative (or NaN) gate, scaling / rot on one side only, a row count
+ * >= 2^31 and NULL required arrays.  na = 0 or nb = 0 is valid: the output is the other model.  One wait for the stream in the middle
+ * (the counts), one at the end.  Deterministic: the same inputs give the same bits. */
+typedef struct gsr_model_view {
+    int64_t n;
+    float* xyz;
+    float* cov6;
+    float* dc;
+    float* sh;
+    float* opacity;
+    float* scaling;
+    float* rot;
+} gsr_model_view;
+typedef struct gsr_fuse_params {
+    double max_distance;       /* r > 0 */
+    double kld_max;            /* >= 0 */
+    double color_delta;        /* >= 0; inf disables the colour gate */
+} gsr_fuse_params;
+typedef struct gsr_fuse_report {
+    int64_t n_out, n_pairs, n_a_only, n_b_only, n_invalid_a, n_invalid_b;
+    int64_t gated_pairs;       /* the (a, b) that passed all three gates */
+    int64_t workspace_bytes;   /* device memory the call allocated beyond the caller's arrays (host callers: the staged copies too) */
+    float phase_ms[4];         /* pre-pass + grid, search, pairs + scans, writer: hipEvents on the call's stream */
+} gsr_fuse_report;
+int32_t gsr_model_fuse(const gsr_model_view* a, const gsr_model_view* b, int32_t K, const gsr_fuse_params* params, gsr_model_view* out,
+                       int32_t* pairs, gsr_fuse_report* report, int32_t on_device, int32_t device, void* stream);
+
 /* ------------------------------------------------------------------- splat rasteriser and image metrics (evaluation) */
 
 /* Forward tile rasteriser of a splat model for one pinhole camera: what the reference's Evaluation tab asks of gsplat's

@@ -1,7 +1,8 @@
 """Image-based evaluation of a registration result, headless: the reference's Evaluation tab without the GUI.
 
     python scripts/evaluate_registration.py a.ply b.ply --transform T.txt --cameras cameras.json --images DIR --log out.json
-                                            [--rotate-sh] [--with-scaling] [--save-renders DIR] [--background R G B] [--cpu-metrics]
+                                            [--rotate-sh] [--with-scaling] [--fuse-overlap MAX_DIST [--fuse-kld X] [--fuse-color X]]
+                                            [--save-renders DIR] [--background R G B] [--cpu-metrics]
 
 ``a.ply`` is moved by the 4x4 in ``T.txt`` (whitespace-separated, row-major) and merged with ``b.ply``; the merged model is rendered
 from every camera of ``cameras.json`` (the file a 3DGS training run writes) and compared with ``DIR/<img_name>.png``.  The log has the
@@ -31,6 +32,10 @@ def main():
     ap.add_argument("--rotate-sh", action="store_true", help="turn the SH coefficients of the first cloud with it")
     ap.add_argument("--with-scaling", action="store_true", help="the transform is a similarity [c R | t] (register_ply.py --with-scaling): the first "
                     "cloud's sizes and log-scales move with it")
+    ap.add_argument("--fuse-overlap", type=float, metavar="MAX_DIST", help="fuse the splats the two clouds share before rendering (fuse_overlap: mutual "
+                    "best matches within this distance); implies --rotate-sh")
+    ap.add_argument("--fuse-kld", type=float, default=0.5, help="largest symmetrised KL divergence of a fused pair")
+    ap.add_argument("--fuse-color", type=float, default=float("inf"), help="largest L2 distance of the DC colours of a fused pair")
     ap.add_argument("--save-renders", metavar="DIR", help="write every render as DIR/<img_name>.png")
     ap.add_argument("--background", type=float, nargs=3, default=(0.0, 0.0, 0.0))
     ap.add_argument("--cpu-metrics", action="store_true", help="use_gpu=False: the metrics in host torch arithmetic")
@@ -41,7 +46,10 @@ def main():
     from gaussiansplattingregistration_amd.models.camera import load_cameras
     from gaussiansplattingregistration_amd.models.data_repository import DataRepository, UIStateRepository
     from gaussiansplattingregistration_amd.models.gaussian_model import GaussianModel
+    from gaussiansplattingregistration_amd.params import FuseOverlapParams
     from gaussiansplattingregistration_amd.workers.evaluator import RegistrationEvaluator
+    fuse = FuseOverlapParams(a.fuse_overlap, a.fuse_kld, a.fuse_color) if a.fuse_overlap is not None else None
+    a.rotate_sh = a.rotate_sh or fuse is not None
     repo, ui = DataRepository(), UIStateRepository()
     repo.pc_gaussian_list_first.append(GaussianModel("cuda:0").from_ply(a.first))
     repo.pc_gaussian_list_second.append(GaussianModel("cuda:0").from_ply(a.second))
@@ -56,12 +64,12 @@ def main():
             img = render[0].clamp(0, 1).mul(255).add(0.5).floor().to("cpu").numpy().astype(np.uint8)
             Image.fromarray(img).save(os.path.join(a.save_renders, camera.image_name + ".png"))
         worker = RegistrationEvaluator(repo.pc_gaussian_list_first[0], repo.pc_gaussian_list_second[0], ui.transformation_matrix, cameras, a.images, a.log,
-                                       tuple(a.background), None, not a.cpu_metrics, rotate_sh=a.rotate_sh, with_scaling=a.with_scaling)
+                                       tuple(a.background), None, not a.cpu_metrics, rotate_sh=a.rotate_sh, with_scaling=a.with_scaling, fuse=fuse)
         worker.on_render = keep
         result = worker.run()
     else:
         result = RegistrationController(repo, ui).evaluate_registration(cameras, a.images, a.log, tuple(a.background), not a.cpu_metrics, rotate_sh=a.rotate_sh,
-                                                                        with_scaling=a.with_scaling)
+                                                                        with_scaling=a.with_scaling, fuse=fuse)
     print(json.dumps({"cameras": len(cameras), "mse": result.mse, "rmse": result.rmse, "psnr": result.psnr, "ssim": result.ssim, "lpips": result.lpips,
                       "errors": len(result.error_list), "log": a.log}))
 
