@@ -103,6 +103,7 @@ SIGNATURES = {
     "gsr_icp_register": (_i32, [_vp, _vp, _i32, _i32, _f64, _f64, _f64, _i32, _vp, C.POINTER(_f64), C.POINTER(_f64),
                                 C.POINTER(_i32)]),
     "gsr_icp_correspondences": (_i32, [_vp, _vp, _vp, _vp]),
+    "gsr_icp_information": (_i32, [_vp, _vp, _vp, C.POINTER(_i64)]),
     "gsr_icp_get_timing": (_i32, [_vp, C.POINTER(_f32)]),
     "gsr_normals_from_cov": (_i32, [_vp, _i64, _vp, _i32, _i32, _vp]),
     "gsr_normals_knn": (_i32, [_vp, _i64, _i32, _vp, _i32, _i32, _vp]),
@@ -123,6 +124,7 @@ SIGNATURES = {
     "gsr_ransac_correspondence": (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _i32, _i32, _vp]),
     "gsr_fgr_tuple_test": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, C.POINTER(_i64), C.POINTER(_i64), _i32, _i32, _vp]),
     "gsr_fgr_optimize": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i32, _i32, _vp]),
+    "gsr_posegraph_optimize": (_i32, [_i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "gsr_raster_create": (_i32, [C.POINTER(_vp), _i32, _vp]),
     "gsr_raster_destroy": (_i32, [_vp]),
     "gsr_raster_render": (_i32, [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, C.POINTER(_f32), _f32, _f32, _f32, _f32, _i32, _i32, C.POINTER(_f32), _f32,
@@ -201,6 +203,26 @@ class FuseReport(C.Structure):
     """gsr_fuse_report (include/gsr_hip.h)."""
     _fields_ = [("n_out", C.c_int64), ("n_pairs", C.c_int64), ("n_a_only", C.c_int64), ("n_b_only", C.c_int64), ("n_invalid_a", C.c_int64),
                 ("n_invalid_b", C.c_int64), ("gated_pairs", C.c_int64), ("workspace_bytes", C.c_int64), ("phase_ms", C.c_float * 4)]
+
+
+class PoseEdge(C.Structure):
+    """gsr_pose_edge (include/gsr_hip.h)."""
+    _fields_ = [("source", C.c_int32), ("target", C.c_int32), ("uncertain", C.c_int32), ("reserved", C.c_int32), ("T", C.c_double * 16),
+                ("information", C.c_double * 36)]
+
+
+class PoseGraphOption(C.Structure):
+    """gsr_posegraph_option (include/gsr_hip.h)."""
+    _fields_ = [("max_correspondence_distance", C.c_double), ("edge_prune_threshold", C.c_double), ("preference_loop_closure", C.c_double),
+                ("reference_node", C.c_int32), ("max_iteration", C.c_int32), ("max_iteration_lm", C.c_int32), ("reserved", C.c_int32),
+                ("min_relative_increment", C.c_double), ("min_relative_residual_increment", C.c_double), ("min_right_term", C.c_double),
+                ("min_residual", C.c_double)]
+
+
+class PoseGraphResult(C.Structure):
+    """gsr_posegraph_result (include/gsr_hip.h)."""
+    _fields_ = [("iterations", C.c_int32 * 2), ("n_pruned", C.c_int32), ("reserved", C.c_int32), ("E_initial", C.c_double), ("E_final", C.c_double),
+                ("mu", C.c_double), ("mu_first", C.c_double)]
 
 
 GSR_CHECK_EDGE_LENGTH = 0

@@ -64,6 +64,22 @@ class RegistrationController:
             self.handle_registration_result_local(result)
         return result
 
+    def execute_multiway_registration(self, clouds, params, edges="sequential", init=None, option=None, criteria=None):
+        """N clouds into one frame (``workers/multiway.py``): pairwise ICP per edge, information matrices, pose-graph optimisation.
+        The repository holds two clouds, so the N ``PointCloud`` records are arguments.  Returns the worker's ``ResultData`` (poses,
+        graph, per-edge report) or ``None`` with ``self.errors`` set; the pairwise ``transformation_matrix`` is left alone."""
+        from ..workers.multiway import MultiwayRegistrator
+        worker = MultiwayRegistrator(clouds, params, edges=edges, init=init, option=option, criteria=criteria)
+        result = worker.run()
+        self.errors = worker.errors
+        return result
+
+    @staticmethod
+    def merge_multiway(models, poses, rotate_sh=False):
+        """The N ``GaussianModel`` s moved by their poses into one model (``GaussianModel.get_merged_gaussian_point_clouds_multi``)."""
+        from ..models.gaussian_model import GaussianModel
+        return GaussianModel.get_merged_gaussian_point_clouds_multi(models, poses, rotate_sh=rotate_sh)
+
     def evaluate_registration(self, cameras_list, images_path, log_path, color, use_gpu, registration_result=None, rotate_sh=False, with_scaling=False,
                               fuse=None):
         """``with_scaling``: the current transform is a similarity (a registration with scaling); the merge before rendering applies it as one.

@@ -807,6 +807,41 @@ __global__ __launch_bounds__(256) void k_icp_accumulate(int64_t ns, const float*
     block_reduce_store<NACC>(acc, partials);
 }
 
+// Information matrix of a registered pair (gsr_icp_information): Lambda = sum G^T G over the correspondences, G = [-[q]x | I3] at the
+// matched TARGET point q, depends on them only through n, sum q and sum q q^T -- ten float64 sums per lane (the 6x6 is put together on
+// the host).  A kernel of its own, not a KIND of k_icp_accumulate: that template's instantiations keep their registers.  Same search as
+// an evaluation (fused icp_nearest, or nn_j from k_icp_nn), same grid, same fold: bit-reproducible, no atomics.
+#define ICP_INFO_NACC 10
+__global__ __launch_bounds__(256) void k_icp_information(int64_t ns, const float* __restrict__ src, Xform T, IcpGrid g,
+                                                         const int* __restrict__ cellStart, const int* __restrict__ nn_j,
+                                                         const float4* __restrict__ Tq, double max_corr2, double* __restrict__ partials) {
+    double acc[ICP_INFO_NACC];
+#pragma unroll
+    for (int k = 0; k < ICP_INFO_NACC; ++k) acc[k] = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < ns; i += (int64_t)gridDim.x * blockDim.x) {
+        int j;
+        if (nn_j) {
+            j = nn_j[i];
+            if (j < 0) continue;
+        } else {
+            const double x = (double)src[3 * i], y = (double)src[3 * i + 1], z = (double)src[3 * i + 2];
+            const double px = T.m[0] * x + T.m[1] * y + T.m[2] * z + T.m[3];
+            const double py = T.m[4] * x + T.m[5] * y + T.m[6] * z + T.m[7];
+            const double pz = T.m[8] * x + T.m[9] * y + T.m[10] * z + T.m[11];
+            double dd;
+            j = icp_nearest<0>(g, cellStart, Tq, px, py, pz, dd, max_corr2);
+            if (j < 0 || !(dd < max_corr2)) continue;
+        }
+        const float4 q = Tq[j];
+        const double qx = (double)q.x, qy = (double)q.y, qz = (double)q.z;
+        acc[0] += 1.0;
+        acc[1] += qx; acc[2] += qy; acc[3] += qz;
+        acc[4] += qx * qx; acc[5] += qx * qy; acc[6] += qx * qz;
+        acc[7] += qy * qy; acc[8] += qy * qz; acc[9] += qz * qz;
+    }
+    block_reduce_store<ICP_INFO_NACC>(acc, partials);
+}
+
 // One wavefront per accumulator: lane l sums the partials of blocks l, l+64, ... in order, then a fixed
 // shuffle tree combines the 64 lane sums -- a deterministic order whatever the launch.
 __global__ __launch_bounds__(64) void k_icp_finalize(int nblocks, const double* __restrict__ partials, double* __restrict__ out) {
@@ -1760,6 +1795,51 @@ int32_t gsr_icp_correspondences(gsr_icp_ctx* c, const double* T, int64_t* idx, d
     GSR_HIP(hipMemcpyAsync(idx, c->corr_idx.p, (size_t)c->ns * 8, hipMemcpyDeviceToHost, c->stream));
     GSR_HIP(hipMemcpyAsync(d2, c->corr_d2.p, (size_t)c->ns * 8, hipMemcpyDeviceToHost, c->stream));
     GSR_HIP(hipStreamSynchronize(c->stream));
+    return GSR_OK;
+}
+
+int32_t gsr_icp_information(gsr_icp_ctx* c, const double* T, double* info36, int64_t* n_corr) {
+    if (!c || !T || !info36) return fail(GSR_E_INVALID, "gsr_icp_information: NULL argument");
+    if (!c->have_target || !c->have_source) return fail(GSR_E_INVALID, "gsr_icp_information: target and source must be set first");
+    if (c->comm || c->allreduce || c->allreduce_dev)
+        return fail(GSR_E_INVALID, "gsr_icp_information: one process, one GPU -- this context has a communicator or an all-reduce callback installed "
+                                   "(the sums of a source shard are not the pair's information matrix)");
+    for (int i = 0; i < 16; ++i)
+        if (!(fabs(T[i]) <= DBL_MAX)) return fail(GSR_E_INVALID, "gsr_icp_information: T[%d] is not finite", i);
+    GSR_HIP(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    Xform X;
+    for (int i = 0; i < 12; ++i) X.m[i] = T[i];
+    const int nb = icp_blocks(c->ns, c->nblocks);
+    GSR_TRY(c->partials.reserve((size_t)nb * GSR_ICP_ACC_LEN * 8));
+    GSR_TRY(c->acc_dev.reserve(GSR_ICP_ACC_LEN * 8));
+    GSR_HIP(hipMemsetAsync(c->partials.p, 0, (size_t)nb * GSR_ICP_ACC_LEN * 8, st));
+    const double mc2 = c->max_corr * c->max_corr;
+    const int* nnj = nullptr;
+    if (c->nn_mode()) {                             // the search an evaluation of this context would take (run_accumulate)
+        GSR_TRY(c->nn_j.reserve((size_t)c->ns * 4));
+        launch_icp_nn<false>(c, st, X, (const IcpState*)nullptr, mc2, false);
+        nnj = c->nn_j.as<int>();
+    }
+    hipLaunchKernelGGL(k_icp_information, dim3(nb), dim3(256), 0, st, c->ns, c->src.as<float>(), X, c->grid, c->cellStart.as<int>(), nnj, c->Tq.as<float4>(),
+                       mc2, c->partials.as<double>());
+    hipLaunchKernelGGL(k_icp_finalize, dim3(ICP_INFO_NACC), dim3(64), 0, st, nb, c->partials.as<double>(), c->acc_dev.as<double>());
+    double a[ICP_INFO_NACC];
+    GSR_HIP(hipMemcpyAsync(a, c->acc_dev.p, sizeof(a), hipMemcpyDeviceToHost, st));
+    GSR_HIP(hipStreamSynchronize(st));
+    // Lambda = [[tr(S) I - S, [m]x], [[m]x^T, n I]]  with  n = a[0], m = sum q = a[1..3], S = sum q q^T = a[4..9] (xx xy xz yy yz zz)
+    const double n = a[0], mx = a[1], my = a[2], mz = a[3];
+    const double nxy = 0.0 - a[5], nxz = 0.0 - a[6], nyz = 0.0 - a[8];                 // 0.0 - x: no negative zeros in an empty matrix
+    const double A[3][3] = {{a[7] + a[9], nxy, nxz}, {nxy, a[4] + a[9], nyz}, {nxz, nyz, a[4] + a[7]}};      // tr(S) I - S
+    const double Mx[3][3] = {{0.0, 0.0 - mz, my}, {mz, 0.0, 0.0 - mx}, {0.0 - my, mx, 0.0}};
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) {
+            info36[6 * i + j] = A[i][j];
+            info36[6 * i + 3 + j] = Mx[i][j];
+            info36[6 * (3 + i) + j] = Mx[j][i];
+            info36[6 * (3 + i) + 3 + j] = i == j ? n : 0.0;
+        }
+    if (n_corr) *n_corr = (int64_t)n;
     return GSR_OK;
 }
 

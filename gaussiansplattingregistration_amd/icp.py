@@ -291,6 +291,16 @@ class IcpContext:
         _lib.check(self._L.gsr_icp_correspondences(self._h, T.ctypes.data, idx.ctypes.data, d2.ctypes.data), "gsr_icp_correspondences")
         return idx, d2
 
+    def information(self, T):
+        """Information matrix (6, 6) float64 of the pair at transform ``T`` and the number of correspondences
+        (``gsr_icp_information``): ``sum G^T G`` with ``G = [-[q]x | I]`` at the matched target points, at the context's
+        ``max_corr``.  Open3D's ``get_information_matrix_from_point_clouds``; no correspondence gives the zero matrix and 0."""
+        T = np.ascontiguousarray(T, dtype=np.float64).reshape(4, 4)
+        info = np.zeros((6, 6), np.float64)
+        n = C.c_int64(0)
+        _lib.check(self._L.gsr_icp_information(self._h, T.ctypes.data, info.ctypes.data, C.byref(n)), "gsr_icp_information")
+        return info, int(n.value)
+
     def timing(self):
         t = (C.c_float * 3)()
         _lib.check(self._L.gsr_icp_get_timing(self._h, t), "gsr_icp_get_timing")

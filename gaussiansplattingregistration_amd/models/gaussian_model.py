@@ -418,6 +418,52 @@ class GaussianModel:
         return m
 
     @staticmethod
+    def get_merged_gaussian_point_clouds_multi(models, poses, rotate_sh=False):
+        """N models, each moved by its rigid pose (4x4, the model's frame -> the common frame: the node poses of a multiway
+        registration), concatenated in the order given.  The output arrays are allocated once and every model's fused transform
+        kernel (``_transform_kernel(..., into=)``) writes straight into the model's rows: no clone, no ``cat``.  Rows
+        ``[sum(n_0..n_i-1), sum(n_0..n_i))`` are bit for bit what ``transform_gaussian_model(poses[i], rotate_sh)`` gives for model
+        ``i`` alone; a model whose pose is the identity is copied as it is, as in the pairwise merge.  The models stay as they
+        were.  All of them must live on one CUDA device, with one SH degree and the same set of arrays."""
+        models, poses = list(models), [np.asarray(p, dtype=np.float64).reshape(4, 4) for p in poses]
+        if not models or len(models) != len(poses):
+            raise ValueError(f"{len(models)} models and {len(poses)} poses")
+        names = ("_xyz", "_rotation", "_scaling", "_features_dc", "_features_rest", "_opacity", "_covariance")
+        moved = ("_xyz", "_covariance", "_rotation", "_features_rest")
+        first = models[0]
+        dev = first._xyz.device
+        for g in models:
+            if g.sh_degree != first.sh_degree:
+                raise ValueError("the models differ in SH degree")
+            if not g._xyz.is_cuda or g._xyz.device != dev:
+                raise RuntimeError("get_merged_gaussian_point_clouds_multi: the models must all live on one CUDA device")
+        sizes = [len(g) for g in models]
+        total = sum(sizes)
+        m = GaussianModel(first.device_name)
+        m.sh_degree = first.sh_degree
+        for name in names:
+            arrays = [getattr(g, name) for g in models]
+            if all(a.numel() == 0 and a.dim() < 2 for a in arrays):               # an array no model carries (no decompose)
+                setattr(m, name, torch.empty(0, device=dev))
+                continue
+            if any(a.shape[0] != n or tuple(a.shape[1:]) != tuple(arrays[0].shape[1:]) for a, n in zip(arrays, sizes)):
+                raise RuntimeError(f"{name}: the models do not carry it alike")
+            setattr(m, name, torch.empty((total,) + tuple(arrays[0].shape[1:]), dtype=torch.float32, device=dev))
+        off = 0
+        for g, T, n in zip(models, poses, sizes):
+            moves = n > 0 and not np.array_equal(T, np.eye(4))
+            if moves:
+                g._transform_kernel(T, rotate_sh, into={k: getattr(m, k)[off:off + n] for k in moved})
+            for name in names:
+                o = getattr(m, name)
+                if o.numel() == 0 or o.shape[0] != total:
+                    continue
+                if not (moves and name in moved):
+                    o[off:off + n].copy_(getattr(g, name))
+            off += n
+        return m
+
+    @staticmethod
     def get_fused_gaussian_point_clouds(gaussian1, gaussian2, transformation_matrix, fuse, rotate_sh=False, with_scaling=False):
         """``gaussian1`` moved by the matrix, then ``fuse_overlap`` with ``gaussian2`` -> ``(model, info)``: what
         ``get_merged_gaussian_point_clouds(..., fuse=params)`` returns the model of, with the report.  As in the plain merge,

@@ -256,3 +256,24 @@ def do_icp_registration(point_cloud_first, point_cloud_second, init_transform, r
         return registration_colored_icp(point_cloud_first, point_cloud_second, max_correspondence, init_transform,
                                         estimation_method, convergence_criteria, **kw)
     return None
+
+
+def get_information_matrix_from_point_clouds(source, target, max_correspondence_distance, transformation, device=None, ctx=None):
+    """``o3d.pipelines.registration.get_information_matrix_from_point_clouds`` on ``PointCloud`` records: the (6, 6) float64
+    information matrix of the pair at ``transformation`` (``IcpContext.information``: rotation rows first, ``[5, 5]`` = the number
+    of correspondences within ``max_correspondence_distance``), the weight of the pair's edge in a pose graph (``pose_graph.py``)."""
+    if not (max_correspondence_distance > 0.0):
+        raise RuntimeError("[Open3D Error] Invalid max_correspondence_distance.")
+    own = ctx is None
+    if own:
+        ctx = _icp.IcpContext(device=device if device is not None else getattr(target, "device_index", 0))
+    try:
+        ctx.set_comm(None, 0)
+        ctx.set_allreduce_device(None, 0)
+        ctx.set_allreduce(None, 0)
+        ctx.set_target(target.xyz32, None, max_correspondence_distance)
+        ctx.set_source(source.xyz32)
+        return ctx.information(np.asarray(transformation, dtype=np.float64))[0]
+    finally:
+        if own:
+            ctx.close()

@@ -381,6 +381,14 @@ int32_t gsr_icp_register_multiscale(gsr_icp_ctx* ctx, int32_t n_entries, const g
                                     double* out_T);
 /* Nearest target index (or -1) and squared distance for every source point at transform T. */
 int32_t gsr_icp_correspondences(gsr_icp_ctx* ctx, const double* T, int64_t* idx, double* d2);
+/* Information matrix of the pair at transform T (Open3D's get_information_matrix_from_point_clouds): every source point is moved by T,
+ * its correspondence is its nearest target point q with |T p - q|^2 < max_corr^2 (strict; the context's max_corr, the search of an
+ * evaluation), and info36 = sum over the correspondences of G^T G with G = [ -[q]x | I3 ] at the TARGET point -- rotation columns
+ * first, row-major 6x6 float64 on the host; info36[35] = *n_corr = the number of correspondences (n_corr may be NULL).  No
+ * correspondence: the zero matrix and 0, not an error.  One kernel of ten float64 sums per lane (n, sum q, sum q q^T) and the
+ * fixed-order reduction of gsr_icp_accumulate: the same inputs give the same bits.  One process, one GPU: a context with a communicator
+ * or an all-reduce callback installed is GSR_E_INVALID. */
+int32_t gsr_icp_information(gsr_icp_ctx* ctx, const double* T, double* info36, int64_t* n_corr);
 /* Device milliseconds: [0] target index build, [1] all correspondence/accumulate kernels of the last
  * gsr_icp_register, [2] their count. */
 int32_t gsr_icp_get_timing(gsr_icp_ctx* ctx, float* out3);
@@ -705,6 +713,45 @@ typedef struct gsr_fuse_report {
 } gsr_fuse_report;
 int32_t gsr_model_fuse(const gsr_model_view* a, const gsr_model_view* b, int32_t K, const gsr_fuse_params* params, gsr_model_view* out,
                        int32_t* pairs, gsr_fuse_report* report, int32_t on_device, int32_t device, void* stream);
+
+/* ------------------------------------------------------------------- multiway registration: pose-graph optimisation (host only) */
+
+/* Pose graph of N scenes (Open3D's PoseGraph + global_optimization; Choi, Zhou, Koltun 2015).  Node i has a rigid pose X_i (row-major
+ * 4x4 float64) from its own frame into the global one; edge (source, target, T, information, uncertain) has T from the source's frame
+ * into the target's -- what a pairwise registration of (source, target) returns -- so a consistent graph has X_t T = X_s.  Residual of
+ * an edge: D = X_t^-1 X_s T^-1, r = [log_SO3(R_D); t_D], chi = r^T information r.  Objective: sum over the certain edges of chi plus,
+ * over the uncertain ones, l chi + mu (sqrt(l) - 1)^2 with l = (mu / (mu + chi))^2 in closed form and
+ * mu = preference_loop_closure * max_correspondence_distance^2 * mean over the uncertain edges of information[35].  Levenberg-Marquardt
+ * on the poses; then every uncertain edge with l < edge_prune_threshold is pruned and the rest is optimised again (mu from the rest).
+ * The pose of reference_node is not touched.  csrc/gsr_posegraph.h; no device is involved (like gsr_icp_solve). */
+typedef struct gsr_pose_edge {
+    int32_t source, target;
+    int32_t uncertain;              /* 0: certain ("odometry"), else a loop closure under the line process */
+    int32_t reserved;
+    double T[16];                   /* source frame -> target frame */
+    double information[36];         /* symmetric positive semi-definite, rotation rows / columns first (gsr_icp_information) */
+} gsr_pose_edge;
+typedef struct gsr_posegraph_option {
+    double max_correspondence_distance;        /* Open3D: 0.075 */
+    double edge_prune_threshold;               /* 0.25 */
+    double preference_loop_closure;            /* 1.0 */
+    int32_t reference_node;                    /* 0 */
+    int32_t max_iteration, max_iteration_lm;   /* 100, 20 */
+    int32_t reserved;
+    double min_relative_increment, min_relative_residual_increment, min_right_term, min_residual;      /* 1e-6 each */
+} gsr_posegraph_option;
+typedef struct gsr_posegraph_result {
+    int32_t iterations[2];          /* accepted Levenberg-Marquardt steps of the first pass and of the pass after pruning */
+    int32_t n_pruned, reserved;
+    double E_initial, E_final;      /* the objective (l eliminated) at the input poses / at the returned ones over the remaining edges */
+    double mu, mu_first;            /* mu of the last pass (what line_process belongs to) and of the first (what pruned by); 0 without uncertain edges */
+} gsr_posegraph_result;
+/* poses[n_nodes*16] in and out; line_process[n_edges] (1 for a certain edge; a pruned edge keeps the value it was pruned with),
+ * pruned[n_edges] (0 / 1) and result may each be NULL; option NULL = the defaults above.  GSR_E_INVALID with a message: an index out of
+ * range, source == target, a node no edge path connects to reference_node, a non-finite pose or transform, an information matrix that is
+ * not symmetric positive semi-definite to rounding, a bad option. */
+int32_t gsr_posegraph_optimize(int32_t n_nodes, double* poses, int32_t n_edges, const gsr_pose_edge* edges, const gsr_posegraph_option* option,
+                               double* line_process, int32_t* pruned, gsr_posegraph_result* result);
 
 /* ------------------------------------------------------------------- splat rasteriser and image metrics (evaluation) */
 

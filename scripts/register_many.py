@@ -1,0 +1,120 @@
+#!/usr/bin/env python3
+"""Headless multiway registration of N 3DGS .ply scenes on one MI355X: pairwise ICP per edge, the information matrix of every
+registered pair, a pose graph with a line process that prunes wrongly registered pairs, and the merged cloud.
+
+    python scripts/register_many.py a.ply b.ply c.ply ... --out merged.ply [--poses-out poses.json]
+           [--edges sequential|all] [--edge S T ...] [--global-fgr VOXEL | --global-ransac VOXEL]
+           [--type point|plane|color|general] [--loss none|tukey|cauchy|gm|huber --k 0.1] [--max-corr 0.05] [--iters 30]
+           [--prune 0.25] [--preference 1.0] [--reference 0] [--rotate-sh]
+
+Edges: `--edges sequential` registers each scene to the next (a chain), `--edges all` every pair; `--edge S T` (repeatable) adds the pair
+(S, T).  An edge (i, i + 1) is certain ("odometry"); every other edge is a loop closure the optimiser may prune (`--prune`: the line
+process value below which it does).  Without a global method every pair starts from the identity: the scenes must be roughly aligned.
+The poses map each scene into the frame of scene `--reference`; `--poses-out` holds them with the edges, their line process values
+and the pruned edges.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("scenes", nargs="+")
+    ap.add_argument("--out", help="the merged cloud (.ply)")
+    ap.add_argument("--poses-out", help="poses, edges with their line process values and the pruned edges (.json)")
+    ap.add_argument("--edges", choices=["sequential", "all"], default=None, help="default: sequential (nothing when --edge is given)")
+    ap.add_argument("--edge", type=int, nargs=2, action="append", default=[], metavar=("S", "T"))
+    method = ap.add_mutually_exclusive_group()
+    method.add_argument("--global-fgr", type=float, metavar="VOXEL", help="initial transform of every pair by Fast Global Registration at this voxel size")
+    method.add_argument("--global-ransac", type=float, metavar="VOXEL", help="initial transform of every pair by FPFH + RANSAC at this voxel size")
+    ap.add_argument("--ransac-iters", type=int, default=100000)
+    ap.add_argument("--type", choices=["point", "plane", "color", "general"], default="plane")
+    ap.add_argument("--loss", choices=["none", "tukey", "cauchy", "gm", "huber"], default="none")
+    ap.add_argument("--k", type=float, default=0.0)
+    ap.add_argument("--max-corr", type=float, default=0.075, help="correspondence distance of the ICP, of the information matrices and of the optimiser")
+    ap.add_argument("--iters", type=int, default=30)
+    ap.add_argument("--prune", type=float, default=0.25, help="edge_prune_threshold")
+    ap.add_argument("--preference", type=float, default=1.0, help="preference_loop_closure")
+    ap.add_argument("--reference", type=int, default=0, help="reference_node: the scene whose frame the result is in")
+    ap.add_argument("--rotate-sh", action="store_true", help="turn the SH coefficients of every moved scene with it in the merged output")
+    a = ap.parse_args()
+    n = len(a.scenes)
+    if n < 2:
+        raise SystemExit("at least two scenes")
+
+    import __graft_entry__ as g
+    g.build_hip()
+    from gaussiansplattingregistration_amd.models.gaussian_model import GaussianModel
+    from gaussiansplattingregistration_amd.params.registration_parameters import (FGRRegistrationParams, LocalRegistrationParams,
+                                                                                  RANSACRegistrationParams)
+    from gaussiansplattingregistration_amd.utils import global_registration_util as G
+    from gaussiansplattingregistration_amd.utils.local_registration_util import KernelLossFunctionType as K, LocalRegistrationType as T
+    from gaussiansplattingregistration_amd.utils.point_cloud_converter import convert_gs_to_open3d_pc
+    from gaussiansplattingregistration_amd.utils.pose_graph import GlobalOptimizationOption
+    from gaussiansplattingregistration_amd.workers.multiway import MultiwayRegistrator, edge_list
+
+    edges = edge_list(n, a.edges or ("sequential" if not a.edge else []))
+    for s, t in edge_list(n, a.edge):
+        if (s, t) not in edges:
+            edges.append((s, t))
+    rtype = {"point": T.ICP_Point_To_Point, "plane": T.ICP_Point_To_Plane, "color": T.ICP_Color, "general": T.ICP_General}[a.type]
+    loss = {"none": K.Loss_None, "tukey": K.Tukey_Loss, "cauchy": K.Cauchy_Loss, "gm": K.GMLoss, "huber": K.Huber_Loss}[a.loss]
+    t0 = time.perf_counter()
+    models = [GaussianModel("cuda:0").from_ply(p) for p in a.scenes]
+    clouds = [convert_gs_to_open3d_pc(m) for m in models]
+    for p, m in zip(a.scenes, models):
+        print(f"{p}: {len(m)} splats, SH degree {m.sh_degree}")
+    t1 = time.perf_counter()
+
+    init = None
+    if a.global_fgr:
+        gp = FGRRegistrationParams(voxel_size=a.global_fgr, maximum_correspondence=1.5 * a.global_fgr)
+        init = lambda s, t, cs, ct: G.do_fgr_registration(cs, ct, gp).transformation
+    elif a.global_ransac:
+        v = a.global_ransac
+        gp = RANSACRegistrationParams(voxel_size=v, max_correspondence=1.5 * v, max_iteration=a.ransac_iters, confidence=0.999,
+                                      checkers=[G.CorrespondenceCheckerBasedOnEdgeLength(0.9), G.CorrespondenceCheckerBasedOnDistance(1.5 * v)])
+        init = lambda s, t, cs, ct: G.do_ransac_registration(cs, ct, gp).transformation
+    params = LocalRegistrationParams(registration_type=rtype, max_correspondence=a.max_corr, max_iteration=a.iters, rejection_type=loss, k_value=a.k)
+    option = GlobalOptimizationOption(max_correspondence_distance=a.max_corr, edge_prune_threshold=a.prune, preference_loop_closure=a.preference,
+                                      reference_node=a.reference)
+    worker = MultiwayRegistrator(clouds, params, edges=edges, init=init, option=option)
+    res = worker.run()
+    t2 = time.perf_counter()
+    if res is None:
+        raise SystemExit("multiway registration failed: " + "; ".join(worker.errors))
+    np.set_printoptions(precision=6, suppress=True)
+    for r in res.edge_reports:
+        print(f"edge ({r['source']}, {r['target']}){' loop' if r['uncertain'] else ''}: fitness {r['fitness']:.4f}  rmse {r['inlier_rmse']:.6f}  "
+              f"correspondences {r['n_correspondences']}  l {r['line_process']:.4f}{'  PRUNED' if r['pruned'] else ''}")
+    print(res.optimization)
+    for i, X in enumerate(res.poses):
+        print(f"pose of scene {i} (-> scene {a.reference}):\n", X)
+    print(f"load {t1 - t0:.2f} s, registration {t2 - t1:.3f} s (pairwise {worker.timing['pairwise_s']:.3f}, information "
+          f"{worker.timing['information_s']:.3f}, optimisation {worker.timing['optimization_s']:.3f})")
+    if a.poses_out:
+        doc = {"reference_node": a.reference, "poses": [X.tolist() for X in res.poses],
+               "edges": [{"source": r["source"], "target": r["target"], "uncertain": r["uncertain"], "transformation": np.asarray(r["transformation"]).tolist(),
+                          "fitness": r["fitness"], "inlier_rmse": r["inlier_rmse"], "n_correspondences": r["n_correspondences"],
+                          "line_process": r["line_process"], "pruned": r["pruned"]} for r in res.edge_reports],
+               "pruned": [[r["source"], r["target"]] for r in res.edge_reports if r["pruned"]],
+               "optimization": {"iterations": list(res.optimization.iterations), "E_initial": res.optimization.E_initial, "E_final": res.optimization.E_final,
+                                "mu": res.optimization.mu, "n_pruned": res.optimization.n_pruned}}
+        with open(a.poses_out, "w") as f:
+            json.dump(doc, f, indent=1)
+        print(f"poses -> {a.poses_out}")
+    if a.out:
+        merged = GaussianModel.get_merged_gaussian_point_clouds_multi(models, res.poses, rotate_sh=a.rotate_sh)
+        merged.save_ply(a.out)
+        print(f"merged cloud ({len(merged)} splats) -> {a.out}")
+
+
+if __name__ == "__main__":
+    main()
