@@ -115,6 +115,8 @@ SIGNATURES = {
     "gsr_model_transform": (_i32, [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp]),
     "gsr_model_similarity": (_i32, [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp]),
     "gsr_model_fuse": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _vp]),
+    "gsr_outlier_mask": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp]),
+    "gsr_model_select": (_i32, [_vp, _i32, _vp, _vp, _vp, C.POINTER(_i64), _i32, _i32, _vp]),
     "gsr_plane_score": (_i32, [_vp, _vp, _i64, _vp, _i32, _f32, _f32, _vp, _vp, C.POINTER(_i32), _i32, _i32, _vp]),
     "gsr_icp_solve": (_i32, [_vp, _i32, _vp, _vp]),
     "gsr_icp_get_centre": (_i32, [_vp, _vp]),
@@ -203,6 +205,19 @@ class FuseReport(C.Structure):
     """gsr_fuse_report (include/gsr_hip.h)."""
     _fields_ = [("n_out", C.c_int64), ("n_pairs", C.c_int64), ("n_a_only", C.c_int64), ("n_b_only", C.c_int64), ("n_invalid_a", C.c_int64),
                 ("n_invalid_b", C.c_int64), ("gated_pairs", C.c_int64), ("workspace_bytes", C.c_int64), ("phase_ms", C.c_float * 4)]
+
+
+class CleanParams(C.Structure):
+    """gsr_clean_params (include/gsr_hip.h)."""
+    _fields_ = [("min_raw_opacity", C.c_double), ("max_log_scale", C.c_double), ("nb_neighbors", C.c_int32), ("reserved0", C.c_int32),
+                ("std_ratio", C.c_double), ("radius", C.c_double), ("nb_points", C.c_int32), ("reserved1", C.c_int32)]
+
+
+class CleanReport(C.Structure):
+    """gsr_clean_report (include/gsr_hip.h)."""
+    _fields_ = [("n", C.c_int64), ("n_nonfinite", C.c_int64), ("n_gate_opacity", C.c_int64), ("n_gate_scale", C.c_int64), ("n_statistical", C.c_int64),
+                ("n_radius", C.c_int64), ("n_kept", C.c_int64), ("cloud_mean", C.c_double), ("std_dev", C.c_double), ("threshold", C.c_double),
+                ("deferred_queries", C.c_int64), ("workspace_bytes", C.c_int64), ("phase_ms", C.c_float * 4)]
 
 
 class PoseEdge(C.Structure):

@@ -9,12 +9,14 @@ class DownsamplerController:
         self.data_repository = data_repository
         self.last_stats = None
 
-    def create_mixture(self, params):
+    def create_mixture(self, params, clean=None):
+        """``clean`` (a ``CleanParams``; default ``None``: off): level 0 of both clouds goes through ``remove_floaters`` before the
+        mixtures are built; the repository's level 0 is left as it was."""
         repo = self.data_repository
         pc1 = repo.pc_gaussian_list_first[0]            # level 0 = original cloud (:23-26)
         pc2 = repo.pc_gaussian_list_second[0]
         worker = GaussianMixtureWorker(pc1, pc2, params.hem_reduction, params.distance_delta, params.color_delta,
-                                       params.decay_rate, params.cluster_level)
+                                       params.decay_rate, params.cluster_level, clean=clean)
         result = worker.run()
         self.last_stats = worker.stats
         if result is not None:

@@ -32,6 +32,7 @@
 #include "gsr_normals.h"
 #include "gsr_solve.h"
 #include "gsr_features.h"
+#include "gsr_grid.h"
 #include "gsr_oneshot.h"
 #include "gsr_prims.h"
 
@@ -58,20 +59,6 @@ using icp_sort_cfg = rocprim::radix_sort_config<rocprim::default_config, icp_mer
 #ifndef ICP_CELL_FLOOR_DIV
 #define ICP_CELL_FLOOR_DIV 64.0     // a grid cell is never finer than max_corr / this (bounds the rings of a query that finds nothing)
 #endif
-struct IcpGrid {
-    double ox, oy, oz, inv_c, c;
-    double cx, cy, cz;     // centre used to condition the point-to-point sums
-    int gx, gy, gz, ncells;
-    int rings;             // ceil(max_corr / c): cells beyond this Chebyshev ring cannot hold an accepted neighbour
-    double bx0, by0, bz0, bx1, by1, bz1;      // box of ALL finite target points (the grid may lie over a trimmed one): a query farther from it than max_corr has no neighbour
-};
-
-__device__ __forceinline__ int icp_cell(double v, double o, double inv_c, int g) {
-    double t = (v - o) * inv_c;
-    t = fmin(fmax(t, 0.0), (double)(g - 1));      // NaN -> 0
-    return (int)t;
-}
-
 __global__ __launch_bounds__(256) void k_icp_bbox(int64_t n, const float* __restrict__ xyz, float* __restrict__ bbox_part) {
     float mn[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, mx[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
@@ -253,16 +240,6 @@ __device__ __forceinline__ void icp_scan_span(const int* __restrict__ cellStart,
         const unsigned qi = __float_as_uint(q.w);
         if (d2 < bd || (d2 == bd && qi < best_i)) { bd = d2; best = j; best_i = qi; }
     }
-}
-
-// Distance from coordinate v to the slab of cell k along one axis (0 inside), shrunk by a relative 1e-9 so that the
-// float64 rounding of the cell classification can never make a bound too large.
-// The first and the last cell of an axis also hold every point CLAMPED in from beyond the grid's box (the box is a robust one when
-// the cloud has far outliers, gsr_icp_set_target): they are half-infinite slabs.
-__device__ __forceinline__ double icp_slab_dist(double v, double o, double c, int k, double eps, int g) {
-    const double lo = o + (double)k * c, hi = o + (double)(k + 1) * c;
-    const double d = ((v < lo && k > 0) ? lo - v : ((v > hi && k < g - 1) ? v - hi : 0.0)) * 0.999999999 - eps;
-    return d > 0.0 ? d : 0.0;
 }
 
 __device__ __forceinline__ void icp_consider(const float4 q, int j, double px, double py, double pz, double& bd, int& best, unsigned& best_i) {
@@ -1978,42 +1955,6 @@ int32_t gsr_normals_knn(const float* xyz, int64_t n, int32_t knn, double* normal
 // taken.  At the end each entry's rank among the list is its slot: the output is sorted by (d^2, index) without a sort.
 namespace gsr {
 
-__device__ __forceinline__ bool hyb_less(double da, unsigned ia, double db, unsigned ib) { return da < db || (da == db && ia < ib); }
-
-// keeps the min(cnt, keep) best entries of sd / si[0..cnt) at slots 0..keep-1 in (d^2, index) order; returns the new count.
-// With `out` the kept entries are written there instead (the final pass).  One wave; the list lives in LDS.
-__device__ int hyb_rank_cut(double* sd, unsigned* si, int cnt, int keep, int* out) {
-    const int lane = threadIdx.x;
-    constexpr int PER = GSR_HYBRID_CAP / 64;
-    double md[PER];
-    unsigned mi[PER];
-    int rk[PER];
-#pragma unroll
-    for (int t = 0; t < PER; ++t) {
-        const int e = lane + 64 * t;
-        md[t] = e < cnt ? sd[e] : 0.0;
-        mi[t] = e < cnt ? si[e] : 0u;
-        rk[t] = 0;
-    }
-    for (int f = 0; f < cnt; ++f) {
-        const double fd = sd[f];
-        const unsigned fi = si[f];
-#pragma unroll
-        for (int t = 0; t < PER; ++t) rk[t] += hyb_less(fd, fi, md[t], mi[t]) ? 1 : 0;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int t = 0; t < PER; ++t) {
-        const int e = lane + 64 * t;
-        if (e < cnt && rk[t] < keep) {
-            if (out) out[rk[t]] = (int)mi[t];
-            else { sd[rk[t]] = md[t]; si[rk[t]] = mi[t]; }
-        }
-    }
-    __syncthreads();
-    return cnt < keep ? cnt : keep;
-}
-
 __global__ __launch_bounds__(64) void k_hybrid_search(int64_t n, IcpGrid g, const int* __restrict__ cellStart, const float4* __restrict__ Tq,
                                                       double r2, int R, int max_nn, int* __restrict__ nbr, int* __restrict__ cnt_out) {
     __shared__ double sd[GSR_HYBRID_CAP];
@@ -2092,6 +2033,22 @@ int32_t hybrid_search_dev(const float* xyz_dev, int64_t n, double radius, int ma
     }
     (void)gsr_icp_destroy(c);
     return r;
+}
+
+int32_t grid_borrow(const float* xyz_dev, int64_t n, double max_corr, int device, hipStream_t stream, gsr_icp_ctx** ctx, GridView* view) {
+    *ctx = nullptr;
+    gsr_icp_ctx* c = nullptr;
+    GSR_TRY(gsr_icp_create(&c, device, stream));
+    *ctx = c;                         // the caller destroys it, also after a failure below
+    c->defer_sync = true;             // the borrower waits for the stream
+    GSR_TRY(gsr_icp_set_target(c, xyz_dev, nullptr, n, max_corr, 1));
+    view->g = c->grid;
+    view->cellStart = c->cellStart.as<int>();
+    view->Tq = c->Tq.as<float4>();
+    view->n = n;
+    view->bytes = 0;
+    for (const DevBuf* b : {&c->bbox, &c->hist, &c->keys, &c->idx, &c->skeys, &c->order, &c->cellStart, &c->Tq, &c->rocprim_tmp}) view->bytes += b->cap;
+    return GSR_OK;
 }
 
 }  // namespace gsr

@@ -489,6 +489,43 @@ class GaussianModel:
             g1.move_to_device(str(gaussian2._xyz.device))
         return GaussianModel.fuse_overlap(g1, gaussian2, fuse)
 
+    # -- cleaning (csrc/clean.hip; the reference has no such step) -------------------------------------------------------------
+    def select_by_mask(self, mask):
+        """The splats with ``mask != 0`` as a new model, every tensor (``_covariance`` included) bit for bit, in ascending row order;
+        ``sh_degree`` is kept.  One ``gsr_model_select``; on the device for CUDA tensors."""
+        from .. import clean
+        n = len(self)
+        K = int(self._features_rest.shape[1]) if self._features_rest.dim() == 3 else 0
+        with_sr = self._scaling.numel() > 0 and self._rotation.numel() > 0
+        arrays = {"xyz": self._xyz, "cov6": self._covariance, "dc": self._features_dc.reshape(n, 3), "opacity": self._opacity.reshape(n),
+                  "sh": self._features_rest.reshape(n, 3 * K) if K else None,
+                  "scaling": self._scaling if with_sr else None, "rot": self._rotation if with_sr else None}
+        device = self._xyz.device.index if self._xyz.is_cuda else 0
+        sel, _ = clean.select_rows(arrays, mask, device=device)
+        m = GaussianModel(self.device_name)
+        m.sh_degree = self.sh_degree
+        t = {k: torch.as_tensor(v) for k, v in sel.items()}
+        k = int(t["xyz"].shape[0])
+        m._xyz, m._covariance = t["xyz"], t["cov6"]
+        m._features_dc = t["dc"].view(k, 1, 3)
+        m._opacity = t["opacity"].view((k,) + tuple(self._opacity.shape[1:]))
+        m._features_rest = t["sh"].view(k, K, 3) if K else torch.empty((k, 0, 3), dtype=torch.float32, device=m._xyz.device)
+        if with_sr:
+            m._scaling, m._rotation = t["scaling"], t["rot"]
+        return m
+
+    def remove_floaters(self, params):
+        """-> ``(model, info)``: this model without its floaters (``params``: a ``CleanParams``).  ``gsr_outlier_mask`` -- finite test,
+        opacity and extent gates, statistical filter, radius filter -- then ``gsr_model_select``, back to back: for a model on the
+        device nothing but the report comes to the host.  ``info``: the report of ``clean.outlier_mask``.  This model is left as it
+        was.  Applying it twice is NOT the identity: the survivors have a new mean and deviation."""
+        from .. import clean
+        n = len(self)
+        device = self._xyz.device.index if self._xyz.is_cuda else 0
+        scaling = self._scaling if self._scaling.numel() > 0 else None
+        mask, info = clean.outlier_mask(self._xyz, params, raw_opacity=self._opacity.reshape(n), scaling=scaling, device=device)
+        return self.select_by_mask(mask), info
+
     def clone_gaussian(self):
         m = GaussianModel(self.device_name)
         m.sh_degree = self.sh_degree

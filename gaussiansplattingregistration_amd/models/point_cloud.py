@@ -78,6 +78,52 @@ class PointCloud:
         f32 = (lambda a: None if a is None else (a.float() if _is_tensor(a) else a.astype(np.float32)))
         return PointCloud(xyz32=f32(xyz), colors=f32(col), cov6=f32(cov6))
 
+    # -- cleaning (Open3D's names and return pairs; csrc/clean.hip) --------------------------------------------------
+    def _rows(self, mask):
+        """(cloud of the rows with mask != 0, their indices): every array the record carries goes through one ``gsr_model_select``"""
+        from .. import clean
+        f32 = lambda a: None if a is None else (a.float() if _is_tensor(a) else np.asarray(a, np.float32))
+        arrays = {"xyz": f32(self.xyz32), "dc": f32(self.colors), "cov6": f32(self.cov6)}
+        sel, index = clean.select_rows(arrays, mask, device=self.device_index)
+        cloud = PointCloud(xyz32=sel["xyz"], colors=sel.get("dc"), cov6=sel.get("cov6"))
+        if self.normals is not None:            # float64: not a row of the float32 view; gathered through the index list
+            idx = index.long() if _is_tensor(index) else np.asarray(index, np.int64)
+            if _is_tensor(self.normals):
+                cloud.normals = self.normals[idx.to(self.normals.device) if _is_tensor(idx) else torch.as_tensor(idx, device=self.normals.device)]
+            else:
+                cloud.normals = np.asarray(self.normals)[idx.cpu().numpy() if _is_tensor(idx) else idx]
+        return cloud, index
+
+    def remove_statistical_outlier(self, nb_neighbors, std_ratio):
+        """``o3d.geometry.PointCloud.remove_statistical_outlier`` -> ``(cloud, index)``: the points whose mean distance to their
+        ``nb_neighbors`` nearest points (the point itself included, as Open3D counts) is positive and below the cloud's mean +
+        ``std_ratio`` standard deviations, and their indices.  Points with a non-finite coordinate are dropped first.  On the GPU;
+        tensors stay tensors."""
+        from .. import clean
+        from ..params.clean_parameters import CleanParams
+        mask, _ = clean.outlier_mask(self.xyz32, CleanParams(nb_neighbors=nb_neighbors, std_ratio=std_ratio), device=self.device_index)
+        return self._rows(mask)
+
+    def remove_radius_outlier(self, nb_points, radius):
+        """``o3d.geometry.PointCloud.remove_radius_outlier`` -> ``(cloud, index)``: the points with more than ``nb_points`` points
+        (themselves included) strictly within ``radius``."""
+        from .. import clean
+        from ..params.clean_parameters import CleanParams
+        mask, _ = clean.outlier_mask(self.xyz32, CleanParams(nb_neighbors=0, radius=radius, nb_points=nb_points), device=self.device_index)
+        return self._rows(mask)
+
+    def select_by_index(self, index, invert=False):
+        """``o3d.geometry.PointCloud.select_by_index``: the points listed in ``index`` (``invert``: all the others), in ascending
+        order of their index whatever the order of the list."""
+        n = len(self)
+        if _is_tensor(self.xyz32) and self.xyz32.is_cuda:
+            mask = torch.zeros(n, dtype=torch.uint8, device=self.xyz32.device)
+            mask[torch.as_tensor(index, device=self.xyz32.device).long()] = 1
+        else:
+            mask = np.zeros(n, np.uint8)
+            mask[index.cpu().numpy() if _is_tensor(index) else np.asarray(index, np.int64)] = 1
+        return self._rows(1 - mask if invert else mask)[0]
+
     def transform(self, T):
         """``o3d.geometry.PointCloud.transform``: points p -> R p + t, normals n -> R n, covariances C -> R C R^T (Open3D's
         PointCloud::Transform).  Every array keeps its placement and dtype (a cuda tensor stays a cuda tensor)."""

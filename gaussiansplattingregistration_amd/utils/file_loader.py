@@ -36,12 +36,15 @@ def load_sparse_pc(pc_path):
     return convert_input_pc_to_open3d_pc(vertices)
 
 
-def load_gaussian_pc(pc_path, device_name="cuda:0"):
-    """``load_gaussian_pc`` (``file_loader.py:53-66``): (point cloud, GaussianModel) or (None, None)."""
+def load_gaussian_pc(pc_path, device_name="cuda:0", clean=None):
+    """``load_gaussian_pc`` (``file_loader.py:53-66``): (point cloud, GaussianModel) or (None, None).  ``clean`` (a ``CleanParams``;
+    default ``None``: the file as it is): the model goes through ``GaussianModel.remove_floaters`` first."""
     from ..models.gaussian_model import GaussianModel
     if not pc_path or not os.path.isfile(pc_path):
         return None, None
     if check_point_cloud_type(ply_io.read_ply_property_names(pc_path)) is not PointCloudType.GAUSSIAN:       # the header decides
         return None, None
     g = GaussianModel(device_name).from_ply(pc_path)          # a CUDA device: pinned chunks straight into device SoA (ply_io.load_gaussian_device)
+    if clean is not None:
+        g, _ = g.remove_floaters(clean)
     return convert_gs_to_open3d_pc(g), g

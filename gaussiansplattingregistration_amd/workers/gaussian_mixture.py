@@ -24,7 +24,7 @@ class GaussianMixtureWorker:
             self.list_open3d_second = list_open3d_second
 
     def __init__(self, pc1, pc2, hem_reduction, distance_delta, color_delta, decay_rate, cluster_level,
-                 progress=None, device_name=None):
+                 progress=None, device_name=None, clean=None):
         self.hem_reduction = hem_reduction
         self.distance_delta = distance_delta
         self.color_delta = color_delta
@@ -38,8 +38,13 @@ class GaussianMixtureWorker:
         self._progress = progress
         self.device_name = device_name or pc1.device_name
         self.stats = []
+        self.clean = clean              # CleanParams or None: floater removal of level 0 before the mixture (off by default)
+        self.clean_info = []
 
     def _mixture(self, pc):
+        if self.clean is not None:
+            pc, info = pc.remove_floaters(self.clean)
+            self.clean_info.append(info)
         level = mixture_bind.MixtureLevel.CreateMixtureLevel(
             pc.get_xyz.detach(), pc.get_colors.detach(), pc.get_raw_opacity.detach().view(-1),
             pc.get_covariance(1).detach(), pc.get_spherical_harmonics.detach())

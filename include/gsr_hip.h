@@ -714,6 +714,58 @@ typedef struct gsr_fuse_report {
 int32_t gsr_model_fuse(const gsr_model_view* a, const gsr_model_view* b, int32_t K, const gsr_fuse_params* params, gsr_model_view* out,
                        int32_t* pairs, gsr_fuse_report* report, int32_t on_device, int32_t device, void* stream);
 
+/* ------------------------------------------------------------------- floater removal: outlier masks and row selection */
+
+/* Which rows of a cloud or splat model survive cleaning: Open3D 0.16's RemoveStatisticalOutlier and RemoveRadiusOutlier, restated
+ * (recalled from the published source: parity with Open3D is unpinned), behind a finite test and two splat gates.  csrc/clean.hip;
+ * DESIGN.md section 18; restated in float64 NumPy in tests/clean_model.py.  All arithmetic is float64 on the float32 inputs and
+ * every comparison is written so that NaN fails it;  d2(i, j) = (xi - xj)^2 + (yi - yj)^2 + (zi - zj)^2 summed left to right.
+ * The stages run in this order, each over the survivors of the one before; a dropped row is neither a query nor a candidate.
+ *   finite       a row with a non-finite coordinate is dropped (n_nonfinite).  A stated deviation: nanoflann on NaN is undefined.
+ *   gates        kept iff raw_opacity >= min_raw_opacity (-inf: off; pass logit(min_opacity)), then iff each of scaling[i, 0..2]
+ *                <= max_log_scale (+inf: off; pass ln(max_extent)).  A gate that is on without its array is GSR_E_INVALID.
+ *   statistical  on iff nb_neighbors >= 1 (then std_ratio > 0, else GSR_E_INVALID).  A = the rows alive, k' = min(nb_neighbors, |A|);
+ *                mean_i = (sum of sqrt(d2) over the k' smallest d2(i, j), j in A INCLUDING j = i, added in ascending order from 0.0)
+ *                / k';  valid = |A|;  cloud_mean = sum over mean_i > 0 of mean_i / valid;  std_dev = sqrt(sum over mean_i > 0 of
+ *                (mean_i - cloud_mean)^2 / (valid - 1));  threshold = cloud_mean + std_ratio std_dev;  kept iff mean_i > 0 and
+ *                mean_i < threshold (valid <= 1: the threshold is NaN and nothing survives).
+ *   radius       on iff radius > 0.  count_i = #{j alive : d2(i, j) < radius radius}, self included, STRICT;  kept iff
+ *                count_i > nb_points.
+ * mask[n] uint8 (1 = kept); mean_dist[n] float64 and count[n] int32, each or NULL: -1 for a row that did not reach its stage.
+ * raw_opacity[n], scaling[n*3]: float32 or NULL.  nb_neighbors in [0, 32]; n in [0, 2^31) (n = 0 is valid).  All arrays on the host
+ * or all on the device as on_device says; the two structs on the host.  The two moments are reduced in per-block partials whose
+ * count depends on n alone and combined in block order, without float atomics: the same input gives the same bits from host or
+ * device arrays, run to run.  Host waits: the box read-backs of the grid build, then one at the end (the report). */
+typedef struct gsr_clean_params {
+    double min_raw_opacity;    /* -inf: gate off */
+    double max_log_scale;      /* +inf: gate off */
+    int32_t nb_neighbors;      /* 0: no statistical stage */
+    int32_t reserved0;
+    double std_ratio;
+    double radius;             /* <= 0: no radius stage */
+    int32_t nb_points;
+    int32_t reserved1;
+} gsr_clean_params;
+typedef struct gsr_clean_report {
+    int64_t n, n_nonfinite, n_gate_opacity, n_gate_scale, n_statistical, n_radius, n_kept;      /* rows in, dropped per stage, kept */
+    double cloud_mean, std_dev, threshold;      /* of the statistical stage (0 when it is off) */
+    int64_t deferred_queries;  /* k-NN queries that left the lane-per-query ring walk for the cooperative kernel */
+    int64_t workspace_bytes;   /* device memory the call reserves itself: a function of n and of which arrays are present alone (host
+                                  callers: the staged copies too); the grid index of gsr_icp_set_target comes on top */
+    float phase_ms[4];         /* pre-pass + grid, k-NN + moments, radius count, mask: hipEvents on the call's stream */
+} gsr_clean_report;
+int32_t gsr_outlier_mask(const float* xyz, const float* raw_opacity, const float* scaling, int64_t n, const gsr_clean_params* params,
+                         uint8_t* mask, double* mean_dist, int32_t* count, gsr_clean_report* report, int32_t on_device, int32_t device,
+                         void* stream);
+/* The rows of `in` with mask != 0, in ascending order, bit for bit, over every array the view carries (the layout of
+ * gsr_model_fuse's views: sh[n*3K] coefficient-major, K in {0, 3, 8, 15}; scaling and rot both or neither; NULL arrays are skipped,
+ * in `in` and `out` alike).  out->n = the capacity in rows on entry and n_out on return; index (int32, as many entries as out holds
+ * rows, or NULL) receives the kept input rows -- Open3D's second return value; *n_out the count.  More kept rows than `out` holds:
+ * GSR_E_INVALID, nothing is written past the capacity.  NOT in place: any overlap between an output and another array of the call
+ * is GSR_E_INVALID, as in gsr_model_fuse.  in->n in [0, 2^31).  One wait for the stream in the middle (the count), one at the end. */
+int32_t gsr_model_select(const gsr_model_view* in, int32_t K, const uint8_t* mask, gsr_model_view* out, int32_t* index, int64_t* n_out,
+                         int32_t on_device, int32_t device, void* stream);
+
 /* ------------------------------------------------------------------- multiway registration: pose-graph optimisation (host only) */
 
 /* Pose graph of N scenes (Open3D's PoseGraph + global_optimization; Choi, Zhou, Koltun 2015).  Node i has a rigid pose X_i (row-major

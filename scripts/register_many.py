@@ -6,12 +6,14 @@ registered pair, a pose graph with a line process that prunes wrongly registered
            [--edges sequential|all] [--edge S T ...] [--global-fgr VOXEL | --global-ransac VOXEL]
            [--type point|plane|color|general] [--loss none|tukey|cauchy|gm|huber --k 0.1] [--max-corr 0.05] [--iters 30]
            [--prune 0.25] [--preference 1.0] [--reference 0] [--rotate-sh]
+           [--clean-knn K --clean-std R [--clean-radius R --clean-nb N] [--clean-min-opacity A] [--clean-max-extent S]]
 
 Edges: `--edges sequential` registers each scene to the next (a chain), `--edges all` every pair; `--edge S T` (repeatable) adds the pair
 (S, T).  An edge (i, i + 1) is certain ("odometry"); every other edge is a loop closure the optimiser may prune (`--prune`: the line
 process value below which it does).  Without a global method every pair starts from the identity: the scenes must be roughly aligned.
 The poses map each scene into the frame of scene `--reference`; `--poses-out` holds them with the edges, their line process values
-and the pruned edges.
+and the pruned edges.  `--clean-*`: every scene goes through floater removal right after loading (scripts/clean_ply.py has the stages);
+prints n -> n_kept per scene.
 """
 import argparse
 import json
@@ -44,7 +46,10 @@ def main():
     ap.add_argument("--preference", type=float, default=1.0, help="preference_loop_closure")
     ap.add_argument("--reference", type=int, default=0, help="reference_node: the scene whose frame the result is in")
     ap.add_argument("--rotate-sh", action="store_true", help="turn the SH coefficients of every moved scene with it in the merged output")
+    from gaussiansplattingregistration_amd.clean import add_clean_arguments, clean_params_from_args
+    add_clean_arguments(ap)
     a = ap.parse_args()
+    clean = clean_params_from_args(a)
     n = len(a.scenes)
     if n < 2:
         raise SystemExit("at least two scenes")
@@ -68,6 +73,10 @@ def main():
     loss = {"none": K.Loss_None, "tukey": K.Tukey_Loss, "cauchy": K.Cauchy_Loss, "gm": K.GMLoss, "huber": K.Huber_Loss}[a.loss]
     t0 = time.perf_counter()
     models = [GaussianModel("cuda:0").from_ply(p) for p in a.scenes]
+    if clean is not None:
+        for i, p in enumerate(a.scenes):
+            models[i], info = models[i].remove_floaters(clean)
+            print(f"{p}: cleaned {info['n']} -> {info['n_kept']} splats")
     clouds = [convert_gs_to_open3d_pc(m) for m in models]
     for p, m in zip(a.scenes, models):
         print(f"{p}: {len(m)} splats, SH degree {m.sh_degree}")

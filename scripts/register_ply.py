@@ -5,6 +5,7 @@
     python scripts/register_ply.py first.ply second.ply --levels 3 --max-corr 0.5 0.3 0.2 0.1 --iters 50 30 20 10 \\
            [--type plane|point|color|general] [--loss none|tukey|cauchy|gm|huber --k 0.1] [--voxel] [--out merged.ply [--rotate-sh]]
            [--with-scaling] [--fuse-overlap MAX_DIST [--fuse-kld X] [--fuse-color X]]
+           [--clean-knn K --clean-std R [--clean-radius R --clean-nb N] [--clean-min-opacity A] [--clean-max-extent S]]
 
 `--with-scaling`: the two scenes do not share a unit of length (separate structure-from-motion runs).  Point-to-point ICP with scaling
 (`--type point` is implied, any other type is refused); without a global method the start is `initial_similarity` (centroids and RMS
@@ -13,6 +14,9 @@ radii aligned); the result is a similarity [c R | t], and the merged .ply has th
 `--fuse-overlap MAX_DIST` (with `--out`): the merged cloud stores the splats the two scenes share once (`GaussianModel.fuse_overlap`:
 mutual best matches within MAX_DIST, a symmetrised KL divergence of at most `--fuse-kld` and DC colours within `--fuse-color` are
 replaced by their moment-matched union); prints n_pairs / n_out.  Implies `--rotate-sh`.
+
+`--clean-*`: both scenes go through floater removal (`GaussianModel.remove_floaters`, scripts/clean_ply.py has the stages) right after
+loading: mixtures, registration and the merged cloud see the cleaned scenes.  Prints n -> n_kept per scene.
 
 Prints the 4x4 transformation (first -> second), fitness and inlier RMSE; `--out` saves the merged cloud.
 """
@@ -52,7 +56,10 @@ def main():
                     "matches within this distance); implies --rotate-sh")
     ap.add_argument("--fuse-kld", type=float, default=0.5, help="largest symmetrised KL divergence of a fused pair")
     ap.add_argument("--fuse-color", type=float, default=float("inf"), help="largest L2 distance of the DC colours of a fused pair")
+    from gaussiansplattingregistration_amd.clean import add_clean_arguments, clean_params_from_args
+    add_clean_arguments(ap)
     a = ap.parse_args()
+    clean = clean_params_from_args(a)
     if a.fuse_overlap is not None:
         a.rotate_sh = True
     if a.with_scaling and a.type not in (None, "point"):
@@ -78,10 +85,13 @@ def main():
                          (a.second, repo.pc_gaussian_list_second, repo.pc_open3d_list_second)):
         tm = {}
         gm = GaussianModel("cuda:0").from_ply(path, timing=tm)        # pinned chunks -> HBM -> device SoA (utils/ply_io.load_gaussian_device)
-        gl.append(gm)
-        ol.append(convert_gs_to_open3d_pc(gm))
         print(f"{path}: {len(gm)} splats, SH degree {gm.sh_degree}; file -> device arrays {tm['seconds'] * 1e3:.1f} ms "
               f"({tm['bytes'] / tm['seconds'] / 1e9:.2f} GB/s of file bytes)")
+        if clean is not None:
+            gm, info = gm.remove_floaters(clean)
+            print(f"{path}: cleaned {info['n']} -> {info['n_kept']} splats")
+        gl.append(gm)
+        ol.append(convert_gs_to_open3d_pc(gm))
     t1 = time.perf_counter()
     if not a.voxel:
         if len(a.max_corr) != a.levels + 1 or len(a.iters) != a.levels + 1:
