@@ -117,6 +117,8 @@ SIGNATURES = {
     "gsr_model_fuse": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _vp]),
     "gsr_outlier_mask": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp]),
     "gsr_model_select": (_i32, [_vp, _i32, _vp, _vp, _vp, C.POINTER(_i64), _i32, _i32, _vp]),
+    "gsr_orient_normals_graph": (_i32, [_vp, _vp, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _vp]),
+    "gsr_orient_normals": (_i32, [_vp, _vp, _i64, _f64, _i32, _vp, _vp, _vp, _i32, _i32, _vp]),
     "gsr_plane_score": (_i32, [_vp, _vp, _i64, _vp, _i32, _f32, _f32, _vp, _vp, C.POINTER(_i32), _i32, _i32, _vp]),
     "gsr_icp_solve": (_i32, [_vp, _i32, _vp, _vp]),
     "gsr_icp_get_centre": (_i32, [_vp, _vp]),
@@ -218,6 +220,12 @@ class CleanReport(C.Structure):
     _fields_ = [("n", C.c_int64), ("n_nonfinite", C.c_int64), ("n_gate_opacity", C.c_int64), ("n_gate_scale", C.c_int64), ("n_statistical", C.c_int64),
                 ("n_radius", C.c_int64), ("n_kept", C.c_int64), ("cloud_mean", C.c_double), ("std_dev", C.c_double), ("threshold", C.c_double),
                 ("deferred_queries", C.c_int64), ("workspace_bytes", C.c_int64), ("phase_ms", C.c_float * 4)]
+
+
+class OrientReport(C.Structure):
+    """gsr_orient_report (include/gsr_hip.h)."""
+    _fields_ = [("n", C.c_int64), ("n_components", C.c_int64), ("n_flipped", C.c_int64), ("n_not_live", C.c_int64), ("rounds", C.c_int32),
+                ("reserved", C.c_int32), ("workspace_bytes", C.c_int64), ("phase_ms", C.c_float * 4)]
 
 
 class PoseEdge(C.Structure):

@@ -124,6 +124,37 @@ class PointCloud:
             mask[index.cpu().numpy() if _is_tensor(index) else np.asarray(index, np.int64)] = 1
         return self._rows(1 - mask if invert else mask)[0]
 
+    def orient_normals_consistent_tangent_plane(self, k, radius=None, reference="centroid"):
+        """``o3d.geometry.PointCloud.orient_normals_consistent_tangent_plane(k)``: the normals' signs propagated along the minimum
+        spanning forest of the neighbour graph (weight ``1 - |n_i . n_j|``), on the GPU (``csrc/orient.hip``).  The lists are the
+        hybrid search's: the ``k`` nearest points within ``radius`` (and the point itself).  A finite ``radius`` is needed: the
+        grid search walks ``radius / cell`` rings of cells around every point, so it has no pure k-NN mode.  Unlike Open3D no
+        Delaunay edges join pieces further apart than ``radius``: each connected piece is oriented on its own and then takes the
+        sign most of its normals need to look towards ``reference``: ``"centroid"`` (the cloud's, as
+        ``orient_normals_towards_centroid`` computes it), a point, or ``None`` (the lowest vertex of each piece keeps its sign).
+        The normals keep their placement; returns the cloud."""
+        from .. import orient
+        if not self.has_normals():
+            raise RuntimeError("[Open3D Error] No normals in the PointCloud. Call estimate_normals() first.")
+        if radius is None or not np.isfinite(radius) or not radius > 0:
+            raise ValueError("orient_normals_consistent_tangent_plane needs a finite radius > 0: the neighbour lists come from the grid "
+                             "search, which walks radius / cell rings of cells around every point (there is no pure k-NN mode)")
+        if int(k) < 1:
+            raise ValueError("k must be >= 1")
+        nrm, xyz = self.normals, self.xyz32
+        on = _is_tensor(nrm) and nrm.is_cuda
+        if on != (_is_tensor(xyz) and xyz.is_cuda):                     # the coordinates go where the normals live
+            xyz = torch.as_tensor(np.asarray(xyz, np.float32), device=nrm.device) if on else xyz.detach().cpu().numpy()
+        if isinstance(reference, str):
+            if reference != "centroid":
+                raise ValueError(f"reference must be 'centroid', a point or None (got {reference!r})")
+            reference = (xyz.detach().double().mean(0).cpu().numpy() if _is_tensor(xyz) else np.asarray(self.points, np.float64).mean(0))
+        out, info = orient.orient_normals(xyz, nrm, float(radius), int(k) + 1, reference=reference,
+                                          device=nrm.device.index if on else self.device_index, with_component=False)
+        self.normals = out.to(nrm.dtype) if _is_tensor(out) else out.astype(np.asarray(nrm).dtype, copy=False)
+        self.orient_info = info
+        return self
+
     def transform(self, T):
         """``o3d.geometry.PointCloud.transform``: points p -> R p + t, normals n -> R n, covariances C -> R C R^T (Open3D's
         PointCloud::Transform).  Every array keeps its placement and dtype (a cuda tensor stays a cuda tensor)."""

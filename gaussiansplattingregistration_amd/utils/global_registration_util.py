@@ -7,6 +7,7 @@ for the voxel multiscale path), then every normal is turned towards the cloud's 
 orientation is a deviation from the reference, whose normals keep the eigen-solver's arbitrary sign: FPFH is not invariant under a
 normal's sign, and with arbitrary signs only ~7 % of the mutual feature matches of the project's test scene are right (57 % oriented,
 DESIGN.md section 12).  The centroid moves with the cloud, so the orientation is the same for a cloud and its rigidly moved copy.
+``orient="consistent"`` propagates the signs along the neighbour graph instead (``orient_normals_consistent``).
 Both methods of the reference's tab are here: ``do_ransac_registration`` and ``do_fgr_registration`` (Fast Global Registration;
 its tuple test draws with the library's counter-based sampler, so it is deterministic for a given ``seed``).
 """
@@ -234,18 +235,38 @@ def orient_normals_towards_centroid(pcd):
     return pcd
 
 
-def preprocess_point_cloud(pcd, voxel_size):
+def orient_normals_consistent(pcd, radius, max_nn=30):
+    """Propagate the normals' signs along the minimum spanning forest of the hybrid ``(radius, max_nn)`` neighbour graph and let
+    every connected piece look towards the cloud's centroid by majority (``orient.orient_normals``).  Right
+    for shapes the centroid rule splits (a torus, the far side of a wall, two objects); a single point still follows the centroid
+    rule.  Keeps the normals' placement."""
+    if not pcd.has_normals():
+        raise RuntimeError("[Open3D Error] No normals in the PointCloud. Call estimate_normals() first.")
+    return pcd.orient_normals_consistent_tangent_plane(int(max_nn) - 1, radius=radius, reference="centroid")
+
+
+ORIENT_MODES = ("centroid", "consistent")
+
+
+def preprocess_point_cloud(pcd, voxel_size, orient="centroid"):
+    """``orient``: ``"centroid"`` (the default: every normal towards the cloud's centroid) or ``"consistent"`` (the centroid-voted
+    propagation over the hybrid lists of ``radius = 2 * voxel_size, max_nn = 30``)."""
+    if orient not in ORIENT_MODES:
+        raise ValueError(f"orient must be one of {ORIENT_MODES} (got {orient!r})")
     pcd_down = pcd.voxel_down_sample(voxel_size)
     pcd_down.estimate_normals()
-    orient_normals_towards_centroid(pcd_down)
+    if orient == "consistent":
+        orient_normals_consistent(pcd_down, radius=2 * voxel_size, max_nn=30)
+    else:
+        orient_normals_towards_centroid(pcd_down)
     radius_feature = voxel_size * 5
     pcd_fpfh = compute_fpfh_feature(pcd_down, KDTreeSearchParamHybrid(radius=radius_feature, max_nn=100))
     return pcd_down, pcd_fpfh
 
 
 def do_ransac_registration(point_cloud_first, point_cloud_second, params):
-    source_down, source_fpfh = preprocess_point_cloud(point_cloud_first, params.voxel_size)
-    target_down, target_fpfh = preprocess_point_cloud(point_cloud_second, params.voxel_size)
+    source_down, source_fpfh = preprocess_point_cloud(point_cloud_first, params.voxel_size, orient=getattr(params, "orient_normals", "centroid"))
+    target_down, target_fpfh = preprocess_point_cloud(point_cloud_second, params.voxel_size, orient=getattr(params, "orient_normals", "centroid"))
     real_estimation_method = get_estimation_method_from_enum(params.estimation_method)
     result = registration_ransac_based_on_feature_matching(
         source_down, target_down, source_fpfh, target_fpfh, params.mutual_filter,
@@ -316,8 +337,8 @@ def registration_fgr_based_on_feature_matching(source, target, source_feature, t
 
 
 def do_fgr_registration(point_cloud_first, point_cloud_second, registration_params):
-    source_down, source_fpfh = preprocess_point_cloud(point_cloud_first, registration_params.voxel_size)
-    target_down, target_fpfh = preprocess_point_cloud(point_cloud_second, registration_params.voxel_size)
+    source_down, source_fpfh = preprocess_point_cloud(point_cloud_first, registration_params.voxel_size, orient=getattr(registration_params, "orient_normals", "centroid"))
+    target_down, target_fpfh = preprocess_point_cloud(point_cloud_second, registration_params.voxel_size, orient=getattr(registration_params, "orient_normals", "centroid"))
 
     options = FastGlobalRegistrationOption(registration_params.division_factor,
                                            registration_params.use_absolute_scale,

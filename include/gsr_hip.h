@@ -837,6 +837,37 @@ int32_t gsr_raster_get_timing(gsr_raster_ctx* ctx, float* ms);
 int32_t gsr_image_metrics(const float* a, const float* b, int32_t height, int32_t width, int32_t on_device, double* out, int32_t device,
                           void* stream);
 
+/* ------------------------------------------------------------------- consistent normal orientation */
+/* Hoppe's propagation of the normals' signs along the minimum spanning forest of a neighbour graph, on the device.
+ * Lists: nbr[n*stride] int32 and count[n] int32 in gsr_hybrid_search's layout (row v holds count[v] entries, clamped to
+ * [0, stride]); an entry equal to v or outside [0, n) is skipped (bounds-checked, never dereferenced), duplicates are harmless.
+ * A vertex is live when its three normal components are finite.  An undirected edge {i, j} exists when j is in i's list OR i is in
+ * j's (the symmetric closure) and both are live.  dot = nix*njx + niy*njy + niz*njz and w = 1 - |dot| in float64, left to right;
+ * edges are totally ordered by (w, min(i,j), max(i,j)) (a NaN weight, from overflowing normals, after every number), so the
+ * minimum spanning tree of every connected component is unique whatever ties.  A tree edge with dot < 0 joins opposite signs,
+ * dot >= 0 equal signs: this fixes every live vertex's flip relative to the lowest-index vertex of its component.
+ * Component sign: with reference (host, 3 doubles) every live vertex with finite coordinates votes with
+ * t = (cx-px)*nx + (cy-py)*ny + (cz-pz)*nz (float64, left to right, n as oriented so far): t > 0 toward, t < 0 away; away > toward
+ * flips the whole component.  On a tie, or with reference == NULL, the component's lowest-index vertex keeps its input sign.
+ * Output: every normal is its input or its exact negation (normals[n*3] float64, in place); a non-live vertex is its own component
+ * and is never written.  component[n] (int32 or NULL) = the lowest vertex index of the vertex's component.
+ * xyz[n*3] float32 may be NULL when reference is NULL.  n in [0, 2^31) and n * stride < 2^30; n == 0: GSR_OK and a zero report.
+ * Arrays all on the host or all on the device; the host waits once for the edge count and once per round (at most 32) for a 4-byte
+ * counter.  Integer atomics only: the same inputs give the same bits. */
+typedef struct gsr_orient_report {
+    int64_t n, n_components, n_flipped, n_not_live;   /* components: the non-live singletons included */
+    int32_t rounds, reserved;                         /* Boruvka rounds that hooked at least one component */
+    int64_t workspace_bytes;                          /* device memory the call reserves itself (host callers: the staged copies too) */
+    float phase_ms[4];                                /* lists, CSR and weights, rounds, labels + vote + flip: hipEvents on the stream */
+} gsr_orient_report;
+int32_t gsr_orient_normals_graph(const float* xyz, double* normals, int64_t n, const int32_t* nbr, int32_t stride, const int32_t* count,
+                                 const double* reference, int32_t* component, gsr_orient_report* report, int32_t on_device, int32_t device,
+                                 void* stream);
+/* The same over the lists of KDTreeSearchParamHybrid(radius, max_nn) (gsr_hybrid_search's, made on the device); xyz is required,
+ * radius finite and > 0, max_nn in [1, 512]. */
+int32_t gsr_orient_normals(const float* xyz, double* normals, int64_t n, double radius, int32_t max_nn, const double* reference,
+                           int32_t* component, gsr_orient_report* report, int32_t on_device, int32_t device, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -49,6 +49,9 @@ def main():
     method.add_argument("--global-fgr", type=float, metavar="VOXEL", help="global registration first by Fast Global Registration (FPFH + FGR at "
                     "this voxel size, the tab's other method); its pose is the multiscale ICP's initial transform")
     ap.add_argument("--ransac-iters", type=int, default=100000, help="RANSAC hypotheses (max_iteration) of --global-ransac")
+    ap.add_argument("--orient-normals", choices=("centroid", "consistent"), default="centroid", help="how --global-ransac / --global-fgr fix the "
+                    "normals' signs before FPFH: towards the cloud's centroid, or propagated along the neighbour graph's spanning forest "
+                    "(for scenes that are not star-shaped)")
     ap.add_argument("--out")
     ap.add_argument("--rotate-sh", action="store_true", help="turn the SH coefficients (view-dependent colour) of the moved cloud with it in the "
                     "merged output")
@@ -113,6 +116,7 @@ def main():
         v = a.global_ransac
         gp = RANSACRegistrationParams(voxel_size=v, max_correspondence=1.5 * v, max_iteration=a.ransac_iters, confidence=0.999,
                                       checkers=[G.CorrespondenceCheckerBasedOnEdgeLength(0.9), G.CorrespondenceCheckerBasedOnDistance(1.5 * v)])
+        gp.orient_normals = a.orient_normals                          # read by do_ransac_registration; not a field of the reference's record
         tg = time.perf_counter()
         g = rc.execute_ransac_registration_normal(gp)
         print(f"global RANSAC: fitness {g.fitness:.4f}  rmse {g.inlier_rmse:.6f}  hypotheses {g.info.get('n_evaluated')}  "
@@ -121,7 +125,9 @@ def main():
         from gaussiansplattingregistration_amd.params.registration_parameters import FGRRegistrationParams
         v = a.global_fgr
         tg = time.perf_counter()
-        g = rc.execute_fgr_registration_normal(FGRRegistrationParams(voxel_size=v, maximum_correspondence=1.5 * v))
+        fp = FGRRegistrationParams(voxel_size=v, maximum_correspondence=1.5 * v)
+        fp.orient_normals = a.orient_normals
+        g = rc.execute_fgr_registration_normal(fp)
         print(f"global FGR: fitness {g.fitness:.4f}  rmse {g.inlier_rmse:.6f}  reciprocal pairs {g.info.get('n_reciprocal')}  "
               f"tuples {g.info.get('n_tuples')} of {g.info.get('n_trials')} trials  {time.perf_counter() - tg:.3f} s")
     res = rc.execute_multiscale_registration(False, "", "", rtype, 1e-6, 1e-6, a.max_corr, a.iters, loss, a.k, not a.voxel, with_scaling=a.with_scaling)
