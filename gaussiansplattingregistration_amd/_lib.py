@@ -115,6 +115,7 @@ SIGNATURES = {
     "gsr_model_transform": (_i32, [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp]),
     "gsr_model_similarity": (_i32, [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp]),
     "gsr_model_fuse": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _vp]),
+    "gsr_fuse_multi": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _vp]),
     "gsr_outlier_mask": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp]),
     "gsr_model_select": (_i32, [_vp, _i32, _vp, _vp, _vp, C.POINTER(_i64), _i32, _i32, _vp]),
     "gsr_orient_normals_graph": (_i32, [_vp, _vp, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _vp]),
@@ -207,6 +208,16 @@ class FuseReport(C.Structure):
     """gsr_fuse_report (include/gsr_hip.h)."""
     _fields_ = [("n_out", C.c_int64), ("n_pairs", C.c_int64), ("n_a_only", C.c_int64), ("n_b_only", C.c_int64), ("n_invalid_a", C.c_int64),
                 ("n_invalid_b", C.c_int64), ("gated_pairs", C.c_int64), ("workspace_bytes", C.c_int64), ("phase_ms", C.c_float * 4)]
+
+
+GSR_FUSE_MAX_MODELS = 16
+
+
+class FuseMultiReport(C.Structure):
+    """gsr_fuse_multi_report (include/gsr_hip.h)."""
+    _fields_ = [("n_out", C.c_int64), ("n_groups", C.c_int64), ("n_grouped_rows", C.c_int64), ("n_invalid", C.c_int64), ("gated_pairs", C.c_int64),
+                ("mutual_edges", C.c_int64), ("rejected_edges", C.c_int64), ("rounds", C.c_int64), ("workspace_bytes", C.c_int64),
+                ("groups_of_size", C.c_int64 * (GSR_FUSE_MAX_MODELS + 1)), ("phase_ms", C.c_float * 6)]
 
 
 class CleanParams(C.Structure):

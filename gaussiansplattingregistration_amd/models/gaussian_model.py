@@ -364,6 +364,82 @@ class GaussianModel:
         return m, info
 
     @staticmethod
+    def fuse_overlap_multi(models, params):
+        """Overlap-aware merge of N models that are ALREADY IN ONE FRAME, in one pass (``gsr_fuse_multi``, ``csrc/fuse_multi.hip``;
+        1 <= N <= 16).  Splats of different models that match under the gates of ``params`` (``FuseOverlapParams``) form GROUPS with at
+        most one splat per model; a group is replaced by the moment-matched union of its members, every other row is kept bit for
+        bit.  Returns ``(model, info)``: the rows in no group in the order of the models, then the fused rows (ascending by lowest
+        member); ``info`` holds the report (``n_out``, ``n_groups``, ``n_grouped_rows``, ``n_invalid``, ``gated_pairs``,
+        ``mutual_edges``, ``rejected_edges``, ``rounds``, ``workspace_bytes``, ``groups_of_size``), ``group_of`` ((n_total,) int32: the
+        output row of each input row's group, -1 for a copied row) and ``phase_ms`` (device events).  The result tensors are views
+        ``[:n_out]`` of arrays allocated for all rows.  Host tensors are staged by the library; no GPU: ``RuntimeError``."""
+        import ctypes as C
+        models = list(models)
+        if not 1 <= len(models) <= _lib.GSR_FUSE_MAX_MODELS:
+            raise ValueError(f"{len(models)} models (1 to {_lib.GSR_FUSE_MAX_MODELS})")
+        L = _lib.load(require_device=True)
+        first = models[0]
+        N = len(models)
+        sizes = [len(g) for g in models]
+        total = sum(sizes)
+        Ks = [int(g._features_rest.shape[1]) if g._features_rest.dim() == 3 else 0 for g in models]
+        if any(g.sh_degree != first.sh_degree for g in models) or any(k != Ks[0] for k in Ks):
+            raise RuntimeError("the models carry different numbers of SH coefficients")
+        K = Ks[0]
+        on = bool(first._xyz.is_cuda)
+        if any(bool(g._xyz.is_cuda) != on or (on and g._xyz.device != first._xyz.device) for g in models):
+            raise RuntimeError("the models must all live on one device")
+        device = first._xyz.device.index if on else 0
+        have = [g._scaling.numel() > 0 and g._rotation.numel() > 0 for g, n in zip(models, sizes) if n > 0]
+        if have and any(h != have[0] for h in have):
+            raise RuntimeError("_scaling / _rotation: some models carry them, others do not")
+        with_sr = bool(have and have[0])
+        views = (_lib.ModelView * N)()
+        out_view = _lib.ModelView()
+        out_view.n = total
+        keep, outs = [], {}
+        field = {"_xyz": "xyz", "_covariance": "cov6", "_features_dc": "dc", "_features_rest": "sh", "_opacity": "opacity", "_scaling": "scaling",
+                 "_rotation": "rot"}
+        for name, width in GaussianModel._FUSE_ARRAYS:
+            width = 3 * K if width is None else width
+            if width == 0 or (name in ("_scaling", "_rotation") and not with_sr):
+                continue
+            for v, g, n in zip(views, models, sizes):
+                v.n = n
+                if n == 0:
+                    continue
+                p, k, t_on = _m.prep(getattr(g, name), (n, width), np.float32, device)
+                if t_on != on:
+                    raise RuntimeError("the model's tensors must all live on one device")
+                keep.append(k)
+                setattr(v, field[name], p)
+            outs[name], p = _m.out((total, width), np.float32, device, on)
+            setattr(out_view, field[name], p)
+        group_of, pgroup = _m.out((total,), np.int32, device, on)
+        P = _lib.FuseParams(float(params.max_distance), float(params.kld_max), float(params.color_delta))
+        R = _lib.FuseMultiReport()
+        if on:
+            torch.cuda.current_stream(device).synchronize()
+        _lib.check(L.gsr_fuse_multi(C.addressof(views), N, K, C.addressof(P), C.addressof(out_view), pgroup, C.addressof(R), 1 if on else 0,
+                                          device, C.c_void_p(_m.stream_ptr(device, on))), "gsr_fuse_multi")
+        n_out = int(R.n_out)
+        m = GaussianModel(first.device_name)
+        m.sh_degree = first.sh_degree
+        shapes = {"_features_dc": (1, 3), "_features_rest": (K, 3)}
+        for name, _ in GaussianModel._FUSE_ARRAYS:
+            if name in outs:
+                t = torch.as_tensor(outs[name])[:n_out]
+                setattr(m, name, t.view((n_out,) + shapes[name]) if name in shapes else t)
+            elif name == "_features_rest":
+                setattr(m, name, torch.empty((n_out, 0, 3), dtype=torch.float32, device=m._xyz.device))
+        info = {k: int(getattr(R, k)) for k in ("n_out", "n_groups", "n_grouped_rows", "n_invalid", "gated_pairs", "mutual_edges", "rejected_edges", "rounds",
+                                                "workspace_bytes")}
+        info["groups_of_size"] = [int(x) for x in R.groups_of_size]
+        info["group_of"] = torch.as_tensor(group_of)
+        info["phase_ms"] = dict(zip(("prepass_grid", "search", "edges", "rounds", "write"), (float(x) for x in R.phase_ms)))      # device events of the call
+        return m, info
+
+    @staticmethod
     def get_merged_gaussian_point_clouds(gaussian1, gaussian2, transformation_matrix, rotate_sh=False, with_scaling=False, fuse=None):
         """``gaussian1`` moved by the registration result, concatenated with ``gaussian2`` (the merged-cloud save).
         ``with_scaling``: the matrix is a similarity (``similarity_transform_gaussian_model``); ``_scaling`` moves too.
@@ -418,13 +494,18 @@ class GaussianModel:
         return m
 
     @staticmethod
-    def get_merged_gaussian_point_clouds_multi(models, poses, rotate_sh=False):
+    def get_merged_gaussian_point_clouds_multi(models, poses, rotate_sh=False, fuse=None):
         """N models, each moved by its rigid pose (4x4, the model's frame -> the common frame: the node poses of a multiway
         registration), concatenated in the order given.  The output arrays are allocated once and every model's fused transform
         kernel (``_transform_kernel(..., into=)``) writes straight into the model's rows: no clone, no ``cat``.  Rows
         ``[sum(n_0..n_i-1), sum(n_0..n_i))`` are bit for bit what ``transform_gaussian_model(poses[i], rotate_sh)`` gives for model
         ``i`` alone; a model whose pose is the identity is copied as it is, as in the pairwise merge.  The models stay as they
-        were.  All of them must live on one CUDA device, with one SH degree and the same set of arrays."""
+        were.  All of them must live on one CUDA device, with one SH degree and the same set of arrays.
+        ``fuse`` (``FuseOverlapParams``; default ``None``: the plain concatenation above): move, then ``fuse_overlap_multi`` -- a surface
+        that k models share is stored once.  Refused (``RuntimeError``) when the models have SH coefficients, a pose rotates and
+        ``rotate_sh`` is false."""
+        if fuse is not None:
+            return GaussianModel.get_merged_gaussian_point_clouds_fused_multi(models, poses, fuse, rotate_sh=rotate_sh)[0]
         models, poses = list(models), [np.asarray(p, dtype=np.float64).reshape(4, 4) for p in poses]
         if not models or len(models) != len(poses):
             raise ValueError(f"{len(models)} models and {len(poses)} poses")
@@ -462,6 +543,28 @@ class GaussianModel:
                     o[off:off + n].copy_(getattr(g, name))
             off += n
         return m
+
+    @staticmethod
+    def get_merged_gaussian_point_clouds_fused_multi(models, poses, fuse, rotate_sh=False):
+        """Every model moved by its pose, then ``fuse_overlap_multi`` -> ``(model, info)``: what
+        ``get_merged_gaussian_point_clouds_multi(..., fuse=params)`` returns the model of, with the report.  The models stay as they
+        were; a model whose pose is the identity is used as it is."""
+        models, poses = list(models), [np.asarray(p, dtype=np.float64).reshape(4, 4) for p in poses]
+        if not models or len(models) != len(poses):
+            raise ValueError(f"{len(models)} models and {len(poses)} poses")
+        moved = []
+        for g, T in zip(models, poses):
+            if len(g) == 0 or np.array_equal(T, np.eye(4)):
+                moved.append(g)
+                continue
+            A = T[:3, :3]
+            rotates = not (np.count_nonzero(A - np.diag(np.diag(A))) == 0 and A[0, 0] == A[1, 1] == A[2, 2] and A[0, 0] > 0)
+            K = int(g._features_rest.shape[1]) if g._features_rest.dim() == 3 else 0
+            if K > 0 and rotates and not rotate_sh:
+                raise RuntimeError("fuse needs rotate_sh=True when a pose rotates a model with SH coefficients: an average of SH rows "
+                                   "in two frames means nothing")
+            moved.append(g.clone_gaussian().transform_gaussian_model(T, rotate_sh=rotate_sh))
+        return GaussianModel.fuse_overlap_multi(moved, fuse)
 
     @staticmethod
     def get_fused_gaussian_point_clouds(gaussian1, gaussian2, transformation_matrix, fuse, rotate_sh=False, with_scaling=False):

@@ -63,10 +63,11 @@ class MultiwayRegistrator:
             self.edge_reports = edge_reports        # one dict per requested edge
             self.optimization = optimization        # GlobalOptimizationReport
 
-    def __init__(self, clouds, params, edges="sequential", init=None, option=None, criteria=None, progress=None):
+    def __init__(self, clouds, params, edges="sequential", init=None, option=None, criteria=None, progress=None, fuse=None):
         """``clouds``: the ``PointCloud`` records; ``params``: ``LocalRegistrationParams`` of every pairwise ICP; ``init``: ``None``
         (identity), ``{(s, t): T}`` (missing pairs: identity) or ``callable(s, t, cloud_s, cloud_t) -> T`` (e.g. a global
-        registration); ``option`` (``GlobalOptimizationOption``): default ``max_correspondence_distance = params.max_correspondence``."""
+        registration); ``option`` (``GlobalOptimizationOption``): default ``max_correspondence_distance = params.max_correspondence``;
+        ``fuse`` (``FuseOverlapParams`` or ``None``): what ``merge`` hands to ``get_merged_gaussian_point_clouds_multi``."""
         self.clouds, self.params = list(clouds), params
         self.edges = edge_list(len(self.clouds), edges)
         self.init = init
@@ -76,6 +77,18 @@ class MultiwayRegistrator:
         self.signal_cancel = False
         self._progress = progress
         self.timing = {}
+        self.fuse = fuse                    # FuseOverlapParams or None: the merge stores a surface that k scenes share once
+        self.fuse_info = None               # the report of the last merge with `fuse`
+
+    def merge(self, models, result, rotate_sh=False):
+        """The ``GaussianModel`` s of the clouds, each moved by its pose of ``result`` (what ``run`` returned), in one model:
+        concatenated, or -- with ``fuse`` -- with the overlaps fused (``GaussianModel.fuse_overlap_multi``; the report goes to
+        ``fuse_info``)."""
+        from ..models.gaussian_model import GaussianModel
+        if self.fuse is None:
+            return GaussianModel.get_merged_gaussian_point_clouds_multi(models, result.poses, rotate_sh=rotate_sh)
+        merged, self.fuse_info = GaussianModel.get_merged_gaussian_point_clouds_fused_multi(models, result.poses, self.fuse, rotate_sh=rotate_sh)
+        return merged
 
     def cancel(self):
         self.signal_cancel = True

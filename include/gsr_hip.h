@@ -714,6 +714,42 @@ typedef struct gsr_fuse_report {
 int32_t gsr_model_fuse(const gsr_model_view* a, const gsr_model_view* b, int32_t K, const gsr_fuse_params* params, gsr_model_view* out,
                        int32_t* pairs, gsr_fuse_report* report, int32_t on_device, int32_t device, void* stream);
 
+/* Fuse the overlaps of N models that are ALREADY IN ONE FRAME, in one pass: csrc/fuse_multi.hip; restated in
+ * float64 NumPy in tests/fuse_multi_model.py.  Rows get a GLOBAL index g, model-major (the rows of models[0] first, ascending).
+ *   valid, gates, J   exactly gsr_model_fuse's; J of a pair is evaluated with the lower global index in the role of `a`.
+ *   best[i][m]        for a valid row i and every model m other than its own: the gated candidate j of model m with the smallest
+ *                     (J32, j), or none.
+ *   mutual edge       {i, j}, i < j, iff best[i][model(j)] = j and best[j][model(i)] = i; its key is (J32, i, j), a strict total order.
+ *   groups            by rounds.  Every row starts as a component with the model mask 1 << model.  An edge is LIVE while its ends lie
+ *                     in different components with disjoint masks.  In a round every component picks the live edge with the smallest
+ *                     key among those that touch it, and an edge picked by BOTH its components merges them (the label becomes the
+ *                     lower one -- the lowest member --, the masks are OR-ed).  Rounds repeat until one has no live edge.  A group
+ *                     never holds two rows of one model; the partition depends on nothing but the keys.
+ *   fusion            a group with members i_1 < ... < i_k, k >= 2: sums in ascending member order in float64, narrowed once:
+ *                     W = sum w;  m = (sum w m_i) / W;  C = (sum w (C_i + (m_i - m)(m_i - m)^T)) / W;  dc, every sh coefficient and
+ *                     the RAW opacity (sum w v_i) / W.  With scaling / rot: GSR_DECOMP_EXACT of the fused (float32) covariance.
+ *   output            the rows in no group of two or more, in global order, bit for bit; then the fused rows, ascending by lowest
+ *                     member: n_out = n_total - sum (k - 1).
+ * models[n_models], 1 <= n_models <= GSR_FUSE_MAX_MODELS, views as in gsr_model_fuse (scaling / rot: in every model that has rows, or
+ * in none).  out->n: the capacity in rows (>= n_total) on entry, n_out on return.  group_of: int32 n_total (or NULL) -- the output row
+ * of each input row's group, -1 for a copied row.  n_total and n_total * n_models must be below 2^31.  Everything else (where the
+ * arrays live, the overlap rule, the refused arguments) is gsr_model_fuse's; n_models = 1 copies the model.  One stream; the host
+ * waits once for the edge count, once per round (the merge count) and once for the group count.  Deterministic. */
+#define GSR_FUSE_MAX_MODELS 16
+typedef struct gsr_fuse_multi_report {
+    int64_t n_out, n_groups, n_grouped_rows;   /* n_out = n_total - n_grouped_rows + n_groups */
+    int64_t n_invalid;                         /* over all models */
+    int64_t gated_pairs;                       /* the unordered pairs of rows of two models that passed all three gates */
+    int64_t mutual_edges;
+    int64_t rejected_edges;                    /* mutual edges that died between two components whose masks intersect */
+    int64_t rounds;                            /* the rounds that had a live edge */
+    int64_t workspace_bytes;                   /* device memory the call allocated beyond the caller's arrays and the staged copies */
+    int64_t groups_of_size[GSR_FUSE_MAX_MODELS + 1];      /* [k] = the groups of k members (k >= 2) */
+    float phase_ms[6];                         /* pre-pass + grid, search, edge list, rounds, ranks + writer, 0: hipEvents on the stream */
+} gsr_fuse_multi_report;
+int32_t gsr_fuse_multi(const gsr_model_view* models, int32_t n_models, int32_t K, const gsr_fuse_params* params, gsr_model_view* out,
+                             int32_t* group_of, gsr_fuse_multi_report* report, int32_t on_device, int32_t device, void* stream);
+
 /* ------------------------------------------------------------------- floater removal: outlier masks and row selection */
 
 /* Which rows of a cloud or splat model survive cleaning: Open3D 0.16's RemoveStatisticalOutlier and RemoveRadiusOutlier, restated

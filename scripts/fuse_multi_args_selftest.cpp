@@ -1,0 +1,89 @@
+// fuse_multi_args_selftest.cpp -- the host-only argument checks of gsr_fuse_multi (csrc/gsr_fuse_multi_args.h) as a stand-alone
+// program for the host sanitizers:
+//
+//     g++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=all scripts/fuse_multi_args_selftest.cpp -o fuse_multi_args_selftest
+//     ./fuse_multi_args_selftest
+//
+// Prints "ok" and returns 0, or says which case went wrong.
+#include <math.h>
+#include <string.h>
+
+#include <vector>
+
+#include "../gaussiansplattingregistration_amd/csrc/gsr_fuse_multi_args.h"
+
+using namespace gsr;
+
+struct Call {
+    static constexpr int N = 3, ROWS = 8, K = 15;
+    std::vector<std::vector<float>> store;
+    gsr_model_view models[GSR_FUSE_MAX_MODELS + 1];
+    gsr_model_view out;
+    gsr_fuse_params params{0.25, 0.5, INFINITY};
+    gsr_fuse_multi_report report;
+    std::vector<int32_t> group_of;
+    float* arr(size_t n) { store.emplace_back(n, 0.5f); return store.back().data(); }
+    void fill(gsr_model_view* v, int64_t rows, bool sr) {
+        memset(v, 0, sizeof(*v));
+        v->n = rows;
+        v->xyz = arr(rows * 3); v->cov6 = arr(rows * 6); v->dc = arr(rows * 3); v->sh = arr(rows * 3 * K); v->opacity = arr(rows);
+        if (sr) { v->scaling = arr(rows * 3); v->rot = arr(rows * 4); }
+    }
+    explicit Call(bool sr = false) : group_of(N * ROWS) {
+        store.reserve(256);
+        for (int m = 0; m < N; ++m) fill(models + m, ROWS, sr);
+        fill(&out, N * ROWS, sr);
+    }
+    const char* check(int n_models = N, int k = K) {
+        int64_t off[GSR_FUSE_MAX_MODELS + 1];
+        size_t width[FM_NARR];
+        bool used[FM_NARR], with_sr = false;
+        char buf[256];
+        const char* r = fuse_multi_check_args(models, n_models, k, &params, &out, group_of.data(), &report, off, width, used, &with_sr, buf, sizeof buf);
+        if (!r && off[n_models] != (int64_t)n_models * ROWS) return "wrong offsets";
+        return r ? "refused" : nullptr;
+    }
+};
+
+static int failures = 0;
+#define EXPECT(cond, what) do { if (!(cond)) { printf("FAILED: %s\n", what); ++failures; } } while (0)
+
+int main() {
+    { Call c; EXPECT(!c.check(), "a valid call"); }
+    { Call c(true); EXPECT(!c.check(), "a valid call with scaling / rot"); }
+    { Call c; EXPECT(!c.check(1) && !c.check(2), "fewer models"); }
+    for (int n : {-1, 0, 17, 1 << 30}) { Call c; EXPECT(c.check(n), "n_models out of range"); }
+    for (int k : {-1, 1, 2, 4, 16}) { Call c; EXPECT(c.check(Call::N, k), "K"); }
+    for (double r : {0.0, -1.0, (double)INFINITY, (double)NAN}) { Call c; c.params.max_distance = r; EXPECT(c.check(), "max_distance"); }
+    { Call c; c.params.kld_max = NAN; EXPECT(c.check(), "kld_max NaN"); }
+    { Call c; c.params.color_delta = -1.0; EXPECT(c.check(), "color_delta < 0"); }
+    { Call c; c.models[2].cov6 = nullptr; EXPECT(c.check(), "NULL input array"); }
+    { Call c; c.out.opacity = nullptr; EXPECT(c.check(), "NULL output array"); }
+    { Call c(true); c.models[1].scaling = nullptr; EXPECT(c.check(), "scaling without rot"); }
+    { Call c(true); c.models[1].scaling = c.models[1].rot = nullptr; EXPECT(c.check(), "mixed array sets"); }
+    { Call c; c.models[0].n = (int64_t)1 << 31; EXPECT(c.check(), "row count 2^31"); }
+    { Call c; c.models[2].n = -1; EXPECT(c.check(), "negative row count"); }
+    { Call c; c.out.n = 23; EXPECT(c.check(), "capacity below n_total"); }
+    { Call c; c.out.xyz = c.models[2].xyz; EXPECT(c.check(), "output on an input"); }
+    { Call c; c.out.sh = c.models[1].sh + 4; EXPECT(c.check(), "output inside an input"); }
+    { Call c; c.out.dc = c.out.xyz + 3; EXPECT(c.check(), "two outputs overlap"); }
+    {   // an empty model among full ones carries no arrays and decides nothing
+        Call c(true);
+        memset(&c.models[1], 0, sizeof(gsr_model_view));
+        int64_t off[GSR_FUSE_MAX_MODELS + 1];
+        size_t width[FM_NARR];
+        bool used[FM_NARR], with_sr = false;
+        char buf[256];
+        const char* r = fuse_multi_check_args(c.models, 3, 15, &c.params, &c.out, nullptr, &c.report, off, width, used, &with_sr, buf, sizeof buf);
+        EXPECT(!r && with_sr && off[1] == 8 && off[2] == 8 && off[3] == 16 && used[5] && used[6] && width[3] == 45, "an empty model among full ones");
+    }
+    {   // n_total * n_models must stay below 2^31: 16 models of 2^27 rows (the arrays are never touched by the checks up to there)
+        Call c;
+        for (int m = 0; m < 16; ++m) { c.models[m] = c.models[0]; c.models[m].n = (int64_t)1 << 27; }
+        c.out.n = (int64_t)1 << 31;
+        EXPECT(c.check(16), "n_total * n_models >= 2^31");
+    }
+    if (failures) return 1;
+    printf("ok\n");
+    return 0;
+}

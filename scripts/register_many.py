@@ -7,13 +7,16 @@ registered pair, a pose graph with a line process that prunes wrongly registered
            [--type point|plane|color|general] [--loss none|tukey|cauchy|gm|huber --k 0.1] [--max-corr 0.05] [--iters 30]
            [--prune 0.25] [--preference 1.0] [--reference 0] [--rotate-sh]
            [--clean-knn K --clean-std R [--clean-radius R --clean-nb N] [--clean-min-opacity A] [--clean-max-extent S]]
+           [--fuse-overlap MAX_DIST [--fuse-kld 0.5] [--fuse-color X]]
 
 Edges: `--edges sequential` registers each scene to the next (a chain), `--edges all` every pair; `--edge S T` (repeatable) adds the pair
 (S, T).  An edge (i, i + 1) is certain ("odometry"); every other edge is a loop closure the optimiser may prune (`--prune`: the line
 process value below which it does).  Without a global method every pair starts from the identity: the scenes must be roughly aligned.
 The poses map each scene into the frame of scene `--reference`; `--poses-out` holds them with the edges, their line process values
 and the pruned edges.  `--clean-*`: every scene goes through floater removal right after loading (scripts/clean_ply.py has the stages);
-prints n -> n_kept per scene.
+prints n -> n_kept per scene.  `--fuse-overlap MAX_DIST`: the merged cloud stores a surface that k scenes share once
+(GaussianModel.fuse_overlap_multi: groups of at most one splat per scene, moment-matched); it implies --rotate-sh and prints n_groups, the
+histogram of the group sizes and n_out.
 """
 import argparse
 import json
@@ -46,6 +49,9 @@ def main():
     ap.add_argument("--preference", type=float, default=1.0, help="preference_loop_closure")
     ap.add_argument("--reference", type=int, default=0, help="reference_node: the scene whose frame the result is in")
     ap.add_argument("--rotate-sh", action="store_true", help="turn the SH coefficients of every moved scene with it in the merged output")
+    ap.add_argument("--fuse-overlap", type=float, metavar="MAX_DIST", help="fuse the splats the scenes share (within this distance) in the merged output; implies --rotate-sh")
+    ap.add_argument("--fuse-kld", type=float, default=0.5, help="symmetrised KL gate of --fuse-overlap")
+    ap.add_argument("--fuse-color", type=float, default=float("inf"), help="DC colour gate of --fuse-overlap (default: none)")
     from gaussiansplattingregistration_amd.clean import add_clean_arguments, clean_params_from_args
     add_clean_arguments(ap)
     a = ap.parse_args()
@@ -94,7 +100,11 @@ def main():
     params = LocalRegistrationParams(registration_type=rtype, max_correspondence=a.max_corr, max_iteration=a.iters, rejection_type=loss, k_value=a.k)
     option = GlobalOptimizationOption(max_correspondence_distance=a.max_corr, edge_prune_threshold=a.prune, preference_loop_closure=a.preference,
                                       reference_node=a.reference)
-    worker = MultiwayRegistrator(clouds, params, edges=edges, init=init, option=option)
+    fuse = None
+    if a.fuse_overlap is not None:
+        from gaussiansplattingregistration_amd.params import FuseOverlapParams
+        fuse = FuseOverlapParams(a.fuse_overlap, a.fuse_kld, a.fuse_color)
+    worker = MultiwayRegistrator(clouds, params, edges=edges, init=init, option=option, fuse=fuse)
     res = worker.run()
     t2 = time.perf_counter()
     if res is None:
@@ -120,7 +130,12 @@ def main():
             json.dump(doc, f, indent=1)
         print(f"poses -> {a.poses_out}")
     if a.out:
-        merged = GaussianModel.get_merged_gaussian_point_clouds_multi(models, res.poses, rotate_sh=a.rotate_sh)
+        merged = worker.merge(models, res, rotate_sh=a.rotate_sh or fuse is not None)
+        if fuse is not None:
+            info = worker.fuse_info
+            sizes = "  ".join(f"{k}: {c}" for k, c in enumerate(info["groups_of_size"]) if c)
+            print(f"fuse: n_groups {info['n_groups']}  sizes {{{sizes}}}  n_grouped_rows {info['n_grouped_rows']}  rejected_edges {info['rejected_edges']}  "
+                  f"rounds {info['rounds']}  n_out {info['n_out']}")
         merged.save_ply(a.out)
         print(f"merged cloud ({len(merged)} splats) -> {a.out}")
 

@@ -1,0 +1,251 @@
+"""The float64 model of the N-way overlap merge (tests/fuse_multi_model.py) against the pairwise model and planted groups, the
+unambiguity of every fixture the GPU tests use, and the ABI of gsr_fuse_multi.  No GPU."""
+import ctypes as C
+import inspect
+
+import numpy as np
+import pytest
+import torch
+
+import fuse_model as F
+import fuse_multi_model as M
+from gaussiansplattingregistration_amd import synth
+
+
+# torch looks for the device before the library's first call does: the other way round, the HIP runtime the library links is up first
+# and torch.cuda.is_available() of the same process -- which later test files of a run decide by -- reports no device
+torch.cuda.is_available()
+
+
+def _no_two_rows_of_a_model(r):
+    for g in r["groups"]:
+        assert len(g) >= 2 and np.all(np.diff(g) > 0)
+        assert len(set(r["model_id"][g])) == len(g)
+
+
+def _arithmetic(r):
+    n = len(r["group_of"])
+    sizes = [len(g) for g in r["groups"]]
+    assert r["n_groups"] == len(sizes) and r["n_grouped_rows"] == sum(sizes)
+    assert r["n_out"] == n - sum(k - 1 for k in sizes) == r["n_copied"] + r["n_groups"]
+    assert r["groups_of_size"] == [sizes.count(k) for k in range(M.MAX_MODELS + 1)]
+    assert len(r["xyz"]) == r["n_out"]
+    lowest = [g[0] for g in r["groups"]]
+    assert lowest == sorted(lowest)
+    for rank, g in enumerate(r["groups"]):
+        assert (r["group_of"][g] == r["n_copied"] + rank).all()
+    assert (r["group_of"] == -1).sum() == r["n_copied"]
+
+
+@pytest.mark.parametrize("name", F.CASES)
+def test_two_models_give_the_pairwise_model(name):
+    """N = 2: the pair set and the fused float64 rows of fuse_model.fuse, on every case of fuse_model"""
+    A, B, gates, want = F.case(name)
+    got = M.fuse_multi([A, B], *gates)
+    na = len(A["xyz"])
+    pairs = np.array([[g[0], g[1] - na] for g in got["groups"]], np.int64).reshape(-1, 2)
+    assert np.array_equal(pairs, want["pairs"])
+    assert got["n_out"] == want["n_out"] and got["n_invalid"] == want["n_invalid_a"] + want["n_invalid_b"]
+    assert got["gated_pairs"] == want["n_gated"] and got["rejected_edges"] == 0 and got["rounds"] == (1 if len(pairs) else 0)
+    for k, v in want["fused"].items():
+        if k in ("scaling", "rot"):
+            continue
+        assert np.array_equal(got["fused"][k], v), k             # the same float64 expression for two members
+    # the copied rows: A's then B's in order (the pairwise output puts the fused block between them)
+    a0, p0 = want["n_a_only"], want["n_a_only"] + want["n_pairs"]
+    for k in ("xyz", "cov6", "dc", "opacity"):
+        w = np.asarray(want[k], np.float32).reshape(want["n_out"], -1)
+        cat = np.concatenate([w[:a0], w[p0:]])
+        assert np.array_equal(got[k][:got["n_copied"]].view(np.uint32), cat.view(np.uint32)), k
+    _arithmetic(got)
+
+
+def _planted(n_models, sizes_of_groups, seed):
+    """far-apart anchors, each with noisy copies in `k` distinct models: the groups are known"""
+    rng = np.random.default_rng(seed)
+    base = F.model_of(synth.make_cloud(len(sizes_of_groups), seed=seed, h=50.0, sh_degree=1))
+    base["xyz"] = (np.arange(len(sizes_of_groups))[:, None] * np.float32([3.0, 0, 0]) + rng.normal(size=(len(sizes_of_groups), 3))).astype(np.float32)
+    rows = [[] for _ in range(n_models)]
+    want = []
+    for a, k in enumerate(sizes_of_groups):
+        members = []
+        for m in sorted(rng.choice(n_models, k, replace=False)):
+            row = {name: v[a].copy() for name, v in base.items()}
+            row["xyz"] = (row["xyz"] + 1e-3 * rng.normal(size=3)).astype(np.float32)
+            members.append((int(m), len(rows[m])))
+            rows[m].append(row)
+        want.append(members)
+    models = [{name: np.stack([r[name] for r in rs]) if rs else base[name][:0].copy() for name in base} for rs in rows]
+    return models, want
+
+
+@pytest.mark.parametrize("n_models,k", [(3, 3), (4, 4), (7, 4), (16, 16)])
+def test_planted_groups_are_recovered_exactly(n_models, k):
+    sizes = [k, 1, k, 2, k - 1, 1, k] * 6
+    models, want = _planted(n_models, sizes, seed=10 * n_models + k)
+    r = M.fuse_multi(models, 0.25, 50.0, np.inf)
+    off = r["offsets"]
+    expect = sorted(sorted(off[m] + i for m, i in g) for g in want if len(g) >= 2)
+    assert sorted(sorted(int(x) for x in g) for g in r["groups"]) == expect
+    assert r["rejected_edges"] == 0 and not r["ambiguous"], r["why"]
+    _no_two_rows_of_a_model(r)
+    _arithmetic(r)
+
+
+def test_conflict_chain():
+    models, gates, r = M.case("chain")
+    assert [list(g) for g in r["groups"]] == [[0, 2], [1, 3]]       # {a1, b1}, {a2, c1}
+    assert r["mutual_edges"] == 3 and r["rejected_edges"] == 1 and r["rounds"] == 1
+    _no_two_rows_of_a_model(r)
+
+
+@pytest.mark.parametrize("name", M.GPU_CASES + tuple("pair_" + c for c in F.CASES if c not in ("ties", "large")))
+def test_gpu_fixtures_are_unambiguous(name):
+    """what tests/test_fuse_multi_gpu.py compares exactly must not depend on which correct float64 implementation computed it"""
+    models, gates, r = M.case(name)
+    assert not r["ambiguous"], r["why"]
+    _no_two_rows_of_a_model(r)
+    _arithmetic(r)
+
+
+def test_fixtures_cover_what_they_are_for():
+    assert M.case("grid_16_64_0")[2]["rejected_edges"] > 0 and M.case("one_cell")[2]["rejected_edges"] > 0
+    assert max(k for k, c in enumerate(M.case("grid_16_3000_0")[2]["groups_of_size"]) if c) >= 12
+    assert M.case("invalid")[2]["n_invalid"] == 12
+    assert M.case("large")[2]["n_groups"] > 100000 and len(M.case("large")[2]["group_of"]) > 2048 * 256
+    assert M.case("scaling_rot")[2]["n_groups"] > 100 and "scaling" in M.case("scaling_rot")[2]
+
+
+def test_library_exports_the_entry_point_and_the_report_matches_the_stub(hip_lib):
+    """the call clears exactly sizeof(gsr_fuse_multi_report) bytes of the report before it looks for a device"""
+    from gaussiansplattingregistration_amd import _lib
+    assert hasattr(hip_lib, "gsr_fuse_multi") and hasattr(hip_lib, "gsr_model_fuse_multi")       # (the second: the same function, exported only)
+    assert "gsr_fuse_multi" in _lib.SIGNATURES and _lib.GSR_FUSE_MAX_MODELS == 16
+    size = C.sizeof(_lib.FuseMultiReport)
+    assert size == 9 * 8 + 17 * 8 + 6 * 4
+    buf = (C.c_ubyte * (size + 64))(*([0xAB] * (size + 64)))
+    view, out = _lib.ModelView(), _lib.ModelView()              # one empty model: valid arguments
+    P = _lib.FuseParams(0.25, 0.5, float("inf"))
+    rc = hip_lib.gsr_fuse_multi(C.addressof(view), 1, 0, C.addressof(P), C.addressof(out), None, C.addressof(buf), 0, 0, None)
+    assert rc in (_lib.GSR_OK, _lib.GSR_E_NO_DEVICE), hip_lib.gsr_last_error()
+    raw = bytes(buf)
+    assert raw[:size] == bytes(size) and raw[size:] == bytes([0xAB] * 64)
+    # refused arguments are refused before anything is written
+    buf2 = (C.c_ubyte * size)(*([0xCD] * size))
+    for n_models in (0, 17):
+        assert hip_lib.gsr_fuse_multi(C.addressof(view), n_models, 0, C.addressof(P), C.addressof(out), None, C.addressof(buf2), 0, 0, None) == _lib.GSR_E_INVALID
+        assert b"n_models" in hip_lib.gsr_last_error()
+    assert bytes(buf2) == bytes([0xCD] * size)
+
+
+def test_python_signatures():
+    from gaussiansplattingregistration_amd.models.gaussian_model import GaussianModel
+    from gaussiansplattingregistration_amd.workers.multiway import MultiwayRegistrator
+    sig = inspect.signature(GaussianModel.get_merged_gaussian_point_clouds_multi)
+    assert list(sig.parameters) == ["models", "poses", "rotate_sh", "fuse"]
+    assert sig.parameters["fuse"].default is None and sig.parameters["rotate_sh"].default is False
+    assert inspect.signature(MultiwayRegistrator.__init__).parameters["fuse"].default is None
+    assert callable(GaussianModel.fuse_overlap_multi) and callable(GaussianModel.get_merged_gaussian_point_clouds_fused_multi)
+
+
+def _views(N=3, n=8, K=15, with_sr=False):
+    from gaussiansplattingregistration_amd import _lib
+    rng = np.random.default_rng(0)
+    keep = []
+
+    def arr(*shape):
+        keep.append(rng.random(shape).astype(np.float32))
+        return keep[-1].ctypes.data
+
+    def fill(v, rows):
+        v.n = rows
+        v.xyz, v.dc, v.sh, v.opacity = arr(rows, 3), arr(rows, 3), arr(rows, 3 * K), arr(rows)
+        keep.append(np.tile(np.float32([1, 0, 0, 1, 0, 1]), (rows, 1)))
+        v.cov6 = keep[-1].ctypes.data
+        if with_sr:
+            v.scaling, v.rot = arr(rows, 3), arr(rows, 4)
+    views, o = (_lib.ModelView * N)(), _lib.ModelView()
+    for v in views:
+        fill(v, n)
+    fill(o, N * n)
+    return views, o, _lib.FuseParams(0.25, 0.5, float("inf")), _lib.FuseMultiReport(), keep
+
+
+def test_invalid_arguments(hip_lib):
+    """the checks come before the device is opened: GSR_E_INVALID with or without a GPU"""
+    L = hip_lib
+
+    def refused(mutate, K=15, with_sr=False, null=None, n_models=3):
+        m, o, P, R, keep = _views(with_sr=with_sr)
+        group_of = np.zeros(24, np.int32)
+        keep.append(group_of)
+        extra = mutate(m, o, P)
+        args = [C.addressof(m), n_models, K, C.addressof(P), C.addressof(o), extra if isinstance(extra, int) else group_of.ctypes.data, C.addressof(R), 0, 0, None]
+        if null is not None:
+            args[null] = None
+        assert L.gsr_fuse_multi(*args) == -1, mutate
+        assert b"gsr_fuse_multi" in L.gsr_last_error()
+    nothing = lambda m, o, P: None
+    for i in (0, 3, 4, 6):
+        refused(nothing, null=i)                                        # NULL models, params, out, report
+    for n_models in (-1, 0, 17):
+        refused(nothing, n_models=n_models)
+    for K in (-1, 1, 2, 4, 16):
+        refused(nothing, K=K)
+    for r in (0.0, -1.0, float("inf"), float("nan")):
+        refused(lambda m, o, P: setattr(P, "max_distance", r))
+    refused(lambda m, o, P: setattr(P, "kld_max", float("nan")))
+    refused(lambda m, o, P: setattr(P, "color_delta", -1.0))
+    for f in ("xyz", "cov6", "dc", "sh", "opacity"):
+        refused(lambda m, o, P: setattr(m[2], f, None))
+        refused(lambda m, o, P: setattr(o, f, None))
+    refused(lambda m, o, P: setattr(m[1], "scaling", None), with_sr=True)       # scaling without rot
+    refused(lambda m, o, P: (setattr(m[1], "scaling", None), setattr(m[1], "rot", None)), with_sr=True)      # mixed array sets
+    refused(lambda m, o, P: (setattr(o, "scaling", None), setattr(o, "rot", None)), with_sr=True)
+    refused(lambda m, o, P: setattr(m[0], "n", 1 << 31))
+    refused(lambda m, o, P: setattr(m[2], "n", -1))
+    refused(lambda m, o, P: setattr(o, "n", 23))                        # capacity below n_total
+    refused(lambda m, o, P: setattr(o, "xyz", m[2].xyz))                # not in place
+    refused(lambda m, o, P: setattr(o, "sh", m[1].sh + 16))
+    refused(lambda m, o, P: setattr(o, "dc", o.xyz + 12))               # two outputs overlap
+    refused(lambda m, o, P: o.opacity + 4)                              # group_of inside an output
+
+
+def test_with_and_without_a_device(hip_lib):
+    """valid host arrays: GSR_E_NO_DEVICE and a message that names the function where the library sees no device, GSR_OK where it does"""
+    m, o, P, R, keep = _views()
+    rc = hip_lib.gsr_fuse_multi(C.addressof(m), 3, 15, C.addressof(P), C.addressof(o), None, C.addressof(R), 0, 0, None)
+    if hip_lib.gsr_device_count() <= 0:
+        msg = hip_lib.gsr_last_error()
+        assert rc == -3 and b"no HIP device" in msg and b"gsr_fuse_multi" in msg, (rc, msg)      # GSR_E_NO_DEVICE
+    else:
+        assert rc == 0 and o.n == R.n_out <= 24 and R.n_invalid == 0, (rc, hip_lib.gsr_last_error())
+
+
+def test_register_many_shows_the_flags():
+    import os
+    import subprocess
+    import sys
+    from conftest import ROOT
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "scripts", "register_many.py"), "--help"], capture_output=True, text=True, check=True).stdout
+    for flag in ("--fuse-overlap", "--fuse-kld", "--fuse-color"):
+        assert flag in out
+
+
+def test_args_selftest_is_clean_under_the_host_sanitizers(tmp_path):
+    """scripts/fuse_multi_args_selftest.cpp: the argument checks of csrc/gsr_fuse_multi_args.h as a stand-alone program, built with
+    AddressSanitizer and UBSan"""
+    import os
+    import shutil
+    import subprocess
+    from conftest import ROOT
+    cxx = shutil.which("g++") or shutil.which("clang++") or shutil.which("c++")
+    if cxx is None:
+        pytest.skip("no host compiler")
+    exe = str(tmp_path / "fuse_multi_args_selftest")
+    cmd = [cxx, "-std=c++17", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", os.path.join(ROOT, "scripts", "fuse_multi_args_selftest.cpp"),
+           "-o", exe]
+    b = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+    assert b.returncode == 0, b.stdout + b.stderr
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0 and r.stdout.strip().endswith("ok"), r.stdout[-2000:] + r.stderr[-2000:]
