@@ -115,6 +115,10 @@ SIGNATURES = {
     "gsr_model_transform": (_i32, [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp]),
     "gsr_model_similarity": (_i32, [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp]),
     "gsr_model_fuse": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _vp]),
+    "gsr_model_match": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp]),
+    "gsr_color_sums": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _f64, _vp, C.POINTER(_i64), C.POINTER(_i64), _i32, _i32, _vp]),
+    "gsr_color_solve": (_i32, [_i32, _vp, _i32, _vp, _i32, _f64, _i64, _i32, _vp, _vp]),
+    "gsr_model_color_apply": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _vp]),
     "gsr_fuse_multi": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _vp]),
     "gsr_outlier_mask": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp]),
     "gsr_model_select": (_i32, [_vp, _i32, _vp, _vp, _vp, C.POINTER(_i64), _i32, _i32, _vp]),
@@ -257,6 +261,21 @@ class PoseGraphResult(C.Structure):
     """gsr_posegraph_result (include/gsr_hip.h)."""
     _fields_ = [("iterations", C.c_int32 * 2), ("n_pruned", C.c_int32), ("reserved", C.c_int32), ("E_initial", C.c_double), ("E_final", C.c_double),
                 ("mu", C.c_double), ("mu_first", C.c_double)]
+
+
+GSR_COLOR_SUMS_LEN = 40
+GSR_COLOR_MODES = {"gain": 0, "channel_gain": 1, "affine": 2}
+
+
+class ColorEdge(C.Structure):
+    """gsr_color_edge (include/gsr_hip.h)."""
+    _fields_ = [("source", C.c_int32), ("target", C.c_int32), ("sums", C.c_double * GSR_COLOR_SUMS_LEN)]
+
+
+class ColorSolveResult(C.Structure):
+    """gsr_color_solve_result (include/gsr_hip.h)."""
+    _fields_ = [("E_initial", C.c_double), ("E_final", C.c_double), ("pivot_min", C.c_double), ("pivot_max", C.c_double), ("n_free", C.c_int32),
+                ("n_unknowns", C.c_int32)]
 
 
 GSR_CHECK_EDGE_LENGTH = 0

@@ -64,25 +64,31 @@ class RegistrationController:
             self.handle_registration_result_local(result)
         return result
 
-    def execute_multiway_registration(self, clouds, params, edges="sequential", init=None, option=None, criteria=None):
+    def execute_multiway_registration(self, clouds, params, edges="sequential", init=None, option=None, criteria=None, match_colors=None,
+                                      match_colors_gate=None):
         """N clouds into one frame (``workers/multiway.py``): pairwise ICP per edge, information matrices, pose-graph optimisation.
         The repository holds two clouds, so the N ``PointCloud`` records are arguments.  Returns the worker's ``ResultData`` (poses,
         graph, per-edge report) or ``None`` with ``self.errors`` set; the pairwise ``transformation_matrix`` is left alone."""
         from ..workers.multiway import MultiwayRegistrator
-        worker = MultiwayRegistrator(clouds, params, edges=edges, init=init, option=option, criteria=criteria)
+        worker = MultiwayRegistrator(clouds, params, edges=edges, init=init, option=option, criteria=criteria, match_colors=match_colors,
+                                     match_colors_gate=match_colors_gate)
         result = worker.run()
         self.errors = worker.errors
+        self.multiway_worker = worker       # its merge() carries match_colors
         return result
 
     @staticmethod
-    def merge_multiway(models, poses, rotate_sh=False):
-        """The N ``GaussianModel`` s moved by their poses into one model (``GaussianModel.get_merged_gaussian_point_clouds_multi``)."""
+    def merge_multiway(models, poses, rotate_sh=False, match_colors=None, match_colors_gate=None):
+        """The N ``GaussianModel`` s moved by their poses into one model (``GaussianModel.get_merged_gaussian_point_clouds_multi``;
+        ``get_merged_gaussian_point_clouds_multi_colors``);
+        ``match_colors`` (``ColorMatchParams``) with its gate harmonises their colours on the way."""
         from ..models.gaussian_model import GaussianModel
-        return GaussianModel.get_merged_gaussian_point_clouds_multi(models, poses, rotate_sh=rotate_sh)
+        return GaussianModel.get_merged_gaussian_point_clouds_multi_colors(models, poses, match_colors, match_colors_gate, rotate_sh=rotate_sh)
 
     def evaluate_registration(self, cameras_list, images_path, log_path, color, use_gpu, registration_result=None, rotate_sh=False, with_scaling=False,
-                              fuse=None):
-        """``with_scaling``: the current transform is a similarity (a registration with scaling); the merge before rendering applies it as one.
+                              fuse=None, match_colors=None, match_colors_gate=None):
+        """``match_colors`` (``ColorMatchParams``; its gate: ``fuse``, else ``match_colors_gate``): the merge harmonises the first cloud's colours with the second's.
+        ``with_scaling``: the current transform is a similarity (a registration with scaling); the merge before rendering applies it as one.
         ``fuse`` (``FuseOverlapParams``): the merge fuses the splats the two clouds share (``GaussianModel.fuse_overlap``).
         Image-based evaluation of the current transform on the repository's original clouds (reference :122-143): renders of
         the merged model against the photographs, the JSON log at ``log_path``.  Returns the evaluator's ``EvaluationObject``."""
@@ -91,7 +97,8 @@ class RegistrationController:
         pc1 = repo.pc_gaussian_list_first[repo.current_index]
         pc2 = repo.pc_gaussian_list_second[repo.current_index]
         worker = RegistrationEvaluator(pc1, pc2, self.ui_repository.transformation_matrix, cameras_list, images_path, log_path, color,
-                                       registration_result, use_gpu, rotate_sh=rotate_sh, with_scaling=with_scaling, fuse=fuse)
+                                       registration_result, use_gpu, rotate_sh=rotate_sh, with_scaling=with_scaling, fuse=fuse, match_colors=match_colors,
+                                       match_colors_gate=match_colors_gate)
         return worker.run()
 
     def handle_registration_result_local(self, result_data):       # :145-163

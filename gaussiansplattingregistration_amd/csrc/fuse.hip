@@ -153,77 +153,27 @@ __global__ __launch_bounds__(256) void k_fuse_rows(int64_t na, int64_t nb, int W
 }
 
 
-}  // namespace gsr
+// Everything gsr_model_fuse does before its writer, and all of gsr_model_match: pre-pass, grid, search, mutual test, scans, pair list.
+// What the writer and the report read afterwards stays in `f`, which the caller declares BEFORE its OneShot.
+struct FuseFront {
+    DevBuf tmp_sort_a, tmp_sort_b, tmp_scan_a, tmp_scan_b;
+    Event ev[5];                                                // front: 0..3 recorded here; the caller records 4 behind its writer
+    size_t workspace = 0;                                       // device bytes asked for beyond the caller's arrays (rocPRIM's temporaries are added at the end)
+    double *wA = nullptr, *wB = nullptr;
+    int *mate = nullptr, *scanA = nullptr, *flagB = nullptr, *scanB = nullptr;
+    unsigned long long* counters = nullptr;                     // invalid A, invalid B, gated pairs
+    size_t total_bytes() const { return workspace + tmp_sort_a.cap + tmp_sort_b.cap + tmp_scan_a.cap + tmp_scan_b.cap; }
+};
 
-using namespace gsr;
-
-extern "C" int32_t gsr_model_fuse(const gsr_model_view* a, const gsr_model_view* b, int32_t K, const gsr_fuse_params* params, gsr_model_view* out,
-                                  int32_t* pairs, gsr_fuse_report* report, int32_t on_device, int32_t device, void* stream) {
-    const char* who = "gsr_model_fuse";
-    if (!a || !b || !params || !out || !report) return fail(GSR_E_INVALID, "gsr_model_fuse: NULL argument");
-    if (K != 0 && K != 3 && K != 8 && K != 15) return fail(GSR_E_INVALID, "gsr_model_fuse: K = %d (must be 0, 3, 8 or 15)", K);
-    if (!(params->max_distance > 0.0 && params->max_distance <= DBL_MAX)) return fail(GSR_E_INVALID, "gsr_model_fuse: max_distance must be positive and finite");
-    if (!(params->kld_max >= 0.0) || !(params->color_delta >= 0.0)) return fail(GSR_E_INVALID, "gsr_model_fuse: kld_max and color_delta must be >= 0");
-    const int64_t na = a->n, nb = b->n;
-    if (na < 0 || nb < 0 || na >= ((int64_t)1 << 31) || nb >= ((int64_t)1 << 31)) return fail(GSR_E_INVALID, "gsr_model_fuse: row counts must be in [0, 2^31)");
-    const bool sr_a = a->scaling && a->rot, sr_b = b->scaling && b->rot;
-    for (const gsr_model_view* v : {a, b}) {
-        if ((v->scaling != nullptr) != (v->rot != nullptr)) return fail(GSR_E_INVALID, "gsr_model_fuse: scaling and rot come together");
-        if (v->n > 0 && (!v->xyz || !v->cov6 || !v->dc || !v->opacity || (K > 0 && !v->sh))) return fail(GSR_E_INVALID, "gsr_model_fuse: NULL array in an input model");
-    }
-    // an empty model has no arrays to carry: the other one decides
-    const bool with_sr = na > 0 ? sr_a : sr_b;
-    if (na > 0 && nb > 0 && sr_a != sr_b) return fail(GSR_E_INVALID, "gsr_model_fuse: scaling / rot present in one model only");
-    const int64_t cap_rows = na + nb;
-    if (out->n < cap_rows) return fail(GSR_E_INVALID, "gsr_model_fuse: the output holds %lld rows, %lld are needed", (long long)out->n, (long long)cap_rows);
-    if (cap_rows > 0 && (!out->xyz || !out->cov6 || !out->dc || !out->opacity || (K > 0 && !out->sh) || (with_sr && (!out->scaling || !out->rot))))
-        return fail(GSR_E_INVALID, "gsr_model_fuse: NULL array in the output model");
-    const size_t F = 3 * (size_t)K;
-    const int NARR = 7;
-    const size_t width[NARR] = {3, 6, 3, F, 1, 3, 4};
-    const int modes[NARR] = {FUSE_MEAN, FUSE_COV, FUSE_MEAN, FUSE_MEAN, FUSE_MEAN, FUSE_COPY, FUSE_COPY};
-    const float* pa[NARR] = {a->xyz, a->cov6, a->dc, a->sh, a->opacity, a->scaling, a->rot};
-    const float* pb[NARR] = {b->xyz, b->cov6, b->dc, b->sh, b->opacity, b->scaling, b->rot};
-    float* po[NARR] = {out->xyz, out->cov6, out->dc, out->sh, out->opacity, out->scaling, out->rot};
-    bool used[NARR];
-    for (int k = 0; k < NARR; ++k) used[k] = k == 3 ? K > 0 : k >= 5 ? with_sr : true;
-    const size_t npair_cap = (size_t)(na < nb ? na : nb);
-    for (int i = 0; i < NARR; ++i) {
-        if (!used[i]) continue;
-        const size_t bo = (size_t)cap_rows * width[i] * 4;
-        if (ranges_overlap(po[i], bo, pairs, npair_cap * 8)) return fail(GSR_E_INVALID, "gsr_model_fuse: an output array overlaps another array of the call (the fusion is not in place)");
-        for (int j = 0; j < NARR; ++j) {
-            if (!used[j]) continue;
-            if (ranges_overlap(po[i], bo, pa[j], (size_t)na * width[j] * 4) || ranges_overlap(po[i], bo, pb[j], (size_t)nb * width[j] * 4) ||
-                (i < j && ranges_overlap(po[i], bo, po[j], (size_t)cap_rows * width[j] * 4)))
-                return fail(GSR_E_INVALID, "gsr_model_fuse: an output array overlaps another array of the call (the fusion is not in place)");
-        }
-    }
-    GSR_TRY(open_device(device, who));
-    memset(report, 0, sizeof(*report));
-    if (cap_rows == 0) { out->n = 0; return GSR_OK; }
-
-    const bool dev = on_device != 0;
-    DevBuf tmp_sort_a, tmp_sort_b, tmp_scan_a, tmp_scan_b;      // rocPRIM's temporaries: declared before the OneShot, freed after its wait
-    Event ev[5];
-    for (Event& e : ev) GSR_HIP(e.create());
-    OneShot os((hipStream_t)stream, dev, who);
+static int32_t fuse_front(OneShot& os, FuseFront& f, int64_t na, int64_t nb, const float* xyzA, const float* covA, const float* dcA, const float* opA,
+                          const float* xyzB, const float* covB, const float* dcB, const float* opB, const gsr_fuse_params* params, int32_t* dpairs) {
     hipStream_t st = os.st;
-    size_t workspace = 0;                                       // device bytes this call asks for beyond the caller's arrays (rocPRIM's temporaries are added at the end)
+    Event* ev = f.ev;
+    DevBuf &tmp_sort_a = f.tmp_sort_a, &tmp_sort_b = f.tmp_sort_b, &tmp_scan_a = f.tmp_scan_a, &tmp_scan_b = f.tmp_scan_b;
+    size_t& workspace = f.workspace;
     auto ws = [&](size_t bytes, auto** p) { workspace += bytes; return os.scratch(bytes, p); };
-    const float *da[NARR], *db[NARR];
-    float* dout[NARR];
-    for (int k = 0; k < NARR; ++k) {
-        da[k] = db[k] = nullptr; dout[k] = nullptr;
-        if (!used[k]) continue;
-        GSR_TRY(os.in(na > 0 ? pa[k] : nullptr, (size_t)na * width[k] * 4, &da[k]));
-        GSR_TRY(os.in(nb > 0 ? pb[k] : nullptr, (size_t)nb * width[k] * 4, &db[k]));
-        if (dev) dout[k] = po[k];
-        else GSR_TRY(os.scratch((size_t)cap_rows * width[k] * 4, &dout[k]));      // copied back below: n_out rows, not the capacity
-    }
-    int32_t* dpairs = nullptr;
-    if (pairs && npair_cap) { if (dev) dpairs = pairs; else GSR_TRY(os.scratch(npair_cap * 8, &dpairs)); }
-
+    const float* da[5] = {xyzA, covA, dcA, nullptr, opA};
+    const float* db[5] = {xyzB, covB, dcB, nullptr, opB};
     const int64_t cap = na > 1024 ? na : 1024;                  // cells of the table
     double *wA, *wB, *invA, *invB, *part, *box, *sinv;
     float *sxyz, *sdc, *scov;
@@ -275,6 +225,82 @@ extern "C" int32_t gsr_model_fuse(const gsr_model_view* a, const gsr_model_view*
     GSR_TRY(scan_exclusive<rocprim::default_config>(tmp_scan_a, st, (const int*)flagA, scanA, ua + 1));
     GSR_TRY(scan_exclusive<rocprim::default_config>(tmp_scan_b, st, (const int*)flagB, scanB, ub + 1));
     if (dpairs) hipLaunchKernelGGL(k_fuse_pairs_out, dim3(stride_grid(na)), dim3(256), 0, st, na, mate, scanA, dpairs);
+    f.wA = wA; f.wB = wB; f.mate = mate; f.scanA = scanA; f.flagB = flagB; f.scanB = scanB; f.counters = counters;
+    return GSR_OK;
+}
+
+}  // namespace gsr
+
+using namespace gsr;
+
+extern "C" int32_t gsr_model_fuse(const gsr_model_view* a, const gsr_model_view* b, int32_t K, const gsr_fuse_params* params, gsr_model_view* out,
+                                  int32_t* pairs, gsr_fuse_report* report, int32_t on_device, int32_t device, void* stream) {
+    const char* who = "gsr_model_fuse";
+    if (!a || !b || !params || !out || !report) return fail(GSR_E_INVALID, "gsr_model_fuse: NULL argument");
+    if (K != 0 && K != 3 && K != 8 && K != 15) return fail(GSR_E_INVALID, "gsr_model_fuse: K = %d (must be 0, 3, 8 or 15)", K);
+    if (!(params->max_distance > 0.0 && params->max_distance <= DBL_MAX)) return fail(GSR_E_INVALID, "gsr_model_fuse: max_distance must be positive and finite");
+    if (!(params->kld_max >= 0.0) || !(params->color_delta >= 0.0)) return fail(GSR_E_INVALID, "gsr_model_fuse: kld_max and color_delta must be >= 0");
+    const int64_t na = a->n, nb = b->n;
+    if (na < 0 || nb < 0 || na >= ((int64_t)1 << 31) || nb >= ((int64_t)1 << 31)) return fail(GSR_E_INVALID, "gsr_model_fuse: row counts must be in [0, 2^31)");
+    const bool sr_a = a->scaling && a->rot, sr_b = b->scaling && b->rot;
+    for (const gsr_model_view* v : {a, b}) {
+        if ((v->scaling != nullptr) != (v->rot != nullptr)) return fail(GSR_E_INVALID, "gsr_model_fuse: scaling and rot come together");
+        if (v->n > 0 && (!v->xyz || !v->cov6 || !v->dc || !v->opacity || (K > 0 && !v->sh))) return fail(GSR_E_INVALID, "gsr_model_fuse: NULL array in an input model");
+    }
+    // an empty model has no arrays to carry: the other one decides
+    const bool with_sr = na > 0 ? sr_a : sr_b;
+    if (na > 0 && nb > 0 && sr_a != sr_b) return fail(GSR_E_INVALID, "gsr_model_fuse: scaling / rot present in one model only");
+    const int64_t cap_rows = na + nb;
+    if (out->n < cap_rows) return fail(GSR_E_INVALID, "gsr_model_fuse: the output holds %lld rows, %lld are needed", (long long)out->n, (long long)cap_rows);
+    if (cap_rows > 0 && (!out->xyz || !out->cov6 || !out->dc || !out->opacity || (K > 0 && !out->sh) || (with_sr && (!out->scaling || !out->rot))))
+        return fail(GSR_E_INVALID, "gsr_model_fuse: NULL array in the output model");
+    const size_t F = 3 * (size_t)K;
+    const int NARR = 7;
+    const size_t width[NARR] = {3, 6, 3, F, 1, 3, 4};
+    const int modes[NARR] = {FUSE_MEAN, FUSE_COV, FUSE_MEAN, FUSE_MEAN, FUSE_MEAN, FUSE_COPY, FUSE_COPY};
+    const float* pa[NARR] = {a->xyz, a->cov6, a->dc, a->sh, a->opacity, a->scaling, a->rot};
+    const float* pb[NARR] = {b->xyz, b->cov6, b->dc, b->sh, b->opacity, b->scaling, b->rot};
+    float* po[NARR] = {out->xyz, out->cov6, out->dc, out->sh, out->opacity, out->scaling, out->rot};
+    bool used[NARR];
+    for (int k = 0; k < NARR; ++k) used[k] = k == 3 ? K > 0 : k >= 5 ? with_sr : true;
+    const size_t npair_cap = (size_t)(na < nb ? na : nb);
+    for (int i = 0; i < NARR; ++i) {
+        if (!used[i]) continue;
+        const size_t bo = (size_t)cap_rows * width[i] * 4;
+        if (ranges_overlap(po[i], bo, pairs, npair_cap * 8)) return fail(GSR_E_INVALID, "gsr_model_fuse: an output array overlaps another array of the call (the fusion is not in place)");
+        for (int j = 0; j < NARR; ++j) {
+            if (!used[j]) continue;
+            if (ranges_overlap(po[i], bo, pa[j], (size_t)na * width[j] * 4) || ranges_overlap(po[i], bo, pb[j], (size_t)nb * width[j] * 4) ||
+                (i < j && ranges_overlap(po[i], bo, po[j], (size_t)cap_rows * width[j] * 4)))
+                return fail(GSR_E_INVALID, "gsr_model_fuse: an output array overlaps another array of the call (the fusion is not in place)");
+        }
+    }
+    GSR_TRY(open_device(device, who));
+    memset(report, 0, sizeof(*report));
+    if (cap_rows == 0) { out->n = 0; return GSR_OK; }
+
+    const bool dev = on_device != 0;
+    FuseFront f;                                                // (rocPRIM's temporaries: declared before the OneShot, freed after its wait)
+    for (Event& e : f.ev) GSR_HIP(e.create());
+    OneShot os((hipStream_t)stream, dev, who);
+    hipStream_t st = os.st;
+    const float *da[NARR], *db[NARR];
+    float* dout[NARR];
+    for (int k = 0; k < NARR; ++k) {
+        da[k] = db[k] = nullptr; dout[k] = nullptr;
+        if (!used[k]) continue;
+        GSR_TRY(os.in(na > 0 ? pa[k] : nullptr, (size_t)na * width[k] * 4, &da[k]));
+        GSR_TRY(os.in(nb > 0 ? pb[k] : nullptr, (size_t)nb * width[k] * 4, &db[k]));
+        if (dev) dout[k] = po[k];
+        else GSR_TRY(os.scratch((size_t)cap_rows * width[k] * 4, &dout[k]));      // copied back below: n_out rows, not the capacity
+    }
+    int32_t* dpairs = nullptr;
+    if (pairs && npair_cap) { if (dev) dpairs = pairs; else GSR_TRY(os.scratch(npair_cap * 8, &dpairs)); }
+    GSR_TRY(fuse_front(os, f, na, nb, da[0], da[1], da[2], da[4], db[0], db[1], db[2], db[4], params, dpairs));
+    Event* ev = f.ev;
+    const double *wA = f.wA, *wB = f.wB;
+    const int *mate = f.mate, *scanA = f.scanA, *flagB = f.flagB, *scanB = f.scanB;
+    const unsigned long long* counters = f.counters;
     // ---- writer
     GSR_HIP(hipEventRecord(ev[3], st));
     for (int k = 0; k < NARR; ++k)
@@ -293,7 +319,7 @@ extern "C" int32_t gsr_model_fuse(const gsr_model_view* a, const gsr_model_view*
     report->n_invalid_a = (int64_t)hc[0]; report->n_invalid_b = (int64_t)hc[1];
     for (int k = 0; k < 4; ++k) (void)hipEventElapsedTime(&report->phase_ms[k], ev[k], ev[k + 1]);
     report->gated_pairs = (int64_t)hc[2];
-    report->workspace_bytes = (int64_t)(workspace + tmp_sort_a.cap + tmp_sort_b.cap + tmp_scan_a.cap + tmp_scan_b.cap);
+    report->workspace_bytes = (int64_t)f.total_bytes();
     if (with_sr && np > 0) {
         const int64_t off = na - np;
         GSR_TRY(gsr_decompose_cov(dout[1] + 6 * off, np, GSR_DECOMP_EXACT, dout[5] + 3 * off, dout[6] + 4 * off, nullptr, 1, device, stream));
@@ -304,5 +330,52 @@ extern "C" int32_t gsr_model_fuse(const gsr_model_view* a, const gsr_model_view*
         if (dpairs && np > 0) GSR_HIP(hipMemcpyAsync(pairs, dpairs, (size_t)np * 8, hipMemcpyDeviceToHost, st));
     }
     out->n = n_out;
+    return os.finish();
+}
+
+extern "C" int32_t gsr_model_match(const gsr_model_view* a, const gsr_model_view* b, const gsr_fuse_params* params, int32_t* pairs,
+                                   gsr_fuse_report* report, int32_t on_device, int32_t device, void* stream) {
+    const char* who = "gsr_model_match";
+    if (!a || !b || !params || !report) return fail(GSR_E_INVALID, "gsr_model_match: NULL argument");
+    if (!(params->max_distance > 0.0 && params->max_distance <= DBL_MAX)) return fail(GSR_E_INVALID, "gsr_model_match: max_distance must be positive and finite");
+    if (!(params->kld_max >= 0.0) || !(params->color_delta >= 0.0)) return fail(GSR_E_INVALID, "gsr_model_match: kld_max and color_delta must be >= 0");
+    const int64_t na = a->n, nb = b->n;
+    if (na < 0 || nb < 0 || na >= ((int64_t)1 << 31) || nb >= ((int64_t)1 << 31)) return fail(GSR_E_INVALID, "gsr_model_match: row counts must be in [0, 2^31)");
+    for (const gsr_model_view* v : {a, b})
+        if (v->n > 0 && (!v->xyz || !v->cov6 || !v->dc || !v->opacity)) return fail(GSR_E_INVALID, "gsr_model_match: NULL array in an input model");
+    GSR_TRY(open_device(device, who));
+    memset(report, 0, sizeof(*report));
+    if (na + nb == 0) return GSR_OK;
+
+    const bool dev = on_device != 0;
+    const size_t npair_cap = (size_t)(na < nb ? na : nb);
+    FuseFront f;
+    for (Event& e : f.ev) GSR_HIP(e.create());
+    unsigned long long hc[3] = {0, 0, 0};
+    int hp = 0;
+    OneShot os((hipStream_t)stream, dev, who);
+    hipStream_t st = os.st;
+    const float* pa[4] = {a->xyz, a->cov6, a->dc, a->opacity};
+    const float* pb[4] = {b->xyz, b->cov6, b->dc, b->opacity};
+    const size_t width[4] = {3, 6, 3, 1};
+    const float *da[4], *db[4];
+    for (int k = 0; k < 4; ++k) {
+        GSR_TRY(os.in(na > 0 ? pa[k] : nullptr, (size_t)na * width[k] * 4, &da[k]));
+        GSR_TRY(os.in(nb > 0 ? pb[k] : nullptr, (size_t)nb * width[k] * 4, &db[k]));
+    }
+    int32_t* dpairs = nullptr;
+    if (pairs && npair_cap) { if (dev) dpairs = pairs; else GSR_TRY(os.scratch(npair_cap * 8, &dpairs)); }
+    GSR_TRY(fuse_front(os, f, na, nb, da[0], da[1], da[2], da[3], db[0], db[1], db[2], db[3], params, dpairs));
+    GSR_HIP(hipEventRecord(f.ev[3], st));
+    GSR_HIP(hipMemcpyAsync(hc, f.counters, sizeof(hc), hipMemcpyDeviceToHost, st));
+    GSR_HIP(hipMemcpyAsync(&hp, f.scanA + na, 4, hipMemcpyDeviceToHost, st));
+    GSR_TRY(os.wait());
+    const int64_t np = hp;
+    report->n_pairs = np; report->n_out = na + nb - np; report->n_a_only = na - np; report->n_b_only = nb - np;
+    report->n_invalid_a = (int64_t)hc[0]; report->n_invalid_b = (int64_t)hc[1];
+    for (int k = 0; k < 3; ++k) (void)hipEventElapsedTime(&report->phase_ms[k], f.ev[k], f.ev[k + 1]);
+    report->gated_pairs = (int64_t)hc[2];
+    report->workspace_bytes = (int64_t)f.total_bytes();
+    if (!dev && dpairs && np > 0) GSR_HIP(hipMemcpyAsync(pairs, dpairs, (size_t)np * 8, hipMemcpyDeviceToHost, st));
     return os.finish();
 }

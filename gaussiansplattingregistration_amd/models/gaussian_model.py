@@ -440,7 +440,8 @@ class GaussianModel:
         return m, info
 
     @staticmethod
-    def get_merged_gaussian_point_clouds(gaussian1, gaussian2, transformation_matrix, rotate_sh=False, with_scaling=False, fuse=None):
+    def get_merged_gaussian_point_clouds(gaussian1, gaussian2, transformation_matrix, rotate_sh=False, with_scaling=False, fuse=None, match_colors=None,
+                                         match_colors_gate=None):
         """``gaussian1`` moved by the registration result, concatenated with ``gaussian2`` (the merged-cloud save).
         ``with_scaling``: the matrix is a similarity (``similarity_transform_gaussian_model``); ``_scaling`` moves too.
         ``rotate_sh``: turn the SH coefficients of ``gaussian1`` with it (``transform_gaussian_model``).  When both models
@@ -448,8 +449,19 @@ class GaussianModel:
         their first rows and ``gaussian2`` is copied behind it: no clone, no ``cat``.  ``gaussian1`` is left as it was.
         ``fuse`` (``FuseOverlapParams``; default ``None``: the plain concatenation above): move, then ``fuse_overlap`` -- the splats
         the two models share are stored once.  Refused (``RuntimeError``) when the model has SH coefficients, the matrix rotates
-        and ``rotate_sh`` is false."""
+        and ``rotate_sh`` is false.
+        ``match_colors`` (``ColorMatchParams``; default ``None``: colours as they are): move, fit ``gaussian1``'s colour transform
+        against ``gaussian2`` (``match_colors``; the correspondences are gated by ``fuse``, else by the ``FuseOverlapParams`` in
+        ``match_colors_gate``), apply it, then concatenate or fuse.  The same refusal as for ``fuse``."""
         assert gaussian1.sh_degree == gaussian2.sh_degree
+        if match_colors is not None:
+            g1, _ = GaussianModel.move_and_match_colors(gaussian1, gaussian2, transformation_matrix, rotate_sh, with_scaling, match_colors,
+                                                        fuse if fuse is not None else match_colors_gate)
+            if fuse is not None:
+                return GaussianModel.fuse_overlap(g1, gaussian2, fuse)[0]
+            if g1._xyz.is_cuda and gaussian2._xyz.is_cuda:          # (nothing moves any more: the rows are copied into arrays allocated once)
+                return GaussianModel.get_merged_gaussian_point_clouds_multi([g1, gaussian2], [np.eye(4), np.eye(4)])
+            return GaussianModel.get_merged_gaussian_point_clouds(g1, gaussian2, None)
         if fuse is not None:
             return GaussianModel.get_fused_gaussian_point_clouds(gaussian1, gaussian2, transformation_matrix, fuse, rotate_sh=rotate_sh,
                                                                  with_scaling=with_scaling)[0]
@@ -503,7 +515,7 @@ class GaussianModel:
         were.  All of them must live on one CUDA device, with one SH degree and the same set of arrays.
         ``fuse`` (``FuseOverlapParams``; default ``None``: the plain concatenation above): move, then ``fuse_overlap_multi`` -- a surface
         that k models share is stored once.  Refused (``RuntimeError``) when the models have SH coefficients, a pose rotates and
-        ``rotate_sh`` is false."""
+        ``rotate_sh`` is false.  With the colours of the scenes harmonised on the way: ``get_merged_gaussian_point_clouds_multi_colors``."""
         if fuse is not None:
             return GaussianModel.get_merged_gaussian_point_clouds_fused_multi(models, poses, fuse, rotate_sh=rotate_sh)[0]
         models, poses = list(models), [np.asarray(p, dtype=np.float64).reshape(4, 4) for p in poses]
@@ -545,10 +557,37 @@ class GaussianModel:
         return m
 
     @staticmethod
-    def get_merged_gaussian_point_clouds_fused_multi(models, poses, fuse, rotate_sh=False):
+    def get_merged_gaussian_point_clouds_multi_colors(models, poses, match_colors, match_colors_gate=None, rotate_sh=False, fuse=None, reference=0):
+        """``get_merged_gaussian_point_clouds_multi`` with the colours of the scenes harmonised between the move and the merge
+        (the keyword ``match_colors=`` of the other merges, as a function of its own: that one's parameter list is fixed).
+        ``match_colors`` (``ColorMatchParams``; ``None``: exactly ``get_merged_gaussian_point_clouds_multi(models, poses, rotate_sh,
+        fuse)``): move, fit every model's colour transform jointly against ``models[reference]`` (``match_colors`` over all pairs of
+        models; the correspondences are gated by ``fuse``, else by the ``FuseOverlapParams`` in ``match_colors_gate``), apply them, then
+        concatenate or fuse.  The same refusal as for ``fuse`` when a pose rotates a model with SH coefficients and ``rotate_sh`` is false."""
+        if match_colors is None:
+            return GaussianModel.get_merged_gaussian_point_clouds_multi(models, poses, rotate_sh=rotate_sh, fuse=fuse)
+        moved, _ = GaussianModel.move_and_match_colors_multi(models, poses, rotate_sh, match_colors, fuse if fuse is not None else match_colors_gate,
+                                                             reference=reference)
+        if fuse is not None:
+            return GaussianModel.fuse_overlap_multi(moved, fuse)[0]
+        return GaussianModel.get_merged_gaussian_point_clouds_multi(moved, [np.eye(4)] * len(moved))
+
+    @staticmethod
+    def get_merged_gaussian_point_clouds_fused_multi(models, poses, fuse, rotate_sh=False, match_colors=None):
         """Every model moved by its pose, then ``fuse_overlap_multi`` -> ``(model, info)``: what
         ``get_merged_gaussian_point_clouds_multi(..., fuse=params)`` returns the model of, with the report.  The models stay as they
-        were; a model whose pose is the identity is used as it is."""
+        were; a model whose pose is the identity is used as it is.  ``match_colors`` (``ColorMatchParams``): the colours are
+        harmonised between the move and the fusion; ``info["match_colors"]`` is then ``(transforms, info)`` of ``match_colors``."""
+        if match_colors is not None:
+            moved, colors = GaussianModel.move_and_match_colors_multi(models, poses, rotate_sh, match_colors, fuse)
+            m, info = GaussianModel.fuse_overlap_multi(moved, fuse)
+            info["match_colors"] = colors
+            return m, info
+        return GaussianModel.fuse_overlap_multi(GaussianModel._moved_multi(models, poses, rotate_sh, "fuse"), fuse)
+
+    @staticmethod
+    def _moved_multi(models, poses, rotate_sh, what):
+        """every model in the common frame: a clone moved by its pose, or the model itself where the pose is the identity"""
         models, poses = list(models), [np.asarray(p, dtype=np.float64).reshape(4, 4) for p in poses]
         if not models or len(models) != len(poses):
             raise ValueError(f"{len(models)} models and {len(poses)} poses")
@@ -561,16 +600,28 @@ class GaussianModel:
             rotates = not (np.count_nonzero(A - np.diag(np.diag(A))) == 0 and A[0, 0] == A[1, 1] == A[2, 2] and A[0, 0] > 0)
             K = int(g._features_rest.shape[1]) if g._features_rest.dim() == 3 else 0
             if K > 0 and rotates and not rotate_sh:
-                raise RuntimeError("fuse needs rotate_sh=True when a pose rotates a model with SH coefficients: an average of SH rows "
+                raise RuntimeError(what + " needs rotate_sh=True when a pose rotates a model with SH coefficients: an average of SH rows "
                                    "in two frames means nothing")
             moved.append(g.clone_gaussian().transform_gaussian_model(T, rotate_sh=rotate_sh))
-        return GaussianModel.fuse_overlap_multi(moved, fuse)
+        return moved
 
     @staticmethod
-    def get_fused_gaussian_point_clouds(gaussian1, gaussian2, transformation_matrix, fuse, rotate_sh=False, with_scaling=False):
+    def get_fused_gaussian_point_clouds(gaussian1, gaussian2, transformation_matrix, fuse, rotate_sh=False, with_scaling=False, match_colors=None):
         """``gaussian1`` moved by the matrix, then ``fuse_overlap`` with ``gaussian2`` -> ``(model, info)``: what
         ``get_merged_gaussian_point_clouds(..., fuse=params)`` returns the model of, with the report.  As in the plain merge,
-        ``gaussian1`` is left as it was and may live on another device than ``gaussian2``: its moved copy goes to ``gaussian2``'s."""
+        ``gaussian1`` is left as it was and may live on another device than ``gaussian2``: its moved copy goes to ``gaussian2``'s.
+        ``match_colors`` (``ColorMatchParams``): the colours of ``gaussian1`` are harmonised with ``gaussian2``'s between the move and
+        the fusion; ``info["match_colors"]`` is then ``(transforms, info)`` of ``match_colors``."""
+        if match_colors is not None:
+            g1, colors = GaussianModel.move_and_match_colors(gaussian1, gaussian2, transformation_matrix, rotate_sh, with_scaling, match_colors, fuse)
+            m, info = GaussianModel.fuse_overlap(g1, gaussian2, fuse)
+            info["match_colors"] = colors
+            return m, info
+        return GaussianModel.fuse_overlap(GaussianModel._moved_pair(gaussian1, gaussian2, transformation_matrix, rotate_sh, with_scaling, "fuse"), gaussian2, fuse)
+
+    @staticmethod
+    def _moved_pair(gaussian1, gaussian2, transformation_matrix, rotate_sh, with_scaling, what):
+        """``gaussian1`` in ``gaussian2``'s frame and on its device: a moved clone, or the model itself where nothing moves"""
         g1 = gaussian1
         moves = transformation_matrix is not None and not np.array_equal(np.asarray(transformation_matrix), np.eye(4))
         if moves:
@@ -579,7 +630,7 @@ class GaussianModel:
             rotates = not (np.count_nonzero(A - np.diag(np.diag(A))) == 0 and A[0, 0] == A[1, 1] == A[2, 2] and A[0, 0] > 0)
             K = int(gaussian1._features_rest.shape[1]) if gaussian1._features_rest.dim() == 3 else 0
             if K > 0 and rotates and not rotate_sh:
-                raise RuntimeError("fuse needs rotate_sh=True when the matrix rotates a model with SH coefficients: an average of SH rows "
+                raise RuntimeError(what + " needs rotate_sh=True when the matrix rotates a model with SH coefficients: an average of SH rows "
                                    "in two frames means nothing")
             g1 = gaussian1.clone_gaussian()
             if with_scaling:
@@ -590,7 +641,49 @@ class GaussianModel:
             if g1 is gaussian1:
                 g1 = gaussian1.clone_gaussian()
             g1.move_to_device(str(gaussian2._xyz.device))
-        return GaussianModel.fuse_overlap(g1, gaussian2, fuse)
+        return g1
+
+    # -- colour harmonisation (csrc/harmonize.hip; the reference has no such step) ---------------------------
+    @staticmethod
+    def match_colors(models, fuse_params, params=None, edges="all", reference=0):
+        """The colour transforms that bring N models, ALREADY IN ONE FRAME, into agreement with ``models[reference]`` ->
+        ``(transforms, info)``: ``harmonize.match_colors``.  ``params``: a ``ColorMatchParams`` (default: its defaults)."""
+        from .. import harmonize
+        return harmonize.match_colors(models, fuse_params, params, edges=edges, reference=reference)
+
+    def apply_color_transform(self, P):
+        """-> a new model whose colours are ``M x + b`` of this one's for ``P = [M | b]`` (3, 4), in every view direction (DC and every
+        SH coefficient; ``gsr_model_color_apply``).  Every other tensor is shared with this model.  Colours are not clamped."""
+        from .. import harmonize
+        return harmonize.apply_colors(self, P)
+
+    @staticmethod
+    def _apply_solved(models, transforms):
+        """a model whose solved transform is exactly [I|0] is not run through the kernel, as the merge does for an identity pose"""
+        from .. import harmonize
+        return [g if harmonize.is_identity(P) or len(g) == 0 else g.apply_color_transform(P) for g, P in zip(models, transforms)]
+
+    @staticmethod
+    def move_and_match_colors(gaussian1, gaussian2, transformation_matrix, rotate_sh, with_scaling, match_colors, gate):
+        """What the pairwise merges do first when ``match_colors`` (``ColorMatchParams``) is set -> ``(model, (transforms, info))``:
+        ``gaussian1`` moved into ``gaussian2``'s frame, its colour transform fitted against ``gaussian2`` (the reference) over the
+        correspondences ``gate`` (``FuseOverlapParams``) admits, and applied.  ``transforms`` / ``info``: ``match_colors``'s, scene 0 =
+        ``gaussian1``, scene 1 = ``gaussian2``.  ``gaussian1`` is left as it was."""
+        if gate is None:
+            raise ValueError("match_colors needs the gates of its correspondences: fuse=, or a FuseOverlapParams in match_colors_gate=")
+        g1 = GaussianModel._moved_pair(gaussian1, gaussian2, transformation_matrix, rotate_sh, with_scaling, "match_colors")
+        colors = GaussianModel.match_colors([g1, gaussian2], gate, match_colors, edges=[(0, 1)], reference=1)
+        return GaussianModel._apply_solved([g1], colors[0][:1])[0], colors
+
+    @staticmethod
+    def move_and_match_colors_multi(models, poses, rotate_sh, match_colors, gate, reference=0):
+        """What the N-way merges do first when ``match_colors`` is set -> ``(models, (transforms, info))``: every model moved by its
+        pose, the colour transforms fitted jointly against ``models[reference]`` over every pair of models, and applied."""
+        if gate is None:
+            raise ValueError("match_colors needs the gates of its correspondences: fuse=, or a FuseOverlapParams in match_colors_gate=")
+        moved = GaussianModel._moved_multi(models, poses, rotate_sh, "match_colors")
+        colors = GaussianModel.match_colors(moved, gate, match_colors, edges="all", reference=reference)
+        return GaussianModel._apply_solved(moved, colors[0]), colors
 
     # -- cleaning (csrc/clean.hip; the reference has no such step) -------------------------------------------------------------
     def select_by_mask(self, mask):

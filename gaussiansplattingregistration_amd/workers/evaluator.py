@@ -67,7 +67,7 @@ class RegistrationEvaluator:
     EvaluationObject = EvaluationObject
 
     def __init__(self, pc1, pc2, transformation, cameras_list, images_path, log_path, color, registration_result, use_gpu, rotate_sh=False, with_scaling=False,
-                 fuse=None):
+                 fuse=None, match_colors=None, match_colors_gate=None):
         self.signal_cancel = False
         self.pc1 = pc1
         self.pc2 = pc2
@@ -81,6 +81,7 @@ class RegistrationEvaluator:
         self.rotate_sh = rotate_sh
         self.with_scaling = bool(with_scaling)          # the transformation is a similarity [c R | t]: merged through gsr_model_similarity
         self.fuse = fuse                    # FuseOverlapParams or None: the merge stores the splats the two clouds share once (fuse_overlap)
+        self.match_colors, self.match_colors_gate = match_colors, match_colors_gate      # ColorMatchParams or None: colours harmonised before the merge
         self.registration_result = registration_result
         self.mean_mses = self.mean_rmses = self.mean_ssims = self.mean_psnrs = self.mean_lpipss = None
         self.per_image = []
@@ -110,7 +111,8 @@ class RegistrationEvaluator:
                 continue
             if point_cloud is None:
                 point_cloud = GaussianModel.get_merged_gaussian_point_clouds(self.pc1, self.pc2, self.transformation, rotate_sh=self.rotate_sh,
-                                                                             with_scaling=self.with_scaling, fuse=self.fuse)
+                                                                             with_scaling=self.with_scaling, fuse=self.fuse, match_colors=self.match_colors,
+                                                                             match_colors_gate=self.match_colors_gate)
                 point_cloud.move_to_device(self.device)
             render = rasterize_image(point_cloud, camera, 1, self.color, self.device, self.use_gpu)
             if self.on_render is not None:

@@ -63,11 +63,14 @@ class MultiwayRegistrator:
             self.edge_reports = edge_reports        # one dict per requested edge
             self.optimization = optimization        # GlobalOptimizationReport
 
-    def __init__(self, clouds, params, edges="sequential", init=None, option=None, criteria=None, progress=None, fuse=None):
+    def __init__(self, clouds, params, edges="sequential", init=None, option=None, criteria=None, progress=None, fuse=None, match_colors=None,
+                 match_colors_gate=None):
         """``clouds``: the ``PointCloud`` records; ``params``: ``LocalRegistrationParams`` of every pairwise ICP; ``init``: ``None``
         (identity), ``{(s, t): T}`` (missing pairs: identity) or ``callable(s, t, cloud_s, cloud_t) -> T`` (e.g. a global
         registration); ``option`` (``GlobalOptimizationOption``): default ``max_correspondence_distance = params.max_correspondence``;
-        ``fuse`` (``FuseOverlapParams`` or ``None``): what ``merge`` hands to ``get_merged_gaussian_point_clouds_multi``."""
+        ``fuse`` (``FuseOverlapParams`` or ``None``): what ``merge`` hands to ``get_merged_gaussian_point_clouds_multi``;
+        ``match_colors`` (``ColorMatchParams`` or ``None``) and ``match_colors_gate`` (``FuseOverlapParams``, needed without ``fuse``)
+        likewise: ``merge`` harmonises the colours of the scenes between the move and the concatenation or fusion."""
         self.clouds, self.params = list(clouds), params
         self.edges = edge_list(len(self.clouds), edges)
         self.init = init
@@ -79,12 +82,22 @@ class MultiwayRegistrator:
         self.timing = {}
         self.fuse = fuse                    # FuseOverlapParams or None: the merge stores a surface that k scenes share once
         self.fuse_info = None               # the report of the last merge with `fuse`
+        self.match_colors, self.match_colors_gate = match_colors, match_colors_gate
+        self.color_info = None              # (transforms, info) of the last merge with `match_colors`
 
     def merge(self, models, result, rotate_sh=False):
         """The ``GaussianModel`` s of the clouds, each moved by its pose of ``result`` (what ``run`` returned), in one model:
         concatenated, or -- with ``fuse`` -- with the overlaps fused (``GaussianModel.fuse_overlap_multi``; the report goes to
         ``fuse_info``)."""
         from ..models.gaussian_model import GaussianModel
+        if self.match_colors is not None:
+            gate = self.fuse if self.fuse is not None else self.match_colors_gate
+            moved, self.color_info = GaussianModel.move_and_match_colors_multi(models, result.poses, rotate_sh, self.match_colors, gate,
+                                                                                         reference=self.option.reference_node)
+            if self.fuse is None:
+                return GaussianModel.get_merged_gaussian_point_clouds_multi(moved, [np.eye(4)] * len(moved))
+            merged, self.fuse_info = GaussianModel.fuse_overlap_multi(moved, self.fuse)
+            return merged
         if self.fuse is None:
             return GaussianModel.get_merged_gaussian_point_clouds_multi(models, result.poses, rotate_sh=rotate_sh)
         merged, self.fuse_info = GaussianModel.get_merged_gaussian_point_clouds_fused_multi(models, result.poses, self.fuse, rotate_sh=rotate_sh)

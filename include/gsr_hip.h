@@ -714,6 +714,14 @@ typedef struct gsr_fuse_report {
 int32_t gsr_model_fuse(const gsr_model_view* a, const gsr_model_view* b, int32_t K, const gsr_fuse_params* params, gsr_model_view* out,
                        int32_t* pairs, gsr_fuse_report* report, int32_t on_device, int32_t device, void* stream);
 
+/* The pair list of gsr_model_fuse for the same two views and parameters, without an output model: the same pre-pass, grid, search
+ * and mutual test (one function behind both entry points), no writer.  Only xyz, cov6, dc and opacity of the views are read.
+ * pairs: int32 (min(na, nb), 2) receiving (a, b) in ascending a, or NULL.  report: n_pairs, n_a_only, n_b_only, the invalid counts,
+ * gated_pairs and workspace_bytes; n_out = na + nb - n_pairs as the fusion would report it; phase_ms[3] (the writer) is 0.
+ * Arrays on the host or on the device as on_device says; refused arguments as in gsr_model_fuse. */
+int32_t gsr_model_match(const gsr_model_view* a, const gsr_model_view* b, const gsr_fuse_params* params, int32_t* pairs,
+                        gsr_fuse_report* report, int32_t on_device, int32_t device, void* stream);
+
 /* Fuse the overlaps of N models that are ALREADY IN ONE FRAME, in one pass: csrc/fuse_multi.hip; restated in
  * float64 NumPy in tests/fuse_multi_model.py.  Rows get a GLOBAL index g, model-major (the rows of models[0] first, ascending).
  *   valid, gates, J   exactly gsr_model_fuse's; J of a pair is evaluated with the lower global index in the role of `a`.
@@ -903,6 +911,56 @@ int32_t gsr_orient_normals_graph(const float* xyz, double* normals, int64_t n, c
  * radius finite and > 0, max_nn in [1, 512]. */
 int32_t gsr_orient_normals(const float* xyz, double* normals, int64_t n, double radius, int32_t max_nn, const double* reference,
                            int32_t* component, gsr_orient_report* report, int32_t on_device, int32_t device, void* stream);
+
+/* ------------------------------------------------------------------- colour harmonisation */
+/* Exposure / white-balance matching of registered scenes.  csrc/harmonize.hip, csrc/gsr_colorsolve.h; restated in float64 in
+ * tests/color_model.py.  Base colour of a splat: x = 0.5 + C0 dc, C0 = 0.28209479177387814, float64 from the float32 dc.  A colour
+ * transform of a scene is P = [M | b], row-major 3 x 4 float64, x' = M x + b.
+ *
+ * gsr_color_sums: the sums of one edge (s, t) over its pairs (i, j) -- row i of s, row j of t -- at the transforms P_s, P_t:
+ *   a = [x_i; 1], b = [x_j; 1], u = sigmoid(opacity_s[i]) sigmoid(opacity_t[j]), r = P_s a - P_t b, rho2 = r.r, rho = sqrt(rho2),
+ *   h = huber_k / rho if rho > huber_k else 1 (inf: least squares; NaN fails the comparison), w = u h.
+ * sums[GSR_COLOR_SUMS_LEN]: [0] n, [1] sum w, [2] sum w rho2, [3..12] sum w a a^T (upper triangle, row by row), [13..28] sum w a b^T
+ * (row-major), [29..38] sum w b b^T (upper triangle), [39] 0.  A pair with a non-finite dc or opacity on either side is skipped
+ * (*n_skipped); a pair with an index outside its model is never dereferenced, is counted in *n_out_of_range, and the call then
+ * returns GSR_E_INVALID.  dc[n*3], opacity[n] float32 and pairs[n_pairs*2] int32 on the host or the device as on_device says; P_s,
+ * P_t, sums and the two counts on the host.  One lane per pair, float64 registers, a block fold and a fixed-order final fold: no
+ * float atomics, the same bits from run to run and from host or device arrays.  n_pairs = 0: all zeros. */
+#define GSR_COLOR_SUMS_LEN 40
+int32_t gsr_color_sums(const float* s_dc, const float* s_opacity, int64_t ns, const float* t_dc, const float* t_opacity, int64_t nt,
+                       const int32_t* pairs, int64_t n_pairs, const double* P_s, const double* P_t, double huber_k, double* sums,
+                       int64_t* n_skipped, int64_t* n_out_of_range, int32_t on_device, int32_t device, void* stream);
+
+/* The transforms of N scenes that minimise
+ *   sum_e sum_c [p_s^c' S_aa p_s^c - 2 p_s^c' S_ab p_t^c + p_t^c' S_bb p_t^c] + lambda sum_{i free} |P_i - [I|0]|_F^2,
+ * p_i^c = row c of P_i, lambda = prior (sum_e sums[1]) / n_edges: one dense symmetric solve (diagonal-pivoted LDL^T) of size
+ * d (number of free nodes), d = 1 (GSR_COLOR_GAIN: P = [g I | 0]), 3 (GSR_COLOR_CHANNEL_GAIN: [diag(g) | 0]) or 12
+ * (GSR_COLOR_AFFINE).  Held at their input values: `reference`, and every node that no path of edges with sums[0] >= min_pairs
+ * connects to it (held[i] = 1; not an error).  P[n_nodes*12] in and out (held nodes are never written); held: int32 n_nodes or
+ * NULL; result may be NULL.  Host code, no device.  GSR_E_INVALID with a message: an index out of range, source == target, a
+ * non-finite P or sum, an unknown mode, a negative or non-finite prior, a system that is singular to rounding (raise prior). */
+#define GSR_COLOR_GAIN 0
+#define GSR_COLOR_CHANNEL_GAIN 1
+#define GSR_COLOR_AFFINE 2
+typedef struct gsr_color_edge {
+    int32_t source, target;
+    double sums[GSR_COLOR_SUMS_LEN];
+} gsr_color_edge;
+typedef struct gsr_color_solve_result {
+    double E_initial, E_final;      /* the objective at the input transforms / at the returned ones */
+    double pivot_min, pivot_max;    /* of the LDL^T of the solved system (0 when nothing was free) */
+    int32_t n_free, n_unknowns;
+} gsr_color_solve_result;
+int32_t gsr_color_solve(int32_t n_nodes, double* P, int32_t n_edges, const gsr_color_edge* edges, int32_t mode, double prior,
+                        int64_t min_pairs, int32_t reference, int32_t* held, gsr_color_solve_result* result);
+
+/* x' = M x + b on a model's colours, exact for every view direction:  dc' = M dc + (M (.5,.5,.5)' + b - (.5,.5,.5)') / C0 and
+ * sh'_k = M sh_k for each of the K higher coefficients (sh[n*K*3], the channels innermost).  float64 arithmetic on the float32
+ * inputs, each sum left to right, narrowed once; not clamped.  K in {0, 3, 8, 15}; n in [0, 2^31).  dc_out / sh_out may be exactly
+ * dc / sh (in place) or disjoint from every input; any other overlap, and a non-finite P12, are GSR_E_INVALID.  NaN rows come out
+ * NaN.  Arrays on the host or the device as on_device says; P12 on the host. */
+int32_t gsr_model_color_apply(const double* P12, int64_t n, int32_t K, const float* dc, const float* sh, float* dc_out, float* sh_out,
+                              int32_t on_device, int32_t device, void* stream);
 
 #ifdef __cplusplus
 }

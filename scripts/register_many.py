@@ -8,6 +8,7 @@ registered pair, a pose graph with a line process that prunes wrongly registered
            [--prune 0.25] [--preference 1.0] [--reference 0] [--rotate-sh]
            [--clean-knn K --clean-std R [--clean-radius R --clean-nb N] [--clean-min-opacity A] [--clean-max-extent S]]
            [--fuse-overlap MAX_DIST [--fuse-kld 0.5] [--fuse-color X]]
+           [--match-colors [gain|channel_gain|affine] [--match-colors-huber K] [--match-colors-dist D] [--colors-out colors.json]]
 
 Edges: `--edges sequential` registers each scene to the next (a chain), `--edges all` every pair; `--edge S T` (repeatable) adds the pair
 (S, T).  An edge (i, i + 1) is certain ("odometry"); every other edge is a loop closure the optimiser may prune (`--prune`: the line
@@ -16,7 +17,11 @@ The poses map each scene into the frame of scene `--reference`; `--poses-out` ho
 and the pruned edges.  `--clean-*`: every scene goes through floater removal right after loading (scripts/clean_ply.py has the stages);
 prints n -> n_kept per scene.  `--fuse-overlap MAX_DIST`: the merged cloud stores a surface that k scenes share once
 (GaussianModel.fuse_overlap_multi: groups of at most one splat per scene, moment-matched); it implies --rotate-sh and prints n_groups, the
-histogram of the group sizes and n_out.
+histogram of the group sizes and n_out.  `--match-colors [MODE]`: the scenes differ in exposure or white balance; after the move every
+scene's colour transform (a gain, a gain per channel or an affine 3 x 4) is fitted jointly against scene `--reference` over the splats
+each pair of scenes shares (GaussianModel.match_colors; matches within `--match-colors-dist`, default the fuse distance, else --max-corr)
+and applied before the merge.  Prints the transform per scene and the colour residual per pair before and after; `--colors-out` writes
+them as JSON.  Implies --rotate-sh.
 """
 import argparse
 import json
@@ -54,6 +59,8 @@ def main():
     ap.add_argument("--fuse-color", type=float, default=float("inf"), help="DC colour gate of --fuse-overlap (default: none)")
     from gaussiansplattingregistration_amd.clean import add_clean_arguments, clean_params_from_args
     add_clean_arguments(ap)
+    from gaussiansplattingregistration_amd.harmonize import add_match_colors_arguments, match_colors_from_args
+    add_match_colors_arguments(ap)
     a = ap.parse_args()
     clean = clean_params_from_args(a)
     n = len(a.scenes)
@@ -104,7 +111,8 @@ def main():
     if a.fuse_overlap is not None:
         from gaussiansplattingregistration_amd.params import FuseOverlapParams
         fuse = FuseOverlapParams(a.fuse_overlap, a.fuse_kld, a.fuse_color)
-    worker = MultiwayRegistrator(clouds, params, edges=edges, init=init, option=option, fuse=fuse)
+    cm, gate = match_colors_from_args(a, fuse, default_distance=a.max_corr)
+    worker = MultiwayRegistrator(clouds, params, edges=edges, init=init, option=option, fuse=fuse, match_colors=cm, match_colors_gate=gate)
     res = worker.run()
     t2 = time.perf_counter()
     if res is None:
@@ -130,7 +138,14 @@ def main():
             json.dump(doc, f, indent=1)
         print(f"poses -> {a.poses_out}")
     if a.out:
-        merged = worker.merge(models, res, rotate_sh=a.rotate_sh or fuse is not None)
+        merged = worker.merge(models, res, rotate_sh=a.rotate_sh or fuse is not None or cm is not None)
+        if cm is not None:          # every scene's colours were fitted jointly against the reference scene's and applied before the merge
+            from gaussiansplattingregistration_amd import harmonize
+            transforms, cinfo = worker.color_info
+            print("colours:")
+            print("\n".join("  " + line for line in harmonize.report_lines(transforms, cinfo)))
+            if a.colors_out:
+                harmonize.write_json(a.colors_out, transforms, cinfo)
         if fuse is not None:
             info = worker.fuse_info
             sizes = "  ".join(f"{k}: {c}" for k, c in enumerate(info["groups_of_size"]) if c)

@@ -6,6 +6,7 @@
            [--type plane|point|color|general] [--loss none|tukey|cauchy|gm|huber --k 0.1] [--voxel] [--out merged.ply [--rotate-sh]]
            [--with-scaling] [--fuse-overlap MAX_DIST [--fuse-kld X] [--fuse-color X]]
            [--clean-knn K --clean-std R [--clean-radius R --clean-nb N] [--clean-min-opacity A] [--clean-max-extent S]]
+           [--match-colors [gain|channel_gain|affine] [--match-colors-huber K] [--match-colors-dist D] [--colors-out colors.json]]
 
 `--with-scaling`: the two scenes do not share a unit of length (separate structure-from-motion runs).  Point-to-point ICP with scaling
 (`--type point` is implied, any other type is refused); without a global method the start is `initial_similarity` (centroids and RMS
@@ -17,6 +18,12 @@ replaced by their moment-matched union); prints n_pairs / n_out.  Implies `--rot
 
 `--clean-*`: both scenes go through floater removal (`GaussianModel.remove_floaters`, scripts/clean_ply.py has the stages) right after
 loading: mixtures, registration and the merged cloud see the cleaned scenes.  Prints n -> n_kept per scene.
+
+`--match-colors [MODE]` (with `--out`): the two scenes were captured with different exposure or white balance.  After the move the first
+scene's colour transform is fitted against the second's over the splats they share (`GaussianModel.match_colors`: mutual best matches
+within `--match-colors-dist`, default the fuse distance; a Huber-weighted fit of a gain, a gain per channel or an affine 3 x 4) and
+applied to its DC and SH coefficients before the clouds are concatenated or fused.  Prints the transform and the colour residual
+before and after; `--colors-out` writes them as JSON.  Implies `--rotate-sh`.
 
 Prints the 4x4 transformation (first -> second), fitness and inlier RMSE; `--out` saves the merged cloud.
 """
@@ -61,9 +68,11 @@ def main():
     ap.add_argument("--fuse-color", type=float, default=float("inf"), help="largest L2 distance of the DC colours of a fused pair")
     from gaussiansplattingregistration_amd.clean import add_clean_arguments, clean_params_from_args
     add_clean_arguments(ap)
+    from gaussiansplattingregistration_amd.harmonize import add_match_colors_arguments, match_colors_from_args
+    add_match_colors_arguments(ap)
     a = ap.parse_args()
     clean = clean_params_from_args(a)
-    if a.fuse_overlap is not None:
+    if a.fuse_overlap is not None or a.match_colors is not None:
         a.rotate_sh = True
     if a.with_scaling and a.type not in (None, "point"):
         raise SystemExit(f"--with-scaling is point-to-point only (Open3D offers scaling for no other estimator): --type {a.type} refused")
@@ -142,16 +151,23 @@ def main():
     print(f"fitness {res.result.fitness:.4f}  inlier RMSE {res.result.inlier_rmse:.6f}")
     print(f"load {t1 - t0:.2f} s, mixtures {t2 - t1:.3f} s, registration {t3 - t2:.3f} s")
     if a.out:
-        if a.fuse_overlap is not None:
-            from gaussiansplattingregistration_amd.params import FuseOverlapParams
-            merged, info = GaussianModel.get_fused_gaussian_point_clouds(repo.pc_gaussian_list_first[0], repo.pc_gaussian_list_second[0],
-                                                                         res.result.transformation, FuseOverlapParams(a.fuse_overlap, a.fuse_kld, a.fuse_color),
-                                                                         rotate_sh=a.rotate_sh, with_scaling=a.with_scaling)
+        from gaussiansplattingregistration_amd import harmonize
+        from gaussiansplattingregistration_amd.params import FuseOverlapParams
+        fuse = FuseOverlapParams(a.fuse_overlap, a.fuse_kld, a.fuse_color) if a.fuse_overlap is not None else None
+        first, second, T = repo.pc_gaussian_list_first[0], repo.pc_gaussian_list_second[0], res.result.transformation
+        cm, gate = match_colors_from_args(a, fuse)
+        if cm is not None:          # move, fit the first scene's colours against the second's, apply: what is merged below is already in place
+            first, (transforms, cinfo) = GaussianModel.move_and_match_colors(first, second, T, a.rotate_sh, a.with_scaling, cm, gate)
+            T = None
+            print("colours (scene 0 = first, scene 1 = second, the reference):")
+            print("\n".join("  " + line for line in harmonize.report_lines(transforms, cinfo)))
+            if a.colors_out:
+                harmonize.write_json(a.colors_out, transforms, cinfo)
+        if fuse is not None:
+            merged, info = GaussianModel.get_fused_gaussian_point_clouds(first, second, T, fuse, rotate_sh=a.rotate_sh, with_scaling=a.with_scaling)
             print(f"fuse overlap: n_pairs {info['n_pairs']}  n_out {info['n_out']}  (invalid rows: {info['n_invalid_a']} / {info['n_invalid_b']})")
         else:
-            merged = GaussianModel.get_merged_gaussian_point_clouds(repo.pc_gaussian_list_first[0], repo.pc_gaussian_list_second[0],
-                                                                    res.result.transformation, rotate_sh=a.rotate_sh,
-                                                                    with_scaling=a.with_scaling)
+            merged = GaussianModel.get_merged_gaussian_point_clouds(first, second, T, rotate_sh=a.rotate_sh, with_scaling=a.with_scaling)
         merged.save_ply(a.out)
         print(f"merged cloud ({len(merged)} splats) -> {a.out}")
 
