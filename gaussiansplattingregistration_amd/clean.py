@@ -13,15 +13,8 @@ import numpy as np
 
 from . import _lib
 from . import _marshal as _m
+from . import _model_view as _mv
 
-_VIEW_FIELDS = ("xyz", "cov6", "dc", "sh", "opacity", "scaling", "rot")
-_VIEW_WIDTH = {"xyz": 3, "cov6": 6, "dc": 3, "opacity": 1, "scaling": 3, "rot": 4}
-
-
-def _sync(device, on):
-    if on:
-        import torch
-        torch.cuda.current_stream(device).synchronize()
 
 
 def outlier_mask(xyz, params, raw_opacity=None, scaling=None, device=0, with_mean_dist=False, with_count=False):
@@ -50,9 +43,7 @@ def outlier_mask(xyz, params, raw_opacity=None, scaling=None, device=0, with_mea
     P = _lib.CleanParams(params.min_raw_opacity, params.max_log_scale, int(params.nb_neighbors), 0, float(params.std_ratio), float(params.radius),
                          int(params.nb_points), 0)
     R = _lib.CleanReport()
-    _sync(device, on)
-    _lib.check(L.gsr_outlier_mask(p_xyz, p_op, p_sc, n, C.addressof(P), p_mask, p_mean, p_cnt, C.addressof(R), 1 if on else 0, device,
-                                  C.c_void_p(_m.stream_ptr(device, on))), "gsr_outlier_mask")
+    _lib.check(L.gsr_outlier_mask(p_xyz, p_op, p_sc, n, C.addressof(P), p_mask, p_mean, p_cnt, C.addressof(R), *_mv.call_tail(device, on)), "gsr_outlier_mask")
     info = {k: int(getattr(R, k)) for k in ("n", "n_nonfinite", "n_gate_opacity", "n_gate_scale", "n_statistical", "n_radius", "n_kept",
                                             "deferred_queries", "workspace_bytes")}
     info.update({k: float(getattr(R, k)) for k in ("cloud_mean", "std_dev", "threshold")})
@@ -71,7 +62,7 @@ def select_rows(arrays, mask, device=0):
     ``dc``, ``sh``, ``opacity``, ``scaling``, ``rot``): ``sh`` has 3K floats per row, K in {0, 3, 8, 15}; ``scaling`` and ``rot``
     come both or neither.  One library call for all arrays."""
     L = _lib.load(require_device=True)
-    unknown = set(arrays) - set(_VIEW_FIELDS)
+    unknown = set(arrays) - {field for field, _, _ in _mv.FIELDS}
     if unknown:
         raise ValueError(f"unknown arrays {sorted(unknown)}")
     given = {k: a for k, a in arrays.items() if a is not None}
@@ -88,14 +79,12 @@ def select_rows(arrays, mask, device=0):
         if w % 3:
             raise ValueError("sh must hold 3K floats per row")
         K = w // 3
-        if K == 0:
-            del given["sh"]
     vin, vout, keep, outs, shapes = _lib.ModelView(), _lib.ModelView(), [], {}, {}
     vin.n, vout.n = n, n
-    for name, a in given.items():
+    for name, _, width in _mv.carried(K, True, fields=given):          # (K = 0: sh is not carried)
+        a = given[name]
         if int(a.shape[0]) != n:
             raise ValueError(f"{name}: {a.shape[0]} rows, expected {n}")
-        width = 3 * K if name == "sh" else _VIEW_WIDTH[name]
         p, k, a_on = _m.prep(a, (n, width), np.float32, device)
         if a_on != on:
             raise RuntimeError("the arrays must all live on the host or all on one device")
@@ -109,9 +98,7 @@ def select_rows(arrays, mask, device=0):
         raise RuntimeError("the mask must live where the arrays live")
     index, p_index = _m.out((n,), np.int32, device, on)
     n_out = C.c_int64(0)
-    _sync(device, on)
-    _lib.check(L.gsr_model_select(C.addressof(vin), K, p_mask, C.addressof(vout), p_index, C.byref(n_out), 1 if on else 0, device,
-                                  C.c_void_p(_m.stream_ptr(device, on))), "gsr_model_select")
+    _lib.check(L.gsr_model_select(C.addressof(vin), K, p_mask, C.addressof(vout), p_index, C.byref(n_out), *_mv.call_tail(device, on)), "gsr_model_select")
     m = int(n_out.value)
     return {name: o[:m].reshape((m,) + shapes[name]) for name, o in outs.items()}, index[:m]
 

@@ -518,15 +518,13 @@ extern "C" int32_t gsr_outlier_mask(const float* xyz, const float* raw_opacity, 
 extern "C" int32_t gsr_model_select(const gsr_model_view* in, int32_t K, const uint8_t* mask, gsr_model_view* out, int32_t* index, int64_t* n_out,
                                     int32_t on_device, int32_t device, void* stream) {
     const char* who = "gsr_model_select";
-    size_t width[GSR_SELECT_NARR];
-    bool used[GSR_SELECT_NARR];
+    size_t width[GSR_MODEL_NARR];
+    bool used[GSR_MODEL_NARR];
     if (const char* why = select_check_args(in, K, mask, out, index, n_out, width, used)) return fail(GSR_E_INVALID, "%s: %s", who, why);
     GSR_TRY(open_device(device, who));
     const int64_t n = in->n, cap = out->n;
     *n_out = 0;
     if (n == 0) { out->n = 0; return GSR_OK; }
-    const float* pi[GSR_SELECT_NARR] = {in->xyz, in->cov6, in->dc, in->sh, in->opacity, in->scaling, in->rot};
-    float* po[GSR_SELECT_NARR] = {out->xyz, out->cov6, out->dc, out->sh, out->opacity, out->scaling, out->rot};
     const bool dev = on_device != 0;
     const size_t un = (size_t)n, ucap = (size_t)cap;
     DevBuf tmp_scan;                                                   // rocPRIM's temporary: declared before the OneShot, freed after its wait
@@ -535,15 +533,10 @@ extern "C" int32_t gsr_model_select(const gsr_model_view* in, int32_t K, const u
     hipStream_t st = os.st;
     const uint8_t* dmask = nullptr;
     GSR_TRY(os.in(mask, un, &dmask));
-    const float* din[GSR_SELECT_NARR];
-    float* dout[GSR_SELECT_NARR];
-    for (int k = 0; k < GSR_SELECT_NARR; ++k) {
-        din[k] = nullptr; dout[k] = nullptr;
-        if (!used[k] || cap == 0) continue;
-        GSR_TRY(os.in(pi[k], un * width[k] * 4, &din[k]));
-        if (dev) dout[k] = po[k];
-        else GSR_TRY(os.scratch(ucap * width[k] * 4, &dout[k]));      // copied back below: n_out rows, not the capacity
-    }
+    const float* din[GSR_MODEL_NARR] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    float* dout[GSR_MODEL_NARR];
+    if (cap > 0) GSR_TRY(model_in(os, in, width, used, din));          // (an output without rows takes none)
+    GSR_TRY(model_out(os, out, cap, width, used, dout));
     int32_t* dindex = nullptr;
     if (index && cap > 0) { if (dev) dindex = index; else GSR_TRY(os.scratch(ucap * 4, &dindex)); }
     int *flag, *scan, *sel;
@@ -552,7 +545,7 @@ extern "C" int32_t gsr_model_select(const gsr_model_view* in, int32_t K, const u
     GSR_TRY(scan_exclusive<rocprim::default_config>(tmp_scan, st, (const int*)flag, scan, un + 1));
     hipLaunchKernelGGL(k_select_index, dim3(stride_grid(n)), dim3(256), 0, st, n, dmask, (const int*)scan, cap, sel, dindex);
     const int64_t rows_max = n < cap ? n : cap;
-    for (int k = 0; k < GSR_SELECT_NARR; ++k)
+    for (int k = 0; k < GSR_MODEL_NARR; ++k)
         if (dout[k])
             hipLaunchKernelGGL(k_model_select, dim3(stride_grid(rows_max * (int64_t)width[k])), dim3(256), 0, st, (const int*)scan + n, cap, (int)width[k],
                                (const int*)sel, reinterpret_cast<const uint32_t*>(din[k]), reinterpret_cast<uint32_t*>(dout[k]));
@@ -561,11 +554,8 @@ extern "C" int32_t gsr_model_select(const gsr_model_view* in, int32_t K, const u
     GSR_TRY(os.wait());
     *n_out = total;
     if (total > cap) return fail(GSR_E_INVALID, "%s: %d rows are kept, the output holds %lld", who, total, (long long)cap);
-    if (!dev && total > 0) {
-        for (int k = 0; k < GSR_SELECT_NARR; ++k)
-            if (dout[k]) GSR_HIP(hipMemcpyAsync(po[k], dout[k], (size_t)total * width[k] * 4, hipMemcpyDeviceToHost, st));
-        if (dindex) GSR_HIP(hipMemcpyAsync(index, dindex, (size_t)total * 4, hipMemcpyDeviceToHost, st));
-    }
+    GSR_TRY(model_copy_back(os, out, dout, total, width));
+    if (!dev && dindex && total > 0) GSR_HIP(hipMemcpyAsync(index, dindex, (size_t)total * 4, hipMemcpyDeviceToHost, st));
     out->n = total;
     return os.finish();
 }

@@ -20,6 +20,7 @@
 // covariances, which lie in one contiguous block of the output.
 #include "gsr_common.h"
 #include "gsr_oneshot.h"
+#include "gsr_fuse_args.h"
 #include "gsr_fuse_dev.h"
 #include "gsr_prims.h"
 
@@ -153,81 +154,86 @@ __global__ __launch_bounds__(256) void k_fuse_rows(int64_t na, int64_t nb, int W
 }
 
 
-// Everything gsr_model_fuse does before its writer, and all of gsr_model_match: pre-pass, grid, search, mutual test, scans, pair list.
-// What the writer and the report read afterwards stays in `f`, which the caller declares BEFORE its OneShot.
+// Everything gsr_model_fuse does before its writer, and all of gsr_model_match: staging, pre-pass, grid, search, mutual test, scans,
+// pair list (run), then the one read-back (counts).  What the writer and the report read stays here: the caller declares its
+// FuseFront BEFORE its OneShot.
 struct FuseFront {
     DevBuf tmp_sort_a, tmp_sort_b, tmp_scan_a, tmp_scan_b;
-    Event ev[5];                                                // front: 0..3 recorded here; the caller records 4 behind its writer
+    Event ev[5];                                                // run() records 0..2; the caller records 3 and, behind a writer, 4
     size_t workspace = 0;                                       // device bytes asked for beyond the caller's arrays (rocPRIM's temporaries are added at the end)
+    const float *da[GSR_MODEL_NARR], *db[GSR_MODEL_NARR];       // the used arrays of the two models on the device
+    int32_t* dpairs = nullptr;
     double *wA = nullptr, *wB = nullptr;
     int *mate = nullptr, *scanA = nullptr, *flagB = nullptr, *scanB = nullptr;
     unsigned long long* counters = nullptr;                     // invalid A, invalid B, gated pairs
-    size_t total_bytes() const { return workspace + tmp_sort_a.cap + tmp_sort_b.cap + tmp_scan_a.cap + tmp_scan_b.cap; }
+    unsigned long long hc[3] = {0, 0, 0};                       // the counters and the pair count on the host: read back asynchronously, so they
+    int hp = 0;                                                 // live here, beyond the OneShot's last wait, not in a frame that may be left early
+
+    int32_t run(OneShot& os, const gsr_model_view* a, const gsr_model_view* b, const size_t width[GSR_MODEL_NARR], const bool used[GSR_MODEL_NARR],
+                const gsr_fuse_params* params, int32_t* pairs) {
+        hipStream_t st = os.st;
+        auto ws = [&](size_t bytes, auto** p) { workspace += bytes; return os.scratch(bytes, p); };
+        const int64_t na = a->n, nb = b->n;
+        GSR_TRY(model_in(os, a, width, used, da));
+        GSR_TRY(model_in(os, b, width, used, db));
+        const size_t npair_cap = (size_t)(na < nb ? na : nb);
+        if (pairs && npair_cap) { if (os.on_device) dpairs = pairs; else GSR_TRY(os.scratch(npair_cap * 8, &dpairs)); }
+        double *invA, *invB, *sinv;
+        float *sxyz, *sdc, *scov;
+        unsigned *keysB, *idxB, *skeysB, *orderB;
+        int *best_b, *flagA;
+        unsigned long long* best_a;
+        FuseCells c;                                            // the grid over A
+        const size_t ua = (size_t)na, ub = (size_t)nb;
+        GSR_TRY(ws(ua * 8 + 8, &wA)); GSR_TRY(ws(ub * 8 + 8, &wB));
+        GSR_TRY(ws(ua * 48 + 8, &invA)); GSR_TRY(ws(ub * 48 + 8, &invB));
+        GSR_TRY(ws(ua * 48 + 8, &sinv)); GSR_TRY(ws(ua * 12 + 8, &sxyz)); GSR_TRY(ws(ua * 12 + 8, &sdc)); GSR_TRY(ws(ua * 24 + 8, &scov));
+        GSR_TRY(ws(ub * 4 + 8, &keysB)); GSR_TRY(ws(ub * 4 + 8, &idxB)); GSR_TRY(ws(ub * 4 + 8, &skeysB)); GSR_TRY(ws(ub * 4 + 8, &orderB));
+        GSR_TRY(ws(ua * 8 + 8, &best_a)); GSR_TRY(ws(ub * 4 + 8, &best_b)); GSR_TRY(ws(ua * 4 + 8, &mate));
+        GSR_TRY(ws((ua + 1) * 4, &flagA)); GSR_TRY(ws((ub + 1) * 4, &flagB)); GSR_TRY(ws((ua + 1) * 4, &scanA)); GSR_TRY(ws((ub + 1) * 4, &scanB));
+        GSR_TRY(ws(3 * 8, &counters));
+        GSR_TRY(c.reserve(os, workspace, na));
+        GSR_HIP(hipMemsetAsync(counters, 0, 3 * 8, st));
+        GSR_HIP(hipMemsetAsync(flagA, 0, (ua + 1) * 4, st));
+        GSR_HIP(hipMemsetAsync(flagB, 0, (ub + 1) * 4, st));
+        GSR_HIP(hipMemsetAsync(best_a, 0xff, ua * 8 + 8, st));
+
+        // ---- pre-pass and grid; B gets keys of A's grid and the order they give
+        GSR_HIP(hipEventRecord(ev[0], st));
+        GSR_TRY(c.launch(st, tmp_sort_a, da[0], da[1], da[4], wA, invA, counters, params->max_distance));
+        hipLaunchKernelGGL(k_fuse_prep, dim3(stride_grid(nb)), dim3(256), 0, st, nb, db[0], db[1], db[4], wB, invB, counters + 1);
+        hipLaunchKernelGGL(k_fuse_keys, dim3(stride_grid(nb)), dim3(256), 0, st, nb, db[0], (const FuseGrid*)c.grid, keysB, idxB);
+        if (nb > 0) GSR_TRY(sort_pairs_by_key<rocprim::default_config>(tmp_sort_b, st, (const unsigned*)keysB, skeysB, (const unsigned*)idxB, orderB, ub, 0u, c.bits));
+        hipLaunchKernelGGL(k_fuse_gather_a, dim3(stride_grid(na)), dim3(256), 0, st, na, (const unsigned*)c.order, da[0], da[2], da[1], wA, invA, sxyz, sdc, scov, sinv);
+        // ---- search
+        GSR_HIP(hipEventRecord(ev[1], st));
+        const double r2 = params->max_distance * params->max_distance, cd2 = params->color_delta * params->color_delta;
+        hipLaunchKernelGGL(k_fuse_search, dim3(stride_grid(nb)), dim3(256), 0, st, nb, orderB, db[0], db[2], db[1], wB, invB, (const FuseGrid*)c.grid,
+                           (const int*)c.cellStart, sxyz, sdc, scov, sinv, (const unsigned*)c.order, r2, params->kld_max, cd2, best_a, best_b, counters + 2);
+        // ---- pairs and scans
+        GSR_HIP(hipEventRecord(ev[2], st));
+        hipLaunchKernelGGL(k_fuse_pair, dim3(stride_grid(na)), dim3(256), 0, st, na, best_a, best_b, flagA, flagB, mate);
+        GSR_TRY(scan_exclusive<rocprim::default_config>(tmp_scan_a, st, (const int*)flagA, scanA, ua + 1));
+        GSR_TRY(scan_exclusive<rocprim::default_config>(tmp_scan_b, st, (const int*)flagB, scanB, ub + 1));
+        if (dpairs) hipLaunchKernelGGL(k_fuse_pairs_out, dim3(stride_grid(na)), dim3(256), 0, st, na, mate, scanA, dpairs);
+        return GSR_OK;
+    }
+
+    // the one read-back: the counts into the report with the first `phases` phase times, the pair list to a host caller
+    int32_t counts(OneShot& os, int64_t na, int64_t nb, int phases, gsr_fuse_report* r, int32_t* pairs) {
+        GSR_HIP(hipMemcpyAsync(hc, counters, sizeof(hc), hipMemcpyDeviceToHost, os.st));
+        GSR_HIP(hipMemcpyAsync(&hp, scanA + na, 4, hipMemcpyDeviceToHost, os.st));
+        GSR_TRY(os.wait());
+        const int64_t np = hp;
+        r->n_pairs = np; r->n_out = na + nb - np; r->n_a_only = na - np; r->n_b_only = nb - np;
+        r->n_invalid_a = (int64_t)hc[0]; r->n_invalid_b = (int64_t)hc[1];
+        for (int k = 0; k < phases; ++k) (void)hipEventElapsedTime(&r->phase_ms[k], ev[k], ev[k + 1]);
+        r->gated_pairs = (int64_t)hc[2];
+        r->workspace_bytes = (int64_t)(workspace + tmp_sort_a.cap + tmp_sort_b.cap + tmp_scan_a.cap + tmp_scan_b.cap);
+        if (!os.on_device && dpairs && np > 0) GSR_HIP(hipMemcpyAsync(pairs, dpairs, (size_t)np * 8, hipMemcpyDeviceToHost, os.st));
+        return GSR_OK;
+    }
 };
-
-static int32_t fuse_front(OneShot& os, FuseFront& f, int64_t na, int64_t nb, const float* xyzA, const float* covA, const float* dcA, const float* opA,
-                          const float* xyzB, const float* covB, const float* dcB, const float* opB, const gsr_fuse_params* params, int32_t* dpairs) {
-    hipStream_t st = os.st;
-    Event* ev = f.ev;
-    DevBuf &tmp_sort_a = f.tmp_sort_a, &tmp_sort_b = f.tmp_sort_b, &tmp_scan_a = f.tmp_scan_a, &tmp_scan_b = f.tmp_scan_b;
-    size_t& workspace = f.workspace;
-    auto ws = [&](size_t bytes, auto** p) { workspace += bytes; return os.scratch(bytes, p); };
-    const float* da[5] = {xyzA, covA, dcA, nullptr, opA};
-    const float* db[5] = {xyzB, covB, dcB, nullptr, opB};
-    const int64_t cap = na > 1024 ? na : 1024;                  // cells of the table
-    double *wA, *wB, *invA, *invB, *part, *box, *sinv;
-    float *sxyz, *sdc, *scov;
-    unsigned *keysA, *idxA, *skeysA, *orderA, *keysB, *idxB, *skeysB, *orderB;
-    int *cellStart, *best_b, *flagA, *flagB, *scanA, *scanB, *mate;
-    unsigned long long *best_a, *counters;                      // counters: invalid A, invalid B, gated pairs
-    FuseGrid* grid;
-    const size_t ua = (size_t)na, ub = (size_t)nb;
-    const int nblk = stride_grid(na);
-    GSR_TRY(ws(ua * 8 + 8, &wA)); GSR_TRY(ws(ub * 8 + 8, &wB));
-    GSR_TRY(ws(ua * 48 + 8, &invA)); GSR_TRY(ws(ub * 48 + 8, &invB));
-    GSR_TRY(ws((size_t)nblk * FUSE_MOM * 8, &part)); GSR_TRY(ws(6 * 8, &box)); GSR_TRY(ws(sizeof(FuseGrid), &grid));
-    GSR_TRY(ws(ua * 48 + 8, &sinv)); GSR_TRY(ws(ua * 12 + 8, &sxyz)); GSR_TRY(ws(ua * 12 + 8, &sdc)); GSR_TRY(ws(ua * 24 + 8, &scov));
-    GSR_TRY(ws(ua * 4 + 8, &keysA)); GSR_TRY(ws(ua * 4 + 8, &idxA)); GSR_TRY(ws(ua * 4 + 8, &skeysA)); GSR_TRY(ws(ua * 4 + 8, &orderA));
-    GSR_TRY(ws(ub * 4 + 8, &keysB)); GSR_TRY(ws(ub * 4 + 8, &idxB)); GSR_TRY(ws(ub * 4 + 8, &skeysB)); GSR_TRY(ws(ub * 4 + 8, &orderB));
-    GSR_TRY(ws(((size_t)cap + 2) * 4, &cellStart));
-    GSR_TRY(ws(ua * 8 + 8, &best_a)); GSR_TRY(ws(ub * 4 + 8, &best_b)); GSR_TRY(ws(ua * 4 + 8, &mate));
-    GSR_TRY(ws((ua + 1) * 4, &flagA)); GSR_TRY(ws((ub + 1) * 4, &flagB)); GSR_TRY(ws((ua + 1) * 4, &scanA)); GSR_TRY(ws((ub + 1) * 4, &scanB));
-    GSR_TRY(ws(3 * 8, &counters));
-    GSR_HIP(hipMemsetAsync(counters, 0, 3 * 8, st));
-    GSR_HIP(hipMemsetAsync(flagA, 0, (ua + 1) * 4, st));
-    GSR_HIP(hipMemsetAsync(flagB, 0, (ub + 1) * 4, st));
-    GSR_HIP(hipMemsetAsync(best_a, 0xff, ua * 8 + 8, st));
-
-    // ---- pre-pass and grid
-    GSR_HIP(hipEventRecord(ev[0], st));
-    hipLaunchKernelGGL(k_fuse_prep, dim3(stride_grid(na)), dim3(256), 0, st, na, da[0], da[1], da[4], wA, invA, counters);
-    hipLaunchKernelGGL(k_fuse_prep, dim3(stride_grid(nb)), dim3(256), 0, st, nb, db[0], db[1], db[4], wB, invB, counters + 1);
-    hipLaunchKernelGGL(k_fuse_moments, dim3(nblk), dim3(256), 0, st, na, da[0], wA, (const double*)nullptr, part);
-    hipLaunchKernelGGL(k_fuse_box, dim3(1), dim3(64), 0, st, nblk, part, 0, params->max_distance, cap, box, grid);
-    hipLaunchKernelGGL(k_fuse_moments, dim3(nblk), dim3(256), 0, st, na, da[0], wA, (const double*)box, part);
-    hipLaunchKernelGGL(k_fuse_box, dim3(1), dim3(64), 0, st, nblk, part, 1, params->max_distance, cap, box, grid);
-    hipLaunchKernelGGL(k_fuse_keys, dim3(stride_grid(na)), dim3(256), 0, st, na, da[0], grid, keysA, idxA);
-    hipLaunchKernelGGL(k_fuse_keys, dim3(stride_grid(nb)), dim3(256), 0, st, nb, db[0], grid, keysB, idxB);
-    unsigned bits = 1;
-    while (bits < 32 && ((int64_t)1 << bits) < cap) ++bits;
-    if (na > 0) GSR_TRY(sort_pairs_by_key<rocprim::default_config>(tmp_sort_a, st, (const unsigned*)keysA, skeysA, (const unsigned*)idxA, orderA, ua, 0u, bits));
-    if (nb > 0) GSR_TRY(sort_pairs_by_key<rocprim::default_config>(tmp_sort_b, st, (const unsigned*)keysB, skeysB, (const unsigned*)idxB, orderB, ub, 0u, bits));
-    hipLaunchKernelGGL(k_fuse_cell_starts, dim3(stride_grid(cap + 1)), dim3(256), 0, st, na, skeysA, cap, cellStart);
-    hipLaunchKernelGGL(k_fuse_gather_a, dim3(stride_grid(na)), dim3(256), 0, st, na, orderA, da[0], da[2], da[1], wA, invA, sxyz, sdc, scov, sinv);
-    // ---- search
-    GSR_HIP(hipEventRecord(ev[1], st));
-    const double r2 = params->max_distance * params->max_distance, cd2 = params->color_delta * params->color_delta;
-    hipLaunchKernelGGL(k_fuse_search, dim3(stride_grid(nb)), dim3(256), 0, st, nb, orderB, db[0], db[2], db[1], wB, invB, grid, cellStart, sxyz, sdc, scov, sinv,
-                       orderA, r2, params->kld_max, cd2, best_a, best_b, counters + 2);
-    // ---- pairs and scans
-    GSR_HIP(hipEventRecord(ev[2], st));
-    hipLaunchKernelGGL(k_fuse_pair, dim3(stride_grid(na)), dim3(256), 0, st, na, best_a, best_b, flagA, flagB, mate);
-    GSR_TRY(scan_exclusive<rocprim::default_config>(tmp_scan_a, st, (const int*)flagA, scanA, ua + 1));
-    GSR_TRY(scan_exclusive<rocprim::default_config>(tmp_scan_b, st, (const int*)flagB, scanB, ub + 1));
-    if (dpairs) hipLaunchKernelGGL(k_fuse_pairs_out, dim3(stride_grid(na)), dim3(256), 0, st, na, mate, scanA, dpairs);
-    f.wA = wA; f.wB = wB; f.mate = mate; f.scanA = scanA; f.flagB = flagB; f.scanB = scanB; f.counters = counters;
-    return GSR_OK;
-}
 
 }  // namespace gsr
 
@@ -236,99 +242,39 @@ using namespace gsr;
 extern "C" int32_t gsr_model_fuse(const gsr_model_view* a, const gsr_model_view* b, int32_t K, const gsr_fuse_params* params, gsr_model_view* out,
                                   int32_t* pairs, gsr_fuse_report* report, int32_t on_device, int32_t device, void* stream) {
     const char* who = "gsr_model_fuse";
-    if (!a || !b || !params || !out || !report) return fail(GSR_E_INVALID, "gsr_model_fuse: NULL argument");
-    if (K != 0 && K != 3 && K != 8 && K != 15) return fail(GSR_E_INVALID, "gsr_model_fuse: K = %d (must be 0, 3, 8 or 15)", K);
-    if (!(params->max_distance > 0.0 && params->max_distance <= DBL_MAX)) return fail(GSR_E_INVALID, "gsr_model_fuse: max_distance must be positive and finite");
-    if (!(params->kld_max >= 0.0) || !(params->color_delta >= 0.0)) return fail(GSR_E_INVALID, "gsr_model_fuse: kld_max and color_delta must be >= 0");
-    const int64_t na = a->n, nb = b->n;
-    if (na < 0 || nb < 0 || na >= ((int64_t)1 << 31) || nb >= ((int64_t)1 << 31)) return fail(GSR_E_INVALID, "gsr_model_fuse: row counts must be in [0, 2^31)");
-    const bool sr_a = a->scaling && a->rot, sr_b = b->scaling && b->rot;
-    for (const gsr_model_view* v : {a, b}) {
-        if ((v->scaling != nullptr) != (v->rot != nullptr)) return fail(GSR_E_INVALID, "gsr_model_fuse: scaling and rot come together");
-        if (v->n > 0 && (!v->xyz || !v->cov6 || !v->dc || !v->opacity || (K > 0 && !v->sh))) return fail(GSR_E_INVALID, "gsr_model_fuse: NULL array in an input model");
-    }
-    // an empty model has no arrays to carry: the other one decides
-    const bool with_sr = na > 0 ? sr_a : sr_b;
-    if (na > 0 && nb > 0 && sr_a != sr_b) return fail(GSR_E_INVALID, "gsr_model_fuse: scaling / rot present in one model only");
-    const int64_t cap_rows = na + nb;
-    if (out->n < cap_rows) return fail(GSR_E_INVALID, "gsr_model_fuse: the output holds %lld rows, %lld are needed", (long long)out->n, (long long)cap_rows);
-    if (cap_rows > 0 && (!out->xyz || !out->cov6 || !out->dc || !out->opacity || (K > 0 && !out->sh) || (with_sr && (!out->scaling || !out->rot))))
-        return fail(GSR_E_INVALID, "gsr_model_fuse: NULL array in the output model");
-    const size_t F = 3 * (size_t)K;
-    const int NARR = 7;
-    const size_t width[NARR] = {3, 6, 3, F, 1, 3, 4};
-    const int modes[NARR] = {FUSE_MEAN, FUSE_COV, FUSE_MEAN, FUSE_MEAN, FUSE_MEAN, FUSE_COPY, FUSE_COPY};
-    const float* pa[NARR] = {a->xyz, a->cov6, a->dc, a->sh, a->opacity, a->scaling, a->rot};
-    const float* pb[NARR] = {b->xyz, b->cov6, b->dc, b->sh, b->opacity, b->scaling, b->rot};
-    float* po[NARR] = {out->xyz, out->cov6, out->dc, out->sh, out->opacity, out->scaling, out->rot};
-    bool used[NARR];
-    for (int k = 0; k < NARR; ++k) used[k] = k == 3 ? K > 0 : k >= 5 ? with_sr : true;
-    const size_t npair_cap = (size_t)(na < nb ? na : nb);
-    for (int i = 0; i < NARR; ++i) {
-        if (!used[i]) continue;
-        const size_t bo = (size_t)cap_rows * width[i] * 4;
-        if (ranges_overlap(po[i], bo, pairs, npair_cap * 8)) return fail(GSR_E_INVALID, "gsr_model_fuse: an output array overlaps another array of the call (the fusion is not in place)");
-        for (int j = 0; j < NARR; ++j) {
-            if (!used[j]) continue;
-            if (ranges_overlap(po[i], bo, pa[j], (size_t)na * width[j] * 4) || ranges_overlap(po[i], bo, pb[j], (size_t)nb * width[j] * 4) ||
-                (i < j && ranges_overlap(po[i], bo, po[j], (size_t)cap_rows * width[j] * 4)))
-                return fail(GSR_E_INVALID, "gsr_model_fuse: an output array overlaps another array of the call (the fusion is not in place)");
-        }
-    }
+    size_t width[GSR_MODEL_NARR];
+    bool used[GSR_MODEL_NARR], with_sr = false;
+    char why[256];
+    if (const char* refused = fuse_check_args(a, b, K, params, out, pairs, report, width, used, &with_sr, why, sizeof why))
+        return fail(GSR_E_INVALID, "gsr_model_fuse: %s", refused);
+    const int64_t na = a->n, nb = b->n, cap_rows = na + nb;
+    const int modes[GSR_MODEL_NARR] = {FUSE_MEAN, FUSE_COV, FUSE_MEAN, FUSE_MEAN, FUSE_MEAN, FUSE_COPY, FUSE_COPY};
     GSR_TRY(open_device(device, who));
     memset(report, 0, sizeof(*report));
     if (cap_rows == 0) { out->n = 0; return GSR_OK; }
 
-    const bool dev = on_device != 0;
     FuseFront f;                                                // (rocPRIM's temporaries: declared before the OneShot, freed after its wait)
     for (Event& e : f.ev) GSR_HIP(e.create());
-    OneShot os((hipStream_t)stream, dev, who);
+    OneShot os((hipStream_t)stream, on_device != 0, who);
     hipStream_t st = os.st;
-    const float *da[NARR], *db[NARR];
-    float* dout[NARR];
-    for (int k = 0; k < NARR; ++k) {
-        da[k] = db[k] = nullptr; dout[k] = nullptr;
-        if (!used[k]) continue;
-        GSR_TRY(os.in(na > 0 ? pa[k] : nullptr, (size_t)na * width[k] * 4, &da[k]));
-        GSR_TRY(os.in(nb > 0 ? pb[k] : nullptr, (size_t)nb * width[k] * 4, &db[k]));
-        if (dev) dout[k] = po[k];
-        else GSR_TRY(os.scratch((size_t)cap_rows * width[k] * 4, &dout[k]));      // copied back below: n_out rows, not the capacity
-    }
-    int32_t* dpairs = nullptr;
-    if (pairs && npair_cap) { if (dev) dpairs = pairs; else GSR_TRY(os.scratch(npair_cap * 8, &dpairs)); }
-    GSR_TRY(fuse_front(os, f, na, nb, da[0], da[1], da[2], da[4], db[0], db[1], db[2], db[4], params, dpairs));
-    Event* ev = f.ev;
-    const double *wA = f.wA, *wB = f.wB;
-    const int *mate = f.mate, *scanA = f.scanA, *flagB = f.flagB, *scanB = f.scanB;
-    const unsigned long long* counters = f.counters;
+    float* dout[GSR_MODEL_NARR];
+    GSR_TRY(model_out(os, out, cap_rows, width, used, dout));
+    GSR_TRY(f.run(os, a, b, width, used, params, pairs));
     // ---- writer
-    GSR_HIP(hipEventRecord(ev[3], st));
-    for (int k = 0; k < NARR; ++k)
+    GSR_HIP(hipEventRecord(f.ev[3], st));
+    for (int k = 0; k < GSR_MODEL_NARR; ++k)
         if (used[k])
-            hipLaunchKernelGGL(k_fuse_rows, dim3(stride_grid(cap_rows * (int64_t)width[k])), dim3(256), 0, st, na, nb, (int)width[k], modes[k], da[k], db[k], dout[k],
-                               mate, scanA, flagB, scanB, wA, wB, da[0], db[0]);
-    GSR_HIP(hipEventRecord(ev[4], st));
-    // ---- the one read-back: the counts
-    unsigned long long hc[3] = {0, 0, 0};
-    int hp = 0;
-    GSR_HIP(hipMemcpyAsync(hc, counters, sizeof(hc), hipMemcpyDeviceToHost, st));
-    GSR_HIP(hipMemcpyAsync(&hp, scanA + na, 4, hipMemcpyDeviceToHost, st));
-    GSR_TRY(os.wait());
-    const int64_t np = hp, n_out = cap_rows - np;
-    report->n_pairs = np; report->n_out = n_out; report->n_a_only = na - np; report->n_b_only = nb - np;
-    report->n_invalid_a = (int64_t)hc[0]; report->n_invalid_b = (int64_t)hc[1];
-    for (int k = 0; k < 4; ++k) (void)hipEventElapsedTime(&report->phase_ms[k], ev[k], ev[k + 1]);
-    report->gated_pairs = (int64_t)hc[2];
-    report->workspace_bytes = (int64_t)f.total_bytes();
+            hipLaunchKernelGGL(k_fuse_rows, dim3(stride_grid(cap_rows * (int64_t)width[k])), dim3(256), 0, st, na, nb, (int)width[k], modes[k], f.da[k], f.db[k], dout[k],
+                               (const int*)f.mate, (const int*)f.scanA, (const int*)f.flagB, (const int*)f.scanB, (const double*)f.wA, (const double*)f.wB, f.da[0],
+                               f.db[0]);
+    GSR_HIP(hipEventRecord(f.ev[4], st));
+    GSR_TRY(f.counts(os, na, nb, 4, report, pairs));
+    const int64_t np = report->n_pairs, n_out = report->n_out;
     if (with_sr && np > 0) {
         const int64_t off = na - np;
         GSR_TRY(gsr_decompose_cov(dout[1] + 6 * off, np, GSR_DECOMP_EXACT, dout[5] + 3 * off, dout[6] + 4 * off, nullptr, 1, device, stream));
     }
-    if (!dev) {
-        for (int k = 0; k < NARR; ++k)
-            if (used[k] && n_out > 0) GSR_HIP(hipMemcpyAsync(po[k], dout[k], (size_t)n_out * width[k] * 4, hipMemcpyDeviceToHost, st));
-        if (dpairs && np > 0) GSR_HIP(hipMemcpyAsync(pairs, dpairs, (size_t)np * 8, hipMemcpyDeviceToHost, st));
-    }
+    GSR_TRY(model_copy_back(os, out, dout, n_out, width));
     out->n = n_out;
     return os.finish();
 }
@@ -336,46 +282,19 @@ extern "C" int32_t gsr_model_fuse(const gsr_model_view* a, const gsr_model_view*
 extern "C" int32_t gsr_model_match(const gsr_model_view* a, const gsr_model_view* b, const gsr_fuse_params* params, int32_t* pairs,
                                    gsr_fuse_report* report, int32_t on_device, int32_t device, void* stream) {
     const char* who = "gsr_model_match";
-    if (!a || !b || !params || !report) return fail(GSR_E_INVALID, "gsr_model_match: NULL argument");
-    if (!(params->max_distance > 0.0 && params->max_distance <= DBL_MAX)) return fail(GSR_E_INVALID, "gsr_model_match: max_distance must be positive and finite");
-    if (!(params->kld_max >= 0.0) || !(params->color_delta >= 0.0)) return fail(GSR_E_INVALID, "gsr_model_match: kld_max and color_delta must be >= 0");
-    const int64_t na = a->n, nb = b->n;
-    if (na < 0 || nb < 0 || na >= ((int64_t)1 << 31) || nb >= ((int64_t)1 << 31)) return fail(GSR_E_INVALID, "gsr_model_match: row counts must be in [0, 2^31)");
-    for (const gsr_model_view* v : {a, b})
-        if (v->n > 0 && (!v->xyz || !v->cov6 || !v->dc || !v->opacity)) return fail(GSR_E_INVALID, "gsr_model_match: NULL array in an input model");
+    if (const char* refused = match_check_args(a, b, params, report)) return fail(GSR_E_INVALID, "gsr_model_match: %s", refused);
     GSR_TRY(open_device(device, who));
     memset(report, 0, sizeof(*report));
-    if (na + nb == 0) return GSR_OK;
+    if (a->n + b->n == 0) return GSR_OK;
 
-    const bool dev = on_device != 0;
-    const size_t npair_cap = (size_t)(na < nb ? na : nb);
     FuseFront f;
     for (Event& e : f.ev) GSR_HIP(e.create());
-    unsigned long long hc[3] = {0, 0, 0};
-    int hp = 0;
-    OneShot os((hipStream_t)stream, dev, who);
-    hipStream_t st = os.st;
-    const float* pa[4] = {a->xyz, a->cov6, a->dc, a->opacity};
-    const float* pb[4] = {b->xyz, b->cov6, b->dc, b->opacity};
-    const size_t width[4] = {3, 6, 3, 1};
-    const float *da[4], *db[4];
-    for (int k = 0; k < 4; ++k) {
-        GSR_TRY(os.in(na > 0 ? pa[k] : nullptr, (size_t)na * width[k] * 4, &da[k]));
-        GSR_TRY(os.in(nb > 0 ? pb[k] : nullptr, (size_t)nb * width[k] * 4, &db[k]));
-    }
-    int32_t* dpairs = nullptr;
-    if (pairs && npair_cap) { if (dev) dpairs = pairs; else GSR_TRY(os.scratch(npair_cap * 8, &dpairs)); }
-    GSR_TRY(fuse_front(os, f, na, nb, da[0], da[1], da[2], da[3], db[0], db[1], db[2], db[3], params, dpairs));
-    GSR_HIP(hipEventRecord(f.ev[3], st));
-    GSR_HIP(hipMemcpyAsync(hc, f.counters, sizeof(hc), hipMemcpyDeviceToHost, st));
-    GSR_HIP(hipMemcpyAsync(&hp, f.scanA + na, 4, hipMemcpyDeviceToHost, st));
-    GSR_TRY(os.wait());
-    const int64_t np = hp;
-    report->n_pairs = np; report->n_out = na + nb - np; report->n_a_only = na - np; report->n_b_only = nb - np;
-    report->n_invalid_a = (int64_t)hc[0]; report->n_invalid_b = (int64_t)hc[1];
-    for (int k = 0; k < 3; ++k) (void)hipEventElapsedTime(&report->phase_ms[k], f.ev[k], f.ev[k + 1]);
-    report->gated_pairs = (int64_t)hc[2];
-    report->workspace_bytes = (int64_t)f.total_bytes();
-    if (!dev && dpairs && np > 0) GSR_HIP(hipMemcpyAsync(pairs, dpairs, (size_t)np * 8, hipMemcpyDeviceToHost, st));
+    OneShot os((hipStream_t)stream, on_device != 0, who);
+    size_t width[GSR_MODEL_NARR];
+    bool used[GSR_MODEL_NARR];
+    model_layout(0, false, width, used);                        // the search reads xyz, cov6, dc and opacity
+    GSR_TRY(f.run(os, a, b, width, used, params, pairs));
+    GSR_HIP(hipEventRecord(f.ev[3], os.st));
+    GSR_TRY(f.counts(os, a->n, b->n, 3, report, pairs));
     return os.finish();
 }

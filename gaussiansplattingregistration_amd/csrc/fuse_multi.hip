@@ -23,7 +23,7 @@
 #include "gsr_common.h"
 #include "gsr_oneshot.h"
 #include "gsr_fuse_dev.h"
-#include "gsr_fuse_multi_args.h"
+#include "gsr_fuse_args.h"
 #include "gsr_prims.h"
 
 #include <float.h>
@@ -36,7 +36,7 @@ namespace gsr {
 
 // where the rows of every model live: p[array][model] (NULL: the array is not carried), off[m] = the global index of model m's row 0
 struct FmTable {
-    const float* p[FM_NARR][GSR_FUSE_MAX_MODELS];
+    const float* p[GSR_MODEL_NARR][GSR_FUSE_MAX_MODELS];
     int64_t off[GSR_FUSE_MAX_MODELS + 1];
 };
 
@@ -294,15 +294,14 @@ extern "C" int32_t gsr_fuse_multi(const gsr_model_view* models, int32_t n_models
                                         int32_t* group_of, gsr_fuse_multi_report* report, int32_t on_device, int32_t device, void* stream) {
     const char* who = "gsr_fuse_multi";
     int64_t off[GSR_FUSE_MAX_MODELS + 1];
-    size_t width[FM_NARR];
-    bool used[FM_NARR], with_sr = false;
+    size_t width[GSR_MODEL_NARR];
+    bool used[GSR_MODEL_NARR], with_sr = false;
     char why[256];
     if (const char* refused = fuse_multi_check_args(models, n_models, K, params, out, group_of, report, off, width, used, &with_sr, why, sizeof why))
         return fail(GSR_E_INVALID, "gsr_fuse_multi: %s", refused);
     const int N = n_models;
     const int64_t n = off[N];
-    const int modes[FM_NARR] = {FM_MEAN, FM_COV, FM_MEAN, FM_MEAN, FM_MEAN, FM_COPY, FM_COPY};
-    auto arr_of = [](const gsr_model_view* v, int k) { return fm_array(v, k); };
+    const int modes[GSR_MODEL_NARR] = {FM_MEAN, FM_COV, FM_MEAN, FM_MEAN, FM_MEAN, FM_COPY, FM_COPY};
     memset(report, 0, sizeof(*report));
     GSR_TRY(open_device(device, who));
     if (n == 0) { out->n = 0; return GSR_OK; }
@@ -320,17 +319,16 @@ extern "C" int32_t gsr_fuse_multi(const gsr_model_view* models, int32_t n_models
     const size_t un = (size_t)n;
 
     // ---- the union copies of the arrays the search reads, the table of the others
-    float* uni[FM_NARR] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    float* dout[FM_NARR];
-    for (int k = 0; k < FM_NARR; ++k) {
-        dout[k] = nullptr;
+    float* uni[GSR_MODEL_NARR] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    float* dout[GSR_MODEL_NARR];
+    for (int k = 0; k < GSR_MODEL_NARR; ++k) {
         if (!used[k]) continue;
         const bool in_union = k == 0 || k == 1 || k == 2 || k == 4;
         if (in_union) GSR_TRY(ws(un * width[k] * 4 + 8, &uni[k]));
         for (int m = 0; m < N; ++m) {
             const int64_t nm = models[m].n;
             if (nm == 0) continue;
-            const float* src = arr_of(models + m, k);
+            const float* src = model_array(models + m, k);
             if (in_union) {
                 float* dst = uni[k] + (size_t)off[m] * width[k];
                 GSR_HIP(hipMemcpyAsync(dst, src, (size_t)nm * width[k] * 4, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
@@ -339,38 +337,33 @@ extern "C" int32_t gsr_fuse_multi(const gsr_model_view* models, int32_t n_models
                 GSR_TRY(os.in(src, (size_t)nm * width[k] * 4, &tab.p[k][m]));
             }
         }
-        if (dev) dout[k] = arr_of(out, k);
-        else GSR_TRY(os.scratch(un * width[k] * 4, &dout[k]));          // copied back below: n_out rows, not the capacity
     }
+    GSR_TRY(model_out(os, out, n, width, used, dout));
     for (int m = 0; m <= GSR_FUSE_MAX_MODELS; ++m) tab.off[m] = off[m <= N ? m : N];
     int32_t* dgroup = nullptr;
     if (group_of) { if (dev) dgroup = group_of; else GSR_TRY(os.scratch(un * 4, &dgroup)); }
 
-    const int64_t cap = n > 1024 ? n : 1024;                    // cells of the table
-    const int64_t slots = n * N;
-    const size_t us = (size_t)slots;
     FmTable* dtab;
     uint8_t *model, *smodel;
-    double *w, *inv, *part, *box, *sinv;
+    double *w, *inv, *sinv;
     float *sxyz, *sdc, *scov;
-    unsigned *keys, *idx, *skeys, *order, *mask;
-    int *cellStart, *eflag, *escan, *label, *parent, *grouped, *root, *scanG, *scanR;
+    unsigned* mask;
+    int *eflag, *escan, *label, *parent, *grouped, *root, *scanG, *scanR;
     unsigned long long *best, *pick, *counters;                 // counters: [0] rejected, [1] merges, [2] invalid, [3] gated, [4 ..] histogram
-    FuseGrid* grid;
-    const int nblk = stride_grid(n);
+    FuseCells c;
+    const int64_t slots = n * N;
+    const size_t us = (size_t)slots;
     const int NCOUNT = 4 + GSR_FUSE_MAX_MODELS + 1;
     GSR_TRY(ws(sizeof(FmTable), &dtab));
     GSR_TRY(ws(un + 8, &model)); GSR_TRY(ws(un + 8, &smodel));
     GSR_TRY(ws(un * 8 + 8, &w)); GSR_TRY(ws(un * 48 + 8, &inv));
-    GSR_TRY(ws((size_t)nblk * FUSE_MOM * 8, &part)); GSR_TRY(ws(6 * 8, &box)); GSR_TRY(ws(sizeof(FuseGrid), &grid));
     GSR_TRY(ws(un * 48 + 8, &sinv)); GSR_TRY(ws(un * 12 + 8, &sxyz)); GSR_TRY(ws(un * 12 + 8, &sdc)); GSR_TRY(ws(un * 24 + 8, &scov));
-    GSR_TRY(ws(un * 4 + 8, &keys)); GSR_TRY(ws(un * 4 + 8, &idx)); GSR_TRY(ws(un * 4 + 8, &skeys)); GSR_TRY(ws(un * 4 + 8, &order));
-    GSR_TRY(ws(((size_t)cap + 2) * 4, &cellStart));
     GSR_TRY(ws(us * 8 + 8, &best));
     GSR_TRY(ws((us + 1) * 4, &eflag)); GSR_TRY(ws((us + 1) * 4, &escan));
     GSR_TRY(ws(un * 4 + 8, &label)); GSR_TRY(ws(un * 4 + 8, &parent)); GSR_TRY(ws(un * 4 + 8, &mask)); GSR_TRY(ws(un * 8 + 8, &pick));
     GSR_TRY(ws((un + 1) * 4, &grouped)); GSR_TRY(ws((un + 1) * 4, &root)); GSR_TRY(ws((un + 1) * 4, &scanG)); GSR_TRY(ws((un + 1) * 4, &scanR));
     GSR_TRY(ws((size_t)NCOUNT * 8, &counters));
+    GSR_TRY(c.reserve(os, workspace, n));
     GSR_HIP(hipMemcpyAsync(dtab, &tab, sizeof(tab), hipMemcpyHostToDevice, st));
     GSR_HIP(hipMemsetAsync(counters, 0, (size_t)NCOUNT * 8, st));
     for (int m = 0; m < N; ++m)
@@ -378,22 +371,13 @@ extern "C" int32_t gsr_fuse_multi(const gsr_model_view* models, int32_t n_models
 
     // ---- pre-pass and grid
     GSR_HIP(hipEventRecord(ev[0], st));
-    hipLaunchKernelGGL(k_fuse_prep, dim3(stride_grid(n)), dim3(256), 0, st, n, (const float*)uni[0], (const float*)uni[1], (const float*)uni[4], w, inv, counters + 2);
-    hipLaunchKernelGGL(k_fuse_moments, dim3(nblk), dim3(256), 0, st, n, (const float*)uni[0], (const double*)w, (const double*)nullptr, part);
-    hipLaunchKernelGGL(k_fuse_box, dim3(1), dim3(64), 0, st, nblk, (const double*)part, 0, params->max_distance, cap, box, grid);
-    hipLaunchKernelGGL(k_fuse_moments, dim3(nblk), dim3(256), 0, st, n, (const float*)uni[0], (const double*)w, (const double*)box, part);
-    hipLaunchKernelGGL(k_fuse_box, dim3(1), dim3(64), 0, st, nblk, (const double*)part, 1, params->max_distance, cap, box, grid);
-    hipLaunchKernelGGL(k_fuse_keys, dim3(stride_grid(n)), dim3(256), 0, st, n, (const float*)uni[0], (const FuseGrid*)grid, keys, idx);
-    unsigned bits = 1;
-    while (bits < 32 && ((int64_t)1 << bits) < cap) ++bits;
-    GSR_TRY(sort_pairs_by_key<rocprim::default_config>(tmp_sort, st, (const unsigned*)keys, skeys, (const unsigned*)idx, order, un, 0u, bits));
-    hipLaunchKernelGGL(k_fuse_cell_starts, dim3(stride_grid(cap + 1)), dim3(256), 0, st, n, (const unsigned*)skeys, cap, cellStart);
-    hipLaunchKernelGGL(k_fm_gather, dim3(stride_grid(n)), dim3(256), 0, st, n, (const unsigned*)order, (const float*)uni[0], (const float*)uni[2], (const float*)uni[1],
+    GSR_TRY(c.launch(st, tmp_sort, uni[0], uni[1], uni[4], w, inv, counters + 2, params->max_distance));
+    hipLaunchKernelGGL(k_fm_gather, dim3(stride_grid(n)), dim3(256), 0, st, n, (const unsigned*)c.order, (const float*)uni[0], (const float*)uni[2], (const float*)uni[1],
                        (const double*)w, (const double*)inv, (const uint8_t*)model, sxyz, sdc, scov, sinv, smodel);
     // ---- search
     GSR_HIP(hipEventRecord(ev[1], st));
     const double r2 = params->max_distance * params->max_distance, cd2 = params->color_delta * params->color_delta;
-    hipLaunchKernelGGL(k_fm_search, dim3(stride_grid(n)), dim3(256), (size_t)N * 256 * 8, st, n, N, (const unsigned*)order, (const FuseGrid*)grid, (const int*)cellStart,
+    hipLaunchKernelGGL(k_fm_search, dim3(stride_grid(n)), dim3(256), (size_t)N * 256 * 8, st, n, N, (const unsigned*)c.order, (const FuseGrid*)c.grid, (const int*)c.cellStart,
                        (const float*)sxyz, (const float*)sdc, (const float*)scov, (const double*)sinv, (const uint8_t*)smodel, r2, params->kld_max, cd2, best, counters + 3);
     // ---- the edge list
     GSR_HIP(hipEventRecord(ev[2], st));
@@ -446,7 +430,7 @@ extern "C" int32_t gsr_fuse_multi(const gsr_model_view* models, int32_t n_models
     hipLaunchKernelGGL(k_fm_members, dim3(stride_grid(n)), dim3(256), 0, st, n, N, (const int*)label, (const int*)grouped, (const int*)scanR, (const int*)scanG,
                        (const uint8_t*)model, member, dgroup);
     // ---- writer
-    for (int k = 0; k < FM_NARR; ++k)
+    for (int k = 0; k < GSR_MODEL_NARR; ++k)
         if (used[k])
             hipLaunchKernelGGL(k_fm_rows, dim3(stride_grid(n * (int64_t)width[k])), dim3(256), 0, st, n, N, (int)width[k], modes[k], k, (const FmTable*)dtab, dout[k],
                                (const int*)label, (const int*)grouped, (const int*)scanG, (const int*)scanR, (const int*)member, (const uint8_t*)model, (const double*)w,
@@ -461,11 +445,8 @@ extern "C" int32_t gsr_fuse_multi(const gsr_model_view* models, int32_t n_models
     report->workspace_bytes = (int64_t)(workspace + tmp_sort.cap + tmp_scan_e.cap + tmp_scan_g.cap + tmp_scan_r.cap);
     if (with_sr && ng > 0)
         GSR_TRY(gsr_decompose_cov(dout[1] + 6 * n_copied, ng, GSR_DECOMP_EXACT, dout[5] + 3 * n_copied, dout[6] + 4 * n_copied, nullptr, 1, device, stream));
-    if (!dev) {
-        for (int k = 0; k < FM_NARR; ++k)
-            if (used[k] && n_out > 0) GSR_HIP(hipMemcpyAsync(arr_of(out, k), dout[k], (size_t)n_out * width[k] * 4, hipMemcpyDeviceToHost, st));
-        if (dgroup) GSR_HIP(hipMemcpyAsync(group_of, dgroup, un * 4, hipMemcpyDeviceToHost, st));
-    }
+    GSR_TRY(model_copy_back(os, out, dout, n_out, width));
+    if (!dev && dgroup) GSR_HIP(hipMemcpyAsync(group_of, dgroup, un * 4, hipMemcpyDeviceToHost, st));
     out->n = n_out;
     return os.finish();
 }

@@ -6,7 +6,7 @@
 #include <stdint.h>
 #include <stdio.h>
 
-#include "../../include/gsr_hip.h"
+#include "gsr_model_arrays.h"
 
 namespace gsr {
 
@@ -29,47 +29,27 @@ inline const char* clean_check_args(const float* xyz, const float* raw_opacity, 
     return nullptr;
 }
 
-inline bool clean_ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
-    if (!a || !b || !na || !nb) return false;
-    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-    return pa < pb + nb && pb < pa + na;
-}
-
-#define GSR_SELECT_NARR 7
-// width[k] = floats per row of array k (xyz, cov6, dc, sh, opacity, scaling, rot); used[k] = the call carries it
+// width[k] = floats per row of array k; used[k] = the input has the array (a selection carries whatever arrays its input has)
 inline const char* select_check_args(const gsr_model_view* in, int32_t K, const uint8_t* mask, const gsr_model_view* out, const int32_t* index,
-                                     const int64_t* n_out, size_t width[GSR_SELECT_NARR], bool used[GSR_SELECT_NARR]) {
+                                     const int64_t* n_out, size_t width[GSR_MODEL_NARR], bool used[GSR_MODEL_NARR]) {
     if (!in || !out || !n_out) return "NULL argument";
-    if (K != 0 && K != 3 && K != 8 && K != 15) return "K must be 0, 3, 8 or 15";
-    if (in->n < 0 || in->n >= ((int64_t)1 << 31)) return "row count must lie in [0, 2^31)";
+    if (!sh_count_ok(K)) return "K must be 0, 3, 8 or 15";
+    if (const char* why = model_check_input(in, K, false)) return why;
     if (out->n < 0) return "negative output capacity";
     if (in->n > 0 && !mask) return "NULL mask";
-    if ((in->scaling != nullptr) != (in->rot != nullptr)) return "scaling and rot come together";
-    const size_t w[GSR_SELECT_NARR] = {3, 6, 3, 3 * (size_t)K, 1, 3, 4};
-    const float* pi[GSR_SELECT_NARR] = {in->xyz, in->cov6, in->dc, in->sh, in->opacity, in->scaling, in->rot};
-    float* po[GSR_SELECT_NARR] = {out->xyz, out->cov6, out->dc, out->sh, out->opacity, out->scaling, out->rot};
     const size_t ni = (size_t)in->n, no = (size_t)out->n;
-    for (int k = 0; k < GSR_SELECT_NARR; ++k) {
-        width[k] = w[k];
-        used[k] = pi[k] != nullptr && w[k] > 0;
-        if (used[k] && !po[k] && no > 0 && ni > 0) return "an array of the input has no place in the output";
+    model_layout(K, true, width, used);
+    for (int k = 0; k < GSR_MODEL_NARR; ++k) {
+        used[k] = used[k] && model_array(in, k) != nullptr;
+        if (used[k] && !model_array(out, k) && no > 0 && ni > 0) return "an array of the input has no place in the output";
     }
-    for (int i = 0; i < GSR_SELECT_NARR; ++i) {
-        if (!used[i]) continue;
-        const size_t bo = no * w[i] * 4;
-        if (clean_ranges_overlap(po[i], bo, mask, ni) || clean_ranges_overlap(po[i], bo, index, no * 4))
-            return "an output array overlaps another array of the call (the selection is not in place)";
-        for (int j = 0; j < GSR_SELECT_NARR; ++j) {
-            if (!used[j]) continue;
-            if (clean_ranges_overlap(po[i], bo, pi[j], ni * w[j] * 4) || (i < j && clean_ranges_overlap(po[i], bo, po[j], no * w[j] * 4)))
-                return "an output array overlaps another array of the call (the selection is not in place)";
-        }
-    }
-    if (index) {
-        if (clean_ranges_overlap(index, no * 4, mask, ni)) return "index overlaps the mask";
-        for (int j = 0; j < GSR_SELECT_NARR; ++j)
-            if (used[j] && clean_ranges_overlap(index, no * 4, pi[j], ni * w[j] * 4)) return "index overlaps an input array";
-    }
+    const ByteRange extra[2] = {{mask, ni}, {index, no * 4}};
+    if (!model_outputs_disjoint(out, no, used, width, &in, 1, extra, 2))
+        return "an output array overlaps another array of the call (the selection is not in place)";
+    ByteRange read[GSR_MODEL_NARR + 1];
+    int n_read = model_ranges(in, ni, used, width, read, 0);
+    read[n_read++] = extra[0];
+    if (!outputs_disjoint(&extra[1], 1, read, n_read)) return "index overlaps the mask or an input array";
     return nullptr;
 }
 

@@ -1,8 +1,10 @@
 // gsr_fuse_dev.h -- what the pairwise overlap merge (fuse.hip) and the N-way one (fuse_multi.hip) share: the per-row pre-pass, the robust
-// box and the grid over the valid centres, the cell keys and starts, and the two forms of the symmetrised KL divergence.  The kernels are
-// `static`: each translation unit that includes this gets its own copy.
+// box and the grid over the valid centres, the cell keys and starts with the host code that launches them (FuseCells), and the two
+// forms of the symmetrised KL divergence.  The kernels are `static`: each translation unit that includes this gets its own copy.
 #pragma once
 #include "gsr_common.h"
+#include "gsr_oneshot.h"
+#include "gsr_prims.h"
 
 #include <float.h>
 #include <math.h>
@@ -158,10 +160,41 @@ __device__ __forceinline__ double sym_quad(const double* P, double x, double y, 
     return ((P[0] * x * x + P[3] * y * y) + P[5] * z * z) + 2.0 * ((P[1] * x * y + P[2] * x * z) + P[4] * y * z);
 }
 
-static bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
-    if (!a || !b || !na || !nb) return false;
-    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-    return pa < pb + nb && pb < pa + na;
-}
+// The front both merges share, for the `n` rows the grid is built over (all of A, or the union): k_fuse_prep into w / inv (n_invalid
+// zeroed by the caller), the robust box over the valid centres, the table of at most `cap` = max(n, 1024) cells, the rows in cell order
+// and the cell starts.  reserve() asks for the device memory (added to `workspace`; rocPRIM's stays in tmp_sort) and launch() enqueues
+// the kernels: two steps, so that a caller can make all its requests before it enqueues anything, as hipMalloc beside a busy stream is slow.
+struct FuseCells {
+    int64_t n = 0, cap = 0;
+    unsigned bits = 1;                                          // of a cell key: what a sort by key looks at
+    double *part = nullptr, *box = nullptr;
+    FuseGrid* grid = nullptr;
+    unsigned *keys = nullptr, *idx = nullptr, *skeys = nullptr, *order = nullptr;
+    int* cellStart = nullptr;
+
+    int32_t reserve(OneShot& os, size_t& workspace, int64_t rows) {
+        auto ws = [&](size_t bytes, auto** p) { workspace += bytes; return os.scratch(bytes, p); };
+        n = rows;
+        cap = n > 1024 ? n : 1024;
+        while (bits < 32 && ((int64_t)1 << bits) < cap) ++bits;
+        const size_t un = (size_t)n;
+        GSR_TRY(ws((size_t)stride_grid(n) * FUSE_MOM * 8, &part)); GSR_TRY(ws(6 * 8, &box)); GSR_TRY(ws(sizeof(FuseGrid), &grid));
+        GSR_TRY(ws(un * 4 + 8, &keys)); GSR_TRY(ws(un * 4 + 8, &idx)); GSR_TRY(ws(un * 4 + 8, &skeys)); GSR_TRY(ws(un * 4 + 8, &order));
+        return ws(((size_t)cap + 2) * 4, &cellStart);
+    }
+    int32_t launch(hipStream_t st, DevBuf& tmp_sort, const float* xyz, const float* cov6, const float* opacity, double* w, double* inv,
+                   unsigned long long* n_invalid, double max_distance) {
+        const int nblk = stride_grid(n);
+        hipLaunchKernelGGL(k_fuse_prep, dim3(stride_grid(n)), dim3(256), 0, st, n, xyz, cov6, opacity, w, inv, n_invalid);
+        hipLaunchKernelGGL(k_fuse_moments, dim3(nblk), dim3(256), 0, st, n, xyz, (const double*)w, (const double*)nullptr, part);
+        hipLaunchKernelGGL(k_fuse_box, dim3(1), dim3(64), 0, st, nblk, (const double*)part, 0, max_distance, cap, box, grid);
+        hipLaunchKernelGGL(k_fuse_moments, dim3(nblk), dim3(256), 0, st, n, xyz, (const double*)w, (const double*)box, part);
+        hipLaunchKernelGGL(k_fuse_box, dim3(1), dim3(64), 0, st, nblk, (const double*)part, 1, max_distance, cap, box, grid);
+        hipLaunchKernelGGL(k_fuse_keys, dim3(stride_grid(n)), dim3(256), 0, st, n, xyz, (const FuseGrid*)grid, keys, idx);
+        if (n > 0) GSR_TRY(sort_pairs_by_key<rocprim::default_config>(tmp_sort, st, (const unsigned*)keys, skeys, (const unsigned*)idx, order, (size_t)n, 0u, bits));
+        hipLaunchKernelGGL(k_fuse_cell_starts, dim3(stride_grid(cap + 1)), dim3(256), 0, st, n, (const unsigned*)skeys, cap, cellStart);
+        return GSR_OK;
+    }
+};
 
 }  // namespace gsr

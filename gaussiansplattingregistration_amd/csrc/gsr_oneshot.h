@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "gsr_common.h"
+#include "gsr_model_arrays.h"
 
 namespace gsr {
 
@@ -77,5 +78,32 @@ private:
     std::vector<DevBuf> owned;
     std::vector<Back> backs;
 };
+
+// ---- whole models (gsr_model_view) in a one-shot call; width[] / used[] are model_layout's
+// device views of the used arrays of an input model (NULL for an unused array and for a model without rows)
+inline int32_t model_in(OneShot& os, const gsr_model_view* v, const size_t width[GSR_MODEL_NARR], const bool used[GSR_MODEL_NARR], const float* dev[GSR_MODEL_NARR]) {
+    for (int k = 0; k < GSR_MODEL_NARR; ++k) {
+        dev[k] = nullptr;
+        if (used[k] && v->n > 0) GSR_TRY(os.in((const float*)model_array(v, k), (size_t)v->n * width[k] * 4, &dev[k]));
+    }
+    return GSR_OK;
+}
+// device destinations of the used arrays of an output model of `rows` rows: the caller's on the device, else scratch of that capacity.
+// The row count is known only after the kernels, so a host caller's rows come back through model_copy_back, not through finish().
+inline int32_t model_out(OneShot& os, const gsr_model_view* out, int64_t rows, const size_t width[GSR_MODEL_NARR], const bool used[GSR_MODEL_NARR], float* dev[GSR_MODEL_NARR]) {
+    for (int k = 0; k < GSR_MODEL_NARR; ++k) {
+        dev[k] = nullptr;
+        if (!used[k] || rows == 0) continue;
+        if (os.on_device) dev[k] = model_array(out, k);
+        else GSR_TRY(os.scratch((size_t)rows * width[k] * 4, &dev[k]));
+    }
+    return GSR_OK;
+}
+// the first n_rows rows of every staged array to a host caller: n_rows rows, not the capacity
+inline int32_t model_copy_back(OneShot& os, const gsr_model_view* out, float* const dev[GSR_MODEL_NARR], int64_t n_rows, const size_t width[GSR_MODEL_NARR]) {
+    for (int k = 0; k < GSR_MODEL_NARR && !os.on_device; ++k)
+        if (dev[k] && n_rows > 0) GSR_HIP(hipMemcpyAsync(model_array(out, k), dev[k], (size_t)n_rows * width[k] * 4, hipMemcpyDeviceToHost, os.st));
+    return GSR_OK;
+}
 
 }  // namespace gsr

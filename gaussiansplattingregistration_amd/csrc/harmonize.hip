@@ -127,12 +127,6 @@ __global__ __launch_bounds__(256) void k_color_apply(int64_t n_dc, int64_t n_tot
     }
 }
 
-static bool color_overlap(const void* a, size_t na, const void* b, size_t nb) {
-    if (!a || !b || !na || !nb) return false;
-    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-    return pa < pb + nb && pb < pa + na;
-}
-
 }  // namespace gsr
 
 using namespace gsr;
@@ -223,8 +217,8 @@ extern "C" int32_t gsr_model_color_apply(const double* P12, int64_t n, int32_t K
         if (!(fabs(P12[k]) <= DBL_MAX)) return fail(GSR_E_INVALID, "gsr_model_color_apply: the transform is not finite");
     if (n > 0 && (!dc || !dc_out || (K > 0 && (!sh || !sh_out)))) return fail(GSR_E_INVALID, "gsr_model_color_apply: NULL array");
     const size_t bd = (size_t)n * 12, bs = (size_t)n * (size_t)K * 12;
-    if ((dc_out != dc && color_overlap(dc_out, bd, dc, bd)) || (K > 0 && sh_out != sh && color_overlap(sh_out, bs, sh, bs)) ||
-        (K > 0 && (color_overlap(dc_out, bd, sh, bs) || color_overlap(sh_out, bs, dc, bd) || color_overlap(dc_out, bd, sh_out, bs))))
+    if ((dc_out != dc && ranges_overlap(dc_out, bd, dc, bd)) || (K > 0 && sh_out != sh && ranges_overlap(sh_out, bs, sh, bs)) ||
+        (K > 0 && (ranges_overlap(dc_out, bd, sh, bs) || ranges_overlap(sh_out, bs, dc, bd) || ranges_overlap(dc_out, bd, sh_out, bs))))
         return fail(GSR_E_INVALID, "gsr_model_color_apply: an output partially overlaps another array of the call (exactly in place, or disjoint)");
     ColorXf X;
     for (int c = 0; c < 3; ++c) {

@@ -464,12 +464,6 @@ extern "C" int32_t gsr_sh_rotation(const double* rotation, int32_t degree, doubl
 }
 
 // ---- gsr_model_transform -----------------------------------------------------------------------------------------------------
-static bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
-    if (!a || !b || !na || !nb) return false;
-    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-    return pa < pb + nb && pb < pa + na;
-}
-
 template <int K, bool SIM> static void launch_model_transform(bool vec, int grid, hipStream_t st, int64_t n, const Rigid& G, const ShRot& D, const float* xyz,
                                                               const float* cov6, const float* rot, const float* sh, float* xyz_o, float* cov6_o, float* rot_o, float* sh_o,
                                                               const float* scl, float* scl_o) {
@@ -494,13 +488,12 @@ static int32_t model_move(const char* who, const double* transform, const double
                           const float* cov6, const float* rot, const float* sh, const float* scaling, float* xyz_out, float* cov6_out, float* rot_out,
                           float* sh_out, float* scaling_out, int32_t on_device, int32_t device, void* stream) {
     const size_t un = (size_t)n, F = 3 * (size_t)K;
-    const void* ins[5] = {xyz, cov6, rot, K ? sh : nullptr, scaling};
-    const void* outs[5] = {xyz_out, cov6_out, rot ? rot_out : nullptr, K ? sh_out : nullptr, scaling ? scaling_out : nullptr};
     const size_t bytes[5] = {un * 12, un * 24, un * 16, un * F * 4, un * 12};
-    for (int i = 0; i < 5; ++i)
-        for (int j = 0; j < 5; ++j)
-            if (ranges_overlap(outs[i], bytes[i], ins[j], bytes[j]) || (i < j && ranges_overlap(outs[i], bytes[i], outs[j], bytes[j])))
-                return fail(GSR_E_INVALID, "%s: an output array overlaps another array of the call (the transform is not in place)", who);
+    const ByteRange ins[5] = {{xyz, bytes[0]}, {cov6, bytes[1]}, {rot, bytes[2]}, {K ? sh : nullptr, bytes[3]}, {scaling, bytes[4]}};
+    const ByteRange outs[5] = {{xyz_out, bytes[0]}, {cov6_out, bytes[1]}, {rot ? rot_out : nullptr, bytes[2]}, {K ? sh_out : nullptr, bytes[3]},
+                               {scaling ? scaling_out : nullptr, bytes[4]}};
+    if (!outputs_disjoint(outs, 5, ins, 5))
+        return fail(GSR_E_INVALID, "%s: an output array overlaps another array of the call (the transform is not in place)", who);
     GSR_TRY(open_device(device, who));
     if (n == 0) return GSR_OK;
     // the motion narrowed to float32 once: rotation, translation, the rotation's unit quaternion (Shepperd's branch, w >= 0)

@@ -17,35 +17,10 @@ import numpy as np
 
 from . import _lib
 from . import _marshal as _m
+from . import _model_view as _mv
 
 C0 = 0.28209479177387814
 IDENTITY = np.hstack([np.eye(3), np.zeros((3, 1))])
-
-
-def _sync(device, on):
-    if on:
-        import torch
-        torch.cuda.current_stream(device).synchronize()
-
-
-def _where(model):
-    on = bool(model._xyz.is_cuda)
-    return on, (model._xyz.device.index if on else 0)
-
-
-def _match_view(model, device, on, keep):
-    n = len(model)
-    v = _lib.ModelView()
-    v.n = n
-    if n == 0:
-        return v
-    for field, t, width in (("xyz", model._xyz, 3), ("cov6", model._covariance, 6), ("dc", model._features_dc, 3), ("opacity", model._opacity, 1)):
-        p, k, t_on = _m.prep(t, (n, width), np.float32, device)
-        if t_on != on:
-            raise RuntimeError("the model's tensors must all live on one device")
-        keep.append(k)
-        setattr(v, field, p)
-    return v
 
 
 def match_pairs(model_a, model_b, fuse_params):
@@ -54,18 +29,13 @@ def match_pairs(model_a, model_b, fuse_params):
     ``report``: ``n_pairs``, ``n_out`` (what the fusion would return), ``n_a_only``, ``n_b_only``, ``n_invalid_a``, ``n_invalid_b``,
     ``gated_pairs``, ``workspace_bytes``, ``phase_ms``.  The two models must be in one frame and on one device."""
     L = _lib.load(require_device=True)
-    on, device = _where(model_a)
-    on_b, device_b = _where(model_b)
-    if on != on_b or (on and device != device_b):
-        raise RuntimeError("the two models must live on one device")
+    on, device = _mv.placement([model_a, model_b])
     keep = []
-    va, vb = _match_view(model_a, device, on, keep), _match_view(model_b, device, on, keep)
+    va, vb = (_mv.view_of(g, 0, False, device, on, keep, fields=("xyz", "cov6", "dc", "opacity")) for g in (model_a, model_b))
     pairs, ppairs = _m.out((min(len(model_a), len(model_b)), 2), np.int32, device, on)
     P = _lib.FuseParams(float(fuse_params.max_distance), float(fuse_params.kld_max), float(fuse_params.color_delta))
     R = _lib.FuseReport()
-    _sync(device, on)
-    _lib.check(L.gsr_model_match(C.addressof(va), C.addressof(vb), C.addressof(P), ppairs, C.addressof(R), 1 if on else 0, device,
-                                 C.c_void_p(_m.stream_ptr(device, on))), "gsr_model_match")
+    _lib.check(L.gsr_model_match(C.addressof(va), C.addressof(vb), C.addressof(P), ppairs, C.addressof(R), *_mv.call_tail(device, on)), "gsr_model_match")
     info = {k: int(getattr(R, k)) for k in ("n_out", "n_pairs", "n_a_only", "n_b_only", "n_invalid_a", "n_invalid_b", "gated_pairs", "workspace_bytes")}
     info["phase_ms"] = dict(zip(("prepass_grid", "search", "pair_scan"), (float(x) for x in R.phase_ms)))
     return pairs[:info["n_pairs"]], info
@@ -98,9 +68,8 @@ def color_sums(s_dc, s_opacity, t_dc, t_opacity, pairs, P_s=IDENTITY, P_t=IDENTI
     Ps, Pt = _p12(P_s), _p12(P_t)
     sums = np.zeros(_lib.GSR_COLOR_SUMS_LEN, np.float64)
     skipped, outside = C.c_int64(0), C.c_int64(0)
-    _sync(device, on)
     _lib.check(L.gsr_color_sums(ptr[0], ptr[1], ns, ptr[2], ptr[3], nt, ptr[4], n_pairs, Ps.ctypes.data, Pt.ctypes.data, float(huber), sums.ctypes.data,
-                                C.byref(skipped), C.byref(outside), 1 if on else 0, device, C.c_void_p(_m.stream_ptr(device, on))), "gsr_color_sums")
+                                C.byref(skipped), C.byref(outside), *_mv.call_tail(device, on)), "gsr_color_sums")
     return sums, {"n_skipped": int(skipped.value), "n_out_of_range": int(outside.value)}
 
 
@@ -154,9 +123,7 @@ def apply_color_arrays(P, dc, sh=None, inplace=False, device=0):
         o_dc, po_dc = _m.out(tuple(dc.shape), np.float32, device, on)
         o_sh, po_sh = _m.out((n, K, 3), np.float32, device, on) if K else (sh, None)
     X = _p12(P)
-    _sync(device, on)
-    _lib.check(L.gsr_model_color_apply(X.ctypes.data, n, K, p_dc, p_sh, po_dc, po_sh, 1 if on else 0, device, C.c_void_p(_m.stream_ptr(device, on))),
-               "gsr_model_color_apply")
+    _lib.check(L.gsr_model_color_apply(X.ctypes.data, n, K, p_dc, p_sh, po_dc, po_sh, *_mv.call_tail(device, on)), "gsr_model_color_apply")
     return o_dc, o_sh
 
 
@@ -164,7 +131,7 @@ def apply_colors(model, P, inplace=False):
     """``model`` with the colour transform ``P`` (3, 4) applied to ``_features_dc`` and ``_features_rest`` -> a model (``model``
     itself when ``inplace``).  Everything else is shared with ``model``: geometry and opacity are not touched, colours not clamped."""
     import torch
-    K = int(model._features_rest.shape[1]) if model._features_rest.dim() == 3 else 0
+    K = _mv.sh_count(model)
     m = model
     if not inplace:
         m = type(model)(model.device_name)

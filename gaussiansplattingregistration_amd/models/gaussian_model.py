@@ -21,6 +21,7 @@ import torch
 
 from .. import _lib
 from .. import _marshal as _m
+from .. import _model_view as _mv
 from .gaussian_mixture_level import GaussianMixtureModel
 
 
@@ -182,9 +183,7 @@ class GaussianModel:
         device = cov.device.index if cov.is_cuda else 0
         p, keep, on = _m.prep(cov, (n, 6), np.float32, device)
         (sc, psc), (q, pq), (mat, pmat) = (_m.out(s, np.float32, device, on) for s in ((n, 3), (n, 4), (n, 3, 3)))
-        if on:
-            torch.cuda.current_stream(device).synchronize()
-        _lib.check(L.gsr_decompose_cov(p, n, mode, psc, pq, pmat, 1 if on else 0, device, C.c_void_p(_m.stream_ptr(device, on))), "gsr_decompose_cov")
+        _lib.check(L.gsr_decompose_cov(p, n, mode, psc, pq, pmat, *_mv.call_tail(device, on)), "gsr_decompose_cov")
         return torch.as_tensor(sc), torch.as_tensor(q), torch.as_tensor(mat)
 
     def decompose_covariance_matrix(self):
@@ -219,7 +218,7 @@ class GaussianModel:
         L = _lib.load(require_device=True)
         T = np.ascontiguousarray(np.asarray(transformation_matrix, dtype=np.float64).reshape(4, 4))
         n = len(self)
-        K = int(self._features_rest.shape[1]) if self._features_rest.numel() or self._features_rest.dim() == 3 else 0
+        K = _mv.sh_count(self)
         on = bool(self._xyz.is_cuda)
         device = self._xyz.device.index if on else 0
         have_rot = self._rotation.numel() > 0
@@ -243,15 +242,9 @@ class GaussianModel:
                 outs[name], ptr[name] = o[:n], o.data_ptr()
             else:
                 outs[name], ptr[name] = _m.out(shape, np.float32, device, on)
-        a = lambda name: ins[name][0]
-        if similarity:
-            _lib.check(L.gsr_model_similarity(T.ctypes.data, n, K, 1 if rotate_sh else 0, a("_xyz"), a("_covariance"), a("_rotation"), a("_features_rest"),
-                                              a("_scaling"), ptr["_xyz"], ptr["_covariance"], ptr["_rotation"], ptr["_features_rest"], ptr["_scaling"],
-                                              1 if on else 0, device, C.c_void_p(_m.stream_ptr(device, on))), "gsr_model_similarity")
-            return {name: torch.as_tensor(o) for name, o in outs.items()}
-        _lib.check(L.gsr_model_transform(T.ctypes.data, n, K, 1 if rotate_sh else 0, a("_xyz"), a("_covariance"), a("_rotation"), a("_features_rest"),
-                                         ptr["_xyz"], ptr["_covariance"], ptr["_rotation"], ptr["_features_rest"], 1 if on else 0, device,
-                                         C.c_void_p(_m.stream_ptr(device, on))), "gsr_model_transform")
+        fn, who = (L.gsr_model_similarity, "gsr_model_similarity") if similarity else (L.gsr_model_transform, "gsr_model_transform")
+        _lib.check(fn(T.ctypes.data, n, K, 1 if rotate_sh else 0, *(ins[name][0] for name in src), *(ptr[name] for name in src), 1 if on else 0, device,
+                      C.c_void_p(_m.stream_ptr(device, on))), who)          # (src is in the order of the entry points' arrays, inputs then outputs)
         return {name: torch.as_tensor(o) for name, o in outs.items()}
 
     # -- rigid motion and merge (reference ``gaussian_model.py:198-222,267-290``) ---------------------------------
@@ -294,8 +287,6 @@ class GaussianModel:
             setattr(self, name, t)
         return self
 
-    _FUSE_ARRAYS = (("_xyz", 3), ("_covariance", 6), ("_features_dc", 3), ("_features_rest", None), ("_opacity", 1), ("_scaling", 3), ("_rotation", 4))
-
     @staticmethod
     def fuse_overlap(gaussian1, gaussian2, params):
         """Overlap-aware merge of two models that are ALREADY IN ONE FRAME (``gsr_model_fuse``, ``csrc/fuse.hip``): a splat of
@@ -310,53 +301,17 @@ class GaussianModel:
         assert gaussian1.sh_degree == gaussian2.sh_degree
         L = _lib.load(require_device=True)
         n1, n2 = len(gaussian1), len(gaussian2)
-        K = int(gaussian1._features_rest.shape[1]) if gaussian1._features_rest.dim() == 3 else 0
-        K2 = int(gaussian2._features_rest.shape[1]) if gaussian2._features_rest.dim() == 3 else 0
-        if K != K2:
-            raise RuntimeError("the two models carry different numbers of SH coefficients")
-        on = bool(gaussian1._xyz.is_cuda)
-        if bool(gaussian2._xyz.is_cuda) != on or (on and gaussian1._xyz.device != gaussian2._xyz.device):
-            raise RuntimeError("the two models must live on one device")
-        device = gaussian1._xyz.device.index if on else 0
-        have = [g._scaling.numel() > 0 and g._rotation.numel() > 0 for g in (gaussian1, gaussian2)]
-        if have[0] != have[1] and n1 > 0 and n2 > 0:
-            raise RuntimeError("_scaling / _rotation: one model carries them, the other does not")
-        with_sr = have[0] if n1 > 0 else have[1]
-        views, keep, outs = [_lib.ModelView(), _lib.ModelView(), _lib.ModelView()], [], {}
-        views[0].n, views[1].n, views[2].n = n1, n2, n1 + n2
-        field = {"_xyz": "xyz", "_covariance": "cov6", "_features_dc": "dc", "_features_rest": "sh", "_opacity": "opacity", "_scaling": "scaling",
-                 "_rotation": "rot"}
-        for name, width in GaussianModel._FUSE_ARRAYS:
-            width = 3 * K if width is None else width
-            if width == 0 or (name in ("_scaling", "_rotation") and not with_sr):
-                continue
-            for v, g, n in ((views[0], gaussian1, n1), (views[1], gaussian2, n2)):
-                if n == 0:
-                    continue
-                p, k, t_on = _m.prep(getattr(g, name), (n, width), np.float32, device)
-                if t_on != on:
-                    raise RuntimeError("the model's tensors must all live on one device")
-                keep.append(k)
-                setattr(v, field[name], p)
-            outs[name], p = _m.out((n1 + n2, width), np.float32, device, on)
-            setattr(views[2], field[name], p)
+        K, with_sr = _mv.layout([gaussian1, gaussian2])
+        on, device = _mv.placement([gaussian1, gaussian2])
+        keep = []
+        va, vb = (_mv.view_of(g, K, with_sr, device, on, keep) for g in (gaussian1, gaussian2))
+        vo, outs = _mv.out_view(n1 + n2, K, with_sr, device, on)
         pairs, ppairs = _m.out((min(n1, n2), 2), np.int32, device, on)
         P = _lib.FuseParams(float(params.max_distance), float(params.kld_max), float(params.color_delta))
         R = _lib.FuseReport()
-        if on:
-            torch.cuda.current_stream(device).synchronize()
-        _lib.check(L.gsr_model_fuse(C.addressof(views[0]), C.addressof(views[1]), K, C.addressof(P), C.addressof(views[2]), ppairs, C.addressof(R),
-                                    1 if on else 0, device, C.c_void_p(_m.stream_ptr(device, on))), "gsr_model_fuse")
-        n_out = int(R.n_out)
-        m = GaussianModel(gaussian2.device_name)
-        m.sh_degree = gaussian1.sh_degree
-        shapes = {"_features_dc": (1, 3), "_features_rest": (K, 3)}
-        for name, _ in GaussianModel._FUSE_ARRAYS:
-            if name in outs:
-                t = torch.as_tensor(outs[name])[:n_out]
-                setattr(m, name, t.view((n_out,) + shapes[name]) if name in shapes else t)
-            elif name == "_features_rest":
-                setattr(m, name, torch.empty((n_out, 0, 3), dtype=torch.float32, device=m._xyz.device))
+        _lib.check(L.gsr_model_fuse(C.addressof(va), C.addressof(vb), K, C.addressof(P), C.addressof(vo), ppairs, C.addressof(R),
+                                    *_mv.call_tail(device, on)), "gsr_model_fuse")
+        m = _mv.model_from_arrays(outs, int(R.n_out), K, gaussian1.sh_degree, gaussian2.device_name)
         info = {k: int(getattr(R, k)) for k in ("n_out", "n_pairs", "n_a_only", "n_b_only", "n_invalid_a", "n_invalid_b")}
         info["pairs"] = torch.as_tensor(pairs)[:info["n_pairs"]]
         info["gated_pairs"], info["workspace_bytes"] = int(R.gated_pairs), int(R.workspace_bytes)
@@ -378,60 +333,18 @@ class GaussianModel:
         if not 1 <= len(models) <= _lib.GSR_FUSE_MAX_MODELS:
             raise ValueError(f"{len(models)} models (1 to {_lib.GSR_FUSE_MAX_MODELS})")
         L = _lib.load(require_device=True)
-        first = models[0]
-        N = len(models)
-        sizes = [len(g) for g in models]
-        total = sum(sizes)
-        Ks = [int(g._features_rest.shape[1]) if g._features_rest.dim() == 3 else 0 for g in models]
-        if any(g.sh_degree != first.sh_degree for g in models) or any(k != Ks[0] for k in Ks):
-            raise RuntimeError("the models carry different numbers of SH coefficients")
-        K = Ks[0]
-        on = bool(first._xyz.is_cuda)
-        if any(bool(g._xyz.is_cuda) != on or (on and g._xyz.device != first._xyz.device) for g in models):
-            raise RuntimeError("the models must all live on one device")
-        device = first._xyz.device.index if on else 0
-        have = [g._scaling.numel() > 0 and g._rotation.numel() > 0 for g, n in zip(models, sizes) if n > 0]
-        if have and any(h != have[0] for h in have):
-            raise RuntimeError("_scaling / _rotation: some models carry them, others do not")
-        with_sr = bool(have and have[0])
-        views = (_lib.ModelView * N)()
-        out_view = _lib.ModelView()
-        out_view.n = total
-        keep, outs = [], {}
-        field = {"_xyz": "xyz", "_covariance": "cov6", "_features_dc": "dc", "_features_rest": "sh", "_opacity": "opacity", "_scaling": "scaling",
-                 "_rotation": "rot"}
-        for name, width in GaussianModel._FUSE_ARRAYS:
-            width = 3 * K if width is None else width
-            if width == 0 or (name in ("_scaling", "_rotation") and not with_sr):
-                continue
-            for v, g, n in zip(views, models, sizes):
-                v.n = n
-                if n == 0:
-                    continue
-                p, k, t_on = _m.prep(getattr(g, name), (n, width), np.float32, device)
-                if t_on != on:
-                    raise RuntimeError("the model's tensors must all live on one device")
-                keep.append(k)
-                setattr(v, field[name], p)
-            outs[name], p = _m.out((total, width), np.float32, device, on)
-            setattr(out_view, field[name], p)
+        N, total = len(models), sum(len(g) for g in models)
+        K, with_sr = _mv.layout(models)
+        on, device = _mv.placement(models)
+        keep = []
+        views = (_lib.ModelView * N)(*(_mv.view_of(g, K, with_sr, device, on, keep) for g in models))
+        out_view, outs = _mv.out_view(total, K, with_sr, device, on)
         group_of, pgroup = _m.out((total,), np.int32, device, on)
         P = _lib.FuseParams(float(params.max_distance), float(params.kld_max), float(params.color_delta))
         R = _lib.FuseMultiReport()
-        if on:
-            torch.cuda.current_stream(device).synchronize()
-        _lib.check(L.gsr_fuse_multi(C.addressof(views), N, K, C.addressof(P), C.addressof(out_view), pgroup, C.addressof(R), 1 if on else 0,
-                                          device, C.c_void_p(_m.stream_ptr(device, on))), "gsr_fuse_multi")
-        n_out = int(R.n_out)
-        m = GaussianModel(first.device_name)
-        m.sh_degree = first.sh_degree
-        shapes = {"_features_dc": (1, 3), "_features_rest": (K, 3)}
-        for name, _ in GaussianModel._FUSE_ARRAYS:
-            if name in outs:
-                t = torch.as_tensor(outs[name])[:n_out]
-                setattr(m, name, t.view((n_out,) + shapes[name]) if name in shapes else t)
-            elif name == "_features_rest":
-                setattr(m, name, torch.empty((n_out, 0, 3), dtype=torch.float32, device=m._xyz.device))
+        _lib.check(L.gsr_fuse_multi(C.addressof(views), N, K, C.addressof(P), C.addressof(out_view), pgroup, C.addressof(R),
+                                    *_mv.call_tail(device, on)), "gsr_fuse_multi")
+        m = _mv.model_from_arrays(outs, int(R.n_out), K, models[0].sh_degree, models[0].device_name)
         info = {k: int(getattr(R, k)) for k in ("n_out", "n_groups", "n_grouped_rows", "n_invalid", "gated_pairs", "mutual_edges", "rejected_edges", "rounds",
                                                 "workspace_bytes")}
         info["groups_of_size"] = [int(x) for x in R.groups_of_size]
@@ -465,33 +378,14 @@ class GaussianModel:
         if fuse is not None:
             return GaussianModel.get_fused_gaussian_point_clouds(gaussian1, gaussian2, transformation_matrix, fuse, rotate_sh=rotate_sh,
                                                                  with_scaling=with_scaling)[0]
-        names = ("_xyz", "_rotation", "_scaling", "_features_dc", "_features_rest", "_opacity", "_covariance")
         moves = transformation_matrix is not None and not np.array_equal(np.asarray(transformation_matrix), np.eye(4))
         x1, x2 = gaussian1._xyz, gaussian2._xyz
+        if moves and x1.is_cuda and x2.is_cuda and x1.device == x2.device:
+            m = GaussianModel._merged_on_device([gaussian1, gaussian2], [transformation_matrix, np.eye(4)], rotate_sh, [with_scaling, False])
+            m.device_name = gaussian2.device_name
+            return m
         m = GaussianModel(gaussian2.device_name)
         m.sh_degree = gaussian1.sh_degree
-        if moves and x1.is_cuda and x2.is_cuda and x1.device == x2.device:
-            n1, n2 = len(gaussian1), len(gaussian2)
-            for name in names:
-                a, b = getattr(gaussian1, name), getattr(gaussian2, name)
-                if a.numel() == 0 and b.numel() == 0 and a.dim() < 2:          # an array neither model carries (no decompose)
-                    setattr(m, name, torch.empty(0, device=x2.device))
-                    continue
-                if a.shape[0] != n1 or b.shape[0] != n2:
-                    raise RuntimeError(f"{name}: one model carries it, the other does not")
-                setattr(m, name, torch.empty((n1 + n2,) + tuple(b.shape[1:]), dtype=torch.float32, device=x2.device))
-            moved = ("_xyz", "_covariance", "_rotation", "_features_rest")
-            if with_scaling:
-                moved += ("_scaling",)
-            gaussian1._transform_kernel(transformation_matrix, rotate_sh, into={k: getattr(m, k) for k in moved}, similarity=with_scaling)
-            for name in names:
-                a, b, o = getattr(gaussian1, name), getattr(gaussian2, name), getattr(m, name)
-                if o.shape[0] != n1 + n2 or o.numel() == 0:
-                    continue
-                if name not in moved:
-                    o[:n1].copy_(a)
-                o[n1:].copy_(b)
-            return m
         g1 = gaussian1
         if moves:
             g1 = gaussian1.clone_gaussian()
@@ -501,7 +395,7 @@ class GaussianModel:
                 g1.transform_gaussian_model(np.asarray(transformation_matrix, dtype=np.float64), rotate_sh=True)
             else:
                 g1.transform_gaussian_model(np.asarray(transformation_matrix, dtype=np.float32))
-        for name in names:
+        for name in _mv.ATTRS:
             setattr(m, name, torch.cat((getattr(g1, name).to(gaussian2.device_name), getattr(gaussian2, name))))
         return m
 
@@ -518,11 +412,16 @@ class GaussianModel:
         ``rotate_sh`` is false.  With the colours of the scenes harmonised on the way: ``get_merged_gaussian_point_clouds_multi_colors``."""
         if fuse is not None:
             return GaussianModel.get_merged_gaussian_point_clouds_fused_multi(models, poses, fuse, rotate_sh=rotate_sh)[0]
+        return GaussianModel._merged_on_device(models, poses, rotate_sh, None)
+
+    @staticmethod
+    def _merged_on_device(models, poses, rotate_sh, similarity):
+        """the plain concatenation of ``get_merged_gaussian_point_clouds_multi``; ``similarity``: per model, whether its pose is a
+        similarity ``[c R | t]`` (``gsr_model_similarity``: ``_scaling`` moves too) -- ``None``: all rigid"""
         models, poses = list(models), [np.asarray(p, dtype=np.float64).reshape(4, 4) for p in poses]
         if not models or len(models) != len(poses):
             raise ValueError(f"{len(models)} models and {len(poses)} poses")
-        names = ("_xyz", "_rotation", "_scaling", "_features_dc", "_features_rest", "_opacity", "_covariance")
-        moved = ("_xyz", "_covariance", "_rotation", "_features_rest")
+        names = _mv.ATTRS
         first = models[0]
         dev = first._xyz.device
         for g in models:
@@ -543,10 +442,11 @@ class GaussianModel:
                 raise RuntimeError(f"{name}: the models do not carry it alike")
             setattr(m, name, torch.empty((total,) + tuple(arrays[0].shape[1:]), dtype=torch.float32, device=dev))
         off = 0
-        for g, T, n in zip(models, poses, sizes):
+        for g, T, n, sim in zip(models, poses, sizes, similarity or [False] * len(models)):
             moves = n > 0 and not np.array_equal(T, np.eye(4))
+            moved = ("_xyz", "_covariance", "_rotation", "_features_rest") + (("_scaling",) if sim else ())
             if moves:
-                g._transform_kernel(T, rotate_sh, into={k: getattr(m, k)[off:off + n] for k in moved})
+                g._transform_kernel(T, rotate_sh, into={k: getattr(m, k)[off:off + n] for k in moved}, similarity=sim)
             for name in names:
                 o = getattr(m, name)
                 if o.numel() == 0 or o.shape[0] != total:
@@ -586,6 +486,15 @@ class GaussianModel:
         return GaussianModel.fuse_overlap_multi(GaussianModel._moved_multi(models, poses, rotate_sh, "fuse"), fuse)
 
     @staticmethod
+    def _require_rotate_sh(model, T, rotate_sh, what):
+        """a model with SH coefficients under a matrix that rotates (anything but a positive multiple of the identity) needs rotate_sh"""
+        A = T[:3, :3]
+        rotates = not (np.count_nonzero(A - np.diag(np.diag(A))) == 0 and A[0, 0] == A[1, 1] == A[2, 2] and A[0, 0] > 0)
+        if _mv.sh_count(model) > 0 and rotates and not rotate_sh:
+            raise RuntimeError(what + " needs rotate_sh=True when the matrix rotates a model with SH coefficients: an average of SH rows "
+                               "in two frames means nothing")
+
+    @staticmethod
     def _moved_multi(models, poses, rotate_sh, what):
         """every model in the common frame: a clone moved by its pose, or the model itself where the pose is the identity"""
         models, poses = list(models), [np.asarray(p, dtype=np.float64).reshape(4, 4) for p in poses]
@@ -596,12 +505,7 @@ class GaussianModel:
             if len(g) == 0 or np.array_equal(T, np.eye(4)):
                 moved.append(g)
                 continue
-            A = T[:3, :3]
-            rotates = not (np.count_nonzero(A - np.diag(np.diag(A))) == 0 and A[0, 0] == A[1, 1] == A[2, 2] and A[0, 0] > 0)
-            K = int(g._features_rest.shape[1]) if g._features_rest.dim() == 3 else 0
-            if K > 0 and rotates and not rotate_sh:
-                raise RuntimeError(what + " needs rotate_sh=True when a pose rotates a model with SH coefficients: an average of SH rows "
-                                   "in two frames means nothing")
+            GaussianModel._require_rotate_sh(g, T, rotate_sh, what)
             moved.append(g.clone_gaussian().transform_gaussian_model(T, rotate_sh=rotate_sh))
         return moved
 
@@ -626,12 +530,7 @@ class GaussianModel:
         moves = transformation_matrix is not None and not np.array_equal(np.asarray(transformation_matrix), np.eye(4))
         if moves:
             T = np.asarray(transformation_matrix, dtype=np.float64).reshape(4, 4)
-            A = T[:3, :3]
-            rotates = not (np.count_nonzero(A - np.diag(np.diag(A))) == 0 and A[0, 0] == A[1, 1] == A[2, 2] and A[0, 0] > 0)
-            K = int(gaussian1._features_rest.shape[1]) if gaussian1._features_rest.dim() == 3 else 0
-            if K > 0 and rotates and not rotate_sh:
-                raise RuntimeError(what + " needs rotate_sh=True when the matrix rotates a model with SH coefficients: an average of SH rows "
-                                   "in two frames means nothing")
+            GaussianModel._require_rotate_sh(gaussian1, T, rotate_sh, what)
             g1 = gaussian1.clone_gaussian()
             if with_scaling:
                 g1.similarity_transform_gaussian_model(T, rotate_sh=rotate_sh)
@@ -691,23 +590,13 @@ class GaussianModel:
         ``sh_degree`` is kept.  One ``gsr_model_select``; on the device for CUDA tensors."""
         from .. import clean
         n = len(self)
-        K = int(self._features_rest.shape[1]) if self._features_rest.dim() == 3 else 0
-        with_sr = self._scaling.numel() > 0 and self._rotation.numel() > 0
-        arrays = {"xyz": self._xyz, "cov6": self._covariance, "dc": self._features_dc.reshape(n, 3), "opacity": self._opacity.reshape(n),
-                  "sh": self._features_rest.reshape(n, 3 * K) if K else None,
-                  "scaling": self._scaling if with_sr else None, "rot": self._rotation if with_sr else None}
+        K, with_sr = _mv.sh_count(self), _mv.has_scaling_rot(self)
+        fields = _mv.carried(K, with_sr)
         device = self._xyz.device.index if self._xyz.is_cuda else 0
-        sel, _ = clean.select_rows(arrays, mask, device=device)
-        m = GaussianModel(self.device_name)
-        m.sh_degree = self.sh_degree
-        t = {k: torch.as_tensor(v) for k, v in sel.items()}
-        k = int(t["xyz"].shape[0])
-        m._xyz, m._covariance = t["xyz"], t["cov6"]
-        m._features_dc = t["dc"].view(k, 1, 3)
-        m._opacity = t["opacity"].view((k,) + tuple(self._opacity.shape[1:]))
-        m._features_rest = t["sh"].view(k, K, 3) if K else torch.empty((k, 0, 3), dtype=torch.float32, device=m._xyz.device)
-        if with_sr:
-            m._scaling, m._rotation = t["scaling"], t["rot"]
+        sel, _ = clean.select_rows({f: getattr(self, attr).reshape(n, w) for f, attr, w in fields}, mask, device=device)
+        k = int(sel["xyz"].shape[0])
+        m = _mv.model_from_arrays({attr: sel[f] for f, attr, _ in fields}, k, K, self.sh_degree, self.device_name)
+        m._opacity = m._opacity.view((k,) + tuple(self._opacity.shape[1:]))
         return m
 
     def remove_floaters(self, params):
@@ -725,7 +614,7 @@ class GaussianModel:
     def clone_gaussian(self):
         m = GaussianModel(self.device_name)
         m.sh_degree = self.sh_degree
-        for name in ("_xyz", "_features_dc", "_features_rest", "_scaling", "_rotation", "_opacity", "_covariance"):
+        for name in _mv.ATTRS:
             setattr(m, name, getattr(self, name).clone().detach())
         return m
 
@@ -733,5 +622,5 @@ class GaussianModel:
         if self.device_name == device_name:
             return
         self.device_name = device_name
-        for name in ("_xyz", "_features_dc", "_features_rest", "_scaling", "_rotation", "_opacity", "_covariance"):
+        for name in _mv.ATTRS:
             setattr(self, name, getattr(self, name).to(device_name))

@@ -55,12 +55,12 @@ int main() {
 
     // the views: one slab per array, laid out one after the other
     const int K = 3;
-    const size_t w[GSR_SELECT_NARR] = {3, 6, 3, 3 * K, 1, 3, 4};
+    const size_t w[GSR_MODEL_NARR] = {3, 6, 3, 3 * K, 1, 3, 4};
     std::vector<float> in_buf, out_buf;
-    size_t off[GSR_SELECT_NARR + 1] = {0};
-    for (int k = 0; k < GSR_SELECT_NARR; ++k) off[k + 1] = off[k] + (size_t)n * w[k];
-    in_buf.assign(off[GSR_SELECT_NARR], 1.0f);
-    out_buf.assign(off[GSR_SELECT_NARR], 0.0f);
+    size_t off[GSR_MODEL_NARR + 1] = {0};
+    for (int k = 0; k < GSR_MODEL_NARR; ++k) off[k + 1] = off[k] + (size_t)n * w[k];
+    in_buf.assign(off[GSR_MODEL_NARR], 1.0f);
+    out_buf.assign(off[GSR_MODEL_NARR], 0.0f);
     auto view = [&](std::vector<float>& b) {
         gsr_model_view v;
         v.n = n; v.xyz = b.data() + off[0]; v.cov6 = b.data() + off[1]; v.dc = b.data() + off[2]; v.sh = b.data() + off[3];
@@ -69,11 +69,11 @@ int main() {
     };
     std::vector<int32_t> index(n);
     int64_t n_out = 0;
-    size_t width[GSR_SELECT_NARR];
-    bool used[GSR_SELECT_NARR];
+    size_t width[GSR_MODEL_NARR];
+    bool used[GSR_MODEL_NARR];
     gsr_model_view vi = view(in_buf), vo = view(out_buf);
     EXPECT(select_check_args(&vi, K, mask.data(), &vo, index.data(), &n_out, width, used) == nullptr);
-    for (int k = 0; k < GSR_SELECT_NARR; ++k) EXPECT(used[k] && width[k] == w[k]);
+    for (int k = 0; k < GSR_MODEL_NARR; ++k) EXPECT(used[k] && width[k] == w[k]);
     EXPECT(select_check_args(&vi, 0, mask.data(), &vo, nullptr, &n_out, width, used) == nullptr && !used[3]);
     for (int badK : {1, 2, 4, 16, -3}) EXPECT(select_check_args(&vi, badK, mask.data(), &vo, nullptr, &n_out, width, used) != nullptr);
     EXPECT(select_check_args(&vi, K, mask.data(), &vi, nullptr, &n_out, width, used) != nullptr);            // in place
@@ -92,7 +92,7 @@ int main() {
     EXPECT(select_check_args(&vi, K, nullptr, &vo, nullptr, &n_out, width, used) == nullptr);                // an empty model
     EXPECT(select_check_args(nullptr, K, mask.data(), &vo, nullptr, &n_out, width, used) != nullptr);
     // adjacent buffers do not overlap
-    EXPECT(!clean_ranges_overlap(in_buf.data(), 16, in_buf.data() + 4, 16) && clean_ranges_overlap(in_buf.data(), 17, in_buf.data() + 4, 16));
+    EXPECT(!ranges_overlap(in_buf.data(), 16, in_buf.data() + 4, 16) && ranges_overlap(in_buf.data(), 17, in_buf.data() + 4, 16));
     if (failures) { printf("%d failures\n", failures); return 1; }
     printf("ok\n");
     return 0;

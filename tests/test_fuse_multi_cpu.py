@@ -233,7 +233,7 @@ def test_register_many_shows_the_flags():
 
 
 def test_args_selftest_is_clean_under_the_host_sanitizers(tmp_path):
-    """scripts/fuse_multi_args_selftest.cpp: the argument checks of csrc/gsr_fuse_multi_args.h as a stand-alone program, built with
+    """scripts/fuse_multi_args_selftest.cpp: the argument checks of csrc/gsr_fuse_args.h as a stand-alone program, built with
     AddressSanitizer and UBSan"""
     import os
     import shutil

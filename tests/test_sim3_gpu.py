@@ -322,6 +322,36 @@ def test_gaussian_model_similarity_and_merge():
     assert np.array_equal(MT.host(host._xyz), MT.host(moved._xyz)) and np.array_equal(MT.host(host._scaling), MT.host(moved._scaling))
 
 
+@pytest.mark.parametrize("with_scaling_array", [True, False])
+def test_pairwise_merge_is_the_multi_merge(with_scaling_array):
+    """Two models on one device, 257 and 130 rows (more than one 256-thread block, an odd tail), K = 3, with and without _scaling:
+    the rigid pairwise merge is bit for bit get_merged_gaussian_point_clouds_multi([g1, g2], [T, I]), and with with_scaling=True
+    it is similarity_transform_gaussian_model followed by concatenation."""
+    from gaussiansplattingregistration_amd.models.gaussian_model import GaussianModel
+    names = ("_xyz", "_covariance", "_rotation", "_scaling", "_features_rest", "_opacity", "_features_dc")
+    g1, _, _ = MT.make_model(257, 1, seed=7)
+    g2, _, _ = MT.make_model(130, 1, seed=8)
+    if not with_scaling_array:
+        g1._scaling, g2._scaling = torch.empty(0), torch.empty(0)
+    before = {k: getattr(g1, k).clone() for k in names}
+    R = M.similarity(1.0, 33.0, (0.3, 1.0, -0.2), (0.2, -0.4, 0.1))
+    pair = GaussianModel.get_merged_gaussian_point_clouds(g1, g2, R, rotate_sh=True)
+    multi = GaussianModel.get_merged_gaussian_point_clouds_multi([g1, g2], [R, np.eye(4)], rotate_sh=True)
+    S = M.similarity(1.7, 33.0, (0.3, 1.0, -0.2), (0.2, -0.4, 0.1))
+    scaled = GaussianModel.get_merged_gaussian_point_clouds(g1, g2, S, rotate_sh=True, with_scaling=True)
+    moved = g1.clone_gaussian().similarity_transform_gaussian_model(S, rotate_sh=True)
+    assert len(pair) == len(multi) == len(scaled) == 387 and pair.sh_degree == scaled.sh_degree == 1
+    for k in names:
+        a, b, c = getattr(pair, k), getattr(multi, k), getattr(scaled, k)
+        assert a.shape == b.shape and torch.equal(a, b), k
+        want = torch.cat((getattr(moved, k).to(c.device), getattr(g2, k).to(c.device)))
+        assert c.shape == want.shape and torch.equal(c, want), k
+        assert torch.equal(getattr(g1, k), before[k]), k                                              # the input is left as it was
+    assert (pair._scaling.numel() > 0) == with_scaling_array and not torch.equal(scaled._xyz[:257], pair._xyz[:257])
+    if with_scaling_array:
+        assert torch.equal(pair._scaling[:257], g1._scaling) and not torch.equal(scaled._scaling[:257], g1._scaling)
+
+
 # --------------------------------------------------------------------------------------------------------------- pipeline
 def test_register_ply_with_scaling(tmp_path):
     """scripts/register_ply.py --with-scaling as a child process on two 20 000-splat models, the second the first scaled by 1.2 and
