@@ -113,6 +113,25 @@ def add_clean_arguments(ap):
     ap.add_argument("--clean-max-extent", type=float, metavar="S", help="floater removal: drop splats whose largest scale exceeds S")
 
 
+def add_prune_arguments(ap):
+    """the visibility-pruning flags the command-line tools share (``GaussianModel.prune_unseen``)"""
+    ap.add_argument("--prune-unseen", action="append", metavar="CAMERAS.json", help="drop the splats no camera of these files shows with a blending "
+                    "weight of --min-contribution (may be given several times: pass the cameras of ALL merged scenes, a splat outside every "
+                    "frustum is dropped like an occluded one)")
+    ap.add_argument("--min-contribution", type=float, default=0.01, help="smallest largest blending weight alpha T of a kept splat (RadSplat: 0.01)")
+
+
+def prune_unseen_from_args(model, a, report=print):
+    """``model`` without the splats the cameras of ``--prune-unseen`` never show (the model itself when the flag is absent)"""
+    if not a.prune_unseen:
+        return model
+    from .models.camera import load_cameras
+    cameras = [c for path in a.prune_unseen for c in load_cameras(path)]
+    pruned, info = model.prune_unseen(cameras, min_contribution=a.min_contribution)
+    report(f"prune unseen: {len(cameras)} cameras, {info['n']} -> {info['n_kept']} splats (largest blending weight below {a.min_contribution:g} dropped)")
+    return pruned
+
+
 def clean_params_from_args(a):
     """-> ``CleanParams`` or ``None`` when no cleaning flag was given"""
     from .params.clean_parameters import CleanParams

@@ -101,6 +101,18 @@ class RegistrationController:
                                        match_colors_gate=match_colors_gate)
         return worker.run()
 
+    def evaluate_geometry(self, cameras_list, log_path, coverage=0.5, registration_result=None, rotate_sh=False, with_scaling=False):
+        """Geometric evaluation of the current transform on the repository's original clouds, without photographs: the depth maps of
+        the first cloud moved by it and of the second, from the same cameras (``GeometryEvaluator``); the JSON log at ``log_path``.
+        Returns the evaluator's ``GeometryEvaluationObject``."""
+        from ..workers.evaluator import GeometryEvaluator
+        repo = self.data_repository
+        pc1 = repo.pc_gaussian_list_first[repo.current_index]
+        pc2 = repo.pc_gaussian_list_second[repo.current_index]
+        worker = GeometryEvaluator(pc1, pc2, self.ui_repository.transformation_matrix, cameras_list, log_path, with_scaling=with_scaling,
+                                   rotate_sh=rotate_sh, coverage=coverage, registration_result=registration_result)
+        return worker.run()
+
     def handle_registration_result_local(self, result_data):       # :145-163
         self.ui_repository.transformation_matrix = result_data.result.transformation
 

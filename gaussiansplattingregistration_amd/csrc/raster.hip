@@ -10,6 +10,10 @@
 // The semantics restate the published 3DGS / gsplat forward pass (EWA projection with the clamped perspective Jacobian, 0.3 px
 // dilation, 3-sigma integer radius, alpha clamp 0.999, 1/255 skip, transmittance stop at 1e-4); gsplat itself is not available on
 // ROCm, so parity with it is unpinned.  tests/raster_model.py is the executable restatement the kernels are held to.
+//
+// gsr_raster_render_aux is the same pipeline with another blend, k_raster_blend_aux: coverage 1 - T, expected
+// depth sum(z w) / alpha and, per splat, the largest blending weight w = alpha T it reaches on any pixel (an integer atomicMax on
+// the float's bits: still no float atomics).  tests/raster_aux_model.py restates it.
 #include <math.h>
 #include <string.h>
 
@@ -229,6 +233,129 @@ __global__ __launch_bounds__(BLEND_THREADS) void k_raster_blend(int32_t W, int32
     }
 }
 
+// The largest value of a wave, in every lane's view of lane 63: four row_shr steps leave each row of 16 lanes its inclusive maxima,
+// row_bcast15 and row_bcast31 carry the row ends across.  A lane without a source keeps `old` = 0, the identity of a maximum of
+// unsigned values.  All 64 lanes must be active.
+__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
+    uint32_t o;
+    o = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false); v = v > o ? v : o;      // row_shr:1
+    o = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false); v = v > o ? v : o;      // row_shr:2
+    o = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, false); v = v > o ? v : o;      // row_shr:4
+    o = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, false); v = v > o ? v : o;      // row_shr:8
+    o = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false); v = v > o ? v : o;      // row_bcast15 into rows 1, 3
+    o = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false); v = v > o ? v : o;      // row_bcast31 into rows 2, 3
+    return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
+}
+
+// The blend with the auxiliary outputs of DESIGN.md 22: the same pixel loop in the same float32 order (a requested image is the bits
+// k_raster_blend writes), plus D = sum z w per pixel (s_z: the tenth staged word, kept out of the stride-9 record) and, with CONTRIB,
+// the largest w = alpha T of every staged splat: s_contrib[j] belongs to the thread that staged splat j, which zeroes it, lets the
+// waves raise it between the barriers and sends it to contribution[id] with one integer atomicMax after the closing barrier
+// (non-negative floats order as their bit patterns: no float atomics, no dependence on the order).  With CONTRIB the j loop is
+// wave-uniform -- it runs while any lane is live, finished lanes offer 0 -- so that the wave's maximum is taken by DPP steps and one
+// lane raises the slot.  image, depth, alpha: each NULL or written (wave-uniform tests).
+template <bool CONTRIB>
+__global__ __launch_bounds__(BLEND_THREADS) void k_raster_blend_aux(int32_t W, int32_t H, int32_t tiles_x, float bg0, float bg1, float bg2, int64_t n,
+                                                                    const int64_t* __restrict__ ranges, const uint32_t* __restrict__ vals,
+                                                                    const float* __restrict__ splat, const float* __restrict__ zs, float* __restrict__ image,
+                                                                    float* __restrict__ depth, float* __restrict__ alpha_out, uint32_t* __restrict__ contribution) {
+    __shared__ float s_splat[BLEND_THREADS * SPLAT_WORDS];
+    __shared__ float s_z[BLEND_THREADS];
+    __shared__ uint32_t s_contrib[CONTRIB ? BLEND_THREADS : 1];
+    __shared__ int s_alive[BLEND_THREADS / 64];
+    const int t = threadIdx.x, wave = t >> 6;
+    const int tile = blockIdx.y * tiles_x + blockIdx.x;
+    const int ix = blockIdx.x * TILE + (t & (TILE - 1)), iy = blockIdx.y * TILE + (t >> 4);
+    const bool inside = ix < W && iy < H;
+    const float px = (float)ix + 0.5f, py = (float)iy + 0.5f;
+    const int64_t first = ranges[2 * (int64_t)tile], last = ranges[2 * (int64_t)tile + 1];
+    float T = 1.0f, r = 0.0f, g = 0.0f, b = 0.0f, D = 0.0f;
+    bool done = !inside;
+    for (int64_t base = first; base < last; base += BLEND_THREADS) {
+        const bool wave_alive = __ballot(!done) != 0ull;
+        if ((t & 63) == 0) s_alive[wave] = wave_alive ? 1 : 0;
+        const int64_t pos = base + t;
+        int64_t my_id = -1;                                        // the splat this thread staged, if it may be reported
+        if (pos < last) {
+            const uint32_t id = vals[pos];
+            if ((int64_t)id < n) {
+                const float* src = splat + (int64_t)SPLAT_WORDS * id;
+#pragma unroll
+                for (int k = 0; k < SPLAT_WORDS; ++k) s_splat[SPLAT_WORDS * t + k] = src[k];
+                s_z[t] = zs[id];
+                my_id = (int64_t)id;
+            } else {                                               // never: an index the emit kernel did not write
+#pragma unroll
+                for (int k = 0; k < SPLAT_WORDS; ++k) s_splat[SPLAT_WORDS * t + k] = 0.0f;
+                s_z[t] = 0.0f;
+            }
+        }
+        if (CONTRIB) s_contrib[t] = 0u;
+        __syncthreads();
+        if (!(s_alive[0] | s_alive[1] | s_alive[2] | s_alive[3])) break;       // (every slot is still zero: nothing to send)
+        if (wave_alive) {
+            const int m = (int)((last - base) < (int64_t)BLEND_THREADS ? (last - base) : (int64_t)BLEND_THREADS);
+            if (CONTRIB) {
+                for (int j = 0; j < m; ++j) {
+                    if (__ballot(!done) == 0ull) break;
+                    float w = 0.0f;
+                    if (!done) {
+                        const float* s = s_splat + SPLAT_WORDS * j;
+                        const float dx = s[0] - px, dy = s[1] - py;
+                        const float sigma = 0.5f * (s[2] * dx * dx + s[4] * dy * dy) + s[3] * dx * dy;
+                        if (!(sigma < 0.0f)) {
+                            const float alpha = fminf(0.999f, s[5] * expf(-sigma));
+                            if (!(alpha < 1.0f / 255.0f)) {
+                                const float Tn = T * (1.0f - alpha);
+                                if (Tn <= 1e-4f) done = true;
+                                else {
+                                    const float vis = alpha * T;
+                                    r = r + s[6] * vis; g = g + s[7] * vis; b = b + s[8] * vis;
+                                    D = D + s_z[j] * vis;
+                                    T = Tn;
+                                    w = vis;
+                                }
+                            }
+                        }
+                    }
+                    const uint32_t top = wave_max_u32(__float_as_uint(w));       // w >= 0: its bits order as it does
+                    if (top != 0u && (t & 63) == 0) atomicMax(&s_contrib[j], top);
+                }
+            } else {
+                for (int j = 0; j < m && !done; ++j) {
+                    const float* s = s_splat + SPLAT_WORDS * j;
+                    const float dx = s[0] - px, dy = s[1] - py;
+                    const float sigma = 0.5f * (s[2] * dx * dx + s[4] * dy * dy) + s[3] * dx * dy;
+                    if (sigma < 0.0f) continue;
+                    const float alpha = fminf(0.999f, s[5] * expf(-sigma));
+                    if (alpha < 1.0f / 255.0f) continue;
+                    const float Tn = T * (1.0f - alpha);
+                    if (Tn <= 1e-4f) { done = true; break; }
+                    const float vis = alpha * T;
+                    r = r + s[6] * vis; g = g + s[7] * vis; b = b + s[8] * vis;
+                    D = D + s_z[j] * vis;
+                    T = Tn;
+                }
+            }
+        }
+        __syncthreads();
+        if (CONTRIB && my_id >= 0) {
+            const uint32_t top = s_contrib[t];
+            if (top != 0u) atomicMax(contribution + my_id, top);
+        }
+    }
+    if (inside) {
+        const int64_t p = (int64_t)iy * W + ix;
+        if (image) {
+            float* o = image + 3 * p;
+            o[0] = r + T * bg0; o[1] = g + T * bg1; o[2] = b + T * bg2;
+        }
+        const float a = 1.0f - T;
+        if (alpha_out) alpha_out[p] = a;
+        if (depth) depth[p] = D / fmaxf(a, 1e-10f);
+    }
+}
+
 }  // namespace
 
 struct gsr_raster_ctx {
@@ -261,16 +388,21 @@ extern "C" int32_t gsr_raster_destroy(gsr_raster_ctx* c) {
     return GSR_OK;
 }
 
-extern "C" int32_t gsr_raster_render(gsr_raster_ctx* c, int64_t n, int32_t K, int32_t sh_degree, const float* xyz, const float* cov6, const float* raw_opacity,
-                                     const float* dc, const float* sh_rest, const float* viewmat, float fx, float fy, float cx, float cy, int32_t width,
-                                     int32_t height, const float* background, float radius_clip, float* image_out, int64_t* stats_out, void* stream) {
-    if (!c) return fail(GSR_E_INVALID, "gsr_raster_render: NULL context");
-    if (n < 0 || n >= ((int64_t)1 << 31) - 1) return fail(GSR_E_INVALID, "gsr_raster_render: n = %lld out of range", (long long)n);
+// Both render entries: validation (messages under the caller's name `who`), camera set-up, preprocess, sort, tile ranges, then the
+// blend the outputs ask for -- k_raster_blend when `rgb_only` (gsr_raster_render), k_raster_blend_aux otherwise.
+static int32_t raster_run(const char* who, bool rgb_only, gsr_raster_ctx* c, int64_t n, int32_t K, int32_t sh_degree, const float* xyz, const float* cov6,
+                          const float* raw_opacity, const float* dc, const float* sh_rest, const float* viewmat, float fx, float fy, float cx, float cy,
+                          int32_t width, int32_t height, const float* background, float radius_clip, float* image_out, float* depth_out, float* alpha_out,
+                          uint32_t* contribution, int64_t* stats_out, void* stream) {
+    if (!c) return fail(GSR_E_INVALID, "%s: NULL context", who);
+    if (n < 0 || n >= ((int64_t)1 << 31) - 1) return fail(GSR_E_INVALID, "%s: n = %lld out of range", who, (long long)n);
     if (sh_degree < 0 || sh_degree > 3 || K < (sh_degree + 1) * (sh_degree + 1) - 1)
-        return fail(GSR_E_INVALID, "gsr_raster_render: sh_degree %d needs %d rest coefficients, K = %d", sh_degree, (sh_degree + 1) * (sh_degree + 1) - 1, K);
-    if (width <= 0 || height <= 0 || width > 16 * 65535 || height > 16 * 65535) return fail(GSR_E_INVALID, "gsr_raster_render: bad image size %d x %d", width, height);
-    if (!viewmat || !background || !image_out || !(fx > 0.0f) || !(fy > 0.0f)) return fail(GSR_E_INVALID, "gsr_raster_render: NULL argument or focal length <= 0");
-    if (n > 0 && (!xyz || !cov6 || !raw_opacity || !dc || (sh_degree > 0 && !sh_rest))) return fail(GSR_E_INVALID, "gsr_raster_render: NULL array");
+        return fail(GSR_E_INVALID, "%s: sh_degree %d needs %d rest coefficients, K = %d", who, sh_degree, (sh_degree + 1) * (sh_degree + 1) - 1, K);
+    if (width <= 0 || height <= 0 || width > 16 * 65535 || height > 16 * 65535) return fail(GSR_E_INVALID, "%s: bad image size %d x %d", who, width, height);
+    if (!rgb_only && !image_out && !depth_out && !alpha_out && !contribution) return fail(GSR_E_INVALID, "%s: no output requested", who);
+    if (!viewmat || ((rgb_only || image_out) && !background) || (rgb_only && !image_out) || !(fx > 0.0f) || !(fy > 0.0f))
+        return fail(GSR_E_INVALID, "%s: NULL argument or focal length <= 0", who);
+    if (n > 0 && (!xyz || !cov6 || !raw_opacity || !dc || (sh_degree > 0 && !sh_rest))) return fail(GSR_E_INVALID, "%s: NULL array", who);
     GSR_HIP(hipSetDevice(c->device));
     hipStream_t st = stream ? (hipStream_t)stream : c->stream;
     c->timed = false;
@@ -294,7 +426,7 @@ extern "C" int32_t gsr_raster_render(gsr_raster_ctx* c, int64_t n, int32_t K, in
     cam.tiles_x = (width + TILE - 1) / TILE; cam.tiles_y = (height + TILE - 1) / TILE;
     cam.degree = sh_degree; cam.K = K;
     const int64_t n_tiles = (int64_t)cam.tiles_x * cam.tiles_y;
-    if (n_tiles >= ((int64_t)1 << 31)) return fail(GSR_E_INVALID, "gsr_raster_render: %d x %d has %lld tiles, the tile index is 31 bits", width, height, (long long)n_tiles);
+    if (n_tiles >= ((int64_t)1 << 31)) return fail(GSR_E_INVALID, "%s: %d x %d has %lld tiles, the tile index is 31 bits", who, width, height, (long long)n_tiles);
     const size_t un = (size_t)n;
 
     GSR_TRY(c->counters.reserve(4 * sizeof(unsigned long long)));
@@ -322,7 +454,7 @@ extern "C" int32_t gsr_raster_render(gsr_raster_ctx* c, int64_t n, int32_t K, in
     int64_t total = 0;
     GSR_HIP(hipMemcpyAsync(&total, c->offsets.as<int64_t>() + n, sizeof(int64_t), hipMemcpyDeviceToHost, st));
     GSR_HIP(hipStreamSynchronize(st));
-    if (total < 0) return fail(GSR_E_HIP, "gsr_raster_render: negative intersection count");
+    if (total < 0) return fail(GSR_E_HIP, "%s: negative intersection count", who);
     GSR_HIP(hipMemcpyAsync(counters + 1, &c->offsets.as<int64_t>()[n], sizeof(int64_t), hipMemcpyDeviceToDevice, st));
 
     if (total > 0) {
@@ -341,7 +473,7 @@ extern "C" int32_t gsr_raster_render(gsr_raster_ctx* c, int64_t n, int32_t K, in
         size_t free_b = 0, total_b = 0;
         GSR_HIP(hipMemGetInfo(&free_b, &total_b));
         if (need > free_b + given_back)
-            return fail(GSR_E_HIP, "gsr_raster_render: %lld splat-tile intersections need %zu more bytes of sort buffers, the device has %zu free",
+            return fail(GSR_E_HIP, "%s: %lld splat-tile intersections need %zu more bytes of sort buffers, the device has %zu free", who,
                         (long long)total, need, free_b + given_back);
         GSR_TRY(c->keys.reserve(ut * 8));
         GSR_TRY(c->keys2.reserve(ut * 8));
@@ -355,8 +487,19 @@ extern "C" int32_t gsr_raster_render(gsr_raster_ctx* c, int64_t n, int32_t K, in
         hipLaunchKernelGGL(k_raster_ranges, dim3(stride_grid(total)), dim3(256), 0, st, total, (int32_t)n_tiles, c->keys2.as<uint64_t>(), c->ranges.as<int64_t>(), counters);
     }
     GSR_HIP(hipEventRecord(c->ev[2], st));
-    hipLaunchKernelGGL(k_raster_blend, dim3(cam.tiles_x, cam.tiles_y), dim3(BLEND_THREADS), 0, st, width, height, cam.tiles_x, background[0], background[1],
-                       background[2], n, c->ranges.as<int64_t>(), c->vals2.as<uint32_t>(), c->splat.as<float>(), image_out);
+    const dim3 tiles(cam.tiles_x, cam.tiles_y);
+    const float bg[3] = {background ? background[0] : 0.0f, background ? background[1] : 0.0f, background ? background[2] : 0.0f};
+    if (rgb_only)
+        hipLaunchKernelGGL(k_raster_blend, tiles, dim3(BLEND_THREADS), 0, st, width, height, cam.tiles_x, bg[0], bg[1], bg[2], n, c->ranges.as<int64_t>(),
+                           c->vals2.as<uint32_t>(), c->splat.as<float>(), image_out);
+    else if (contribution)
+        hipLaunchKernelGGL(k_raster_blend_aux<true>, tiles, dim3(BLEND_THREADS), 0, st, width, height, cam.tiles_x, bg[0], bg[1], bg[2], n,
+                           c->ranges.as<int64_t>(), c->vals2.as<uint32_t>(), c->splat.as<float>(), c->depth.as<float>(), image_out, depth_out, alpha_out,
+                           contribution);
+    else
+        hipLaunchKernelGGL(k_raster_blend_aux<false>, tiles, dim3(BLEND_THREADS), 0, st, width, height, cam.tiles_x, bg[0], bg[1], bg[2], n,
+                           c->ranges.as<int64_t>(), c->vals2.as<uint32_t>(), c->splat.as<float>(), c->depth.as<float>(), image_out, depth_out, alpha_out,
+                           (uint32_t*)nullptr);
     GSR_HIP(hipEventRecord(c->ev[3], st));
     if (stats_out) GSR_HIP(hipMemcpyAsync(stats_out, counters, 3 * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
     GSR_HIP(hipGetLastError());
@@ -364,9 +507,24 @@ extern "C" int32_t gsr_raster_render(gsr_raster_ctx* c, int64_t n, int32_t K, in
     return GSR_OK;
 }
 
+extern "C" int32_t gsr_raster_render(gsr_raster_ctx* c, int64_t n, int32_t K, int32_t sh_degree, const float* xyz, const float* cov6, const float* raw_opacity,
+                                     const float* dc, const float* sh_rest, const float* viewmat, float fx, float fy, float cx, float cy, int32_t width,
+                                     int32_t height, const float* background, float radius_clip, float* image_out, int64_t* stats_out, void* stream) {
+    return raster_run("gsr_raster_render", true, c, n, K, sh_degree, xyz, cov6, raw_opacity, dc, sh_rest, viewmat, fx, fy, cx, cy, width, height, background,
+                      radius_clip, image_out, nullptr, nullptr, nullptr, stats_out, stream);
+}
+
+extern "C" int32_t gsr_raster_render_aux(gsr_raster_ctx* c, int64_t n, int32_t K, int32_t sh_degree, const float* xyz, const float* cov6, const float* raw_opacity,
+                                         const float* dc, const float* sh_rest, const float* viewmat, float fx, float fy, float cx, float cy, int32_t width,
+                                         int32_t height, const float* background, float radius_clip, float* image_out, float* depth_out, float* alpha_out,
+                                         uint32_t* contribution_inout, int64_t* stats_out, void* stream) {
+    return raster_run("gsr_raster_render_aux", false, c, n, K, sh_degree, xyz, cov6, raw_opacity, dc, sh_rest, viewmat, fx, fy, cx, cy, width, height, background,
+                      radius_clip, image_out, depth_out, alpha_out, contribution_inout, stats_out, stream);
+}
+
 extern "C" int32_t gsr_raster_get_timing(gsr_raster_ctx* c, float* ms) {
     if (!c || !ms) return fail(GSR_E_INVALID, "gsr_raster_get_timing: NULL argument");
-    if (!c->timed) return fail(GSR_E_INVALID, "gsr_raster_get_timing: no completed gsr_raster_render on this context");
+    if (!c->timed) return fail(GSR_E_INVALID, "gsr_raster_get_timing: no completed render on this context");
     GSR_HIP(hipSetDevice(c->device));
     GSR_HIP(hipEventSynchronize(c->ev[3]));
     for (int i = 0; i < 3; ++i) GSR_HIP(hipEventElapsedTime(&ms[i], c->ev[i], c->ev[i + 1]));

@@ -611,6 +611,42 @@ class GaussianModel:
         mask, info = clean.outlier_mask(self._xyz, params, raw_opacity=self._opacity.reshape(n), scaling=scaling, device=device)
         return self.select_by_mask(mask), info
 
+    # -- visibility (csrc/raster.hip; the reference has no such step) --------------------------------------------
+    def max_contribution(self, cameras, scale=1.0, radius_clip=0.0):
+        """-> ``(n,)`` float32 tensor on the model's device: for every splat the largest blending weight ``alpha T`` it attains on any
+        pixel of any of ``cameras`` (``models.camera.Camera``), RadSplat's importance score; 0 for a splat no camera shows.  One
+        ``gsr_raster_render_aux`` per camera into one buffer (an integer maximum on the float bits: deterministic).  ``radius_clip`` is
+        0 by default, NOT the evaluation's 3 px: with the clip small distant splats would score 0.  Needs a GPU (host tensors are
+        uploaded); no GPU: ``RuntimeError``."""
+        from .. import raster
+        from ..utils.rasterization_util import _camera_args
+        _lib.load(require_device=True)
+        device = self._xyz.device.index if self._xyz.is_cuda else 0
+        score = torch.zeros(len(self), dtype=torch.float32, device=torch.device("cuda", device))
+        if len(self) == 0:
+            return score.to(self._xyz.device)
+        # every array goes to the device once, not once per camera (a model on the device is used where it lies)
+        on = lambda t: t.detach().to(device=score.device, dtype=torch.float32).contiguous()
+        arrays = (on(self.get_xyz), on(raster.model_cov6(self, scale)), on(self.get_raw_opacity), on(self.get_colors),
+                  on(self._features_rest) if self._features_rest.numel() else None)
+        ctx = raster.context(device)
+        for camera in cameras:
+            ctx.render_aux(*arrays, self.sh_degree, *_camera_args(camera), radius_clip=radius_clip, outputs=(), contribution=score)
+        return score.to(self._xyz.device)
+
+    def prune_unseen(self, cameras, min_contribution=0.01, scale=1.0, radius_clip=0.0):
+        """-> ``(model, info)``: the splats whose ``max_contribution`` over ``cameras`` reaches ``min_contribution`` (RadSplat's
+        threshold 0.01), through ``select_by_mask``: rows kept bit for bit, in order.  ``info``: ``n``, ``n_kept``, ``score`` (the
+        ``(n,)`` tensor) and ``kept`` (the kept row indices, int64).  This model is left as it was.
+
+        A splat OUTSIDE EVERY FRUSTUM scores 0 and is dropped exactly like one buried behind opaque surfaces: pass the cameras of
+        ALL the scenes that were merged into this model, not those of one of them."""
+        score = self.max_contribution(cameras, scale=scale, radius_clip=radius_clip)
+        mask = score >= float(min_contribution)
+        kept = torch.nonzero(mask).reshape(-1)
+        model = self.select_by_mask(mask.to(torch.uint8))
+        return model, {"n": len(self), "n_kept": int(kept.numel()), "score": score, "kept": kept}
+
     def clone_gaussian(self):
         m = GaussianModel(self.device_name)
         m.sh_degree = self.sh_degree

@@ -1,6 +1,7 @@
 """ctypes front of the splat rasteriser and the image metrics (``csrc/raster.hip``; ``gsr_raster_*``, ``gsr_image_metrics``).
 
-``RasterContext`` owns the library's grow-only workspaces; ``render`` takes the SoA arrays ``GaussianModel`` holds, as CUDA tensors
+``RasterContext`` owns the library's grow-only workspaces; ``render`` (RGB) and ``render_aux`` (RGB, expected depth, coverage and the
+per-splat largest blending weight) take the SoA arrays ``GaussianModel`` holds, as CUDA tensors
 (zero-copy) or as host arrays (uploaded through torch first: the library's render entry takes device pointers only).  No GPU:
 ``RuntimeError`` -- there is no CPU fallback.
 """
@@ -35,22 +36,26 @@ class RasterContext:
     def __exit__(self, *exc):
         self.close()
 
-    def render(self, xyz, cov6, raw_opacity, dc, sh_rest, sh_degree, viewmat, fx, fy, cx, cy, width, height, background=(0.0, 0.0, 0.0),
-               radius_clip=3.0, with_stats=False):
-        """-> image ``(H, W, 3)`` float32 CUDA tensor [, stats int64 CUDA tensor (visible splats, intersections, non-empty tiles)].
-        ``sh_rest`` is ``(n, K, 3)`` (or ``(n, 3K)`` coefficient-major); ``viewmat`` the 4x4 world -> camera matrix."""
+    def _inputs(self, xyz, cov6, raw_opacity, dc, sh_rest, viewmat, background):
+        """what both render entries take: the device, n, K, the five arrays as contiguous float32 CUDA tensors, viewmat and background as C arrays"""
         dev = torch.device("cuda", self.device)
 
         def up(a, shape):
             t = a if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a, dtype=np.float32))
             return t.detach().to(device=dev, dtype=torch.float32).reshape(shape).contiguous()
         n = int(xyz.shape[0])
-        sh_degree = int(sh_degree)
         K = 0 if sh_rest is None else int(np.prod(tuple(sh_rest.shape)[1:])) // 3
-        t_xyz, t_cov, t_op, t_dc = up(xyz, (n, 3)), up(cov6, (n, 6)), up(raw_opacity, (n,)), up(dc, (n, 3))
-        t_sh = up(sh_rest, (n, 3 * K)) if K else None
+        arrays = (up(xyz, (n, 3)), up(cov6, (n, 6)), up(raw_opacity, (n,)), up(dc, (n, 3)), up(sh_rest, (n, 3 * K)) if K else None)
         V = (C.c_float * 16)(*np.asarray(viewmat.detach().cpu() if isinstance(viewmat, torch.Tensor) else viewmat, dtype=np.float32).reshape(16))
         bg = (C.c_float * 3)(*np.asarray(background, dtype=np.float32).reshape(3))
+        return dev, n, K, arrays, V, bg
+
+    def render(self, xyz, cov6, raw_opacity, dc, sh_rest, sh_degree, viewmat, fx, fy, cx, cy, width, height, background=(0.0, 0.0, 0.0),
+               radius_clip=3.0, with_stats=False):
+        """-> image ``(H, W, 3)`` float32 CUDA tensor [, stats int64 CUDA tensor (visible splats, intersections, non-empty tiles)].
+        ``sh_rest`` is ``(n, K, 3)`` (or ``(n, 3K)`` coefficient-major); ``viewmat`` the 4x4 world -> camera matrix."""
+        dev, n, K, (t_xyz, t_cov, t_op, t_dc, t_sh), V, bg = self._inputs(xyz, cov6, raw_opacity, dc, sh_rest, viewmat, background)
+        sh_degree = int(sh_degree)
         image = torch.empty((int(height), int(width), 3), dtype=torch.float32, device=dev)
         stats = torch.zeros(3, dtype=torch.int64, device=dev)
         stream = torch.cuda.current_stream(dev).cuda_stream
@@ -59,6 +64,47 @@ class RasterContext:
                                              float(radius_clip), image.data_ptr(), stats.data_ptr(), C.c_void_p(stream)), "gsr_raster_render")
         self._keep = (t_xyz, t_cov, t_op, t_dc, t_sh)         # alive until the next render: the blend is still enqueued
         return (image, stats) if with_stats else image
+
+    def render_aux(self, xyz, cov6, raw_opacity, dc, sh_rest, sh_degree, viewmat, fx, fy, cx, cy, width, height, background=(0.0, 0.0, 0.0),
+                   radius_clip=3.0, outputs=("image", "depth", "alpha"), contribution=None, with_stats=False):
+        """-> dict of float32 CUDA tensors, one per name in ``outputs``: ``image`` ``(H, W, 3)`` (the bits ``render`` gives), ``depth``
+        ``(H, W)`` (expected depth ``sum z w / max(alpha, 1e-10)``, 0 where nothing counted), ``alpha`` ``(H, W)`` (``1 - T``); with
+        ``with_stats`` also ``stats``.  ``contribution``: a contiguous float32 CUDA tensor of ``n``, raised IN PLACE to
+        ``max(its value, the largest blending weight alpha T of each splat on this image)`` and returned under ``contribution`` -- it
+        is not cleared, so one buffer collects the maximum over several cameras.  ``outputs`` may be empty when it is given."""
+        outputs = tuple(outputs)
+        unknown = [o for o in outputs if o not in ("image", "depth", "alpha")]
+        if unknown:
+            raise ValueError(f"render_aux: unknown output {unknown[0]!r} (image, depth, alpha)")
+        dev, n, K, (t_xyz, t_cov, t_op, t_dc, t_sh), V, bg = self._inputs(xyz, cov6, raw_opacity, dc, sh_rest, viewmat, background)
+        if contribution is not None:
+            if not (isinstance(contribution, torch.Tensor) and contribution.is_cuda and contribution.device == dev and contribution.dtype == torch.float32
+                    and contribution.is_contiguous() and contribution.numel() == n):
+                raise ValueError(f"render_aux: contribution must be a contiguous float32 tensor of {n} elements on {dev}")
+        if n == 0 and not outputs and contribution is not None:          # nothing to raise (an empty tensor's pointer is NULL: the library would see no output)
+            return {"contribution": contribution, **({"stats": torch.zeros(3, dtype=torch.int64, device=dev)} if with_stats else {})}
+        sh_degree = int(sh_degree)
+        H, W = int(height), int(width)
+        out = {}
+        if "image" in outputs:
+            out["image"] = torch.empty((H, W, 3), dtype=torch.float32, device=dev)
+        for name in ("depth", "alpha"):
+            if name in outputs:
+                out[name] = torch.empty((H, W), dtype=torch.float32, device=dev)
+        ptr = lambda name: out[name].data_ptr() if name in out else None
+        stats = torch.zeros(3, dtype=torch.int64, device=dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(self._L.gsr_raster_render_aux(self._h, n, K, sh_degree, t_xyz.data_ptr(), t_cov.data_ptr(), t_op.data_ptr(), t_dc.data_ptr(),
+                                                 t_sh.data_ptr() if K else None, V, float(fx), float(fy), float(cx), float(cy), W, H, bg, float(radius_clip),
+                                                 ptr("image"), ptr("depth"), ptr("alpha"), contribution.data_ptr() if contribution is not None else None, stats.data_ptr(),
+                                                 C.c_void_p(stream)),
+                   "gsr_raster_render_aux")
+        self._keep = (t_xyz, t_cov, t_op, t_dc, t_sh)         # alive until the next render: the blend is still enqueued
+        if contribution is not None:
+            out["contribution"] = contribution
+        if with_stats:
+            out["stats"] = stats
+        return out
 
     def timing(self):
         """-> {"preprocess", "sort", "blend"} milliseconds of the last render (device events; waits for it)."""
@@ -83,6 +129,19 @@ def render_model(model, viewmat, fx, fy, cx, cy, width, height, background=(0.0,
     cov6 = torch.stack([full[:, 0, 0], full[:, 0, 1], full[:, 0, 2], full[:, 1, 1], full[:, 1, 2], full[:, 2, 2]], dim=1)
     return context(device).render(model.get_xyz, cov6, model.get_raw_opacity, model.get_colors, model._features_rest, model.sh_degree, viewmat, fx, fy,
                                   cx, cy, width, height, background, radius_clip, with_stats)
+
+
+def model_cov6(model, scale=1.0):
+    """the six covariance terms the render entries take, of ``model.get_full_covariance(scale)``"""
+    full = model.get_full_covariance(scale)
+    return torch.stack([full[:, 0, 0], full[:, 0, 1], full[:, 0, 2], full[:, 1, 1], full[:, 1, 2], full[:, 2, 2]], dim=1)
+
+
+def render_model_aux(model, viewmat, fx, fy, cx, cy, width, height, background=(0.0, 0.0, 0.0), scale=1.0, radius_clip=3.0, device=0,
+                     outputs=("image", "depth", "alpha"), contribution=None, with_stats=False):
+    """``RasterContext.render_aux`` of a ``GaussianModel`` (its covariances times ``scale``^2)."""
+    return context(device).render_aux(model.get_xyz, model_cov6(model, scale), model.get_raw_opacity, model.get_colors, model._features_rest, model.sh_degree, viewmat, fx, fy,
+                                      cx, cy, width, height, background, radius_clip, outputs, contribution, with_stats)
 
 
 def image_metrics(a, b, device=None):

@@ -17,3 +17,19 @@ def rasterize_image(point_cloud, camera, scale, color, device, leave_on_gpu=True
     image = raster.render_model(point_cloud, camera.viewmat[0], float(K[0, 0]), float(K[1, 1]), float(K[0, 2]), float(K[1, 2]), int(camera.width),
                                 int(camera.height), background=color, scale=scale, radius_clip=3.0, device=index)[None]
     return image if leave_on_gpu else image.cpu()
+
+
+def _camera_args(camera):
+    K = camera.intrinsics[0]
+    return camera.viewmat[0], float(K[0, 0]), float(K[1, 1]), float(K[0, 2]), float(K[1, 2]), int(camera.width), int(camera.height)
+
+
+def rasterize_depth(point_cloud, camera, scale, device, leave_on_gpu=True, radius_clip=3.0):
+    """-> ``(depth, alpha)``, two ``(H, W)`` float32 maps of the model seen from ``camera``: the expected depth
+    ``sum z_i w_i / max(alpha, 1e-10)`` (camera-space z, blending weights of the RGB render; 0 where no splat counts) and the
+    coverage ``alpha = 1 - T``.  The same culling as ``rasterize_image``; the reference has no such output."""
+    dev = torch.device(device)
+    index = dev.index if dev.index is not None else 0
+    out = raster.render_model_aux(point_cloud, *_camera_args(camera), scale=scale, radius_clip=radius_clip, device=index, outputs=("depth", "alpha"))
+    depth, alpha = out["depth"], out["alpha"]
+    return (depth, alpha) if leave_on_gpu else (depth.cpu(), alpha.cpu())

@@ -17,7 +17,7 @@ import torch
 
 from ..models.gaussian_model import GaussianModel
 from ..utils.evaluation_utils import metrics
-from ..utils.rasterization_util import rasterize_image
+from ..utils.rasterization_util import rasterize_depth, rasterize_image
 
 LPIPS_NOTE = "lpips: not computed (the pretrained LPIPS network weights are not available to this backend)"
 
@@ -132,6 +132,108 @@ class RegistrationEvaluator:
     def create_and_save_log_file(self, error_list):
         record = vars(self.registration_result) if self.registration_result is not None else {}
         evaluation = EvaluationObject(dict(record), self.mean_mses, self.mean_rmses, self.mean_ssims, self.mean_psnrs, self.mean_lpipss, list(error_list))
+        with open(self.log_path, "w") as out:
+            json.dump(evaluation.to_json(), out, indent=2, allow_nan=False)
+        return evaluation
+
+
+# ---- geometric evaluation: depth maps of the two scenes from the same cameras, no photographs ---------------------
+GEOMETRY_LOG_FIELDS = ("registration_data", "coverage", "depth_mae", "depth_rmse", "depth_rel", "depth_overlap", "per_camera", "error_list")
+DEPTH_KEYS = ("depth_mae", "depth_rmse", "depth_rel", "depth_overlap")
+
+
+def depth_agreement(d1, a1, d2, a2, coverage=0.5):
+    """The depth agreement of two renders from one camera -> dict(depth_mae, depth_rmse, depth_rel, depth_overlap, n_mask, n_union), or
+    ``None`` for the first three when the mask is empty.  ``mask = (a1 >= coverage) & (a2 >= coverage)``; over it the mean of
+    ``|d1 - d2|``, the root mean square of ``d1 - d2`` and the mean of ``|d1 - d2| / ((d1 + d2) / 2)``; ``depth_overlap`` is the mask's
+    size over that of ``(a1 >= coverage) | (a2 >= coverage)`` (``None`` when neither render covers a pixel).  Masked reductions in
+    float64 with torch, wherever the maps live."""
+    d1, a1, d2, a2 = (torch.as_tensor(x) for x in (d1, a1, d2, a2))
+    c1, c2 = a1 >= coverage, a2 >= coverage
+    mask, union = c1 & c2, c1 | c2
+    n_mask, n_union = int(mask.sum()), int(union.sum())
+    out = {"depth_mae": None, "depth_rmse": None, "depth_rel": None, "depth_overlap": n_mask / n_union if n_union else None, "n_mask": n_mask,
+           "n_union": n_union}
+    if n_mask:
+        x, y = d1[mask].to(torch.float64), d2[mask].to(torch.float64)
+        diff = x - y
+        out["depth_mae"] = float(diff.abs().mean())
+        out["depth_rmse"] = float(torch.sqrt((diff * diff).mean()))
+        out["depth_rel"] = float((diff.abs() / (0.5 * (x + y))).mean())
+    return out
+
+
+@dataclass
+class GeometryEvaluationObject:
+    """One geometric evaluation: the means over the cameras with a non-empty mask, and every camera's own figures."""
+    registration_data: dict = field(default_factory=dict)
+    coverage: float = 0.5
+    depth_mae: float = None
+    depth_rmse: float = None
+    depth_rel: float = None
+    depth_overlap: float = None
+    per_camera: list = field(default_factory=list)
+    error_list: list = field(default_factory=list)
+
+    def to_json(self):
+        return {k: _json_value(getattr(self, k)) for k in GEOMETRY_LOG_FIELDS}
+
+
+class GeometryEvaluator:
+    """Does the surface of ``pc1`` moved by ``transformation`` coincide with that of ``pc2``?  Both are rendered SEPARATELY from every
+    camera of ``cameras_list`` (``rasterize_depth``: expected depth and coverage) and compared where both cover the pixel
+    (``depth_agreement``).  Needs no photographs; ``run()`` writes the JSON log ``GEOMETRY_LOG_FIELDS`` and polls ``cancel_evaluation``
+    between cameras like ``RegistrationEvaluator``.  The two models are left as they were."""
+    EvaluationObject = GeometryEvaluationObject
+
+    def __init__(self, pc1, pc2, transformation, cameras_list, log_path, with_scaling=False, rotate_sh=False, coverage=0.5, registration_result=None):
+        self.signal_cancel = False
+        self.pc1, self.pc2 = pc1, pc2
+        self.transformation = transformation
+        self.cameras_list = cameras_list
+        self.log_path = log_path
+        self.with_scaling = bool(with_scaling)
+        self.rotate_sh = rotate_sh
+        self.coverage = float(coverage)
+        self.registration_result = registration_result
+        self.device = "cuda:0"
+        self.per_camera = []
+        self.current_progress = 0
+        self.max_progress = len(cameras_list)
+
+    def cancel_evaluation(self):
+        self.signal_cancel = True
+
+    def run(self):
+        """-> the ``GeometryEvaluationObject`` written to ``log_path``, or ``None`` when cancelled (polled between cameras)."""
+        moved = second = None               # moved and brought to the device at the first camera
+        error_list, rows = [], []
+        for camera in self.cameras_list:
+            if self.signal_cancel:
+                return None
+            self.current_progress += 1
+            if moved is None:
+                moved = self.pc1.clone_gaussian()
+                moved.move_to_device(self.device)
+                if self.with_scaling:
+                    moved.similarity_transform_gaussian_model(self.transformation, rotate_sh=self.rotate_sh)
+                else:
+                    moved.transform_gaussian_model(self.transformation, rotate_sh=self.rotate_sh)
+                second = self.pc2
+                if second.device_name != self.device:
+                    second = second.clone_gaussian()
+                    second.move_to_device(self.device)
+            d1, a1 = rasterize_depth(moved, camera, 1, self.device)
+            d2, a2 = rasterize_depth(second, camera, 1, self.device)
+            row = dict(depth_agreement(d1, a1, d2, a2, self.coverage), image_name=camera.image_name)
+            if row["n_mask"] == 0:
+                error_list.append(f"{camera.image_name}: no pixel is covered (alpha >= {self.coverage:g}) by both scenes")
+            rows.append(row)
+        self.per_camera = rows
+        used = [r for r in rows if r["n_mask"] > 0]
+        mean = lambda k: float(np.mean([r[k] for r in used])) if used else None          # no camera compared: null in the log
+        record = vars(self.registration_result) if self.registration_result is not None else {}
+        evaluation = GeometryEvaluationObject(dict(record), self.coverage, *(mean(k) for k in DEPTH_KEYS), rows, error_list)
         with open(self.log_path, "w") as out:
             json.dump(evaluation.to_json(), out, indent=2, allow_nan=False)
         return evaluation

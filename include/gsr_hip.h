@@ -871,7 +871,21 @@ int32_t gsr_raster_render(gsr_raster_ctx* ctx, int64_t n, int32_t K, int32_t sh_
                           const float* raw_opacity, const float* dc, const float* sh_rest, const float* viewmat, float fx, float fy,
                           float cx, float cy, int32_t width, int32_t height, const float* background, float radius_clip,
                           float* image_out, int64_t* stats_out, void* stream);
-/* ms[3]: preprocess + scan, key emission + sort + tile ranges (the host wait included), blend, of the last render; waits for it. */
+/* The same render with the auxiliary outputs of DESIGN.md section 22, each a DEVICE pointer or NULL (all four NULL: GSR_E_INVALID):
+ * image_out[height*width*3] -- bit for bit what gsr_raster_render writes (background is required only with it); alpha_out[height*width]
+ * = 1 - T with the final transmittance (exactly 0 where no splat counted, otherwise >= 1/255 less the rounding of T, 2^-25); depth_out[height*width] = the expected
+ * depth sum(z_i w_i) / max(alpha, 1e-10), z_i the camera-space z, w_i = alpha_i T_i the blending weight (0 where alpha is 0, no
+ * background term); contribution_inout[n]: float32 bit patterns, contribution[i] = max(its value before the call, the largest w_i of
+ * splat i over the pixels of this image) -- NOT cleared by the call, so several cameras rendered into one buffer leave the maximum
+ * over all of them; rows of splats that were culled or never counted are not written.  An integer maximum on the bits of non-negative
+ * floats: deterministic.  Validation, messages (under this entry's name), stats_out, stream and timing as for gsr_raster_render. */
+int32_t gsr_raster_render_aux(gsr_raster_ctx* ctx, int64_t n, int32_t K, int32_t sh_degree, const float* xyz, const float* cov6,
+                              const float* raw_opacity, const float* dc, const float* sh_rest, const float* viewmat, float fx, float fy,
+                              float cx, float cy, int32_t width, int32_t height, const float* background, float radius_clip,
+                              float* image_out, float* depth_out, float* alpha_out, uint32_t* contribution_inout, int64_t* stats_out,
+                              void* stream);
+/* ms[3]: preprocess + scan, key emission + sort + tile ranges (the host wait included), blend, of the last render (either entry);
+ * waits for it. */
 int32_t gsr_raster_get_timing(gsr_raster_ctx* ctx, float* ms);
 
 /* MSE and SSIM of two (3, height, width) float32 images as the reference's src/utils/evaluation_utils.py defines them: SSIM with the

@@ -3,10 +3,16 @@
     python scripts/evaluate_registration.py a.ply b.ply --transform T.txt --cameras cameras.json --images DIR --log out.json
                                             [--rotate-sh] [--with-scaling] [--fuse-overlap MAX_DIST [--fuse-kld X] [--fuse-color X]]
                                             [--save-renders DIR] [--background R G B] [--cpu-metrics]
+    python scripts/evaluate_registration.py a.ply b.ply --transform T.txt --cameras cameras.json --geometry [--coverage 0.5] --log out.json
 
 ``a.ply`` is moved by the 4x4 in ``T.txt`` (whitespace-separated, row-major) and merged with ``b.ply``; the merged model is rendered
 from every camera of ``cameras.json`` (the file a 3DGS training run writes) and compared with ``DIR/<img_name>.png``.  The log has the
 reference's fields: registration_data, mse, rmse, ssim, psnr, lpips (null: no LPIPS weights here), error_list.
+
+``--geometry`` needs no photographs: ``a.ply`` moved by the transform and ``b.ply`` are rendered separately to depth and coverage maps
+from every camera, and compared where both cover a pixel (coverage >= ``--coverage``): depth_mae, depth_rmse, depth_rel, depth_overlap,
+per camera and as means (``GeometryEvaluator``).  With ``--images`` as well, both evaluations run; the geometric log then goes to
+``<log>.geometry``.
 """
 from __future__ import annotations
 
@@ -27,7 +33,9 @@ def main():
     ap.add_argument("second")
     ap.add_argument("--transform", required=True)
     ap.add_argument("--cameras", required=True)
-    ap.add_argument("--images", required=True)
+    ap.add_argument("--images", help="the photographs DIR/<img_name>.png (required unless only --geometry is asked)")
+    ap.add_argument("--geometry", action="store_true", help="geometric evaluation: depth maps of the two scenes from the same cameras")
+    ap.add_argument("--coverage", type=float, default=0.5, help="--geometry: a pixel is compared when both renders have at least this alpha")
     ap.add_argument("--log", required=True)
     ap.add_argument("--rotate-sh", action="store_true", help="turn the SH coefficients of the first cloud with it")
     ap.add_argument("--with-scaling", action="store_true", help="the transform is a similarity [c R | t] (register_ply.py --with-scaling): the first "
@@ -42,6 +50,8 @@ def main():
     ap.add_argument("--background", type=float, nargs=3, default=(0.0, 0.0, 0.0))
     ap.add_argument("--cpu-metrics", action="store_true", help="use_gpu=False: the metrics in host torch arithmetic")
     a = ap.parse_args()
+    if a.images is None and not a.geometry:
+        ap.error("the following arguments are required: --images")
     import __graft_entry__ as g
     g.build_hip()
     from gaussiansplattingregistration_amd.controllers.registration_controller import RegistrationController
@@ -58,6 +68,13 @@ def main():
     repo.pc_gaussian_list_second.append(GaussianModel("cuda:0").from_ply(a.second))
     ui.transformation_matrix = np.loadtxt(a.transform, dtype=np.float64).reshape(4, 4)
     cameras = load_cameras(a.cameras)
+    if a.geometry:
+        geo_log = a.log if a.images is None else a.log + ".geometry"
+        geo = RegistrationController(repo, ui).evaluate_geometry(cameras, geo_log, coverage=a.coverage, rotate_sh=a.rotate_sh, with_scaling=a.with_scaling)
+        print(json.dumps({"geometry": True, "cameras": len(cameras), "coverage": a.coverage, "depth_mae": geo.depth_mae, "depth_rmse": geo.depth_rmse,
+                          "depth_rel": geo.depth_rel, "depth_overlap": geo.depth_overlap, "errors": len(geo.error_list), "log": geo_log}))
+        if a.images is None:
+            return
     if cm is not None:
         # the effect against the photographs: the same evaluation without the harmonisation first (its log beside the other), then with it
         base = RegistrationController(repo, ui).evaluate_registration(cameras, a.images, a.log + ".no_match_colors", tuple(a.background), not a.cpu_metrics,

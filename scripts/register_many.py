@@ -7,6 +7,7 @@ registered pair, a pose graph with a line process that prunes wrongly registered
            [--type point|plane|color|general] [--loss none|tukey|cauchy|gm|huber --k 0.1] [--max-corr 0.05] [--iters 30]
            [--prune 0.25] [--preference 1.0] [--reference 0] [--rotate-sh]
            [--clean-knn K --clean-std R [--clean-radius R --clean-nb N] [--clean-min-opacity A] [--clean-max-extent S]]
+           [--prune-unseen CAMERAS.json ... [--min-contribution 0.01]]
            [--fuse-overlap MAX_DIST [--fuse-kld 0.5] [--fuse-color X]]
            [--match-colors [gain|channel_gain|affine] [--match-colors-huber K] [--match-colors-dist D] [--colors-out colors.json]]
 
@@ -21,7 +22,9 @@ histogram of the group sizes and n_out.  `--match-colors [MODE]`: the scenes dif
 scene's colour transform (a gain, a gain per channel or an affine 3 x 4) is fitted jointly against scene `--reference` over the splats
 each pair of scenes shares (GaussianModel.match_colors; matches within `--match-colors-dist`, default the fuse distance, else --max-corr)
 and applied before the merge.  Prints the transform per scene and the colour residual per pair before and after; `--colors-out` writes
-them as JSON.  Implies --rotate-sh.
+them as JSON.  Implies --rotate-sh.  `--prune-unseen CAMERAS.json` (repeatable): the merged cloud loses the splats no camera shows with a
+blending weight of `--min-contribution` (GaussianModel.prune_unseen); the cameras must be in the frame of scene `--reference` and cover ALL
+the scenes, since a splat outside every frustum is dropped like an occluded one.
 """
 import argparse
 import json
@@ -57,8 +60,9 @@ def main():
     ap.add_argument("--fuse-overlap", type=float, metavar="MAX_DIST", help="fuse the splats the scenes share (within this distance) in the merged output; implies --rotate-sh")
     ap.add_argument("--fuse-kld", type=float, default=0.5, help="symmetrised KL gate of --fuse-overlap")
     ap.add_argument("--fuse-color", type=float, default=float("inf"), help="DC colour gate of --fuse-overlap (default: none)")
-    from gaussiansplattingregistration_amd.clean import add_clean_arguments, clean_params_from_args
+    from gaussiansplattingregistration_amd.clean import add_clean_arguments, add_prune_arguments, clean_params_from_args, prune_unseen_from_args
     add_clean_arguments(ap)
+    add_prune_arguments(ap)
     from gaussiansplattingregistration_amd.harmonize import add_match_colors_arguments, match_colors_from_args
     add_match_colors_arguments(ap)
     a = ap.parse_args()
@@ -151,6 +155,7 @@ def main():
             sizes = "  ".join(f"{k}: {c}" for k, c in enumerate(info["groups_of_size"]) if c)
             print(f"fuse: n_groups {info['n_groups']}  sizes {{{sizes}}}  n_grouped_rows {info['n_grouped_rows']}  rejected_edges {info['rejected_edges']}  "
                   f"rounds {info['rounds']}  n_out {info['n_out']}")
+        merged = prune_unseen_from_args(merged, a)          # (cameras in the frame of the merged cloud: the second / reference scene's)
         merged.save_ply(a.out)
         print(f"merged cloud ({len(merged)} splats) -> {a.out}")
 

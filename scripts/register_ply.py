@@ -6,6 +6,7 @@
            [--type plane|point|color|general] [--loss none|tukey|cauchy|gm|huber --k 0.1] [--voxel] [--out merged.ply [--rotate-sh]]
            [--with-scaling] [--fuse-overlap MAX_DIST [--fuse-kld X] [--fuse-color X]]
            [--clean-knn K --clean-std R [--clean-radius R --clean-nb N] [--clean-min-opacity A] [--clean-max-extent S]]
+           [--prune-unseen CAMERAS.json ... [--min-contribution 0.01]]
            [--match-colors [gain|channel_gain|affine] [--match-colors-huber K] [--match-colors-dist D] [--colors-out colors.json]]
 
 `--with-scaling`: the two scenes do not share a unit of length (separate structure-from-motion runs).  Point-to-point ICP with scaling
@@ -24,6 +25,10 @@ scene's colour transform is fitted against the second's over the splats they sha
 within `--match-colors-dist`, default the fuse distance; a Huber-weighted fit of a gain, a gain per channel or an affine 3 x 4) and
 applied to its DC and SH coefficients before the clouds are concatenated or fused.  Prints the transform and the colour residual
 before and after; `--colors-out` writes them as JSON.  Implies `--rotate-sh`.
+
+`--prune-unseen CAMERAS.json` (with `--out`, may be repeated): the merged cloud loses the splats no camera shows with a blending weight
+of `--min-contribution` (`GaussianModel.prune_unseen`).  The cameras must be in the merged cloud's frame (the second scene's) and cover
+BOTH scenes: a splat outside every frustum is dropped like an occluded one.
 
 Prints the 4x4 transformation (first -> second), fitness and inlier RMSE; `--out` saves the merged cloud.
 """
@@ -66,8 +71,9 @@ def main():
                     "matches within this distance); implies --rotate-sh")
     ap.add_argument("--fuse-kld", type=float, default=0.5, help="largest symmetrised KL divergence of a fused pair")
     ap.add_argument("--fuse-color", type=float, default=float("inf"), help="largest L2 distance of the DC colours of a fused pair")
-    from gaussiansplattingregistration_amd.clean import add_clean_arguments, clean_params_from_args
+    from gaussiansplattingregistration_amd.clean import add_clean_arguments, add_prune_arguments, clean_params_from_args, prune_unseen_from_args
     add_clean_arguments(ap)
+    add_prune_arguments(ap)
     from gaussiansplattingregistration_amd.harmonize import add_match_colors_arguments, match_colors_from_args
     add_match_colors_arguments(ap)
     a = ap.parse_args()
@@ -168,6 +174,7 @@ def main():
             print(f"fuse overlap: n_pairs {info['n_pairs']}  n_out {info['n_out']}  (invalid rows: {info['n_invalid_a']} / {info['n_invalid_b']})")
         else:
             merged = GaussianModel.get_merged_gaussian_point_clouds(first, second, T, rotate_sh=a.rotate_sh, with_scaling=a.with_scaling)
+        merged = prune_unseen_from_args(merged, a)          # (cameras in the frame of the merged cloud: the second / reference scene's)
         merged.save_ply(a.out)
         print(f"merged cloud ({len(merged)} splats) -> {a.out}")
 
