@@ -1,15 +1,15 @@
 // clean.hip -- floater removal (gsr_outlier_mask) and row selection (gsr_model_select), include/gsr_hip.h; DESIGN.md section 18.
 //
 //   k_clean_prep                 finite test and the two splat gates; the search copy of xyz with every dropped row NaNed out
-//   grid_borrow                  the ICP target index over that copy (csrc/icp.hip: robust box, cell-sorted float4 with the input index)
+//   GridIndex::build             the point grid over that copy (csrc/grid.hip: robust box, cell-sorted float4 with the input index)
 //   k_knn_mean<KMAX>             a lane per cell-sorted query: the KMAX smallest d^2 in registers (compile-time indices only), the
-//                                expanding-ring walk of k_knn_normals capped at CLEAN_RING_CAP rings; what has not met its stop rule
-//                                by then goes to a list (ballot compaction, one integer atomic per wave)
+//                                expanding-ring walk (its own copy of grid_ring_walk) capped at CLEAN_RING_CAP rings; what has not met
+//                                its stop rule by then goes to a list (ballot compaction, one integer atomic per wave)
 //   k_knn_mean_deferred          a wave per listed query: (y, z) rows outward until k' candidates are known, then ONE pass over the
-//                                bounds of all other rows against the k'-th best, rows scanned 64 points at a time
+//                                bounds of all other rows against the k'-th best, rows scanned 64 points at a time (wave_scan_take)
 //   k_clean_moment / _final x2   cloud_mean, then the squared deviations: per-block partials, combined in block order
 //   k_clean_stat                 the statistical verdict; a dropped row is NaNed out of the sorted points
-//   k_radius_count               strict count within radius^2 over ceil(radius / cell) + 1 rings of the same grid
+//   k_radius_count               strict count within radius^2 over grid_box_walk's ceil(radius / cell) + 1 rings of the same grid
 //   k_clean_mask                 mask and the per-stage counts
 //   k_select_flags / scan / k_select_index / k_model_select      kept-index list, then a lane per output float, one launch per array
 //
@@ -39,12 +39,6 @@ namespace gsr {
 #define CLEAN_CTR_DEFERRED 7
 #define CLEAN_NCTR 8
 
-// one integer atomic per wave that has any lane with `flag`
-__device__ __forceinline__ void clean_wave_count(bool flag, unsigned long long* ctr) {
-    const unsigned long long m = __ballot(flag);
-    if (m && (int)(threadIdx.x & 63) == __ffsll((long long)m) - 1) atomicAdd(ctr, (unsigned long long)__popcll(m));
-}
-
 __global__ __launch_bounds__(256) void k_clean_prep(int64_t n, const float* __restrict__ xyz, const float* __restrict__ op, const float* __restrict__ sc,
                                                     double min_op, double max_ls, float* __restrict__ sxyz, uint8_t* __restrict__ stage,
                                                     double* __restrict__ mean_out, int* __restrict__ count_out, unsigned long long* __restrict__ ctr) {
@@ -59,17 +53,19 @@ __global__ __launch_bounds__(256) void k_clean_prep(int64_t n, const float* __re
         sxyz[3 * i] = s ? nanv : x; sxyz[3 * i + 1] = s ? nanv : y; sxyz[3 * i + 2] = s ? nanv : z;
         if (mean_out) mean_out[i] = -1.0;
         if (count_out) count_out[i] = -1;
-        clean_wave_count(s == CLEAN_NONFINITE, ctr + CLEAN_NONFINITE - 1);
-        clean_wave_count(s == CLEAN_GATE_OPACITY, ctr + CLEAN_GATE_OPACITY - 1);
-        clean_wave_count(s == CLEAN_GATE_SCALE, ctr + CLEAN_GATE_SCALE - 1);
-        clean_wave_count(s == 0, ctr + CLEAN_CTR_ALIVE);
+        wave_count(s == CLEAN_NONFINITE, ctr + CLEAN_NONFINITE - 1);
+        wave_count(s == CLEAN_GATE_OPACITY, ctr + CLEAN_GATE_OPACITY - 1);
+        wave_count(s == CLEAN_GATE_SCALE, ctr + CLEAN_GATE_SCALE - 1);
+        wave_count(s == 0, ctr + CLEAN_CTR_ALIVE);
     }
 }
 
 // mean_s[j] for the cell-sorted point j: the mean of the k' smallest distances (self included), -1 for a row that is out of the
 // search.  The list is KMAX float64 in registers, kept ascending by an unrolled compare-exchange chain -- no index into it is a
 // runtime value (an indexed array of this size lives in scratch: k_knn_normals).  `worst` is its k'-th entry: a candidate enters
-// only below it.  Ties among equal distances cannot change the sum, so no index is kept.
+// only below it.  Ties among equal distances cannot change the sum, so no index is kept.  The ring walk is grid_ring_walk's (gsr_grid.h),
+// spelled out here: through the shared template the point loop measured 1.2 % slower where a lane scans a crowded boundary cell
+// (DESIGN.md 6a), and this is the loop a cloud with many floaters spends its time in.
 template <int KMAX>
 __global__ __launch_bounds__(256) void k_knn_mean(int64_t nt, IcpGrid g, const int* __restrict__ cellStart, const float4* __restrict__ Tq, int knn,
                                                   const unsigned long long* __restrict__ ctr, double* __restrict__ mean_s,
@@ -185,35 +181,9 @@ __global__ __launch_bounds__(64) void k_knn_mean_deferred(IcpGrid g, const int* 
         int cnt = 0;
         double kth = 1.0 / 0.0;
         // the points [s0, e0) of the sorted array, 64 at a time (wave-uniform arguments)
-        auto scan = [&](int s0, int e0) {
-            for (int base = s0; base < e0; base += 64) {
-                const int j = base + lane;
-                double d2 = 0.0;
-                unsigned qi = 0u;
-                bool take = false;
-                if (j < e0) {
-                    const float4 q = Tq[j];
-                    const double dx = px - (double)q.x, dy = py - (double)q.y, dz = pz - (double)q.z;
-                    d2 = dx * dx + dy * dy + dz * dz;
-                    qi = __float_as_uint(q.w);
-                    take = d2 < kth;                                   // (NaN: a row that is out of the search)
-                }
-                unsigned long long mask = __ballot(take);
-                int nt = __popcll(mask);
-                if (cnt + nt > GSR_HYBRID_CAP) {                       // (cnt > CAP - 64 >= k': the cut leaves exactly k')
-                    cnt = hyb_rank_cut(sd, si, cnt, kp, nullptr);
-                    kth = sd[kp - 1];
-                    take = take && d2 < kth;
-                    mask = __ballot(take);
-                    nt = __popcll(mask);
-                }
-                if (take) {
-                    const int pos = cnt + __popcll(mask & ((1ull << lane) - 1ull));
-                    sd[pos] = d2; si[pos] = qi;
-                }
-                cnt += nt;
-                __syncthreads();
-            }
+        auto scan = [&](int s0, int e0) {                                  // (overflow: cnt > CAP - 64 >= k', the cut leaves exactly k')
+            wave_scan_take(Tq, s0, e0, px, py, pz, sd, si, cnt, kp, [&](double d2, unsigned) { return d2 < kth; },      // (NaN: a row that is out of the search)
+                           [&]() { kth = sd[kp - 1]; });
         };
         // the rows a lane flagged, one after the other
         auto scan_rows = [&](bool need, int s0, int e0) {
@@ -340,22 +310,15 @@ __global__ __launch_bounds__(256) void k_radius_count(int64_t nt, IcpGrid g, con
         const float4 qv = Tq[jq];
         const double px = (double)qv.x, py = (double)qv.y, pz = (double)qv.z;
         if (!(px == px && py == py && pz == pz)) continue;
-        const int cx = icp_cell(px, g.ox, g.inv_c, g.gx), cy = icp_cell(py, g.oy, g.inv_c, g.gy), cz = icp_cell(pz, g.oz, g.inv_c, g.gz);
-        const int z0 = cz - R > 0 ? cz - R : 0, z1 = cz + R < g.gz - 1 ? cz + R : g.gz - 1;
-        const int y0 = cy - R > 0 ? cy - R : 0, y1 = cy + R < g.gy - 1 ? cy + R : g.gy - 1;
-        const int x0 = cx - R > 0 ? cx - R : 0, x1 = cx + R < g.gx - 1 ? cx + R : g.gx - 1;
         int count = 0;
-        for (int z = z0; z <= z1; ++z)
-            for (int y = y0; y <= y1; ++y) {
-                const int rowbase = (z * g.gy + y) * g.gx;
-                const int s0 = cellStart[rowbase + x0], e0 = cellStart[rowbase + x1 + 1];
-                for (int j = s0; j < e0; ++j) {
-                    const float4 q = Tq[j];
-                    const double dx = px - (double)q.x, dy = py - (double)q.y, dz = pz - (double)q.z;
-                    const double d2 = dx * dx + dy * dy + dz * dz;
-                    count += d2 < r2 ? 1 : 0;
-                }
+        grid_box_walk(g, cellStart, icp_cell(px, g.ox, g.inv_c, g.gx), icp_cell(py, g.oy, g.inv_c, g.gy), icp_cell(pz, g.oz, g.inv_c, g.gz), R, [&](int s0, int e0) {
+            for (int j = s0; j < e0; ++j) {
+                const float4 q = Tq[j];
+                const double dx = px - (double)q.x, dy = py - (double)q.y, dz = pz - (double)q.z;
+                const double d2 = dx * dx + dy * dy + dz * dz;
+                count += d2 < r2 ? 1 : 0;
             }
+        });
         const int64_t row = (int64_t)__float_as_uint(qv.w);
         if (count_out) count_out[row] = count;
         if (!(count > nb_points)) stage[row] = CLEAN_RADIUS;
@@ -366,9 +329,9 @@ __global__ __launch_bounds__(256) void k_clean_mask(int64_t n, const uint8_t* __
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         const int s = stage[i];
         mask[i] = s == 0 ? 1 : 0;
-        clean_wave_count(s == CLEAN_STATISTICAL, ctr + CLEAN_STATISTICAL - 1);
-        clean_wave_count(s == CLEAN_RADIUS, ctr + CLEAN_RADIUS - 1);
-        clean_wave_count(s == 0, ctr + CLEAN_CTR_KEPT);
+        wave_count(s == CLEAN_STATISTICAL, ctr + CLEAN_STATISTICAL - 1);
+        wave_count(s == CLEAN_RADIUS, ctr + CLEAN_RADIUS - 1);
+        wave_count(s == 0, ctr + CLEAN_CTR_KEPT);
     }
 }
 
@@ -405,8 +368,8 @@ struct CleanHost {                       // what the one read-back at the end la
     double stats[3];
 };
 
-int32_t outlier_mask_run(OneShot& os, gsr_icp_ctx** ctx, Event* ev, CleanHost* host, const float* xyz, const float* raw_opacity, const float* scaling, int64_t n,
-                         const gsr_clean_params* P, uint8_t* mask, double* mean_dist, int32_t* count, gsr_clean_report* report, int device) {
+int32_t outlier_mask_run(OneShot& os, GridIndex& gi, Event* ev, CleanHost* host, const float* xyz, const float* raw_opacity, const float* scaling, int64_t n,
+                         const gsr_clean_params* P, uint8_t* mask, double* mean_dist, int32_t* count, gsr_clean_report* report) {
     hipStream_t st = os.st;
     size_t workspace = 0;
     auto ws = [&](size_t bytes, auto** p) { workspace += bytes; return os.scratch(bytes, p); };
@@ -438,8 +401,8 @@ int32_t outlier_mask_run(OneShot& os, gsr_icp_ctx** ctx, Event* ev, CleanHost* h
     // ---- pre-pass and grid
     GSR_HIP(hipEventRecord(ev[0], st));
     hipLaunchKernelGGL(k_clean_prep, dim3(stride_grid(n)), dim3(256), 0, st, n, dxyz, dop, dsc, P->min_raw_opacity, P->max_log_scale, sxyz, stage, dmean, dcount, ctr);
-    GridView gv;
-    if (stat_on || radius_on) GSR_TRY(grid_borrow(sxyz, n, radius_on ? P->radius : 1e-300, device, st, ctx, &gv));
+    if (stat_on || radius_on) GSR_TRY(gi.build(sxyz, n, radius_on ? P->radius : 1e-300, st));
+    const GridView gv = gi.view();
     // ---- k-NN means, moments, the statistical verdict
     GSR_HIP(hipEventRecord(ev[1], st));
     if (stat_on) {
@@ -463,10 +426,8 @@ int32_t outlier_mask_run(OneShot& os, gsr_icp_ctx** ctx, Event* ev, CleanHost* h
     // ---- radius count
     GSR_HIP(hipEventRecord(ev[2], st));
     if (radius_on) {
-        const double rc = ceil(P->radius * gv.g.inv_c) + 1.0;           // +1: a cell index rounded across a boundary
-        const int R = rc > (double)(1 << 20) ? (1 << 20) : (int)rc;
-        hipLaunchKernelGGL(k_radius_count, dim3(stride_grid(n)), dim3(256), 0, st, n, gv.g, gv.cellStart, (const float4*)gv.Tq, P->radius * P->radius, R,
-                           (int)P->nb_points, stage, dcount);
+        hipLaunchKernelGGL(k_radius_count, dim3(stride_grid(n)), dim3(256), 0, st, n, gv.g, gv.cellStart, (const float4*)gv.Tq, P->radius * P->radius,
+                           grid_rings_for_radius(gv.g, P->radius), (int)P->nb_points, stage, dcount);
     }
     // ---- mask
     GSR_HIP(hipEventRecord(ev[3], st));
@@ -505,14 +466,9 @@ extern "C" int32_t gsr_outlier_mask(const float* xyz, const float* raw_opacity, 
     Event ev[5];
     for (Event& e : ev) GSR_HIP(e.create());
     CleanHost host;
-    gsr_icp_ctx* ctx = nullptr;
-    int32_t r;
-    {
-        OneShot os((hipStream_t)stream, on_device != 0, who);          // in this scope: it waits before the grid's buffers are freed
-        r = outlier_mask_run(os, &ctx, ev, &host, xyz, raw_opacity, scaling, n, params, mask, mean_dist, count, report, device);
-    }
-    (void)gsr_icp_destroy(ctx);
-    return r;
+    GridIndex gi;                                                      // declared before the OneShot: it waits before the grid's buffers are freed
+    OneShot os((hipStream_t)stream, on_device != 0, who);
+    return outlier_mask_run(os, gi, ev, &host, xyz, raw_opacity, scaling, n, params, mask, mean_dist, count, report);
 }
 
 extern "C" int32_t gsr_model_select(const gsr_model_view* in, int32_t K, const uint8_t* mask, gsr_model_view* out, int32_t* index, int64_t* n_out,

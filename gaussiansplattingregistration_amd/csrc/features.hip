@@ -1,8 +1,8 @@
 // features.hip -- global registration on MI355X (gfx950), behind include/gsr_hip.h: FPFH features, feature matching and RANSAC over
 // correspondences, the work of the reference's "Global" tab (src/utils/global_registration_util.py) through Open3D 0.16.
 //
-//   gsr_hybrid_search   KDTreeSearchParamHybrid(radius, max_nn) of the cloud against itself (k_hybrid_search in icp.hip, on the
-//                       ICP target grid)
+//   gsr_hybrid_search   KDTreeSearchParamHybrid(radius, max_nn) of the cloud against itself (k_hybrid_search in grid.hip, on a
+//                       point grid of the cloud)
 //   gsr_fpfh            k_spfh (thread per point: pair features of its neighbourhood, bin counts in LDS) then k_fpfh (thread per
 //                       point: 33 float64 accumulators over the neighbours' SPFH rows)
 //   gsr_feature_match   k_fm_nn: exact float64 1-NN over 33 dimensions, a source row per thread in registers against target tiles

@@ -1,4 +1,4 @@
-// gsr_common.h -- host-side plumbing shared by the HEM and ICP halves of libgsr_hip.so.
+// gsr_common.h -- plumbing shared by the translation units of libgsr_hip.so: errors, owning handles, the host's waits, launch sizes.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <sched.h>
@@ -133,6 +133,13 @@ inline int32_t wait_host_flag(hipStream_t st, const volatile unsigned long long*
     }
     if (!seen) GSR_HIP(hipStreamSynchronize(st));
     return GSR_OK;
+}
+
+// one integer atomic per wave: the first lane with `flag` adds how many lanes have it (call it with the whole wave present)
+template <class T>
+__device__ __forceinline__ void wave_count(bool flag, T* ctr) {
+    const unsigned long long m = __ballot(flag);
+    if (m && (int)(threadIdx.x & 63) == __ffsll((long long)m) - 1) atomicAdd(ctr, (T)__popcll(m));
 }
 
 inline int ceil_div(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }

@@ -1,4 +1,4 @@
-// gsr_features.h -- internal interface between csrc/icp.hip (which owns the uniform grid of the ICP target index),
+// gsr_features.h -- internal interface between csrc/grid.hip (the point grid and the hybrid search over it),
 // csrc/features.hip (FPFH, feature matching, RANSAC) and csrc/fgr.hip (Fast Global Registration).  Not part of include/gsr_hip.h.
 #pragma once
 #include "gsr_common.h"
@@ -10,8 +10,8 @@ namespace gsr {
 #define GSR_HYBRID_CAP 1024
 #define GSR_HYBRID_MAX_NN 512
 
-// Open3D KDTreeSearchParamHybrid(radius, max_nn) for every point of the cloud against the cloud itself, on the grid of the ICP
-// target index: nbr[i * max_nn + k] = input index of the k-th neighbour of point i in (d^2, index) order, cnt[i] = how many,
+// Open3D KDTreeSearchParamHybrid(radius, max_nn) for every point of the cloud against the cloud itself, on a point grid of its own
+// (GridIndex, gsr_grid.h): nbr[i * max_nn + k] = input index of the k-th neighbour of point i in (d^2, index) order, cnt[i] = how many,
 // where d^2 = (p_i - p_j)^2 summed x, y, z in float64 from the float32 coordinates and a neighbour satisfies d^2 <= radius^2.
 // xyz_dev, nbr_dev, cnt_dev: device memory.  Enqueued on `stream`, synchronises it before returning.
 int32_t hybrid_search_dev(const float* xyz_dev, int64_t n, double radius, int max_nn, int device, hipStream_t stream, int* nbr_dev,

@@ -5,9 +5,9 @@
 // neighbour within max_corr, residual / Jacobian, and the reduction that the estimator solves.
 // The reference's Open3D walks a KD-tree per point under OpenMP; here:
 //
-//   target (once per call)  cell-sorted float4 {x, y, z, bits(input index)} + optional double3
-//                           normals, dense uniform grid (about 2 points per cell, never finer than
-//                           max_corr/8), prefix table cellStart[cells+1]
+//   target (once per call)  the point grid of csrc/grid.hip (GridIndex): cell-sorted float4 {x, y, z, bits(input index)},
+//                           dense uniform grid (about 2 points per cell, never finer than max_corr/64), prefix table
+//                           cellStart[cells+1]; here the optional double3 normals gathered into the same order
 //   source (once per call)  sorted by the same grid's cell so that neighbouring lanes walk the same cells
 //   k_icp_accumulate<KIND>  ONE fused pass per ICP iteration: p = T*p0 in float64, expanding ring
 //                           search over contiguous row spans of the sorted target, exact 1-NN
@@ -20,7 +20,7 @@
 //                           for sources of >= 10^6 points, where occupancy decides (the search is latency bound)
 //   estimators              point-to-point (Umeyama), point-to-plane, generalized ICP (W = (Ct + R Cs R^T)^-1/2 per
 //                           pair, float64 Jacobi), colored ICP (k_icp_color_gradient prepares the target: 30 nearest
-//                           neighbours within 2 max_corr, tangent-plane intensity gradient); robust kernel weights
+//                           neighbours within 2 max_corr by grid_ring_walk, tangent-plane intensity gradient); robust kernel weights
 //   k_icp_accumulate_dev    the same pass for the device-resident loop: T from the device state, the source dealt to the XCDs in
 //                           contiguous eighths; eight instantiations (estimator x 27-cell block search)
 //   k_icp_step              device-resident loop: reduces the partials, tests convergence, solves (3x3 Jacobi SVD /
@@ -34,7 +34,6 @@
 #include "gsr_features.h"
 #include "gsr_grid.h"
 #include "gsr_oneshot.h"
-#include "gsr_prims.h"
 
 #include <float.h>
 #include <math.h>
@@ -43,160 +42,6 @@
 #include <vector>
 
 namespace gsr {
-// rocPRIM's Onesweep with its gfx950 kernel shapes but 11 bits per pass: the 22-bit cell keys of a 5 M-point grid take two passes
-// instead of three (up to 2^20 keys rocPRIM's merge sort runs as before)
-// (the merge sorts of up to 2^20 keys with block sorts of 1 024 x 4 keys: 20-25 us less per target / source sort at 556 k points than rocPRIM's
-// default shape, equal at 185 k: profiles/r05aj_icp_merge_sort_configs.txt)
-#ifndef GSR_ICP_MERGE_BS
-#define GSR_ICP_MERGE_BS 1024
-#define GSR_ICP_MERGE_IPT 4
-#endif
-using icp_merge_cfg = rocprim::merge_sort_config<512, GSR_ICP_MERGE_BS, GSR_ICP_MERGE_IPT, 128, 128, 4>;
-using icp_sort_cfg = rocprim::radix_sort_config<rocprim::default_config, icp_merge_cfg,
-                                                rocprim::radix_sort_onesweep_config<rocprim::kernel_config<1024, 16>, rocprim::kernel_config<1024, 16>, 11,
-                                                                                    rocprim::block_radix_rank_algorithm::match>>;
-
-#ifndef ICP_CELL_FLOOR_DIV
-#define ICP_CELL_FLOOR_DIV 64.0     // a grid cell is never finer than max_corr / this (bounds the rings of a query that finds nothing)
-#endif
-__global__ __launch_bounds__(256) void k_icp_bbox(int64_t n, const float* __restrict__ xyz, float* __restrict__ bbox_part) {
-    float mn[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, mx[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        float x = xyz[3 * i], y = xyz[3 * i + 1], z = xyz[3 * i + 2];
-        if (fabsf(x) <= FLT_MAX && fabsf(y) <= FLT_MAX && fabsf(z) <= FLT_MAX) {
-            mn[0] = fminf(mn[0], x); mx[0] = fmaxf(mx[0], x);
-            mn[1] = fminf(mn[1], y); mx[1] = fmaxf(mx[1], y);
-            mn[2] = fminf(mn[2], z); mx[2] = fmaxf(mx[2], z);
-        }
-    }
-    // per-block partial box, no atomics (10^4 same-address atomics cost ~0.5 ms: they serialise across the XCDs)
-    __shared__ float s_mn[4][3], s_mx[4][3];
-    for (int k = 0; k < 3; ++k)
-        for (int o = 32; o > 0; o >>= 1) { mn[k] = fminf(mn[k], __shfl_xor(mn[k], o)); mx[k] = fmaxf(mx[k], __shfl_xor(mx[k], o)); }
-    if ((threadIdx.x & 63) == 0)
-        for (int k = 0; k < 3; ++k) { s_mn[threadIdx.x >> 6][k] = mn[k]; s_mx[threadIdx.x >> 6][k] = mx[k]; }
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        const int k = threadIdx.x;
-        float a = s_mn[0][k], b = s_mx[0][k];
-        for (int w = 1; w < 4; ++w) { a = fminf(a, s_mn[w][k]); b = fmaxf(b, s_mx[w][k]); }
-        bbox_part[6 * blockIdx.x + k] = a;
-        bbox_part[6 * blockIdx.x + 3 + k] = b;
-    }
-}
-// bbox[0..2] = min, bbox[3..5] = max over the per-block partial boxes
-__global__ __launch_bounds__(256) void k_icp_bbox_reduce(int nblocks, const float* __restrict__ part, float* __restrict__ bbox) {
-    __shared__ float s_v[4][6];
-    float v[6] = {FLT_MAX, FLT_MAX, FLT_MAX, -FLT_MAX, -FLT_MAX, -FLT_MAX};
-    for (int b = threadIdx.x; b < nblocks; b += blockDim.x)
-        for (int k = 0; k < 3; ++k) { v[k] = fminf(v[k], part[6 * b + k]); v[3 + k] = fmaxf(v[3 + k], part[6 * b + 3 + k]); }
-    for (int k = 0; k < 3; ++k)
-        for (int o = 32; o > 0; o >>= 1) { v[k] = fminf(v[k], __shfl_xor(v[k], o)); v[3 + k] = fmaxf(v[3 + k], __shfl_xor(v[3 + k], o)); }
-    if ((threadIdx.x & 63) == 0)
-        for (int k = 0; k < 6; ++k) s_v[threadIdx.x >> 6][k] = v[k];
-    __syncthreads();
-    if (threadIdx.x < 6) {
-        const int k = threadIdx.x;
-        float r = s_v[0][k];
-        for (int w = 1; w < 4; ++w) r = k < 3 ? fminf(r, s_v[w][k]) : fmaxf(r, s_v[w][k]);
-        bbox[k] = r;
-    }
-}
-
-// A robust box for the grid.  The reference's scenes come with floaters: a dozen points at 50 scene radii make the box of ALL points
-// 10^5 times the scene's volume, the cells -- sized for two points each over that box -- swallow the scene whole, and every query
-// scans millions of points (found with bench.py --workload clustered: 116 s per registration).  So: per-axis histograms over the raw
-// box (ICP_HIST_BINS bins), the range that holds all but the outermost 0.1 % of the points per side; when that range is less than
-// half the raw extent on some axis the grid is laid over it (after ONE refinement pass at the finer resolution), and the points
-// beyond are clamped into the boundary cells, which every search treats as half-infinite (icp_slab_dist; the ring logic skips the
-// boundary faces anyway).  A cloud without outliers keeps the raw box: nothing changes for it.
-#define ICP_HIST_BINS 1024
-__global__ __launch_bounds__(256) void k_icp_hist(int64_t n, const float* __restrict__ xyz, const float* __restrict__ box, unsigned* __restrict__ hist) {
-    __shared__ unsigned s_h[3 * ICP_HIST_BINS];
-    for (int k = threadIdx.x; k < 3 * ICP_HIST_BINS; k += blockDim.x) s_h[k] = 0u;
-    __syncthreads();
-    float mn[3], sc[3];
-    for (int k = 0; k < 3; ++k) {
-        mn[k] = box[k];
-        const float ext = box[3 + k] - mn[k];
-        sc[k] = ext > 0.0f ? (float)ICP_HIST_BINS / ext : 0.0f;
-    }
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const float v[3] = {xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]};
-        if (fabsf(v[0]) <= FLT_MAX && fabsf(v[1]) <= FLT_MAX && fabsf(v[2]) <= FLT_MAX) {
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                float t = (v[k] - mn[k]) * sc[k];
-                t = fminf(fmaxf(t, 0.0f), (float)(ICP_HIST_BINS - 1));
-                atomicAdd(&s_h[k * ICP_HIST_BINS + (int)t], 1u);
-            }
-        }
-    }
-    __syncthreads();
-    for (int k = threadIdx.x; k < 3 * ICP_HIST_BINS; k += blockDim.x)
-        if (s_h[k]) atomicAdd(&hist[k], s_h[k]);
-}
-// box_out = per axis the bins [lo, hi] of box_in that hold all but the outermost 0.1 % of the points per side, widened by one bin on
-// either side; *flag = 1 when on some axis that is less than half of box_in's extent.  One thread per axis.
-__global__ void k_icp_trim(const unsigned* __restrict__ hist, const float* __restrict__ box_in, float* __restrict__ box_out, float* __restrict__ flag) {
-    __shared__ int s_narrow[3];
-    if (threadIdx.x < 3) {
-        const int k = threadIdx.x;
-        const unsigned* h = hist + k * ICP_HIST_BINS;
-        unsigned long long total = 0;
-        for (int b = 0; b < ICP_HIST_BINS; ++b) total += h[b];
-        const unsigned long long trim = total / 1000ull;
-        int lo = 0, hi = ICP_HIST_BINS - 1;
-        unsigned long long acc = 0;
-        while (lo < ICP_HIST_BINS - 1 && acc + h[lo] <= trim) { acc += h[lo]; ++lo; }
-        acc = 0;
-        while (hi > lo && acc + h[hi] <= trim) { acc += h[hi]; --hi; }
-        const float mn = box_in[k], ext = box_in[3 + k] - mn, w = ext / (float)ICP_HIST_BINS;
-        lo = lo > 0 ? lo - 1 : 0;
-        hi = hi < ICP_HIST_BINS - 1 ? hi + 1 : ICP_HIST_BINS - 1;
-        box_out[k] = mn + (float)lo * w;
-        box_out[3 + k] = mn + (float)(hi + 1) * w;
-        s_narrow[k] = (float)(hi + 1 - lo) * w < 0.5f * ext ? 1 : 0;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) *flag = (s_narrow[0] | s_narrow[1] | s_narrow[2]) ? 1.0f : 0.0f;
-}
-
-__global__ __launch_bounds__(256) void k_icp_keys(int64_t n, const float* __restrict__ xyz, IcpGrid g,
-                                                  unsigned* __restrict__ keys, unsigned* __restrict__ idx) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        int cx = icp_cell((double)xyz[3 * i], g.ox, g.inv_c, g.gx);
-        int cy = icp_cell((double)xyz[3 * i + 1], g.oy, g.inv_c, g.gy);
-        int cz = icp_cell((double)xyz[3 * i + 2], g.oz, g.inv_c, g.gz);
-        keys[i] = (unsigned)((cz * g.gy + cy) * g.gx + cx);
-        idx[i] = (unsigned)i;
-    }
-}
-
-__global__ __launch_bounds__(256) void k_icp_cell_starts(int64_t m, const unsigned* __restrict__ skeys, int64_t nkeys,
-                                                         int* __restrict__ start) {
-    for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < m; j += (int64_t)gridDim.x * blockDim.x) {
-        unsigned k = skeys[j];
-        int64_t prev = j == 0 ? -1 : (int64_t)skeys[j - 1];
-        if ((int64_t)k != prev)
-            for (int64_t c = prev + 1; c <= (int64_t)k; ++c) start[c] = (int)j;
-        if (j == m - 1)
-            for (int64_t c = (int64_t)k + 1; c <= nkeys; ++c) start[c] = (int)m;
-    }
-}
-
-__global__ __launch_bounds__(256) void k_icp_gather_target(int64_t n, const unsigned* __restrict__ order,
-                                                           const float* __restrict__ xyz, const double* __restrict__ nrm,
-                                                           float4* __restrict__ Tq, double* __restrict__ Tn) {
-    for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < n; j += (int64_t)gridDim.x * blockDim.x) {
-        const unsigned i = order[j];
-        Tq[j] = make_float4(xyz[3 * (int64_t)i], xyz[3 * (int64_t)i + 1], xyz[3 * (int64_t)i + 2], __uint_as_float(i));
-        if (nrm) {
-            Tn[3 * j] = nrm[3 * (int64_t)i]; Tn[3 * j + 1] = nrm[3 * (int64_t)i + 1]; Tn[3 * j + 2] = nrm[3 * (int64_t)i + 2];
-        }
-    }
-}
-
 __global__ __launch_bounds__(256) void k_icp_gather_source(int64_t n, const unsigned* __restrict__ order, const float* __restrict__ xyz,
                                                            float* __restrict__ out) {
     for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < n; j += (int64_t)gridDim.x * blockDim.x) {
@@ -560,8 +405,7 @@ __device__ __forceinline__ void icp_colored_rows(double (&acc)[NACC], const Colo
 // Colour gradient of every target point (Open3D InitializePointCloudForColoredICP): its ICP_KNN nearest neighbours
 // (itself first) within `radius`, ordered by (distance, input index); with >= 4 of them a 3x3 least-squares fit of the
 // intensity differences over the tangent-plane projections, plus the orthogonality row (nn-1) n.  One thread per
-// point; the k-best list lives in per-thread scratch.  Same expanding-ring search geometry as icp_nearest.
-#define ICP_KNN 30
+// point: grid_ring_walk into a KBest list (gsr_grid.h).
 __global__ __launch_bounds__(256) void k_icp_color_gradient(int64_t nt, IcpGrid g, const int* __restrict__ cellStart, const float4* __restrict__ Tq,
                                                             const double* __restrict__ Tn, const double* __restrict__ t_int, double radius,
                                                             double* __restrict__ t_grad) {
@@ -570,65 +414,14 @@ __global__ __launch_bounds__(256) void k_icp_color_gradient(int64_t nt, IcpGrid 
         const double px = (double)qv.x, py = (double)qv.y, pz = (double)qv.z;
         t_grad[3 * jq] = 0.0; t_grad[3 * jq + 1] = 0.0; t_grad[3 * jq + 2] = 0.0;
         if (!(px == px) || !(py == py) || !(pz == pz)) continue;
-        double kd[ICP_KNN];
-        int kj[ICP_KNN];
-        unsigned ki[ICP_KNN];
-        int cnt = 0;
+        KBest<ICP_KNN> kb;
         const double r2 = radius * radius;
-        const int cx = icp_cell(px, g.ox, g.inv_c, g.gx), cy = icp_cell(py, g.oy, g.inv_c, g.gy), cz = icp_cell(pz, g.oz, g.inv_c, g.gz);
-        const double eps = 1e-13 * (fabs(px) + fabs(py) + fabs(pz) + fabs(g.ox) + fabs(g.oy) + fabs(g.oz) + g.c * (double)(g.gx + g.gy + g.gz));
-        const int rmax = (int)ceil(radius / g.c) + 1;
-        for (int r = 0; r <= rmax; ++r) {
-            for (int dz = -r; dz <= r; ++dz) {
-                const int z = cz + dz;
-                if (z < 0 || z >= g.gz) continue;
-                const int adz = dz < 0 ? -dz : dz;
-                for (int dy = -r; dy <= r; ++dy) {
-                    const int y = cy + dy;
-                    if (y < 0 || y >= g.gy) continue;
-                    const int ady = dy < 0 ? -dy : dy;
-                    const int rowbase = (z * g.gy + y) * g.gx;
-                    int spans[2][2];
-                    int nsp = 0;
-                    if (adz == r || ady == r) {
-                        const int xa = cx - r > 0 ? cx - r : 0, xb = cx + r < g.gx - 1 ? cx + r : g.gx - 1;
-                        if (xa <= xb) { spans[0][0] = rowbase + xa; spans[0][1] = rowbase + xb; nsp = 1; }
-                    } else {
-                        if (cx - r >= 0) { spans[nsp][0] = spans[nsp][1] = rowbase + cx - r; ++nsp; }
-                        if (cx + r < g.gx) { spans[nsp][0] = spans[nsp][1] = rowbase + cx + r; ++nsp; }
-                    }
-                    for (int sidx = 0; sidx < nsp; ++sidx) {
-                        const int s0 = cellStart[spans[sidx][0]], e0 = cellStart[spans[sidx][1] + 1];
-                        for (int j = s0; j < e0; ++j) {
-                            const float4 q = Tq[j];
-                            const double dx = px - (double)q.x, dy2 = py - (double)q.y, dz2 = pz - (double)q.z;
-                            const double d2 = dx * dx + dy2 * dy2 + dz2 * dz2;
-                            const unsigned qi = __float_as_uint(q.w);
-                            if (!(d2 < r2)) continue;                        // the hybrid search keeps d^2 < radius^2
-                            if (cnt == ICP_KNN && !(d2 < kd[cnt - 1] || (d2 == kd[cnt - 1] && qi < ki[cnt - 1]))) continue;
-                            int pos = cnt < ICP_KNN ? cnt : ICP_KNN - 1;     // insertion into the list sorted by (d2, index)
-                            while (pos > 0 && (d2 < kd[pos - 1] || (d2 == kd[pos - 1] && qi < ki[pos - 1]))) {
-                                kd[pos] = kd[pos - 1]; kj[pos] = kj[pos - 1]; ki[pos] = ki[pos - 1];
-                                --pos;
-                            }
-                            kd[pos] = d2; kj[pos] = j; ki[pos] = qi;
-                            if (cnt < ICP_KNN) ++cnt;
-                        }
-                    }
-                }
-            }
-            // an unseen point lies at least `reach` away (see icp_nearest_from); done when the list is full and its
-            // worst entry is strictly closer, or when the radius is covered
-            double reach = 1.0 / 0.0;
-            if (cx - r > 0) reach = fmin(reach, px - (g.ox + (double)(cx - r) * g.c));
-            if (cx + r < g.gx - 1) reach = fmin(reach, (g.ox + (double)(cx + r + 1) * g.c) - px);
-            if (cy - r > 0) reach = fmin(reach, py - (g.oy + (double)(cy - r) * g.c));
-            if (cy + r < g.gy - 1) reach = fmin(reach, (g.oy + (double)(cy + r + 1) * g.c) - py);
-            if (cz - r > 0) reach = fmin(reach, pz - (g.oz + (double)(cz - r) * g.c));
-            if (cz + r < g.gz - 1) reach = fmin(reach, (g.oz + (double)(cz + r + 1) * g.c) - pz);
-            reach = reach * 0.999999999 - eps;
-            if (reach > 0.0 && ((cnt == ICP_KNN && kd[cnt - 1] < reach * reach) || r2 < reach * reach)) break;
-        }
+        // done when the list is full and its worst entry is strictly closer than every unseen point, or when the radius is covered
+        grid_ring_walk(g, cellStart, Tq, px, py, pz, (int)ceil(radius / g.c) + 1,
+                       [&](int j, const float4& q, double d2) { if (d2 < r2) kb.offer(ICP_KNN, d2, j, __float_as_uint(q.w)); },      // the hybrid search keeps d^2 < radius^2
+                       [&](double reach2) { return kb.closed(ICP_KNN, reach2) || r2 < reach2; });
+        const int cnt = kb.cnt;
+        const int* kj = kb.j;
         if (cnt < 4) continue;
         const double nx = Tn[3 * jq], ny = Tn[3 * jq + 1], nz = Tn[3 * jq + 2];
         const double it = t_int[jq];
@@ -888,95 +681,6 @@ __global__ __launch_bounds__(256) void k_cov_from_normals(int64_t n, const doubl
     }
 }
 
-// Normals of a cloud WITHOUT covariances: Open3D EstimateNormals(KDTreeSearchParamKNN(knn)) -- what the reference does to a
-// sparse input cloud (src/utils/point_cloud_converter.py:9-28, default knn = 30).  One thread per point: its knn nearest
-// points (itself included) by (distance, input index) through the same expanding-ring search as the colour gradients;
-// with >= 3 of them the covariance by cumulants (Open3D ComputeCovariance), else the identity; normal_of_cov_d.
-// Output in the CALLER's point order (order[j] = input index of sorted point j).
-__global__ __launch_bounds__(256) void k_knn_normals(int64_t nt, IcpGrid g, const int* __restrict__ cellStart, const float4* __restrict__ Tq,
-                                                     const unsigned* __restrict__ order, int knn, double* __restrict__ out) {
-    for (int64_t jq = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; jq < nt; jq += (int64_t)gridDim.x * blockDim.x) {
-        const float4 qv = Tq[jq];
-        const double px = (double)qv.x, py = (double)qv.y, pz = (double)qv.z;
-        double* o = out + 3 * (int64_t)order[jq];
-        o[0] = 0.0; o[1] = 0.0; o[2] = 1.0;
-        if (!(px == px) || !(py == py) || !(pz == pz)) continue;
-        double kd[ICP_KNN];
-        int kj[ICP_KNN];
-        unsigned ki[ICP_KNN];
-        int cnt = 0;
-        const int cx = icp_cell(px, g.ox, g.inv_c, g.gx), cy = icp_cell(py, g.oy, g.inv_c, g.gy), cz = icp_cell(pz, g.oz, g.inv_c, g.gz);
-        const double eps = 1e-13 * (fabs(px) + fabs(py) + fabs(pz) + fabs(g.ox) + fabs(g.oy) + fabs(g.oz) + g.c * (double)(g.gx + g.gy + g.gz));
-        const int rmax = (g.gx > g.gy ? g.gx : g.gy) > g.gz ? (g.gx > g.gy ? g.gx : g.gy) : g.gz;
-        for (int r = 0; r <= rmax; ++r) {
-            for (int dz = -r; dz <= r; ++dz) {
-                const int z = cz + dz;
-                if (z < 0 || z >= g.gz) continue;
-                const int adz = dz < 0 ? -dz : dz;
-                for (int dy = -r; dy <= r; ++dy) {
-                    const int y = cy + dy;
-                    if (y < 0 || y >= g.gy) continue;
-                    const int ady = dy < 0 ? -dy : dy;
-                    const int rowbase = (z * g.gy + y) * g.gx;
-                    int spans[2][2];
-                    int nsp = 0;
-                    if (adz == r || ady == r) {
-                        const int xa = cx - r > 0 ? cx - r : 0, xb = cx + r < g.gx - 1 ? cx + r : g.gx - 1;
-                        if (xa <= xb) { spans[0][0] = rowbase + xa; spans[0][1] = rowbase + xb; nsp = 1; }
-                    } else {
-                        if (cx - r >= 0) { spans[nsp][0] = spans[nsp][1] = rowbase + cx - r; ++nsp; }
-                        if (cx + r < g.gx) { spans[nsp][0] = spans[nsp][1] = rowbase + cx + r; ++nsp; }
-                    }
-                    for (int sidx = 0; sidx < nsp; ++sidx) {
-                        const int s0 = cellStart[spans[sidx][0]], e0 = cellStart[spans[sidx][1] + 1];
-                        for (int j = s0; j < e0; ++j) {
-                            const float4 q = Tq[j];
-                            const double dx = px - (double)q.x, dy2 = py - (double)q.y, dz2 = pz - (double)q.z;
-                            const double d2 = dx * dx + dy2 * dy2 + dz2 * dz2;
-                            const unsigned qi = __float_as_uint(q.w);
-                            if (!(d2 == d2)) continue;
-                            if (cnt == knn && !(d2 < kd[cnt - 1] || (d2 == kd[cnt - 1] && qi < ki[cnt - 1]))) continue;
-                            int pos = cnt < knn ? cnt : knn - 1;             // insertion into the list sorted by (d2, index)
-                            while (pos > 0 && (d2 < kd[pos - 1] || (d2 == kd[pos - 1] && qi < ki[pos - 1]))) {
-                                kd[pos] = kd[pos - 1]; kj[pos] = kj[pos - 1]; ki[pos] = ki[pos - 1];
-                                --pos;
-                            }
-                            kd[pos] = d2; kj[pos] = j; ki[pos] = qi;
-                            if (cnt < knn) ++cnt;
-                        }
-                    }
-                }
-            }
-            // an unseen point lies at least `reach` away: done when the list is full and its worst entry is strictly closer
-            double reach = 1.0 / 0.0;
-            if (cx - r > 0) reach = fmin(reach, px - (g.ox + (double)(cx - r) * g.c));
-            if (cx + r < g.gx - 1) reach = fmin(reach, (g.ox + (double)(cx + r + 1) * g.c) - px);
-            if (cy - r > 0) reach = fmin(reach, py - (g.oy + (double)(cy - r) * g.c));
-            if (cy + r < g.gy - 1) reach = fmin(reach, (g.oy + (double)(cy + r + 1) * g.c) - py);
-            if (cz - r > 0) reach = fmin(reach, pz - (g.oz + (double)(cz - r) * g.c));
-            if (cz + r < g.gz - 1) reach = fmin(reach, (g.oz + (double)(cz + r + 1) * g.c) - pz);
-            reach = reach * 0.999999999 - eps;
-            if (reach > 0.0 && cnt == knn && kd[cnt - 1] < reach * reach) break;
-        }
-        double c00 = 1, c01 = 0, c02 = 0, c11 = 1, c12 = 0, c22 = 1;        // fewer than 3 neighbours: identity
-        if (cnt >= 3) {
-            double m[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-            for (int i = 0; i < cnt; ++i) {
-                const float4 q = Tq[kj[i]];
-                const double x = (double)q.x, y = (double)q.y, z = (double)q.z;
-                m[0] += x; m[1] += y; m[2] += z;
-                m[3] += x * x; m[4] += x * y; m[5] += x * z; m[6] += y * y; m[7] += y * z; m[8] += z * z;
-            }
-            for (int k = 0; k < 9; ++k) m[k] /= (double)cnt;
-            c00 = m[3] - m[0] * m[0]; c11 = m[6] - m[1] * m[1]; c22 = m[8] - m[2] * m[2];
-            c01 = m[4] - m[0] * m[1]; c02 = m[5] - m[0] * m[2]; c12 = m[7] - m[1] * m[2];
-        }
-        double v[3];
-        normal_of_cov_d(c00, c01, c02, c11, c12, c22, v);
-        o[0] = v[0]; o[1] = v[1]; o[2] = v[2];
-    }
-}
-
 
 // ---- device-resident ICP loop -------------------------------------------------------------------------
 // registration_icp's loop needs, per iteration, one correspondence pass and a 3x3 / 6x6 solve on 32
@@ -1175,7 +879,7 @@ using namespace gsr;
 struct gsr_icp_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
-    IcpGrid grid;
+    GridIndex index;                // the target's point grid: cells, cellStart, the sorted points Tq, order (gsr_grid.h)
     bool have_target = false, have_normals = false, have_source = false;
     int64_t nt = 0, ns = 0, ns_global = 0;
     double max_corr = 0;
@@ -1187,8 +891,6 @@ struct gsr_icp_ctx {
     bool block_search = true;       // GSR_ICP_BLOCK_SEARCH=0: always the ring loop from ring 0
     bool xcd_ranges = true;         // GSR_ICP_XCD=0: logical block = physical block (every XCD walks the whole source)
     gsr_comm* comm = nullptr;       // multi-GPU source split through a communicator (gsr_icp_set_comm)
-    PinnedBlock host_rb;            // small read-backs: unsigned[256] + the sequence flag; empty = no polling (icp_fetch)
-    unsigned long long rb_seq = 0;
     // Search / accumulate split (GSR_ICP_NN_KERNEL): 0 = one fused kernel (120 VGPRs with the 30 float64 accumulators:
     // 4 waves per SIMD); 2 = a thread-per-point search kernel (56 VGPRs, 8 waves per SIMD) writes nn_j and a streaming
     // kernel accumulates -- the search is latency bound, so occupancy wins: 21 % faster at 5 M points, equal at 0.5 M,
@@ -1199,12 +901,7 @@ struct gsr_icp_ctx {
     // measured on the bench's levels with the XCD-contiguous ranges, fused / split: 185 k 51.7 / 59.2 us, 556 k 90.1 / 81.6, 1.67 M 233 / 190,
     // 5 M 563 / 397 per iteration
     int nn_mode() const { return nn_kernel >= 0 ? (nn_kernel ? 2 : 0) : (ns >= 400000 ? 2 : 0); }
-    double cell_target = 2.0;       // target points per grid cell (GSR_ICP_CELL_TARGET).  Measured at 5M x 5M: 0.5 makes a
-                                    // converged iteration 1.7x faster but a cold start (offsets ~ max_corr) 1.6x slower: keep 2
-    DevBuf hist;
-    bool robust_box = false;        // the current target's grid lies over the trimmed box (far outliers clamped into the boundary cells)
-    bool robust_allowed = true;     // GSR_ICP_ROBUST_BOX=0: always the box of all points (test knob: results must not change)
-    DevBuf bbox, keys, idx, skeys, order, cellStart, Tq, Tn, stage_xyz, stage_nrm, src, partials, acc_dev, rocprim_tmp, corr_idx, corr_d2;
+    DevBuf Tn, stage_xyz, stage_nrm, src, partials, acc_dev, corr_idx, corr_d2;
     gsr_allreduce_fn allreduce = nullptr;
     void* allreduce_user = nullptr;
     gsr_allreduce_dev64_fn allreduce_dev = nullptr;      // device-resident loop with a stream-ordered collective per iteration
@@ -1214,7 +911,6 @@ struct gsr_icp_ctx {
     bool build_pending = false;     // ms_build has not been read from eb0 / eb1 yet
     float ms_build = 0, ms_iter = 0;
     int n_iter_kernels = 0;
-    int max_cells = 1 << 25;
     // workgroups of the search + accumulate kernel: three fit a CU (141 VGPRs), 768 are ONE round on the chip.  With 1 024 the last
     // 256 ran as a second, quarter-full round: 108 -> 95 us per iteration at 556 k source points (GSR_ICP_BLOCKS)
     int nblocks = 768;
@@ -1239,10 +935,10 @@ void launch_icp_nn(gsr_icp_ctx* c, hipStream_t st, const Xform& X, const IcpStat
     const dim3 grid(8 * ((g1 + 7) / 8)), blk(256);
     const int nbl = c->xcd_ranges ? g1 : -g1;
     if (blockf)
-        hipLaunchKernelGGL((k_icp_nn<FROM_STATE, 1>), grid, blk, 0, st, c->ns, c->src.as<float>(), X, state, c->grid, c->cellStart.as<int>(), c->Tq.as<float4>(), mc2,
+        hipLaunchKernelGGL((k_icp_nn<FROM_STATE, 1>), grid, blk, 0, st, c->ns, c->src.as<float>(), X, state, c->index.grid, c->index.cellStart.as<int>(), c->index.Tq.as<float4>(), mc2,
                            c->nn_j.as<int>(), nbl);
     else
-        hipLaunchKernelGGL((k_icp_nn<FROM_STATE, 0>), grid, blk, 0, st, c->ns, c->src.as<float>(), X, state, c->grid, c->cellStart.as<int>(), c->Tq.as<float4>(), mc2,
+        hipLaunchKernelGGL((k_icp_nn<FROM_STATE, 0>), grid, blk, 0, st, c->ns, c->src.as<float>(), X, state, c->index.grid, c->index.cellStart.as<int>(), c->index.Tq.as<float4>(), mc2,
                            c->nn_j.as<int>(), nbl);
 }
 
@@ -1290,8 +986,8 @@ void launch_accumulate_dev(gsr_icp_ctx* c, hipStream_t st, int kind, bool blockf
         case 8: kernel = k_icp_accumulate_dev<4, 0>; break;
         default: kernel = k_icp_accumulate_dev<4, 1>; break;
     }
-    hipLaunchKernelGGL(kernel, dim3(8 * ((nb + 7) / 8)), dim3(256), 0, st, c->ns, c->src.as<float>(), c->state.as<IcpState>(), c->grid, c->cellStart.as<int>(), nnj,
-                       c->Tq.as<float4>(), tn, sc, cargs, mc2, loss, k, c->partials.as<double>(), c->xcd_ranges ? nb : -nb);
+    hipLaunchKernelGGL(kernel, dim3(8 * ((nb + 7) / 8)), dim3(256), 0, st, c->ns, c->src.as<float>(), c->state.as<IcpState>(), c->index.grid, c->index.cellStart.as<int>(), nnj,
+                       c->index.Tq.as<float4>(), tn, sc, cargs, mc2, loss, k, c->partials.as<double>(), c->xcd_ranges ? nb : -nb);
 }
 
 int32_t run_accumulate(gsr_icp_ctx* c, const double* T, int kind, int loss, double k, double* acc, bool timed) {
@@ -1313,20 +1009,20 @@ int32_t run_accumulate(gsr_icp_ctx* c, const double* T, int kind, int loss, doub
     }
     const ColorArgs cargs = {c->Ti.as<double>(), c->Tg.as<double>(), c->Si.as<double>(), sqrt(c->lambda_geometric), sqrt(1.0 - c->lambda_geometric)};
     if (kind == GSR_ICP_COLORED)
-        hipLaunchKernelGGL(k_icp_accumulate<3>, dim3(nb), dim3(256), 0, st, c->ns, c->src.as<float>(), X, c->grid, c->cellStart.as<int>(), nnj,
-                           c->Tq.as<float4>(), c->Tn.as<double>(), (const double*)nullptr, cargs, mc2, loss, k, c->partials.as<double>());
+        hipLaunchKernelGGL(k_icp_accumulate<3>, dim3(nb), dim3(256), 0, st, c->ns, c->src.as<float>(), X, c->index.grid, c->index.cellStart.as<int>(), nnj,
+                           c->index.Tq.as<float4>(), c->Tn.as<double>(), (const double*)nullptr, cargs, mc2, loss, k, c->partials.as<double>());
     else if (kind == GSR_ICP_POINT_TO_POINT)
-        hipLaunchKernelGGL(k_icp_accumulate<0>, dim3(nb), dim3(256), 0, st, c->ns, c->src.as<float>(), X, c->grid, c->cellStart.as<int>(), nnj,
-                           c->Tq.as<float4>(), (const double*)nullptr, (const double*)nullptr, cargs, mc2, loss, k, c->partials.as<double>());
+        hipLaunchKernelGGL(k_icp_accumulate<0>, dim3(nb), dim3(256), 0, st, c->ns, c->src.as<float>(), X, c->index.grid, c->index.cellStart.as<int>(), nnj,
+                           c->index.Tq.as<float4>(), (const double*)nullptr, (const double*)nullptr, cargs, mc2, loss, k, c->partials.as<double>());
     else if (kind == GSR_ICP_POINT_TO_POINT_SCALED)
-        hipLaunchKernelGGL(k_icp_accumulate<4>, dim3(nb), dim3(256), 0, st, c->ns, c->src.as<float>(), X, c->grid, c->cellStart.as<int>(), nnj,
-                           c->Tq.as<float4>(), (const double*)nullptr, (const double*)nullptr, cargs, mc2, loss, k, c->partials.as<double>());
+        hipLaunchKernelGGL(k_icp_accumulate<4>, dim3(nb), dim3(256), 0, st, c->ns, c->src.as<float>(), X, c->index.grid, c->index.cellStart.as<int>(), nnj,
+                           c->index.Tq.as<float4>(), (const double*)nullptr, (const double*)nullptr, cargs, mc2, loss, k, c->partials.as<double>());
     else if (kind == GSR_ICP_POINT_TO_PLANE)
-        hipLaunchKernelGGL(k_icp_accumulate<1>, dim3(nb), dim3(256), 0, st, c->ns, c->src.as<float>(), X, c->grid, c->cellStart.as<int>(), nnj,
-                           c->Tq.as<float4>(), c->Tn.as<double>(), (const double*)nullptr, cargs, mc2, loss, k, c->partials.as<double>());
+        hipLaunchKernelGGL(k_icp_accumulate<1>, dim3(nb), dim3(256), 0, st, c->ns, c->src.as<float>(), X, c->index.grid, c->index.cellStart.as<int>(), nnj,
+                           c->index.Tq.as<float4>(), c->Tn.as<double>(), (const double*)nullptr, cargs, mc2, loss, k, c->partials.as<double>());
     else
-        hipLaunchKernelGGL(k_icp_accumulate<2>, dim3(nb), dim3(256), 0, st, c->ns, c->src.as<float>(), X, c->grid, c->cellStart.as<int>(), nnj,
-                           c->Tq.as<float4>(), c->Tc.as<double>(), c->Sc.as<double>(), cargs, mc2, loss, k, c->partials.as<double>());
+        hipLaunchKernelGGL(k_icp_accumulate<2>, dim3(nb), dim3(256), 0, st, c->ns, c->src.as<float>(), X, c->index.grid, c->index.cellStart.as<int>(), nnj,
+                           c->index.Tq.as<float4>(), c->Tc.as<double>(), c->Sc.as<double>(), cargs, mc2, loss, k, c->partials.as<double>());
     hipLaunchKernelGGL(k_icp_finalize, dim3(GSR_ICP_ACC_LEN), dim3(64), 0, st, nb, c->partials.as<double>(), c->acc_dev.as<double>());
     if (timed) GSR_HIP(hipEventRecord(c->e1, st));
     GSR_HIP(hipMemcpyAsync(acc, c->acc_dev.p, GSR_ICP_ACC_LEN * 8, hipMemcpyDeviceToHost, st));
@@ -1348,32 +1044,6 @@ int32_t run_accumulate(gsr_icp_ctx* c, const double* T, int kind, int loss, doub
 
 extern "C" {
 
-// Small device results the host waits for (the bounding box, the loop state) are copied by one tiny kernel into pinned host
-// memory, the sequence number of the round trip last, and the host polls that word: a hipMemcpyAsync into pageable memory
-// plus hipStreamSynchronize costs 30-50 us per round trip (wait_host_flag, gsr_common.h: the HEM read-backs wait the same way).
-__global__ void k_icp_publish(const unsigned* __restrict__ src, int nwords, unsigned* __restrict__ host, unsigned long long* __restrict__ flag,
-                              unsigned long long seq) {
-    for (int t = threadIdx.x; t < nwords; t += blockDim.x) __hip_atomic_store(host + t, src[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    __threadfence_system();
-    __syncthreads();
-    if (threadIdx.x == 0) __hip_atomic_store(flag, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-static int32_t icp_fetch(gsr_icp_ctx* c, const void* dev, void* out, size_t bytes) {
-    hipStream_t st = c->stream;
-    unsigned* const host_rb = c->host_rb.as<unsigned>();
-    if (!host_rb || bytes > 1024 || (bytes & 3)) {
-        GSR_HIP(hipMemcpyAsync(out, dev, bytes, hipMemcpyDeviceToHost, st));
-        GSR_HIP(hipStreamSynchronize(st));
-        return GSR_OK;
-    }
-    const unsigned long long seq = ++c->rb_seq;
-    unsigned long long* flag = reinterpret_cast<unsigned long long*>(host_rb + 256);
-    hipLaunchKernelGGL(k_icp_publish, dim3(1), dim3(64), 0, st, (const unsigned*)dev, (int)(bytes >> 2), host_rb, flag, seq);
-    GSR_HIP(hipGetLastError());
-    GSR_TRY(wait_host_flag(st, flag, seq, true));       // (GSR_ICP_RB_POLL=0 left host_rb empty: the copy above)
-    memcpy(out, (const void*)host_rb, bytes);
-    return GSR_OK;
-}
 
 int32_t gsr_icp_create(gsr_icp_ctx** out, int32_t device, void* stream) {
     if (!out) return fail(GSR_E_INVALID, "gsr_icp_create: out is NULL");
@@ -1389,20 +1059,12 @@ int32_t gsr_icp_create(gsr_icp_ctx** out, int32_t device, void* stream) {
     if (c->e0.create() != hipSuccess || c->e1.create() != hipSuccess || c->eb0.create() != hipSuccess || c->eb1.create() != hipSuccess) {
         delete c; return fail(GSR_E_HIP, "hipEventCreate failed");
     }
-    // Environment knobs (all of them): none changes a result, tests/test_icp_gpu.py::test_icp_knobs_change_nothing
+    // Environment knobs (the grid's own: GridIndex, csrc/grid.hip): none changes a result, tests/test_icp_gpu.py::test_icp_knobs_change_nothing
     if (const char* e = getenv("GSR_ICP_DEVICE_LOOP")) c->device_loop = atoi(e) != 0;
     if (const char* e = getenv("GSR_ICP_BLOCK_SEARCH")) c->block_search = atoi(e) != 0;
     if (const char* e = getenv("GSR_ICP_XCD")) c->xcd_ranges = atoi(e) != 0;
-    if (const char* e = getenv("GSR_ICP_ROBUST_BOX")) c->robust_allowed = atoi(e) != 0;
     if (const char* e = getenv("GSR_ICP_BLOCKS")) { int v = atoi(e); if (v >= 1 && v <= 65536) c->nblocks = v; }
-    // pinned, device-mapped, COHERENT host memory: the device's system-scope stores must reach the host while the stream is still
-    // running (a non-coherent mapping would only show them at the end of the kernel).  GSR_ICP_RB_POLL=0: no polling at all
-    bool poll = true;
-    if (const char* e = getenv("GSR_ICP_RB_POLL")) poll = atoi(e) != 0;
-    if (!poll || c->host_rb.alloc(1024 + 64) != hipSuccess) (void)hipGetLastError();
     if (const char* e = getenv("GSR_ICP_NN_KERNEL")) c->nn_kernel = atoi(e);
-    if (const char* e = getenv("GSR_ICP_CELL_TARGET")) { double v = atof(e); if (v > 0.01 && v < 1000) c->cell_target = v; }
-    if (const char* e = getenv("GSR_ICP_MAX_CELLS")) { int v = atoi(e); if (v >= 1024) c->max_cells = v; }
     *out = c;
     return GSR_OK;
 }
@@ -1432,68 +1094,8 @@ int32_t gsr_icp_set_target(gsr_icp_ctx* c, const float* xyz, const double* norma
             dnrm = c->stage_nrm.as<double>();
         }
     }
-    // bounding box of the finite points
-    const int nbb = stride_grid(n);
-    GSR_TRY(c->bbox.reserve(64 + (size_t)nbb * 24));
-    hipLaunchKernelGGL(k_icp_bbox, dim3(nbb), dim3(256), 0, st, n, dxyz, c->bbox.as<float>() + 16);
-    hipLaunchKernelGGL(k_icp_bbox_reduce, dim3(1), dim3(256), 0, st, nbb, c->bbox.as<float>() + 16, c->bbox.as<float>());
-    // the robust candidate of the raw box: header floats [0..5] raw, [6..11] trimmed, [12] "the raw box is far too large"
-    GSR_TRY(c->hist.reserve(3 * ICP_HIST_BINS * 4));
-    GSR_HIP(hipMemsetAsync(c->hist.p, 0, 3 * ICP_HIST_BINS * 4, st));
-    hipLaunchKernelGGL(k_icp_hist, dim3(nbb > 512 ? 512 : nbb), dim3(256), 0, st, n, dxyz, c->bbox.as<float>(), c->hist.as<unsigned>());
-    hipLaunchKernelGGL(k_icp_trim, dim3(1), dim3(64), 0, st, c->hist.as<unsigned>(), c->bbox.as<float>(), c->bbox.as<float>() + 6, c->bbox.as<float>() + 12);
-    float hb[13];
-    GSR_TRY(icp_fetch(c, c->bbox.p, hb, 13 * 4));
-    const float raw_box[6] = {hb[0], hb[1], hb[2], hb[3], hb[4], hb[5]};
-    c->robust_box = hb[12] != 0.0f && c->robust_allowed;
-    if (c->robust_box) {        // far outliers: one refinement at the resolution of the trimmed range, then the grid goes over THAT
-        GSR_HIP(hipMemsetAsync(c->hist.p, 0, 3 * ICP_HIST_BINS * 4, st));
-        hipLaunchKernelGGL(k_icp_hist, dim3(nbb > 512 ? 512 : nbb), dim3(256), 0, st, n, dxyz, c->bbox.as<float>() + 6, c->hist.as<unsigned>());
-        hipLaunchKernelGGL(k_icp_trim, dim3(1), dim3(64), 0, st, c->hist.as<unsigned>(), c->bbox.as<float>() + 6, c->bbox.as<float>(), c->bbox.as<float>() + 12);
-        GSR_TRY(icp_fetch(c, c->bbox.p, hb, 6 * 4));
-    }
-    double mn[3], mx[3];
-    for (int k = 0; k < 3; ++k) { mn[k] = hb[k]; mx[k] = hb[3 + k]; }
-    IcpGrid g;
-    if (!(mx[0] >= mn[0])) { mn[0] = mn[1] = mn[2] = 0; mx[0] = mx[1] = mx[2] = 0; }
-    // cell: about two target points per cell, but no finer than max_corr/8 (bounds the ring count)
-    double cell;
-    {
-        const double ex = mx[0] - mn[0], ey = mx[1] - mn[1], ez = mx[2] - mn[2];
-        const double emax = fmax(ex, fmax(ey, ez)), eps = emax * 1e-6 + 1e-30;
-        cell = cbrt((ex + eps) * (ey + eps) * (ez + eps) * c->cell_target / (double)n);
-        if (!(cell > 0)) cell = max_corr;
-        // (round 6: max_corr / 64, was / 8.  The floor bounds the ring count of a query that finds nothing; with / 8 the reference's DEFAULT
-        // max_correspondence of 5 scene units put 450 points into every cell of a 1 M-splat cloud and an iteration took 4.9 ms instead of
-        // 0.15, scripts/icp_default_params.py.  A query beyond the target's box + max_corr leaves before the first ring, icp_nearest)
-        if (cell < max_corr / ICP_CELL_FLOOR_DIV) cell = max_corr / ICP_CELL_FLOOR_DIV;
-    }
-    GSR_TRY(c->keys.reserve(n * 4)); GSR_TRY(c->idx.reserve(n * 4)); GSR_TRY(c->skeys.reserve(n * 4)); GSR_TRY(c->order.reserve(n * 4));
-    for (;;) {
-        double fx = floor((mx[0] - mn[0]) / cell) + 1, fy = floor((mx[1] - mn[1]) / cell) + 1, fz = floor((mx[2] - mn[2]) / cell) + 1;
-        if (fx * fy * fz <= (double)c->max_cells) { g.gx = (int)fx; g.gy = (int)fy; g.gz = (int)fz; break; }
-        cell *= 1.2599210498948732;
-    }
-    g.ox = mn[0]; g.oy = mn[1]; g.oz = mn[2];
-    g.c = cell; g.inv_c = 1.0 / cell;
-    g.cx = 0.5 * (mn[0] + mx[0]); g.cy = 0.5 * (mn[1] + mx[1]); g.cz = 0.5 * (mn[2] + mx[2]);
-    g.ncells = g.gx * g.gy * g.gz;
-    g.rings = (int)ceil(max_corr / cell);
-    if (g.rings < 1) g.rings = 1;
-    g.bx0 = raw_box[0]; g.by0 = raw_box[1]; g.bz0 = raw_box[2]; g.bx1 = raw_box[3]; g.by1 = raw_box[4]; g.bz1 = raw_box[5];
-    if (!(raw_box[3] >= raw_box[0])) { g.bx0 = g.by0 = g.bz0 = -1.0 / 0.0; g.bx1 = g.by1 = g.bz1 = 1.0 / 0.0; }      // (no finite point: no box, no early leave)
-    hipLaunchKernelGGL(k_icp_keys, dim3(stride_grid(n)), dim3(256), 0, st, n, dxyz, g, c->keys.as<unsigned>(), c->idx.as<unsigned>());
-    int bits = 1;
-    while (bits < 32 && ((int64_t)1 << bits) < g.ncells) ++bits;
-    GSR_TRY(sort_pairs_by_key<icp_sort_cfg>(c->rocprim_tmp, st, c->keys.as<unsigned>(), c->skeys.as<unsigned>(), c->idx.as<unsigned>(),
-                                            c->order.as<unsigned>(), (size_t)n, 0u, (unsigned)bits));
-    GSR_TRY(c->cellStart.reserve(((size_t)g.ncells + 1) * 4));
-    hipLaunchKernelGGL(k_icp_cell_starts, dim3(stride_grid(n)), dim3(256), 0, st, n, c->skeys.as<unsigned>(), (int64_t)g.ncells, c->cellStart.as<int>());
-    c->grid = g;
-    GSR_TRY(c->Tq.reserve((size_t)n * 16));
     if (normals) GSR_TRY(c->Tn.reserve((size_t)n * 24));
-    hipLaunchKernelGGL(k_icp_gather_target, dim3(stride_grid(n)), dim3(256), 0, st, n, c->order.as<unsigned>(), dxyz, dnrm,
-                       c->Tq.as<float4>(), normals ? c->Tn.as<double>() : (double*)nullptr);
+    GSR_TRY(c->index.build(dxyz, n, max_corr, st, dnrm, c->Tn.as<double>()));
     GSR_HIP(hipEventRecord(c->eb1, st));
     if (c->defer_sync) c->build_pending = true;      // (gsr_icp_register_clouds: the registration behind this waits for the stream)
     else {
@@ -1501,7 +1103,6 @@ int32_t gsr_icp_set_target(gsr_icp_ctx* c, const float* xyz, const double* norma
         (void)hipEventElapsedTime(&c->ms_build, c->eb0, c->eb1);
         c->build_pending = false;
     }
-    GSR_HIP(hipGetLastError());                      // the launches of the index build
     c->nt = n; c->max_corr = max_corr; c->have_target = true; c->have_normals = normals != nullptr;
     c->have_tcov = false; c->have_scov = false; c->have_tcol = false; c->have_scol = false;
     c->have_source = false;              // the source is sorted by the target grid: set it again after a new target
@@ -1528,12 +1129,7 @@ int32_t gsr_icp_set_source(gsr_icp_ctx* c, const float* xyz, int64_t n, int32_t 
             GSR_HIP(hipMemcpyAsync(c->src_raw.p, xyz, (size_t)n * 12, hipMemcpyHostToDevice, st));
             raw = c->src_raw.as<float>();
         }
-        GSR_TRY(c->keys.reserve(n * 4)); GSR_TRY(c->idx.reserve(n * 4)); GSR_TRY(c->skeys.reserve(n * 4)); GSR_TRY(c->src_order.reserve(n * 4));
-        hipLaunchKernelGGL(k_icp_keys, dim3(stride_grid(n)), dim3(256), 0, st, n, raw, c->grid, c->keys.as<unsigned>(), c->idx.as<unsigned>());
-        int bits = 1;
-        while (bits < 32 && ((int64_t)1 << bits) < c->grid.ncells) ++bits;
-        GSR_TRY(sort_pairs_by_key<icp_sort_cfg>(c->rocprim_tmp, st, c->keys.as<unsigned>(), c->skeys.as<unsigned>(), c->idx.as<unsigned>(),
-                                                c->src_order.as<unsigned>(), (size_t)n, 0u, (unsigned)bits));
+        GSR_TRY(c->index.sort_by_cell(raw, n, c->src_order, st));
         hipLaunchKernelGGL(k_icp_gather_source, dim3(stride_grid(n)), dim3(256), 0, st, n, c->src_order.as<unsigned>(), raw, c->src.as<float>());
         c->src_sorted = true;
     } else {
@@ -1563,7 +1159,7 @@ static int32_t set_cov(gsr_icp_ctx* c, const double* cov6, int64_t n, const unsi
 int32_t gsr_icp_set_target_cov(gsr_icp_ctx* c, const double* cov6, int32_t on_device) {
     if (!c || !cov6) return fail(GSR_E_INVALID, "gsr_icp_set_target_cov: NULL argument");
     if (!c->have_target) return fail(GSR_E_PRECONDITION, "gsr_icp_set_target_cov: set the target first");
-    GSR_TRY(set_cov(c, cov6, c->nt, c->order.as<unsigned>(), c->Tc, on_device));
+    GSR_TRY(set_cov(c, cov6, c->nt, c->index.order.as<unsigned>(), c->Tc, on_device));
     c->have_tcov = true;
     return GSR_OK;
 }
@@ -1589,9 +1185,9 @@ int32_t gsr_icp_set_target_color(gsr_icp_ctx* c, const double* rgb, int32_t on_d
         in = c->stage_cov.as<double>();
     }
     GSR_TRY(c->Ti.reserve((size_t)n * 8)); GSR_TRY(c->Tg.reserve((size_t)n * 24));
-    hipLaunchKernelGGL(k_icp_intensity, dim3(stride_grid(n)), dim3(256), 0, st, n, c->order.as<unsigned>(), in, c->Ti.as<double>());
+    hipLaunchKernelGGL(k_icp_intensity, dim3(stride_grid(n)), dim3(256), 0, st, n, c->index.order.as<unsigned>(), in, c->Ti.as<double>());
     // InitializePointCloudForColoredICP: KDTreeSearchParamHybrid(max_distance * 2, 30)
-    hipLaunchKernelGGL(k_icp_color_gradient, dim3(stride_grid(n)), dim3(256), 0, st, n, c->grid, c->cellStart.as<int>(), c->Tq.as<float4>(),
+    hipLaunchKernelGGL(k_icp_color_gradient, dim3(stride_grid(n)), dim3(256), 0, st, n, c->index.grid, c->index.cellStart.as<int>(), c->index.Tq.as<float4>(),
                        c->Tn.as<double>(), c->Ti.as<double>(), c->max_corr * 2.0, c->Tg.as<double>());
     GSR_HIP(hipStreamSynchronize(st));
     c->have_tcol = true;
@@ -1631,7 +1227,7 @@ int32_t gsr_icp_get_color_gradient(gsr_icp_ctx* c, double* out) {
     std::vector<double> sorted((size_t)c->nt * 3);
     std::vector<unsigned> order((size_t)c->nt);
     GSR_HIP(hipMemcpy(sorted.data(), c->Tg.p, (size_t)c->nt * 24, hipMemcpyDeviceToHost));
-    GSR_HIP(hipMemcpy(order.data(), c->order.p, (size_t)c->nt * 4, hipMemcpyDeviceToHost));
+    GSR_HIP(hipMemcpy(order.data(), c->index.order.p, (size_t)c->nt * 4, hipMemcpyDeviceToHost));
     for (int64_t j = 0; j < c->nt; ++j)
         for (int a = 0; a < 3; ++a) out[3 * (size_t)order[j] + a] = sorted[3 * j + a];
     return GSR_OK;
@@ -1683,7 +1279,7 @@ int32_t gsr_icp_register(gsr_icp_ctx* c, const double* init_T, int32_t kind, int
         IcpState hs;
         memset(&hs, 0, sizeof(hs));
         memcpy(hs.T, init_T, sizeof(hs.T));
-        hs.ctr[0] = c->grid.cx; hs.ctr[1] = c->grid.cy; hs.ctr[2] = c->grid.cz;
+        hs.ctr[0] = c->index.grid.cx; hs.ctr[1] = c->index.grid.cy; hs.ctr[2] = c->index.grid.cz;
         hs.nsg = (double)(multi ? c->ns_global : c->ns); hs.rel_fit = rel_fitness; hs.rel_rmse = rel_rmse;
         hs.max_iter = max_iter < 0 ? 0 : max_iter; hs.kind = kind;
         GSR_TRY(c->state.reserve(sizeof(IcpState)));
@@ -1697,7 +1293,7 @@ int32_t gsr_icp_register(gsr_icp_ctx* c, const double* init_T, int32_t kind, int
         const ColorArgs cargs = {c->Ti.as<double>(), c->Tg.as<double>(), c->Si.as<double>(), sqrt(c->lambda_geometric), sqrt(1.0 - c->lambda_geometric)};
         const int total_evals = hs.max_iter + 1;
         // the first 27 cells of the search as one block of batched loads when max_corr spans two or more cells (icp_nearest)
-        const bool blockf = c->block_search && c->grid.rings >= 2;
+        const bool blockf = c->block_search && c->index.grid.rings >= 2;
         int issued = 0;
         GSR_HIP(hipEventRecord(c->e0, st));
         while (issued < total_evals) {
@@ -1721,7 +1317,7 @@ int32_t gsr_icp_register(gsr_icp_ctx* c, const double* init_T, int32_t kind, int
             }
             issued += chunk;
             GSR_HIP(hipGetLastError());              // a failed launch of the chunk (configuration, LDS) is reported here, not as a hang
-            GSR_TRY(icp_fetch(c, c->state.p, &hs, sizeof(hs)));
+            GSR_TRY(c->index.fetch(st, c->state.p, &hs, sizeof(hs)));
             if (hs.done) break;
         }
         GSR_HIP(hipEventRecord(c->e1, st));
@@ -1741,7 +1337,7 @@ int32_t gsr_icp_register(gsr_icp_ctx* c, const double* init_T, int32_t kind, int
     double fit = acc[0] > 0 ? acc[0] / nsg : 0.0, rmse = acc[0] > 0 ? sqrt(acc[1] / acc[0]) : 0.0;
     int it = 0;
     for (; it < max_iter; ++it) {
-        const double ctr[3] = {c->grid.cx, c->grid.cy, c->grid.cz};
+        const double ctr[3] = {c->index.grid.cx, c->index.grid.cy, c->index.grid.cz};
         estimate_update(ctr, kind, acc, update);
         mat4_mul(update, T, T);
         GSR_TRY(run_accumulate(c, T, kind, loss, k, acc, true));
@@ -1767,7 +1363,7 @@ int32_t gsr_icp_correspondences(gsr_icp_ctx* c, const double* T, int64_t* idx, d
     GSR_TRY(c->nn_j.reserve((size_t)c->ns * 4));
     launch_icp_nn<false>(c, c->stream, X, (const IcpState*)nullptr, c->max_corr * c->max_corr, false);
     hipLaunchKernelGGL(k_icp_correspond, dim3(stride_grid(c->ns)), dim3(256), 0, c->stream, c->ns, c->src.as<float>(), X, c->nn_j.as<int>(),
-                       c->Tq.as<float4>(), c->src_sorted ? c->src_order.as<unsigned>() : (const unsigned*)nullptr, c->corr_idx.as<int64_t>(),
+                       c->index.Tq.as<float4>(), c->src_sorted ? c->src_order.as<unsigned>() : (const unsigned*)nullptr, c->corr_idx.as<int64_t>(),
                        c->corr_d2.as<double>());
     GSR_HIP(hipMemcpyAsync(idx, c->corr_idx.p, (size_t)c->ns * 8, hipMemcpyDeviceToHost, c->stream));
     GSR_HIP(hipMemcpyAsync(d2, c->corr_d2.p, (size_t)c->ns * 8, hipMemcpyDeviceToHost, c->stream));
@@ -1798,7 +1394,7 @@ int32_t gsr_icp_information(gsr_icp_ctx* c, const double* T, double* info36, int
         launch_icp_nn<false>(c, st, X, (const IcpState*)nullptr, mc2, false);
         nnj = c->nn_j.as<int>();
     }
-    hipLaunchKernelGGL(k_icp_information, dim3(nb), dim3(256), 0, st, c->ns, c->src.as<float>(), X, c->grid, c->cellStart.as<int>(), nnj, c->Tq.as<float4>(),
+    hipLaunchKernelGGL(k_icp_information, dim3(nb), dim3(256), 0, st, c->ns, c->src.as<float>(), X, c->index.grid, c->index.cellStart.as<int>(), nnj, c->index.Tq.as<float4>(),
                        mc2, c->partials.as<double>());
     hipLaunchKernelGGL(k_icp_finalize, dim3(ICP_INFO_NACC), dim3(64), 0, st, nb, c->partials.as<double>(), c->acc_dev.as<double>());
     double a[ICP_INFO_NACC];
@@ -1831,7 +1427,7 @@ int32_t gsr_icp_solve(const double* acc, int32_t kind, const double* centre, dou
 
 int32_t gsr_icp_get_centre(gsr_icp_ctx* c, double* centre3) {
     if (!c || !centre3 || !c->have_target) return fail(GSR_E_INVALID, "gsr_icp_get_centre: no target set");
-    centre3[0] = c->grid.cx; centre3[1] = c->grid.cy; centre3[2] = c->grid.cz;
+    centre3[0] = c->index.grid.cx; centre3[1] = c->index.grid.cy; centre3[2] = c->index.grid.cz;
     return GSR_OK;
 }
 
@@ -1923,132 +1519,4 @@ int32_t gsr_cov_from_normals(const double* normals, int64_t n, double epsilon, d
     return os.finish();
 }
 
-int32_t gsr_normals_knn(const float* xyz, int64_t n, int32_t knn, double* normals, int32_t on_device, int32_t device, void* stream) {
-    if (n < 0 || (n > 0 && (!xyz || !normals))) return fail(GSR_E_INVALID, "gsr_normals_knn: bad argument");
-    if (knn < 1 || knn > ICP_KNN) return fail(GSR_E_INVALID, "gsr_normals_knn: knn must lie in [1, %d] (got %d)", ICP_KNN, knn);
-    if (n == 0) return GSR_OK;
-    GSR_TRY(open_device(device, "gsr_normals_knn"));
-    gsr_icp_ctx* c = nullptr;
-    GSR_TRY(gsr_icp_create(&c, device, stream));
-    // the grid of the ICP target index (about two points per cell); the correspondence distance plays no role here
-    int32_t r = gsr_icp_set_target(c, xyz, nullptr, n, 1e-300, on_device);
-    if (r == GSR_OK) {
-        OneShot os(c->stream, on_device != 0, "gsr_normals_knn");      // in this scope: it waits before the context's buffers are freed
-        double* out = nullptr;
-        r = os.out(normals, (size_t)n * 24, &out);
-        if (r == GSR_OK) {
-            hipLaunchKernelGGL(k_knn_normals, dim3(stride_grid(n)), dim3(256), 0, c->stream, n, c->grid, c->cellStart.as<int>(), c->Tq.as<float4>(),
-                               c->order.as<unsigned>(), (int)knn, out);
-            r = os.finish();
-        }
-    }
-    (void)gsr_icp_destroy(c);
-    return r;
-}
-
 }  // extern "C"
-
-// ---- hybrid radius / count search (FPFH neighbourhoods, csrc/features.hip) ------------------------------------------------
-// One wave per query point over the ICP target grid of the cloud itself: every cell within ceil(radius / cell) + 1 rings is read as
-// contiguous row spans, the lanes test d^2 <= radius^2 and append the hits to an LDS list by ballot.  When the list would overflow it
-// is cut to the max_nn best by rank (keys (d^2, index) are unique), and from then on only candidates ahead of the max_nn-th key are
-// taken.  At the end each entry's rank among the list is its slot: the output is sorted by (d^2, index) without a sort.
-namespace gsr {
-
-__global__ __launch_bounds__(64) void k_hybrid_search(int64_t n, IcpGrid g, const int* __restrict__ cellStart, const float4* __restrict__ Tq,
-                                                      double r2, int R, int max_nn, int* __restrict__ nbr, int* __restrict__ cnt_out) {
-    __shared__ double sd[GSR_HYBRID_CAP];
-    __shared__ unsigned si[GSR_HYBRID_CAP];
-    const int lane = threadIdx.x;
-    for (int64_t jq = blockIdx.x; jq < n; jq += gridDim.x) {
-        const float4 qv = Tq[jq];
-        const int64_t row = (int64_t)__float_as_uint(qv.w);          // input index of the query
-        const double px = (double)qv.x, py = (double)qv.y, pz = (double)qv.z;
-        int cnt = 0;
-        bool pruned = false;
-        double thr_d = 0.0;
-        unsigned thr_i = 0u;
-        if (px == px && py == py && pz == pz) {
-            const int cx = icp_cell(px, g.ox, g.inv_c, g.gx), cy = icp_cell(py, g.oy, g.inv_c, g.gy), cz = icp_cell(pz, g.oz, g.inv_c, g.gz);
-            const int z0 = cz - R > 0 ? cz - R : 0, z1 = cz + R < g.gz - 1 ? cz + R : g.gz - 1;
-            const int y0 = cy - R > 0 ? cy - R : 0, y1 = cy + R < g.gy - 1 ? cy + R : g.gy - 1;
-            const int x0 = cx - R > 0 ? cx - R : 0, x1 = cx + R < g.gx - 1 ? cx + R : g.gx - 1;
-            for (int z = z0; z <= z1; ++z)
-                for (int y = y0; y <= y1; ++y) {
-                    const int rowbase = (z * g.gy + y) * g.gx;
-                    const int s0 = cellStart[rowbase + x0], e0 = cellStart[rowbase + x1 + 1];
-                    for (int base = s0; base < e0; base += 64) {
-                        const int j = base + lane;
-                        double d2 = 0.0;
-                        unsigned qi = 0u;
-                        bool take = false;
-                        if (j < e0) {
-                            const float4 q = Tq[j];
-                            const double dx = px - (double)q.x, dy = py - (double)q.y, dz = pz - (double)q.z;
-                            d2 = dx * dx + dy * dy + dz * dz;
-                            qi = __float_as_uint(q.w);
-                            take = d2 <= r2 && (!pruned || hyb_less(d2, qi, thr_d, thr_i));
-                        }
-                        unsigned long long mask = __ballot(take);
-                        int nt = __popcll(mask);
-                        if (cnt + nt > GSR_HYBRID_CAP) {
-                            cnt = hyb_rank_cut(sd, si, cnt, max_nn, nullptr);
-                            pruned = true;
-                            thr_d = sd[max_nn - 1]; thr_i = si[max_nn - 1];
-                            take = take && hyb_less(d2, qi, thr_d, thr_i);
-                            mask = __ballot(take);
-                            nt = __popcll(mask);
-                        }
-                        if (take) {
-                            const int pos = cnt + __popcll(mask & ((1ull << lane) - 1ull));
-                            sd[pos] = d2; si[pos] = qi;
-                        }
-                        cnt += nt;
-                        __syncthreads();
-                    }
-                }
-        }
-        const int keep = cnt < max_nn ? cnt : max_nn;
-        hyb_rank_cut(sd, si, cnt, max_nn, nbr + row * max_nn);
-        if (lane == 0) cnt_out[row] = keep;
-        __syncthreads();
-    }
-}
-
-int32_t hybrid_search_dev(const float* xyz_dev, int64_t n, double radius, int max_nn, int device, hipStream_t stream, int* nbr_dev, int* cnt_dev) {
-    if (n <= 0) return GSR_OK;
-    gsr_icp_ctx* c = nullptr;
-    GSR_TRY(gsr_icp_create(&c, device, stream));
-    int32_t r = gsr_icp_set_target(c, xyz_dev, nullptr, n, radius, 1);       // grid: about two points per cell, no finer than radius / 64
-    if (r == GSR_OK) {
-        const IcpGrid g = c->grid;
-        const double rc = ceil(radius * g.inv_c) + 1.0;                     // +1: a cell index rounded across a boundary
-        const int R = rc > (double)(1 << 20) ? (1 << 20) : (int)rc;
-        const int blocks = n < 16384 ? (int)n : 16384;
-        hipLaunchKernelGGL(k_hybrid_search, dim3(blocks), dim3(64), 0, c->stream, n, g, c->cellStart.as<int>(), c->Tq.as<float4>(), radius * radius, R,
-                           max_nn, nbr_dev, cnt_dev);
-        hipError_t e = hipGetLastError();
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) r = fail(GSR_E_HIP, "hybrid search: %s", hipGetErrorString(e));
-    }
-    (void)gsr_icp_destroy(c);
-    return r;
-}
-
-int32_t grid_borrow(const float* xyz_dev, int64_t n, double max_corr, int device, hipStream_t stream, gsr_icp_ctx** ctx, GridView* view) {
-    *ctx = nullptr;
-    gsr_icp_ctx* c = nullptr;
-    GSR_TRY(gsr_icp_create(&c, device, stream));
-    *ctx = c;                         // the caller destroys it, also after a failure below
-    c->defer_sync = true;             // the borrower waits for the stream
-    GSR_TRY(gsr_icp_set_target(c, xyz_dev, nullptr, n, max_corr, 1));
-    view->g = c->grid;
-    view->cellStart = c->cellStart.as<int>();
-    view->Tq = c->Tq.as<float4>();
-    view->n = n;
-    view->bytes = 0;
-    for (const DevBuf* b : {&c->bbox, &c->hist, &c->keys, &c->idx, &c->skeys, &c->order, &c->cellStart, &c->Tq, &c->rocprim_tmp}) view->bytes += b->cap;
-    return GSR_OK;
-}
-
-}  // namespace gsr

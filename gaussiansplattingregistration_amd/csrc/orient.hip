@@ -25,12 +25,6 @@ enum { ORIENT_CTR_FLIPPED = 0, ORIENT_CTR_ROOTS, ORIENT_CTR_NOT_LIVE, ORIENT_CTR
     for (int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, base_ = (int64_t)blockIdx.x * blockDim.x; base_ < n; \
          base_ += (int64_t)gridDim.x * blockDim.x, v += (int64_t)gridDim.x * blockDim.x)
 
-// one add per wave of the lanes with `pred`
-__device__ __forceinline__ void wave_count(bool pred, int* ctr) {
-    const unsigned long long m = __ballot(pred);
-    if (m && (threadIdx.x & 63) == 0) atomicAdd(ctr, __popcll(m));
-}
-
 __global__ __launch_bounds__(256) void k_orient_init(int64_t n, const double* __restrict__ nrm, uint8_t* __restrict__ live, uint32_t* __restrict__ par,
                                                      int* __restrict__ deg, int* __restrict__ cursor) {
     ORIENT_FOR_EACH_VERTEX(v) orient_init_vertex(v, nrm, live, par, deg, cursor);

@@ -11,8 +11,8 @@ per phase by the library's device events (pre-pass + grid, k-NN + moments, radiu
 warm-up call), the wall clock of the mask call and of the selection, deferred_queries, n_kept, and the algorithmic bytes -- 16 B read
 and 1 B written per row for the mask, every kept row read once and written once for the selection (232 B per row at degree 3 with
 scaling / rotation) -- as a fraction of 8.0 TB/s over the time they took.  Yardstick of the k-NN kernel: gsr_normals_knn(knn = 20), the
-library's other k-NN over a whole cloud, on the same 1 M clean cloud in the same run (wall clock of the call on device tensors, which
-like the mask call includes the grid build); the ratio is knn_phase_and_grid_ms / normals_knn_ms.  Yardstick of the floater rows: the 0 %
+library's other k-NN over a whole cloud (the same grid_ring_walk over a GridIndex of its own), on the same 1 M clean cloud in the same
+run (wall clock of the call on device tensors, which like the mask call includes the grid build); the ratio is knn_phase_and_grid_ms / normals_knn_ms.  Yardstick of the floater rows: the 0 %
 row of the same table.  A row whose warm-up call takes longer than --row-limit-s is recorded with that one time and not repeated, and
 larger sizes of the same fraction are skipped (recorded as skipped).  No threshold: this records what is seen.
 """
