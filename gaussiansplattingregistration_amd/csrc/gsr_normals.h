@@ -61,11 +61,14 @@ static __device__ void eigvec1_d(const double A[3][3], const double e0[3], doubl
     }
 }
 // normal of a covariance: eigenvector of its smallest eigenvalue (Open3D ComputeNormal with FastEigen3x3), (0, 0, 1) when
-// that comes out as the zero vector or NaN
+// that comes out as the zero vector or NaN, and for a covariance with any entry that is not finite (fmax drops a NaN, so
+// without the test a NaN off the diagonal would reach the diagonal branch below and leave as a confident axis normal)
 static __device__ void normal_of_cov_d(double c00, double c01, double c02, double c11, double c12, double c22, double v[3]) {
     v[0] = v[1] = v[2] = 0;
+    // x - x is 0 for a finite x and NaN for NaN and +-Inf
+    const bool finite = (c00 - c00) + (c01 - c01) + (c02 - c02) + (c11 - c11) + (c12 - c12) + (c22 - c22) == 0.0;
     double mx = fmax(fmax(fmax(c00, c01), fmax(c02, c11)), fmax(c12, c22));
-    if (mx != 0 && mx == mx) {
+    if (finite && mx != 0) {
         double A[3][3] = {{c00 / mx, c01 / mx, c02 / mx}, {c01 / mx, c11 / mx, c12 / mx}, {c02 / mx, c12 / mx, c22 / mx}};
         const double norm = A[0][1] * A[0][1] + A[0][2] * A[0][2] + A[1][2] * A[1][2];
         if (norm > 0) {

@@ -18,6 +18,8 @@
 //       version unused): scaling = log of the standard deviations (0.5 log lambda_k, lambda clamped at 1e-30), rotation =
 //       the proper rotation [v_0 v_1 v_2] (third column flipped if the determinant is negative) as a unit quaternion by
 //       Shepperd's branch on the largest diagonal term, so that R diag(exp(scaling))^2 R^T reproduces the covariance.
+//       A covariance with a NaN or infinite entry leaves as NaN in all three outputs (REFERENCE mode keeps the reference's
+//       undefined behaviour there).
 //
 // Sign convention of the eigenvectors (torch.linalg.eigh leaves it to the LAPACK / rocSOLVER build): the component of
 // largest magnitude of every eigenvector is positive (first maximum on ties).  Everything the reference path derives from
@@ -127,6 +129,14 @@ __global__ __launch_bounds__(256) void k_decompose_cov(int64_t n, const float* _
             const double nq = sqrt(w * w + x * x + y * y + z * z);
             if (w < 0.0) { w = -w; x = -x; y = -y; z = -z; }
             q[0] = (float)(w / nq); q[1] = (float)(x / nq); q[2] = (float)(y / nq); q[3] = (float)(z / nq);
+            // a covariance with an entry that is not finite has no decomposition: the whole row leaves as NaN, not as the
+            // plausible (V = I, lambda = diagonal) the broken-off Jacobi loop would hand on (x - x is NaN for NaN and +-Inf)
+            if (!((c00 - c00) + (c01 - c01) + (c02 - c02) + (c11 - c11) + (c12 - c12) + (c22 - c22) == 0.0)) {
+                const float nan = __builtin_nanf("");
+                for (int k = 0; k < 3; ++k) sc[k] = nan;
+                for (int k = 0; k < 4; ++k) q[k] = nan;
+                for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) M[r][c] = nan;
+            }
         }
         scaling[3 * i] = sc[0]; scaling[3 * i + 1] = sc[1]; scaling[3 * i + 2] = sc[2];
         quat[4 * i] = q[0]; quat[4 * i + 1] = q[1]; quat[4 * i + 2] = q[2]; quat[4 * i + 3] = q[3];

@@ -395,7 +395,8 @@ int32_t gsr_icp_get_timing(gsr_icp_ctx* ctx, float* out3);
 
 /* Normals = unit eigenvector of the smallest eigenvalue of each 3x3 splat covariance, computed in
  * float64 from the float32 covariance widened to float64 (as Open3D does on the converted cloud);
- * a zero vector becomes (0,0,1).  cov6[n*6] float32 in, normals[n*3] float64 out. */
+ * a zero vector becomes (0,0,1), and so does the normal of a covariance with a NaN or infinite entry.
+ * cov6[n*6] float32 in, normals[n*3] float64 out. */
 int32_t gsr_normals_from_cov(const float* cov6, int64_t n, double* normals, int32_t on_device,
                              int32_t device, void* stream);
 
@@ -435,6 +436,8 @@ int32_t gsr_cov_from_normals(const double* normals, int64_t n, double epsilon, d
  *                         eigenvector matrix (csrc/model.hip spells it out).
  *   GSR_DECOMP_EXACT      scaling = log standard deviations, rotation = unit quaternion of a proper rotation, such that
  *                         R diag(exp(scaling))^2 R^T reproduces the covariance (what save_ply of a level needs).
+ *                         Eigenvalues are clamped at 1e-30; a covariance with a NaN or infinite entry leaves as NaN in
+ *                         scaling, rotation and matrix.
  * cov6[n*6] (xx,xy,xz,yy,yz,zz), scaling[n*3], rotation[n*4], matrix[n*9] or NULL (the 3x3 the quaternion was taken from,
  * row-major); float32, all host or all device as on_device says. */
 #define GSR_DECOMP_REFERENCE 0

@@ -830,14 +830,20 @@ void fast_eigen_min(const double C[3][3], double out[3]) {
         else out[2] = 1;
     }
 }
+// a covariance with an entry that is not finite has no normal: std::max drops a NaN, so fast_eigen_min would scale by a finite
+// maximum, see norm = NaN fail norm > 0, and answer a confident axis from its diagonal branch.  Such a row gets the fallback (0, 0, 1).
+bool all_finite(const double C[3][3]) {
+    for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) if (!std::isfinite(C[i][j])) return false;
+    return true;
+}
 }  // namespace
 
 void gsr_oracle_normals_from_cov(const double* cov3x3, int64_t n, double* out) {
     for (int64_t i = 0; i < n; ++i) {
         double C[3][3];
         std::memcpy(C, cov3x3 + 9 * i, sizeof(C));
-        double v[3];
-        fast_eigen_min(C, v);
+        double v[3] = {0, 0, 0};
+        if (all_finite(C)) fast_eigen_min(C, v);
         double nn = std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
         if (nn == 0.0 || nn != nn) { v[0] = 0; v[1] = 0; v[2] = 1; }
         out[3 * i] = v[0]; out[3 * i + 1] = v[1]; out[3 * i + 2] = v[2];
@@ -875,8 +881,8 @@ void gsr_oracle_normals_knn(const double* pts_, int64_t n, int32_t knn, int32_t 
             C[0][0] = c[3] - c[0] * c[0]; C[1][1] = c[6] - c[1] * c[1]; C[2][2] = c[8] - c[2] * c[2];
             C[0][1] = C[1][0] = c[4] - c[0] * c[1]; C[0][2] = C[2][0] = c[5] - c[0] * c[2]; C[1][2] = C[2][1] = c[7] - c[1] * c[2];
         }
-        double v[3];
-        fast_eigen_min(C, v);
+        double v[3] = {0, 0, 0};
+        if (all_finite(C)) fast_eigen_min(C, v);
         const double nn = std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
         if (nn == 0.0 || nn != nn) { v[0] = 0; v[1] = 0; v[2] = 1; }
         out[3 * i] = v[0]; out[3 * i + 1] = v[1]; out[3 * i + 2] = v[2];

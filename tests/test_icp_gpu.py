@@ -33,7 +33,14 @@ def test_gpu_vs_oracle_100k(oracle, kind, loss, k):
     from gaussiansplattingregistration_amd import icp, synth
     src, tgt, T_gt = synth.make_pair(100000, seed=5, sh_degree=0, angle_deg=2.0)
     nrm = icp.normals_from_cov(tgt["cov6"])
-    assert np.abs(np.abs((nrm * oracle.normals_from_cov(_cov3(tgt["cov6"]))).sum(1)) - 1).max() < 1e-9
+    want_nrm = oracle.normals_from_cov(_cov3(tgt["cov6"]))
+    assert np.abs(np.abs((nrm * want_nrm).sum(1)) - 1).max() < 1e-9
+    # |<got, want>| - 1 is quadratic in the angle: as vectors, up to sign, where the smallest eigenvalue has an eigenvector of its own
+    # (a few rows of this cloud have their two smallest eigenvalues 1e-5 max|lambda| apart; tests/test_eig3_gpu.py is about those)
+    lam = np.linalg.eigvalsh(_cov3(tgt["cov6"]))
+    decided = (lam[:, 1] - lam[:, 0]) >= 1e-2 * np.abs(lam).max(1)
+    assert decided.mean() > 0.9
+    assert np.minimum(np.abs(nrm - want_nrm).max(1), np.abs(nrm + want_nrm).max(1))[decided].max() < 1e-9
     init = np.eye(4)
     init[:3, 3] = [0.01, -0.02, 0.005]
     w = oracle.icp(src["xyz"], tgt["xyz"], nrm, init, kind=kind, loss=loss, k=k, max_corr=0.2, max_iter=15)
