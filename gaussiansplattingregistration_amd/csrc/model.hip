@@ -693,7 +693,8 @@ __global__ __launch_bounds__(256) void k_ply_unpack(int64_t n, const unsigned ch
 
 extern "C" int32_t gsr_ply_unpack(const void* rows_dev, int64_t n, int32_t row_bytes, const int32_t* offsets, int32_t K, float* xyz, float* color,
                                   float* sh, float* opacity, float* scale, float* rot, float* cov6, int32_t device, void* stream) {
-    if (n < 0 || K < 0 || row_bytes <= 0 || !offsets || (n > 0 && (!rows_dev || !xyz || !color || !opacity || !scale || !rot || !cov6 || (K > 0 && !sh))))
+    if (n < 0 || K < 0 || K > 1024 || row_bytes <= 0 || !offsets ||
+        (n > 0 && (!rows_dev || !xyz || !color || !opacity || !scale || !rot || !cov6 || (K > 0 && !sh))))
         return fail(GSR_E_INVALID, "gsr_ply_unpack: bad argument");
     GSR_TRY(open_device(device, "gsr_ply_unpack"));
     PlyLayout L;
@@ -702,8 +703,8 @@ extern "C" int32_t gsr_ply_unpack(const void* rows_dev, int64_t n, int32_t row_b
     L.opacity = offsets[6];
     for (int i = 0; i < 4; ++i) L.rot[i] = offsets[10 + i];
     L.rest0 = offsets[14];
-    for (int i = 0; i < 15; ++i)
-        if (offsets[i] < 0 || offsets[i] + (i == 14 ? 12 * K : 4) > row_bytes) {
+    for (int i = 0; i < 15; ++i)       // in 64 bits: an offset near INT32_MAX plus its extent must not wrap and pass
+        if (offsets[i] < 0 || (int64_t)offsets[i] + (i == 14 ? 12 * (int64_t)K : 4) > (int64_t)row_bytes) {
             if (i == 14 && K == 0) continue;
             return fail(GSR_E_INVALID, "gsr_ply_unpack: property offset %d outside the %d-byte row", offsets[i], row_bytes);
         }

@@ -184,15 +184,12 @@ int32_t gsr_voxel_fetch(gsr_voxel_result* r, double* xyz, double* cov6, double* 
     GSR_HIP(hipSetDevice(r->device));
     const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
     if (r->V > 0) {
+        // refused before anything is copied: no copy into the caller's arrays is under way when an error returns
+        if (cov6 && !r->has_cov) return fail(GSR_E_PRECONDITION, "gsr_voxel_fetch: the input had no covariances");
+        if (color && !r->has_color) return fail(GSR_E_PRECONDITION, "gsr_voxel_fetch: the input had no colours");
         if (xyz) GSR_HIP(hipMemcpyAsync(xyz, r->xyz.p, (size_t)r->V * 24, kind, r->stream));
-        if (cov6) {
-            if (!r->has_cov) return fail(GSR_E_PRECONDITION, "gsr_voxel_fetch: the input had no covariances");
-            GSR_HIP(hipMemcpyAsync(cov6, r->cov6.p, (size_t)r->V * 48, kind, r->stream));
-        }
-        if (color) {
-            if (!r->has_color) return fail(GSR_E_PRECONDITION, "gsr_voxel_fetch: the input had no colours");
-            GSR_HIP(hipMemcpyAsync(color, r->color.p, (size_t)r->V * 24, kind, r->stream));
-        }
+        if (cov6) GSR_HIP(hipMemcpyAsync(cov6, r->cov6.p, (size_t)r->V * 48, kind, r->stream));
+        if (color) GSR_HIP(hipMemcpyAsync(color, r->color.p, (size_t)r->V * 24, kind, r->stream));
         GSR_HIP(hipStreamSynchronize(r->stream));
     }
     return GSR_OK;

@@ -41,6 +41,8 @@ def _read_header(f, path):
         elif tok[0] == "property" and in_vertex:
             if tok[1] == "list":
                 raise ValueError(f"{path}: list properties in the vertex element are not supported")
+            if len(tok) < 3 or tok[1] not in _PLY_TYPES:
+                raise ValueError(f"{path}: unknown ply property type {tok[1] if len(tok) > 1 else ''!r} in {' '.join(tok)!r}")
             props.append((tok[2], _PLY_TYPES[tok[1]]))
         elif tok[0] == "end_header":
             break
@@ -109,6 +111,35 @@ def load_gaussian_arrays(path) -> dict:
             "cov6": cov6, "scale": scale, "rot": rot, "sh_degree": sh_degree}
 
 
+_DEVICE_NEED = ("x", "y", "z", "f_dc_0", "f_dc_1", "f_dc_2", "opacity", "scale_0", "scale_1", "scale_2", "rot_0", "rot_1", "rot_2", "rot_3")
+
+
+def _device_layout(fmt, props, vertex_first=True, path="ply"):
+    """What ``gsr_ply_unpack`` needs to know of a header ``_read_header`` parsed -> ``(row_bytes, offsets, K)``: the size of a vertex
+    row, the 15 byte offsets inside it of ``x y z f_dc_0..2 opacity scale_0..2 rot_0..3 f_rest_0`` (the last one 0 when there is no
+    ``f_rest``) and the SH-rest coefficients per channel.  ``ValueError`` for what the device loader does not read: anything but binary
+    little endian with the vertex element first, a wanted property that is missing or not float32, ``f_rest_*`` that are not
+    ``3 ((d + 1)^2 - 1)`` consecutive float32.  Pure: no file, no device."""
+    if fmt != "binary_little_endian" or not vertex_first:
+        raise ValueError(f"{path}: the device loader reads binary little-endian files with the vertex element first")
+    off, pos = {}, 0
+    for name, t in props:
+        off[name] = (pos, t)
+        pos += np.dtype(t).itemsize
+    for k in _DEVICE_NEED:
+        if k not in off:
+            raise ValueError(f"{path}: not a Gaussian-splat ply (missing property {k})")
+        if off[k][1] != "f4":
+            raise ValueError(f"{path}: property {k} is not float32")
+    rest = sorted([k for k in off if k.startswith("f_rest_")], key=lambda q: int(q.split("_")[-1]))
+    K3 = len(rest)
+    sh_degree = int(round(((K3 + 3) / 3) ** 0.5 - 1))
+    K = (sh_degree + 1) ** 2 - 1
+    if 3 * K != K3 or any(off[k] != (off[rest[0]][0] + 4 * i, "f4") for i, k in enumerate(rest)):
+        raise ValueError(f"{path}: f_rest_* must be {3 * K} consecutive float32 properties")
+    return pos, [off[k][0] for k in _DEVICE_NEED] + [off[rest[0]][0] if K3 else 0], K
+
+
 def load_gaussian_device(path, device=0, chunk_rows: int = 1 << 18, timing: dict | None = None) -> dict:
     """``GaussianModel.from_ply`` straight into device SoA (the reference reads a ``.ply`` onto ``cuda:0``, ``file_loader.py:53-66``,
     ``gaussian_model.py:98-139``): the file's vertex rows are read in chunks into two PINNED host buffers, copied to HBM with
@@ -125,26 +156,9 @@ def load_gaussian_device(path, device=0, chunk_rows: int = 1 << 18, timing: dict
     t0 = time.perf_counter()
     with open(path, "rb") as f:
         fmt, n, props, vertex_first = _read_header(f, path)
-        if fmt != "binary_little_endian" or not vertex_first:
-            raise ValueError(f"{path}: the device loader reads binary little-endian files with the vertex element first")
-        off, pos = {}, 0
-        for name, t in props:
-            off[name] = (pos, t)
-            pos += np.dtype(t).itemsize
-        row_bytes = pos
-        need = ["x", "y", "z", "f_dc_0", "f_dc_1", "f_dc_2", "opacity", "scale_0", "scale_1", "scale_2", "rot_0", "rot_1", "rot_2", "rot_3"]
-        for k in need:
-            if k not in off:
-                raise ValueError(f"{path}: not a Gaussian-splat ply (missing property {k})")
-            if off[k][1] != "f4":
-                raise ValueError(f"{path}: property {k} is not float32")
-        rest = sorted([k for k in off if k.startswith("f_rest_")], key=lambda q: int(q.split("_")[-1]))
-        K3 = len(rest)
-        sh_degree = int(round(((K3 + 3) / 3) ** 0.5 - 1))
-        K = (sh_degree + 1) ** 2 - 1
-        if 3 * K != K3 or any(off[k] != (off[rest[0]][0] + 4 * i, "f4") for i, k in enumerate(rest)):
-            raise ValueError(f"{path}: f_rest_* must be {3 * K} consecutive float32 properties")
-        offsets = (C.c_int32 * 15)(*([off[k][0] for k in need] + [off[rest[0]][0] if K3 else 0]))
+        row_bytes, offsets, K = _device_layout(fmt, props, vertex_first, path)
+        sh_degree = int(round((K + 1) ** 0.5 - 1))
+        offsets = (C.c_int32 * 15)(*offsets)
         dev = torch.device("cuda", int(device))
         out = {"xyz": torch.empty((n, 3), dtype=torch.float32, device=dev), "color": torch.empty((n, 3), dtype=torch.float32, device=dev),
                "sh": torch.empty((n, 3 * K), dtype=torch.float32, device=dev), "opacity": torch.empty((n,), dtype=torch.float32, device=dev),

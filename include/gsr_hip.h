@@ -450,7 +450,9 @@ int32_t gsr_decompose_cov(const float* cov6, int64_t n, int32_t mode, float* sca
  * src/utils/general_utils.py:43-80).  rows_dev: n rows of row_bytes bytes as they are in the file (binary little endian), already in
  * HBM -- the host reads the file in chunks into pinned memory and copies them asynchronously; offsets[15] = byte offsets inside a
  * row of  x y z  f_dc_0..2  opacity  scale_0..2  rot_0..3  f_rest_0  (float32 properties; f_rest_0 .. f_rest_(3K-1) consecutive);
- * K = SH-rest coefficients per channel.  Outputs (device, float32): xyz[n*3], color[n*3] (SH DC), sh[n*3K] coefficient-major
+ * K = SH-rest coefficients per channel, 0 <= K <= 1024 (the bound of gsr_ply_pack).  Every offset must satisfy 0 <= offset and
+ * offset + 4 <= row_bytes (offset + 12 K <= row_bytes for f_rest_0; that entry is ignored when K = 0), checked in 64-bit arithmetic
+ * before anything is launched: GSR_E_INVALID otherwise.  Outputs (device, float32): xyz[n*3], color[n*3] (SH DC), sh[n*3K] coefficient-major
  * (the file is channel-major), opacity[n] (raw), scale[n*3] (log), rot[n*4] (w,x,y,z as stored), cov6[n*6] = R diag(exp(scale))^2 R^T.
  * Enqueued on `stream`; does not synchronise. */
 int32_t gsr_ply_unpack(const void* rows_dev, int64_t n, int32_t row_bytes, const int32_t* offsets, int32_t K, float* xyz, float* color,
