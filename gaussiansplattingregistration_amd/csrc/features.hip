@@ -24,11 +24,13 @@
 namespace gsr {
 
 // ---- FPFH --------------------------------------------------------------------------------------------------------------------
-// Open3D 0.16 ComputePairFeatures (Feature.cpp): (phi, alpha, theta) of the Darboux frame, in float64.  Returns false for the zero
-// vector (coincident points or v_norm == 0).
+// Open3D 0.16 ComputePairFeatures (Feature.cpp): (phi, alpha, theta) of the Darboux frame, in float64.  Returns false, with
+// f = (0, 0, 0) written on both paths, for the zero vector: coincident points (len == 0) or p2 - p1 parallel to the frame normal
+// (v_norm == 0; theta, stored before that test, is cleared again).
 __device__ __forceinline__ bool pair_features(const double p1[3], const double n1[3], const double p2[3], const double n2[3], double f[3]) {
     double dp[3] = {p2[0] - p1[0], p2[1] - p1[1], p2[2] - p1[2]};
     const double len = sqrt(dp[0] * dp[0] + dp[1] * dp[1] + dp[2] * dp[2]);
+    f[0] = 0.0; f[1] = 0.0; f[2] = 0.0;
     if (len == 0.0) return false;
     double a[3] = {n1[0], n1[1], n1[2]}, b[3] = {n2[0], n2[1], n2[2]};
     const double angle1 = (a[0] * dp[0] + a[1] * dp[1] + a[2] * dp[2]) / len;
@@ -41,7 +43,7 @@ __device__ __forceinline__ bool pair_features(const double p1[3], const double n
     }
     double v[3] = {dp[1] * a[2] - dp[2] * a[1], dp[2] * a[0] - dp[0] * a[2], dp[0] * a[1] - dp[1] * a[0]};
     const double vn = sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
-    if (vn == 0.0) return false;
+    if (vn == 0.0) { f[2] = 0.0; return false; }
     v[0] /= vn; v[1] /= vn; v[2] /= vn;
     const double w[3] = {a[1] * v[2] - a[2] * v[1], a[2] * v[0] - a[0] * v[2], a[0] * v[1] - a[1] * v[0]};
     f[1] = v[0] * b[0] + v[1] * b[1] + v[2] * b[2];

@@ -125,6 +125,24 @@ def spfh_fpfh(xyz, normals, radius, max_nn, nbrs=None):
     return spfh, fpfh
 
 
+def _near_edge_rows(xyz, nrm, nbrs, tol=1e-9):
+    """Rows whose FPFH may move by one SPFH increment between two correct implementations: the point itself or one of its neighbours has
+    a pair feature within `tol` of a bin edge (or phi = +-pi, where atan2's sign of zero decides between bins 0 and 10)."""
+    P = xyz.astype(np.float64)
+    rows = np.concatenate([np.full(max(len(x) - 1, 0), i) for i, x in enumerate(nbrs)]).astype(np.int64)
+    cols = np.concatenate([x[1:] for x in nbrs]).astype(np.int64)
+    f = pair_features(P[rows], nrm[rows], P[cols], nrm[cols])
+    u = np.stack([11 * (f[:, 0] + np.pi) / (2 * np.pi), 11 * (f[:, 1] + 1.0) * 0.5, 11 * (f[:, 2] + 1.0) * 0.5], 1)
+    near = np.any(np.abs(u - np.round(u)) < tol * 11, axis=1) | (np.abs(np.abs(f[:, 0]) - np.pi) < tol)
+    bad_spfh = np.zeros(len(xyz), bool)
+    bad_spfh[rows[near]] = True
+    out = bad_spfh.copy()
+    for i, x in enumerate(nbrs):
+        if bad_spfh[x].any():
+            out[i] = True
+    return out
+
+
 # ---------------------------------------------------------------------------------------------------------------- matching
 def nn_rows(a, b, chunk=256):
     """Exact 1-NN of every row of a among the rows of b: d = sum_j (a_j - b_j)^2 in j order, float64, first minimum."""
@@ -188,8 +206,10 @@ EDGE, DIST, NORMAL = 0, 1, 2
 
 
 def ransac(src_xyz, tgt_xyz, corres, max_corr, kind=0, ransac_n=3, checkers=(), max_iteration=1000, confidence=0.999, seed=0,
-           src_normals=None, tgt_normals=None, batch=1024):
-    """Serial Open3D rule (include/gsr_hip.h), evaluated in batches only for speed.  Returns the same dict as features.py."""
+           src_normals=None, tgt_normals=None, batch=1024, probe=None):
+    """Serial Open3D rule (include/gsr_hip.h), evaluated in batches only for speed.  Returns the same dict as features.py.
+    `probe` (a dict) receives "min_gap": the smallest |d2 - max_corr^2| over every correspondence of every valid hypothesis the
+    rule looked at, i.e. how close any inlier decision came to the threshold."""
     P = np.asarray(src_xyz, np.float32).astype(np.float64)[corres[:, 0]]
     Q = np.asarray(tgt_xyz, np.float32).astype(np.float64)[corres[:, 1]]
     have_n = src_normals is not None and tgt_normals is not None
@@ -251,6 +271,8 @@ def ransac(src_xyz, tgt_xyz, corres, max_corr, kind=0, ransac_n=3, checkers=(), 
                 break
             if ok[t]:
                 nvalid += 1
+                if probe is not None:
+                    probe["min_gap"] = min(probe.get("min_gap", math.inf), float(np.abs(d2[t] - mc2).min()))
                 f = good[t] / m
                 r = math.sqrt(sd2[t] / good[t]) if good[t] > 0 else 0.0
                 if f > bf or (f == bf and r < br):
@@ -363,6 +385,21 @@ def transform_scene(sc, T):
     if "frames" in sc:
         out["frames"] = R[None] @ sc["frames"]
     return out
+
+
+def _ransac_case(m=800, inlier=0.4, seed=5, curved=False, T=None):
+    sc = make_scene(4000, seed)
+    T = make_T() if T is None else T
+    src = sc["xyz"]
+    tgt = (src.astype(np.float64) @ T[:3, :3].T + T[:3, 3]).astype(np.float32)
+    rng = np.random.default_rng(seed)
+    # curved: rows from the cylinder and the sphere (the last 28 % of the scene), where six rows give a well-posed 6 x 6 system
+    lo = int(len(src) * 0.72) if curved else 0
+    i = lo + rng.choice(len(src) - lo, m, replace=False)
+    j = i.copy()
+    bad = rng.random(m) > inlier
+    j[bad] = rng.integers(0, len(src), bad.sum())
+    return src, tgt, sc["normals"], sc["normals"] @ T[:3, :3].T, np.stack([i, j], 1).astype(np.int32), T
 
 
 def quat_of(Rm):

@@ -1,11 +1,14 @@
 """Global registration without a GPU: the C ABI of the new entry points, the RANSAC sampler of the library against the NumPy
-restatement (tests/global_model.py), and sanity of the restatement itself."""
+restatement (tests/global_model.py), sanity of the restatement itself, and the proof that the restatement decides every edge-shape
+input (tests/global_edge_cases.py) that tests/test_global_edges_gpu.py puts to the kernels."""
 import ctypes as C
 import os
 import re
 
 import numpy as np
+import pytest
 
+import global_edge_cases as E
 import global_model as G
 from conftest import ROOT
 
@@ -91,3 +94,115 @@ def test_serial_ransac_recovers_T_gt():
         args.update(kw)
         e = G.ransac(src, tgt, corres[:10], args["max_corr"], ransac_n=args["ransac_n"])
         assert e["best_index"] == -1 and np.array_equal(e["transformation"], np.eye(4)) and e["fitness"] == 0.0
+
+
+# ---- the edge-shape inputs of tests/test_global_edges_gpu.py: the restatement decides each one before a GPU sees it -----------
+def test_two_point_parallel_pair_known_answer():
+    """Two points (0, 0, 0) and (0, 0, 1), both normals (0, 0, 1), radius 2, max_nn 10, by hand and without the restatement:
+    each point has k = 2 neighbours (itself and the other), hence one pair, and that pair's p2 - p1 is parallel to the frame normal:
+    v = dp x n = 0, so the pair feature is Open3D's zero vector, which falls into bin 5 of each third (11 * (0 + pi) / 2 pi = 11 *
+    (0 + 1) / 2 = 5.5).  With one pair the increment is 100 / (k - 1) = 100: SPFH = 100 in bins 5, 16 and 27.  d2 = 1, so the
+    neighbour's SPFH enters with weight 1, each third sums to 100 and its scale is 100 / 100 = 1: FPFH = 100 * 1 + SPFH = 200 in
+    bins 5, 16 and 27 and 0 elsewhere, for both rows, exactly in float64."""
+    spfh, fpfh = G.spfh_fpfh(*E.TWO_POINTS)
+    assert np.array_equal(spfh, E.TWO_POINTS_FPFH / 2) and np.array_equal(fpfh, E.TWO_POINTS_FPFH)
+
+
+def test_small_clouds_are_those_of_the_grid_tests():
+    import test_grid_gpu
+    for name in ("n1", "n2", "n3", "dup64"):
+        assert np.array_equal(E._small(name), test_grid_gpu.cloud(name))
+
+
+@pytest.mark.parametrize("name", sorted(E.FPFH_CASES))
+def test_edge_fpfh_inputs_are_decided(name):
+    """No pair feature of the input lies within 1e-9 of a bin edge (or at phi = +-pi): two correct implementations agree on every row."""
+    xyz, nrm, radius, max_nn = E.fpfh_input(name)
+    nbrs, spfh, fpfh = E.fpfh_want(name)
+    assert not G._near_edge_rows(xyz, nrm, nbrs).any()
+    k = np.array([len(x) for x in nbrs])
+    head = name.split("-")[0]
+    if head in ("plusz", "checker", "parity"):
+        # the input reaches what it is there for: a pair with len != 0 and v_norm == 0 in every row ...
+        P, N = xyz.astype(np.float64), nrm
+        for i, x in enumerate(nbrs):
+            dp = P[x[1:]] - P[i]
+            a1 = np.abs(dp @ N[i]) / np.linalg.norm(dp, axis=1)
+            a2 = np.abs((dp * N[x[1:]]).sum(1)) / np.linalg.norm(dp, axis=1)
+            par1, par2 = a1 == 1.0, (a2 == 1.0) & (a2 > a1)
+            # ... without the swap (the point's own normal is the frame's) or through it (the neighbour's is)
+            assert par2.any() if head == "checker" and (xyz[i].sum() % 2) == 0 else par1.any(), i
+    elif head == "zero":
+        assert np.array_equal(fpfh[:, [5, 16, 27]], np.full((len(xyz), 3), 200.0)) and np.count_nonzero(fpfh) == 3 * len(xyz)
+    elif head == "dup64":
+        assert np.all(k == 64) and np.array_equal(fpfh, spfh) and np.array_equal(fpfh[:, [5, 16, 27]], np.full((64, 3), 100.0))
+    elif head == "n1" or name.endswith("-nn1"):
+        assert np.all(k == 1) and not fpfh.any()
+    elif head in ("n2", "n3"):
+        assert np.all(k == min(len(xyz), max_nn)) and fpfh.any()
+    else:
+        assert k.min() >= 2 and k.max() < max_nn
+
+
+@pytest.mark.parametrize("name", sorted(E.FPFH_UNDECIDED))
+def test_edge_fpfh_inputs_left_out_are_the_undecided_ones(name):
+    """+-z by index parity at radius 1.5 and 2.0: the diagonal neighbours' normals are antiparallel, phi = atan2(+-0, -1), and the sign
+    of a zero picks bin 0 or 10.  The three axes by index mod 3: alpha = +-1 sits on the outer edge of its bins, where one ulp of the
+    normalisation moves it.  Every row is touched, at every radius: nothing of these inputs can be held to 1e-9."""
+    xyz, nrm, radius, max_nn = E.fpfh_input(name)
+    assert G._near_edge_rows(xyz, nrm, E.fpfh_want(name)[0]).all()
+
+
+def test_edge_fpfh_two_trip_cloud_is_decided():
+    xyz, nrm = E.two_trip_cloud()
+    assert len(xyz) == E.TRIP + E.TAIL > 4096 * 128 and E.TRIP == 2048 * 256
+    head, tail = xyz[:E.TRIP].astype(np.float64), xyz[E.TRIP:].astype(np.float64)
+    assert np.array_equal(head, np.round(head)) and len(np.unique(head, axis=0)) == E.TRIP      # distinct integer points: 1 apart
+    assert np.linalg.norm(tail - np.round(tail), axis=1).min() > 0.5 > 2 * E.TWO_TRIP_RADIUS - 0.01
+    nbrs = G.hybrid_search(xyz[E.TRIP:], E.TWO_TRIP_RADIUS, E.TWO_TRIP_NN)
+    assert not G._near_edge_rows(xyz[E.TRIP:], nrm[E.TRIP:], nbrs).any()
+    assert max(len(x) for x in nbrs) == E.TWO_TRIP_NN              # the cut at max_nn is taken
+
+
+@pytest.mark.parametrize("na,nb", E.FM_PLANTED)
+def test_edge_feature_match_plants_straddle_the_chunks(na, nb):
+    nch, chunk = E.fm_chunks(na, nb)
+    assert nch >= 2 and E.FM_TIE_TGT // chunk == 0 and (nb - 1) // chunk == (nb - 2) // chunk == nch - 1
+    fs, ft = E.fm_planted(na, nb, True)
+    _, _, nst, _ = G.feature_match(fs, ft, False)
+    assert nst[E.FM_TIE_SRC] == E.FM_TIE_TGT and nst[E.FM_LAST_SRC] == nb - 2 and nst[E.FM_NAN_SRC] == 0
+    # why the NaN row is planted only without `mutual`: in the search back, the restatement's argmin picks the NaN row for every target row
+    assert np.all(G.nn_rows(ft, fs) == E.FM_NAN_SRC)
+    # without it, every minimum of either direction is strict, or an exact tie between the two equal target rows (equal operands in
+    # the same order: the same d on either side), which the lowest index wins
+    fs, ft = E.fm_planted(na, nb, False)
+    for a, b in ((fs, ft), (ft, fs)):
+        d = ((a[:, None, :] - b[None, :, :]) ** 2).sum(2)
+        two = np.sort(d, axis=1)[:, :2]
+        gap = two[:, 1] - two[:, 0]
+        assert np.all((gap == 0.0) | (gap > 1e-9))
+        assert np.all(np.argmin(d, axis=1)[gap == 0.0] == E.FM_TIE_TGT) and ((gap == 0.0).any() == (b is ft))
+
+
+def test_edge_feature_match_shapes_sit_on_the_kernel_edges():
+    chunks = {s: E.fm_chunks(*s) for s in E.FM_SHAPES}
+    assert chunks[(300, 512)] == (1, 512) and chunks[(300, 513)] == (2, 257) and chunks[(70, 1025)] == (3, 342)
+    assert E.fm_chunks(*E.FM_TWO_TRIP) == (1, 40) and E.FM_TWO_TRIP[0] > 2048 * 256
+    # random rows: every nearest row is nearest by far more than a rounding error (and the kernel's sum is the restatement's, term by term)
+    for na, nb in E.FM_SHAPES:
+        fs, ft = E.fm_input(na, nb)
+        for a, b in ((fs, ft), (ft, fs)):
+            if len(b) > 1:
+                two = np.sort(((a[:, None, :] - b[None, :, :]) ** 2).sum(2), axis=1)[:, :2]
+                assert np.all(two[:, 1] - two[:, 0] > 1e-9)
+
+
+@pytest.mark.parametrize("name", sorted(E.RANSAC_CASES))
+def test_edge_ransac_cases_are_decided(name):
+    """The restatement finds a best hypothesis (an empty result would test nothing), no d2 of a valid hypothesis lies within
+    1e-6 max_corr^2 of max_corr^2, and the best hypothesis' own system is well conditioned."""
+    assert E.ransac_undecided(name) == []
+    want, _ = E.ransac_want(name)
+    c = E.RANSAC_CASES[name]
+    if c["confidence"] == 1.0:
+        assert want["exit_index"] == want["n_evaluated"] == c["max_iteration"]

@@ -1,9 +1,12 @@
-"""Global registration on the MI355X (csrc/features.hip) against the NumPy restatement (tests/global_model.py)."""
+"""Global registration on the MI355X (csrc/features.hip) against the NumPy restatement (tests/global_model.py), at workload-like
+shapes.  The small, lattice and degenerate inputs, the sizes on either side of each kernel's tile, chunk and block, and the second
+trips of the grid-stride loops live in tests/test_global_edges_gpu.py."""
 import numpy as np
 import pytest
 import torch
 
 import global_model as G
+from global_model import _near_edge_rows, _ransac_case
 
 pytestmark = pytest.mark.gpu
 
@@ -41,24 +44,6 @@ def test_hybrid_search_equals_restatement(F):
     assert cnt[len(xyz) - 151] == 1 and cnt.max() == 100
     for i in range(len(xyz)):
         assert cnt[i] == len(want[i]) and np.array_equal(nbr[i, :cnt[i]], want[i]), i
-
-
-def _near_edge_rows(xyz, nrm, nbrs, tol=1e-9):
-    """Rows whose FPFH may move by one SPFH increment between two correct implementations: the point itself or one of its neighbours has
-    a pair feature within `tol` of a bin edge (or phi = +-pi, where atan2's sign of zero decides between bins 0 and 10)."""
-    P = xyz.astype(np.float64)
-    rows = np.concatenate([np.full(max(len(x) - 1, 0), i) for i, x in enumerate(nbrs)]).astype(np.int64)
-    cols = np.concatenate([x[1:] for x in nbrs]).astype(np.int64)
-    f = G.pair_features(P[rows], nrm[rows], P[cols], nrm[cols])
-    u = np.stack([11 * (f[:, 0] + np.pi) / (2 * np.pi), 11 * (f[:, 1] + 1.0) * 0.5, 11 * (f[:, 2] + 1.0) * 0.5], 1)
-    near = np.any(np.abs(u - np.round(u)) < tol * 11, axis=1) | (np.abs(np.abs(f[:, 0]) - np.pi) < tol)
-    bad_spfh = np.zeros(len(xyz), bool)
-    bad_spfh[rows[near]] = True
-    out = bad_spfh.copy()
-    for i, x in enumerate(nbrs):
-        if bad_spfh[x].any():
-            out[i] = True
-    return out
 
 
 # splat counts and voxels that give about 1 k, 20 k and 100 k points after down-sampling (plus the 151 special points)
@@ -100,21 +85,6 @@ def test_feature_match_equals_restatement(F):
     # the fall-back: too few mutual pairs for ransac_n = 3000 -> the one-way set
     c, um = F.feature_match(fs, ft, mutual=True, ransac_n=3000)
     assert not um and len(c) == len(fs)
-
-
-def _ransac_case(m=800, inlier=0.4, seed=5, curved=False, T=None):
-    sc = G.make_scene(4000, seed)
-    T = G.make_T() if T is None else T
-    src = sc["xyz"]
-    tgt = (src.astype(np.float64) @ T[:3, :3].T + T[:3, 3]).astype(np.float32)
-    rng = np.random.default_rng(seed)
-    # curved: rows from the cylinder and the sphere (the last 28 % of the scene), where six rows give a well-posed 6 x 6 system
-    lo = int(len(src) * 0.72) if curved else 0
-    i = lo + rng.choice(len(src) - lo, m, replace=False)
-    j = i.copy()
-    bad = rng.random(m) > inlier
-    j[bad] = rng.integers(0, len(src), bad.sum())
-    return src, tgt, sc["normals"], sc["normals"] @ T[:3, :3].T, np.stack([i, j], 1).astype(np.int32), T
 
 
 CHECKS = {"none": [], "edge": [(0, 0.9)], "dist": [(1, 0.03)], "normal": [(2, 0.5)], "all": [(0, 0.9), (1, 0.03), (2, 0.5)]}
