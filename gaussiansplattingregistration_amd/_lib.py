@@ -142,6 +142,8 @@ SIGNATURES = {
                                      _vp, _vp, _vp, _vp, _vp, _vp]),
     "gsr_raster_get_timing": (_i32, [_vp, C.POINTER(_f32)]),
     "gsr_image_metrics": (_i32, [_vp, _vp, _i32, _i32, _i32, C.POINTER(_f64), _i32, _vp]),
+    "gsr_photo_accumulate": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, C.POINTER(_f64), _f64, _f64, _f64, _f64, _f64, _f64, _f64, _i32,
+                                    C.POINTER(_f64), _i32, _vp]),
 }
 # private test hooks (csrc/gsr_test_hooks.h): exported by the library, not part of the public header
 TEST_HOOKS = {
@@ -266,6 +268,7 @@ class PoseGraphResult(C.Structure):
 
 
 GSR_COLOR_SUMS_LEN = 40
+GSR_PHOTO_SUMS_LEN = 30
 GSR_COLOR_MODES = {"gain": 0, "channel_gain": 1, "affine": 2}
 
 

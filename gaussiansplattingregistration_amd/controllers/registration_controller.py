@@ -113,6 +113,22 @@ class RegistrationController:
                                    rotate_sh=rotate_sh, coverage=coverage, registration_result=registration_result)
         return worker.run()
 
+    def refine_photometric(self, cameras_list, params, device=0):
+        """Render-based refinement of the current transform on the repository's original clouds (``photo.PhotometricRefiner``,
+        DESIGN.md 23): both scenes rendered from ``cameras_list`` (in the second cloud's frame), intensity + depth, damped Gauss-Newton.
+        ``params``: ``PhotometricParams`` (``max_depth_diff`` has no default).  The refined transform becomes the current one; returns
+        the ``PhotometricResult`` (``None`` when cancelled: the transform is left alone).  Rigid only: not for a similarity."""
+        from ..photo import PhotometricRefiner
+        repo = self.data_repository
+        pc1 = repo.pc_gaussian_list_first[repo.current_index]
+        pc2 = repo.pc_gaussian_list_second[repo.current_index]
+        self.photometric_worker = worker = PhotometricRefiner(pc1, pc2, cameras_list, params, init=self.ui_repository.transformation_matrix, device=device)
+        result = worker.run()
+        if result is not None:
+            self.errors = list(result.error_list)
+            self.ui_repository.transformation_matrix = result.transformation
+        return result
+
     def handle_registration_result_local(self, result_data):       # :145-163
         self.ui_repository.transformation_matrix = result_data.result.transformation
 

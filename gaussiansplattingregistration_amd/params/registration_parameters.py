@@ -61,3 +61,17 @@ class FGRRegistrationParams:
     max_tuple_count: int = 1000
     tuple_test: bool = True
     seed: int = 0
+
+
+@dataclass
+class PhotometricParams:
+    """Render-based photometric refinement (``photo.PhotometricRefiner``); the reference has no such step.
+    ``max_depth_diff`` has no default: scenes have no common unit of length."""
+    max_depth_diff: float = None        # a pixel counts when the two rendered depths differ by at most this
+    lambda_depth: float = 0.968         # weight of the depth term (Open3D's hybrid RGB-D odometry); the intensity term has 1 - lambda
+    tau: float = 0.5                    # coverage a pixel needs in both renders (depth_agreement's)
+    scales: tuple = (4, 2, 1)           # image pyramid, coarse to fine: W/s x H/s pixels, intrinsics over s
+    max_iteration: int = 20             # per level, rejected steps included
+    min_increment: float = 1e-6         # a level stops when the norm of the accepted increment (omega, v) falls below this
+    damping: float = 0.0                # initial Levenberg-Marquardt mu; a rejected step raises it tenfold, an accepted one lowers it
+    radius_clip: float = 0.0            # splats of this 3-sigma pixel radius or less are not rendered (the evaluation uses 3; coarse levels need 0)

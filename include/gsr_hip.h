@@ -981,6 +981,29 @@ int32_t gsr_color_solve(int32_t n_nodes, double* P, int32_t n_edges, const gsr_c
 int32_t gsr_model_color_apply(const double* P12, int64_t n, int32_t K, const float* dc, const float* sh, float* dc_out, float* sh_out,
                               int32_t on_device, int32_t device, void* stream);
 
+/* ------------------------------------------------------------------- photometric refinement */
+/* The normal equations of one camera of render-based refinement: the hybrid (intensity + depth) term of RGB-D odometry on rendered
+ * maps.  csrc/photo.hip; restated in float64 in tests/photo_model.py.  I_t[height*width*3], D_t, A_t[height*width]: colour, expected
+ * depth and coverage of the TARGET model as gsr_raster_render_aux writes them; I_s, D_s, A_s: the same of the SOURCE model rendered
+ * through viewmat * T, T the current rigid estimate.  viewmat16 (host, row-major, float64) is the camera's own world -> camera matrix
+ * [R_c | t_c].  Everything is computed in float64 from the float32 maps, sums of products left to right, no fused multiply-add.
+ * A pixel (ix, iy) counts when (float64 comparisons of the widened values, a NaN fails) A_s >= tau, all nine target pixels of its
+ * 3 x 3 neighbourhood are inside the image with A_t >= tau, and |D_t - D_s| <= max_depth_diff.  For a counted pixel, with
+ * Y = (0.299 r + 0.587 g) + 0.114 b, z = D_s, p = z ((ix + .5 - cx) / fx, (iy + .5 - cy) / fy, 1), p_w = R_c' (p - t_c),
+ * M = R_c [-[p_w]x | I] (the increment xi = (omega, v) acts on the left in the world frame: T <- [exp(omega) | v] T), gY and gD the
+ * Sobel gradients of the target maps over 8, a = (gY_x fx / z, gY_y fy / z, -(a_0 p_x + a_1 p_y) / z) and d the same of gD with
+ * d_2 one less:  J_I = sqrt(1 - lambda) a M,  r_I = sqrt(1 - lambda) (Y_t - Y_s),  J_D = sqrt(lambda) d M,  r_D = sqrt(lambda) (D_t - z).
+ * out30 (host): [0..20] the upper triangle of sum(J_I' J_I + J_D' J_D) row by row, [21..26] sum(J_I' r_I + J_D' r_D), [27] sum r_I^2,
+ * [28] sum r_D^2, [29] the number of counted pixels.  No counted pixel: thirty zeros, GSR_OK.  D_s > 0 on covered pixels is the
+ * renderer's promise and is not checked.  Maps on the host or the device as on_device says.  A lane per pixel, a fixed-order fold
+ * per 16 x 16 group and a fixed-order fold of the groups: no atomics, the same inputs give the same bits, from host or device maps.
+ * GSR_E_INVALID with a message: a NULL pointer, a non-positive size, lambda outside [0, 1], tau outside (0, 1], max_depth_diff not
+ * positive and finite, a non-finite camera or a non-positive focal length -- all before any device call. */
+#define GSR_PHOTO_SUMS_LEN 30
+int32_t gsr_photo_accumulate(const float* I_s, const float* D_s, const float* A_s, const float* I_t, const float* D_t, const float* A_t,
+                             int32_t height, int32_t width, const double* viewmat16, double fx, double fy, double cx, double cy, double lambda,
+                             double tau, double max_depth_diff, int32_t on_device, double* out30, int32_t device, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

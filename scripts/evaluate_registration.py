@@ -3,6 +3,7 @@
     python scripts/evaluate_registration.py a.ply b.ply --transform T.txt --cameras cameras.json --images DIR --log out.json
                                             [--rotate-sh] [--with-scaling] [--fuse-overlap MAX_DIST [--fuse-kld X] [--fuse-color X]]
                                             [--save-renders DIR] [--background R G B] [--cpu-metrics]
+                                            [--photo-refine --photo-max-depth-diff D [--photo-scales 4,2,1] [--photo-lambda L]]
     python scripts/evaluate_registration.py a.ply b.ply --transform T.txt --cameras cameras.json --geometry [--coverage 0.5] --log out.json
 
 ``a.ply`` is moved by the 4x4 in ``T.txt`` (whitespace-separated, row-major) and merged with ``b.ply``; the merged model is rendered
@@ -13,6 +14,10 @@ reference's fields: registration_data, mse, rmse, ssim, psnr, lpips (null: no LP
 from every camera, and compared where both cover a pixel (coverage >= ``--coverage``): depth_mae, depth_rmse, depth_rel, depth_overlap,
 per camera and as means (``GeometryEvaluator``).  With ``--images`` as well, both evaluations run; the geometric log then goes to
 ``<log>.geometry``.
+
+``--photo-refine`` (rigid transforms only): the evaluations asked for run first on the transform as given, their logs beside the others
+as ``<log>.no_photo_refine``; the transform is then refined on renders of the two scenes from the same cameras (``PhotometricRefiner``;
+``--photo-max-depth-diff`` in scene units is required) and everything is evaluated again with the refined transform, which is printed.
 """
 from __future__ import annotations
 
@@ -46,12 +51,17 @@ def main():
     ap.add_argument("--fuse-color", type=float, default=float("inf"), help="largest L2 distance of the DC colours of a fused pair")
     from gaussiansplattingregistration_amd.harmonize import add_match_colors_arguments, match_colors_from_args
     add_match_colors_arguments(ap)
+    from gaussiansplattingregistration_amd.photo import add_photo_arguments, photo_params_from_args
+    add_photo_arguments(ap, with_cameras=False)
     ap.add_argument("--save-renders", metavar="DIR", help="write every render as DIR/<img_name>.png")
     ap.add_argument("--background", type=float, nargs=3, default=(0.0, 0.0, 0.0))
     ap.add_argument("--cpu-metrics", action="store_true", help="use_gpu=False: the metrics in host torch arithmetic")
     a = ap.parse_args()
     if a.images is None and not a.geometry:
         ap.error("the following arguments are required: --images")
+    photo = photo_params_from_args(a)
+    if photo is not None and a.with_scaling:
+        ap.error("--photo-refine estimates a rigid motion: refused with --with-scaling")
     import __graft_entry__ as g
     g.build_hip()
     from gaussiansplattingregistration_amd.controllers.registration_controller import RegistrationController
@@ -68,6 +78,24 @@ def main():
     repo.pc_gaussian_list_second.append(GaussianModel("cuda:0").from_ply(a.second))
     ui.transformation_matrix = np.loadtxt(a.transform, dtype=np.float64).reshape(4, 4)
     cameras = load_cameras(a.cameras)
+    if photo is not None:
+        # the effect of the refinement: the same evaluations on the transform as given first (their logs beside the others), then with it
+        rc0 = RegistrationController(repo, ui)
+        if a.geometry:
+            geo0 = rc0.evaluate_geometry(cameras, (a.log if a.images is None else a.log + ".geometry") + ".no_photo_refine", coverage=a.coverage,
+                                         rotate_sh=a.rotate_sh, with_scaling=False)
+            print(json.dumps({"photo_refine": False, "geometry": True, "depth_mae": geo0.depth_mae, "depth_rmse": geo0.depth_rmse, "depth_rel": geo0.depth_rel,
+                              "depth_overlap": geo0.depth_overlap}))
+        if a.images is not None:
+            base0 = rc0.evaluate_registration(cameras, a.images, a.log + ".no_photo_refine", tuple(a.background), not a.cpu_metrics, rotate_sh=a.rotate_sh,
+                                              fuse=fuse, match_colors=cm, match_colors_gate=gate)
+            print(json.dumps({"photo_refine": False, "psnr": base0.psnr, "ssim": base0.ssim, "mse": base0.mse}))
+        from gaussiansplattingregistration_amd.photo import report_lines
+        pr = rc0.refine_photometric(cameras, photo)
+        print("photometric refinement:")
+        print("\n".join("  " + line for line in report_lines(pr)))
+        print(json.dumps({"photo_refine": True, "transformation": np.asarray(pr.transformation).tolist(), "energy_initial": pr.energy_initial,
+                          "energy_final": pr.energy_final, "n_pixels": pr.n_pixels, "iterations": pr.iterations}))
     if a.geometry:
         geo_log = a.log if a.images is None else a.log + ".geometry"
         geo = RegistrationController(repo, ui).evaluate_geometry(cameras, geo_log, coverage=a.coverage, rotate_sh=a.rotate_sh, with_scaling=a.with_scaling)

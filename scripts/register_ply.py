@@ -8,6 +8,7 @@
            [--clean-knn K --clean-std R [--clean-radius R --clean-nb N] [--clean-min-opacity A] [--clean-max-extent S]]
            [--prune-unseen CAMERAS.json ... [--min-contribution 0.01]]
            [--match-colors [gain|channel_gain|affine] [--match-colors-huber K] [--match-colors-dist D] [--colors-out colors.json]]
+           [--photo-refine CAMERAS.json --photo-max-depth-diff D [--photo-scales 4,2,1] [--photo-lambda L]]
 
 `--with-scaling`: the two scenes do not share a unit of length (separate structure-from-motion runs).  Point-to-point ICP with scaling
 (`--type point` is implied, any other type is refused); without a global method the start is `initial_similarity` (centroids and RMS
@@ -29,6 +30,11 @@ before and after; `--colors-out` writes them as JSON.  Implies `--rotate-sh`.
 `--prune-unseen CAMERAS.json` (with `--out`, may be repeated): the merged cloud loses the splats no camera shows with a blending weight
 of `--min-contribution` (`GaussianModel.prune_unseen`).  The cameras must be in the merged cloud's frame (the second scene's) and cover
 BOTH scenes: a splat outside every frustum is dropped like an occluded one.
+
+`--photo-refine CAMERAS.json --photo-max-depth-diff D`: after ICP and before the merge, the transform is refined on renders of the
+two scenes from these cameras (in the second scene's frame; `PhotometricRefiner`): intensity and depth, coarse to fine over
+`--photo-scales`, for the motions geometry alone does not constrain (a wall, a floor).  D, in scene units, is how far apart the two
+rendered depths of a pixel may be for it to count.  Rigid only: refused with `--with-scaling`.
 
 Prints the 4x4 transformation (first -> second), fitness and inlier RMSE; `--out` saves the merged cloud.
 """
@@ -76,8 +82,13 @@ def main():
     add_prune_arguments(ap)
     from gaussiansplattingregistration_amd.harmonize import add_match_colors_arguments, match_colors_from_args
     add_match_colors_arguments(ap)
+    from gaussiansplattingregistration_amd.photo import add_photo_arguments, photo_params_from_args
+    add_photo_arguments(ap)
     a = ap.parse_args()
     clean = clean_params_from_args(a)
+    photo = photo_params_from_args(a)
+    if photo is not None and a.with_scaling:
+        raise SystemExit("--photo-refine estimates a rigid motion: refused with --with-scaling")
     if a.fuse_overlap is not None or a.match_colors is not None:
         a.rotate_sh = True
     if a.with_scaling and a.type not in (None, "point"):
@@ -156,11 +167,22 @@ def main():
         print(f"scale {split_similarity(res.result.transformation)[0]:.9f}")
     print(f"fitness {res.result.fitness:.4f}  inlier RMSE {res.result.inlier_rmse:.6f}")
     print(f"load {t1 - t0:.2f} s, mixtures {t2 - t1:.3f} s, registration {t3 - t2:.3f} s")
+    T_final = res.result.transformation
+    if photo is not None:
+        from gaussiansplattingregistration_amd.models.camera import load_cameras
+        from gaussiansplattingregistration_amd.photo import report_lines
+        repo.current_index = 0                                        # the original clouds
+        pr = rc.refine_photometric(load_cameras(a.photo_refine), photo)
+        T_final = pr.transformation
+        print("photometric refinement:")
+        print("\n".join("  " + line for line in report_lines(pr)))
+        print("transformation after the photometric refinement (first -> second):\n", T_final)
+        print(f"photometric refinement {time.perf_counter() - t3:.3f} s")
     if a.out:
         from gaussiansplattingregistration_amd import harmonize
         from gaussiansplattingregistration_amd.params import FuseOverlapParams
         fuse = FuseOverlapParams(a.fuse_overlap, a.fuse_kld, a.fuse_color) if a.fuse_overlap is not None else None
-        first, second, T = repo.pc_gaussian_list_first[0], repo.pc_gaussian_list_second[0], res.result.transformation
+        first, second, T = repo.pc_gaussian_list_first[0], repo.pc_gaussian_list_second[0], T_final
         cm, gate = match_colors_from_args(a, fuse)
         if cm is not None:          # move, fit the first scene's colours against the second's, apply: what is merged below is already in place
             first, (transforms, cinfo) = GaussianModel.move_and_match_colors(first, second, T, a.rotate_sh, a.with_scaling, cm, gate)
