@@ -144,6 +144,14 @@ SIGNATURES = {
     "gsr_image_metrics": (_i32, [_vp, _vp, _i32, _i32, _i32, C.POINTER(_f64), _i32, _vp]),
     "gsr_photo_accumulate": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, C.POINTER(_f64), _f64, _f64, _f64, _f64, _f64, _f64, _f64, _i32,
                                     C.POINTER(_f64), _i32, _vp]),
+    "gsr_warp_create": (_i32, [C.POINTER(_vp), _i32, _vp]),
+    "gsr_warp_destroy": (_i32, [_vp]),
+    "gsr_warp_set_target": (_i32, [_vp, _vp, _vp, _i64, _f64, _i32]),
+    "gsr_warp_set_source": (_i32, [_vp, _vp, _i64, _i32]),
+    "gsr_warp_accumulate": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i64), C.POINTER(_f64)]),
+    "gsr_warp_points": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _i32, _i32, _vp]),
+    "gsr_model_warp": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, C.POINTER(_i64), _i32, _i32, _vp]),
+    "gsr_warp_solve": (_i32, [_vp, _vp, _f64, _f64, _vp, _vp]),
 }
 # private test hooks (csrc/gsr_test_hooks.h): exported by the library, not part of the public header
 TEST_HOOKS = {
@@ -281,6 +289,15 @@ class ColorSolveResult(C.Structure):
     """gsr_color_solve_result (include/gsr_hip.h)."""
     _fields_ = [("E_initial", C.c_double), ("E_final", C.c_double), ("pivot_min", C.c_double), ("pivot_max", C.c_double), ("n_free", C.c_int32),
                 ("n_unknowns", C.c_int32)]
+
+
+GSR_WARP_CELL_LEN = 326
+
+
+class WarpReport(C.Structure):
+    """gsr_warp_report (include/gsr_hip.h)."""
+    _fields_ = [("E_before", C.c_double), ("E_after", C.c_double), ("E_data_before", C.c_double), ("E_data_after", C.c_double), ("n_corr", C.c_int64),
+                ("n_unknowns", C.c_int32), ("half_band", C.c_int32), ("pivot_min", C.c_double), ("pivot_max", C.c_double)]
 
 
 GSR_CHECK_EDGE_LENGTH = 0

@@ -86,8 +86,9 @@ class RegistrationController:
         return GaussianModel.get_merged_gaussian_point_clouds_multi_colors(models, poses, match_colors, match_colors_gate, rotate_sh=rotate_sh)
 
     def evaluate_registration(self, cameras_list, images_path, log_path, color, use_gpu, registration_result=None, rotate_sh=False, with_scaling=False,
-                              fuse=None, match_colors=None, match_colors_gate=None):
-        """``match_colors`` (``ColorMatchParams``; its gate: ``fuse``, else ``match_colors_gate``): the merge harmonises the first cloud's colours with the second's.
+                              fuse=None, match_colors=None, match_colors_gate=None, warp=None):
+        """``warp`` (``warp.WarpField``): the first cloud is warped between the move and the merge (``refine_nonrigid``).
+        ``match_colors`` (``ColorMatchParams``; its gate: ``fuse``, else ``match_colors_gate``): the merge harmonises the first cloud's colours with the second's.
         ``with_scaling``: the current transform is a similarity (a registration with scaling); the merge before rendering applies it as one.
         ``fuse`` (``FuseOverlapParams``): the merge fuses the splats the two clouds share (``GaussianModel.fuse_overlap``).
         Image-based evaluation of the current transform on the repository's original clouds (reference :122-143): renders of
@@ -98,10 +99,10 @@ class RegistrationController:
         pc2 = repo.pc_gaussian_list_second[repo.current_index]
         worker = RegistrationEvaluator(pc1, pc2, self.ui_repository.transformation_matrix, cameras_list, images_path, log_path, color,
                                        registration_result, use_gpu, rotate_sh=rotate_sh, with_scaling=with_scaling, fuse=fuse, match_colors=match_colors,
-                                       match_colors_gate=match_colors_gate)
+                                       match_colors_gate=match_colors_gate, warp=warp)
         return worker.run()
 
-    def evaluate_geometry(self, cameras_list, log_path, coverage=0.5, registration_result=None, rotate_sh=False, with_scaling=False):
+    def evaluate_geometry(self, cameras_list, log_path, coverage=0.5, registration_result=None, rotate_sh=False, with_scaling=False, warp=None):
         """Geometric evaluation of the current transform on the repository's original clouds, without photographs: the depth maps of
         the first cloud moved by it and of the second, from the same cameras (``GeometryEvaluator``); the JSON log at ``log_path``.
         Returns the evaluator's ``GeometryEvaluationObject``."""
@@ -110,7 +111,7 @@ class RegistrationController:
         pc1 = repo.pc_gaussian_list_first[repo.current_index]
         pc2 = repo.pc_gaussian_list_second[repo.current_index]
         worker = GeometryEvaluator(pc1, pc2, self.ui_repository.transformation_matrix, cameras_list, log_path, with_scaling=with_scaling,
-                                   rotate_sh=rotate_sh, coverage=coverage, registration_result=registration_result)
+                                   rotate_sh=rotate_sh, coverage=coverage, registration_result=registration_result, warp=warp)
         return worker.run()
 
     def refine_photometric(self, cameras_list, params, device=0):
@@ -127,6 +128,21 @@ class RegistrationController:
         if result is not None:
             self.errors = list(result.error_list)
             self.ui_repository.transformation_matrix = result.transformation
+        return result
+
+    def refine_nonrigid(self, params, device=None):
+        """Non-rigid refinement behind the current transform (``warp.NonRigidRefiner``) on the repository's current
+        clouds: the first cloud is moved by the current matrix (rigid or a similarity), then a lattice warp is fitted that brings it
+        onto the second.  ``params``: ``WarpParams`` (``max_corr`` has no default).  The matrix is left alone; the field is kept in
+        ``self.warp_field`` for the merges (``GaussianModel.get_merged_gaussian_point_clouds(..., warp=field)``).  Returns the
+        ``WarpResult``."""
+        from ..warp import NonRigidRefiner
+        repo = self.data_repository
+        pc1 = repo.pc_open3d_list_first[repo.current_index]
+        pc2 = repo.pc_open3d_list_second[repo.current_index]
+        self.nonrigid_worker = worker = NonRigidRefiner(pc1, pc2, params, init=self.ui_repository.transformation_matrix, device=device)
+        result = worker.run()
+        self.warp_field = result.field
         return result
 
     def handle_registration_result_local(self, result_data):       # :145-163

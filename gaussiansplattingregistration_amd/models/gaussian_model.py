@@ -287,6 +287,44 @@ class GaussianModel:
             setattr(self, name, t)
         return self
 
+    def warp_gaussian_model(self, field):
+        """Apply a non-rigid ``warp.WarpField`` in place, like ``transform_gaussian_model``: positions
+        ``float32(p + d(p))`` and covariances ``F cov F'`` with ``F = I + sum_k U_k grad w_k'`` in ONE device kernel
+        (``gsr_model_warp``; host tensors are staged by the library, no GPU: ``RuntimeError``); ``_scaling`` / ``_rotation``, when the
+        model carries them, are re-derived from the new covariances (``gsr_decompose_cov``, exact mode).  Opacity, DC colour and the SH
+        coefficients stay: the per-splat rotation of the SH by the polar factor of ``F`` is left out.  ``self.warp_n_folded`` counts the
+        splats with ``det F <= 0`` (reported, not treated specially).  A field with ``U == 0`` leaves every array's bits."""
+        self.warp_n_folded = 0
+        if len(self) == 0 or field.is_identity():
+            return self
+        device = self._xyz.device.index if self._xyz.is_cuda else 0
+        xyz, cov, self.warp_n_folded = field.apply_arrays(self._xyz, self._covariance, device=device)
+        self._xyz, self._covariance = torch.as_tensor(xyz), torch.as_tensor(cov)
+        if _mv.has_scaling_rot(self):
+            sc, q, _ = self._decompose(_lib.GSR_DECOMP_EXACT)
+            self._scaling, self._rotation = sc.to(self._xyz.device), q.to(self._xyz.device)
+        return self
+
+    @staticmethod
+    def _warped_pair(gaussian1, gaussian2, transformation_matrix, rotate_sh, with_scaling, warp, what=None):
+        """``gaussian1`` moved by the matrix, brought to ``gaussian2``'s device and warped by ``warp``: a copy, bit for bit what
+        ``clone_gaussian().transform_gaussian_model(T, rotate_sh)`` (``similarity_transform_gaussian_model`` with ``with_scaling``)
+        followed by ``warp_gaussian_model(warp)`` gives.  ``what``: the merge that averages rows (fuse, colour matching) and so
+        refuses an unrotated SH model under a rotating matrix."""
+        g1 = gaussian1.clone_gaussian()
+        moves = transformation_matrix is not None and not np.array_equal(np.asarray(transformation_matrix), np.eye(4))
+        if moves:
+            T = np.asarray(transformation_matrix, dtype=np.float64).reshape(4, 4)
+            if what is not None:
+                GaussianModel._require_rotate_sh(gaussian1, T, rotate_sh, what)
+            if with_scaling:
+                g1.similarity_transform_gaussian_model(T, rotate_sh=rotate_sh)
+            else:
+                g1.transform_gaussian_model(T, rotate_sh=rotate_sh)
+        if g1._xyz.device != gaussian2._xyz.device:
+            g1.move_to_device(str(gaussian2._xyz.device))
+        return g1.warp_gaussian_model(warp)
+
     @staticmethod
     def fuse_overlap(gaussian1, gaussian2, params):
         """Overlap-aware merge of two models that are ALREADY IN ONE FRAME (``gsr_model_fuse``, ``csrc/fuse.hip``): a splat of
@@ -354,7 +392,7 @@ class GaussianModel:
 
     @staticmethod
     def get_merged_gaussian_point_clouds(gaussian1, gaussian2, transformation_matrix, rotate_sh=False, with_scaling=False, fuse=None, match_colors=None,
-                                         match_colors_gate=None):
+                                         match_colors_gate=None, warp=None):
         """``gaussian1`` moved by the registration result, concatenated with ``gaussian2`` (the merged-cloud save).
         ``with_scaling``: the matrix is a similarity (``similarity_transform_gaussian_model``); ``_scaling`` moves too.
         ``rotate_sh``: turn the SH coefficients of ``gaussian1`` with it (``transform_gaussian_model``).  When both models
@@ -365,8 +403,17 @@ class GaussianModel:
         and ``rotate_sh`` is false.
         ``match_colors`` (``ColorMatchParams``; default ``None``: colours as they are): move, fit ``gaussian1``'s colour transform
         against ``gaussian2`` (``match_colors``; the correspondences are gated by ``fuse``, else by the ``FuseOverlapParams`` in
-        ``match_colors_gate``), apply it, then concatenate or fuse.  The same refusal as for ``fuse``."""
+        ``match_colors_gate``), apply it, then concatenate or fuse.  The same refusal as for ``fuse``.
+        ``warp`` (``warp.WarpField``; default ``None``): ``gaussian1`` is moved, THEN warped (``warp_gaussian_model``), then merged,
+        fused or matched as above."""
         assert gaussian1.sh_degree == gaussian2.sh_degree
+        if warp is not None:
+            g1 = GaussianModel._warped_pair(gaussian1, gaussian2, transformation_matrix, rotate_sh, with_scaling, warp,
+                                            "fuse" if fuse is not None else ("match_colors" if match_colors is not None else None))
+            if fuse is None and match_colors is None and g1._xyz.is_cuda and gaussian2._xyz.is_cuda:      # (nothing moves any more: rows copied into arrays allocated once)
+                return GaussianModel.get_merged_gaussian_point_clouds_multi([g1, gaussian2], [np.eye(4), np.eye(4)])
+            return GaussianModel.get_merged_gaussian_point_clouds(g1, gaussian2, None, rotate_sh=rotate_sh, fuse=fuse, match_colors=match_colors,
+                                                                  match_colors_gate=match_colors_gate)
         if match_colors is not None:
             g1, _ = GaussianModel.move_and_match_colors(gaussian1, gaussian2, transformation_matrix, rotate_sh, with_scaling, match_colors,
                                                         fuse if fuse is not None else match_colors_gate)
@@ -510,12 +557,16 @@ class GaussianModel:
         return moved
 
     @staticmethod
-    def get_fused_gaussian_point_clouds(gaussian1, gaussian2, transformation_matrix, fuse, rotate_sh=False, with_scaling=False, match_colors=None):
+    def get_fused_gaussian_point_clouds(gaussian1, gaussian2, transformation_matrix, fuse, rotate_sh=False, with_scaling=False, match_colors=None, warp=None):
         """``gaussian1`` moved by the matrix, then ``fuse_overlap`` with ``gaussian2`` -> ``(model, info)``: what
         ``get_merged_gaussian_point_clouds(..., fuse=params)`` returns the model of, with the report.  As in the plain merge,
         ``gaussian1`` is left as it was and may live on another device than ``gaussian2``: its moved copy goes to ``gaussian2``'s.
         ``match_colors`` (``ColorMatchParams``): the colours of ``gaussian1`` are harmonised with ``gaussian2``'s between the move and
-        the fusion; ``info["match_colors"]`` is then ``(transforms, info)`` of ``match_colors``."""
+        the fusion; ``info["match_colors"]`` is then ``(transforms, info)`` of ``match_colors``.
+        ``warp`` (``warp.WarpField``): ``gaussian1`` is warped between the move and everything else."""
+        if warp is not None:
+            g1 = GaussianModel._warped_pair(gaussian1, gaussian2, transformation_matrix, rotate_sh, with_scaling, warp, "fuse")
+            return GaussianModel.get_fused_gaussian_point_clouds(g1, gaussian2, None, fuse, rotate_sh=rotate_sh, match_colors=match_colors)
         if match_colors is not None:
             g1, colors = GaussianModel.move_and_match_colors(gaussian1, gaussian2, transformation_matrix, rotate_sh, with_scaling, match_colors, fuse)
             m, info = GaussianModel.fuse_overlap(g1, gaussian2, fuse)
@@ -563,11 +614,15 @@ class GaussianModel:
         return [g if harmonize.is_identity(P) or len(g) == 0 else g.apply_color_transform(P) for g, P in zip(models, transforms)]
 
     @staticmethod
-    def move_and_match_colors(gaussian1, gaussian2, transformation_matrix, rotate_sh, with_scaling, match_colors, gate):
+    def move_and_match_colors(gaussian1, gaussian2, transformation_matrix, rotate_sh, with_scaling, match_colors, gate, warp=None):
         """What the pairwise merges do first when ``match_colors`` (``ColorMatchParams``) is set -> ``(model, (transforms, info))``:
         ``gaussian1`` moved into ``gaussian2``'s frame, its colour transform fitted against ``gaussian2`` (the reference) over the
         correspondences ``gate`` (``FuseOverlapParams``) admits, and applied.  ``transforms`` / ``info``: ``match_colors``'s, scene 0 =
-        ``gaussian1``, scene 1 = ``gaussian2``.  ``gaussian1`` is left as it was."""
+        ``gaussian1``, scene 1 = ``gaussian2``.  ``gaussian1`` is left as it was.  ``warp`` (``warp.WarpField``): ``gaussian1`` is warped
+        between the move and the fit."""
+        if warp is not None:
+            g1 = GaussianModel._warped_pair(gaussian1, gaussian2, transformation_matrix, rotate_sh, with_scaling, warp, "match_colors")
+            return GaussianModel.move_and_match_colors(g1, gaussian2, None, rotate_sh, False, match_colors, gate)
         if gate is None:
             raise ValueError("match_colors needs the gates of its correspondences: fuse=, or a FuseOverlapParams in match_colors_gate=")
         g1 = GaussianModel._moved_pair(gaussian1, gaussian2, transformation_matrix, rotate_sh, with_scaling, "match_colors")

@@ -75,3 +75,15 @@ class PhotometricParams:
     min_increment: float = 1e-6         # a level stops when the norm of the accepted increment (omega, v) falls below this
     damping: float = 0.0                # initial Levenberg-Marquardt mu; a rejected step raises it tenfold, an accepted one lowers it
     radius_clip: float = 0.0            # splats of this 3-sigma pixel radius or less are not rendered (the evaluation uses 3; coarse levels need 0)
+
+
+@dataclass
+class WarpParams:
+    """Non-rigid refinement (``warp.NonRigidRefiner``); the reference has no such step.
+    ``max_corr`` has no default: scenes have no common unit of length."""
+    max_corr: float = None              # a correspondence counts when its squared distance is strictly below max_corr^2
+    levels: int = 3                     # lattices of 2^l + 1 nodes per axis, l = 0 .. levels - 1 (2^3, 3^3, 5^3); at most 5 (17^3)
+    max_iteration: int = 6              # per level; every iteration is one exact solve at fresh correspondences
+    lam: float = 0.01                   # weight of the second differences (they do not see affine drift), per correspondence
+    lam0: float = 1e-6                  # weight of |U|^2 (and, with 0.01 lam, of the first differences): keeps the system definite
+    relative_rmse: float = 1e-6         # a level stops when the point-to-plane RMSE changes by less than this, relatively

@@ -67,8 +67,9 @@ class RegistrationEvaluator:
     EvaluationObject = EvaluationObject
 
     def __init__(self, pc1, pc2, transformation, cameras_list, images_path, log_path, color, registration_result, use_gpu, rotate_sh=False, with_scaling=False,
-                 fuse=None, match_colors=None, match_colors_gate=None):
+                 fuse=None, match_colors=None, match_colors_gate=None, warp=None):
         self.signal_cancel = False
+        self.warp = warp                    # warp.WarpField or None: the first cloud is warped between the move and the merge
         self.pc1 = pc1
         self.pc2 = pc2
         self.transformation = transformation
@@ -112,7 +113,7 @@ class RegistrationEvaluator:
             if point_cloud is None:
                 point_cloud = GaussianModel.get_merged_gaussian_point_clouds(self.pc1, self.pc2, self.transformation, rotate_sh=self.rotate_sh,
                                                                              with_scaling=self.with_scaling, fuse=self.fuse, match_colors=self.match_colors,
-                                                                             match_colors_gate=self.match_colors_gate)
+                                                                             match_colors_gate=self.match_colors_gate, warp=self.warp)
                 point_cloud.move_to_device(self.device)
             render = rasterize_image(point_cloud, camera, 1, self.color, self.device, self.use_gpu)
             if self.on_render is not None:
@@ -186,8 +187,10 @@ class GeometryEvaluator:
     between cameras like ``RegistrationEvaluator``.  The two models are left as they were."""
     EvaluationObject = GeometryEvaluationObject
 
-    def __init__(self, pc1, pc2, transformation, cameras_list, log_path, with_scaling=False, rotate_sh=False, coverage=0.5, registration_result=None):
+    def __init__(self, pc1, pc2, transformation, cameras_list, log_path, with_scaling=False, rotate_sh=False, coverage=0.5, registration_result=None,
+                 warp=None):
         self.signal_cancel = False
+        self.warp = warp                    # warp.WarpField or None: the first cloud is warped behind the move
         self.pc1, self.pc2 = pc1, pc2
         self.transformation = transformation
         self.cameras_list = cameras_list
@@ -219,6 +222,8 @@ class GeometryEvaluator:
                     moved.similarity_transform_gaussian_model(self.transformation, rotate_sh=self.rotate_sh)
                 else:
                     moved.transform_gaussian_model(self.transformation, rotate_sh=self.rotate_sh)
+                if self.warp is not None:
+                    moved.warp_gaussian_model(self.warp)
                 second = self.pc2
                 if second.device_name != self.device:
                     second = second.clone_gaussian()

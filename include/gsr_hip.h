@@ -1004,6 +1004,60 @@ int32_t gsr_photo_accumulate(const float* I_s, const float* D_s, const float* A_
                              int32_t height, int32_t width, const double* viewmat16, double fx, double fy, double cx, double cy, double lambda,
                              double tau, double max_depth_diff, int32_t on_device, double* out30, int32_t device, void* stream);
 
+/* --------------------------------------------------------------------- non-rigid refinement */
+/* A lattice warp that absorbs the smooth drift one matrix leaves between two scenes.  csrc/warp.hip, csrc/gsr_warp.h; restated in
+ * float64 in tests/warp_model.py.
+ * Lattice: dims3 = (nx, ny, nz) nodes per axis, each in [2, 17], over the box lo3 .. hi3 (hi > lo on every axis); spacing
+ * h_a = (hi_a - lo_a) / (n_a - 1); node (ix, iy, iz) has index (ix ny + iy) nz + iz; U[M * 3] (host, float64) are the node
+ * displacements.  Cell (cx, cy, cz) has index (cx (ny - 1) + cy) (nz - 1) + cz; its local node k = 4 bx + 2 by + bz.
+ * Field, in float64 from the float32 coordinates: s_a = (p_a - lo_a) / h_a, sb_a = min(max(s_a, 0), n_a - 1),
+ * c_a = min(floor(sb_a), n_a - 2), f_a = sb_a - c_a; w_k = (X Y) Z with X = f_x or 1 - f_x (b_x = 1 or 0), likewise Y, Z;
+ * d(p) = sum_k w_k U_k (k ascending); dw_k/dp_a is the analytic derivative where 0 < s_a < n_a - 1 strictly and 0 elsewhere;
+ * F(p) = I + sum_k U_k (grad w_k)'.  A row with a non-finite coordinate is passed through unchanged and takes part in no sum.  A
+ * point's cell and weights always come from its UNWARPED position.  No fused multiply-add anywhere.
+ *
+ * gsr_warp_points: xyz_out = float32(p + d(p)).  gsr_model_warp: that, and cov6_out = F cov F' (float64, rounded once);
+ * *n_folded = the finite rows with det F <= 0 (counted, not treated specially).  U == 0 everywhere: the outputs are the inputs'
+ * bits.  The outputs may be the inputs themselves.  Arrays on the host or the device as on_device says; lo3, hi3, dims3, U on the host.
+ *
+ * The context owns the target's point grid with its normals (unit, float64, required) and the source points, which the caller has
+ * already moved by the initial matrix.  gsr_warp_accumulate: for every source point with finite coordinates the nearest target point
+ * q_j of p + d(p) (float64, not rounded) with d^2 < max_corr^2 strictly, the lowest index on a tie; with n_j its normal,
+ * r0 = (p_x - q_x) n_x + (p_y - q_y) n_y + (p_z - q_z) n_z (the UNWARPED p) and g[3 k + a] = w_k n_a.  sums (host,
+ * ncells * GSR_WARP_CELL_LEN) holds for every lattice cell: [0..299] the upper triangle of sum g g' row by row, [300..323] sum g r0,
+ * [324] sum r0^2, [325] the number of correspondences.  *n_corr = their total; *rmse = sqrt(sum (r0 + g' U)^2 / n_corr), evaluated
+ * from the sums (0 without a correspondence).  Order of every sum: the correspondences of a cell in source order, cut into chunks of
+ * 1024; the points of a chunk are added in order, then the chunks in order.  No float atomics: the same inputs give the same bits.
+ *
+ * gsr_warp_solve (host code only, no device is touched): the minimiser of
+ *   E(U) = sum_C (r0 + g' U)^2 + lam (n_C / n_T) sum_triples |U_a - 2 U_b + U_c|^2 + 0.01 lam (n_C / n_E) sum_edges |U_a - U_b|^2
+ *          + lam0 (n_C / M) sum_nodes |U_a|^2
+ * (triples: three consecutive nodes along one axis; edges: axis neighbours; n_T, n_E, M their counts and the nodes'; a term whose
+ * count is 0 is dropped) by one banded Cholesky solve.  U: on entry the displacements the sums were taken at (read for E_before
+ * only), on exit the minimiser.  n_C = 0 gives U = 0.  GSR_E_INVALID with a message: a dimension outside [2, 17], a non-finite
+ * input, a negative weight, a cell whose sums are not those of a symmetric positive semi-definite block to rounding, a system
+ * that is not positive definite (lam0 = 0 with empty cells). */
+#define GSR_WARP_CELL_LEN 326
+typedef struct gsr_warp_ctx gsr_warp_ctx;
+typedef struct gsr_warp_report {
+    double E_before, E_after;              /* E at the U handed in and at the minimiser */
+    double E_data_before, E_data_after;    /* the data term alone */
+    int64_t n_corr;
+    int32_t n_unknowns, half_band;
+    double pivot_min, pivot_max;           /* extreme squared diagonal entries of the Cholesky factor */
+} gsr_warp_report;
+int32_t gsr_warp_create(gsr_warp_ctx** out, int32_t device, void* stream);
+int32_t gsr_warp_destroy(gsr_warp_ctx* ctx);
+int32_t gsr_warp_set_target(gsr_warp_ctx* ctx, const float* xyz, const double* normals, int64_t n, double max_corr, int32_t on_device);
+int32_t gsr_warp_set_source(gsr_warp_ctx* ctx, const float* xyz, int64_t n, int32_t on_device);
+int32_t gsr_warp_accumulate(gsr_warp_ctx* ctx, const double* lo3, const double* hi3, const int32_t* dims3, const double* U, double* sums,
+                            int64_t* n_corr, double* rmse);
+int32_t gsr_warp_points(const double* lo3, const double* hi3, const int32_t* dims3, const double* U, const float* xyz, int64_t n, float* xyz_out,
+                        int32_t on_device, int32_t device, void* stream);
+int32_t gsr_model_warp(const double* lo3, const double* hi3, const int32_t* dims3, const double* U, int64_t n, const float* xyz, const float* cov6,
+                       float* xyz_out, float* cov6_out, int64_t* n_folded, int32_t on_device, int32_t device, void* stream);
+int32_t gsr_warp_solve(const int32_t* dims3, const double* sums, double lam, double lam0, double* U, gsr_warp_report* report);
+
 #ifdef __cplusplus
 }
 #endif

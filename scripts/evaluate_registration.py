@@ -56,6 +56,8 @@ def main():
     ap.add_argument("--save-renders", metavar="DIR", help="write every render as DIR/<img_name>.png")
     ap.add_argument("--background", type=float, nargs=3, default=(0.0, 0.0, 0.0))
     ap.add_argument("--cpu-metrics", action="store_true", help="use_gpu=False: the metrics in host torch arithmetic")
+    ap.add_argument("--warp", metavar="FIELD.npz", help="a non-rigid field (register_ply.py --warp-out): every evaluation runs without it first "
+                    "(logs with the suffix .no_warp), then with the first cloud warped behind the transform")
     a = ap.parse_args()
     if a.images is None and not a.geometry:
         ap.error("the following arguments are required: --images")
@@ -78,6 +80,20 @@ def main():
     repo.pc_gaussian_list_second.append(GaussianModel("cuda:0").from_ply(a.second))
     ui.transformation_matrix = np.loadtxt(a.transform, dtype=np.float64).reshape(4, 4)
     cameras = load_cameras(a.cameras)
+    field = None
+    if a.warp:
+        from gaussiansplattingregistration_amd.warp import WarpField
+        field = WarpField.load(a.warp)
+        rcw = RegistrationController(repo, ui)
+        if a.geometry:
+            gw = rcw.evaluate_geometry(cameras, (a.log if a.images is None else a.log + ".geometry") + ".no_warp", coverage=a.coverage, rotate_sh=a.rotate_sh,
+                                       with_scaling=a.with_scaling)
+            print(json.dumps({"warp": False, "geometry": True, "depth_mae": gw.depth_mae, "depth_rmse": gw.depth_rmse, "depth_rel": gw.depth_rel,
+                              "depth_overlap": gw.depth_overlap}))
+        if a.images is not None:
+            bw = rcw.evaluate_registration(cameras, a.images, a.log + ".no_warp", tuple(a.background), not a.cpu_metrics, rotate_sh=a.rotate_sh,
+                                           with_scaling=a.with_scaling, fuse=fuse, match_colors=cm, match_colors_gate=gate)
+            print(json.dumps({"warp": False, "psnr": bw.psnr, "ssim": bw.ssim, "mse": bw.mse}))
     if photo is not None:
         # the effect of the refinement: the same evaluations on the transform as given first (their logs beside the others), then with it
         rc0 = RegistrationController(repo, ui)
@@ -98,7 +114,7 @@ def main():
                           "energy_final": pr.energy_final, "n_pixels": pr.n_pixels, "iterations": pr.iterations}))
     if a.geometry:
         geo_log = a.log if a.images is None else a.log + ".geometry"
-        geo = RegistrationController(repo, ui).evaluate_geometry(cameras, geo_log, coverage=a.coverage, rotate_sh=a.rotate_sh, with_scaling=a.with_scaling)
+        geo = RegistrationController(repo, ui).evaluate_geometry(cameras, geo_log, coverage=a.coverage, rotate_sh=a.rotate_sh, with_scaling=a.with_scaling, warp=field)
         print(json.dumps({"geometry": True, "cameras": len(cameras), "coverage": a.coverage, "depth_mae": geo.depth_mae, "depth_rmse": geo.depth_rmse,
                           "depth_rel": geo.depth_rel, "depth_overlap": geo.depth_overlap, "errors": len(geo.error_list), "log": geo_log}))
         if a.images is None:
@@ -106,11 +122,11 @@ def main():
     if cm is not None:
         # the effect against the photographs: the same evaluation without the harmonisation first (its log beside the other), then with it
         base = RegistrationController(repo, ui).evaluate_registration(cameras, a.images, a.log + ".no_match_colors", tuple(a.background), not a.cpu_metrics,
-                                                                      rotate_sh=a.rotate_sh, with_scaling=a.with_scaling, fuse=fuse)
+                                                                      rotate_sh=a.rotate_sh, with_scaling=a.with_scaling, fuse=fuse, warp=field)
         print(json.dumps({"match_colors": None, "psnr": base.psnr, "ssim": base.ssim, "mse": base.mse}))
         from gaussiansplattingregistration_amd import harmonize
         _, (transforms, cinfo) = GaussianModel.move_and_match_colors(repo.pc_gaussian_list_first[0], repo.pc_gaussian_list_second[0], ui.transformation_matrix,
-                                                                     a.rotate_sh, a.with_scaling, cm, gate)
+                                                                     a.rotate_sh, a.with_scaling, cm, gate, warp=field)
         print("colours (scene 0 = first, scene 1 = second, the reference):")
         print("\n".join("  " + line for line in harmonize.report_lines(transforms, cinfo)))
         if a.colors_out:
@@ -125,13 +141,13 @@ def main():
             Image.fromarray(img).save(os.path.join(a.save_renders, camera.image_name + ".png"))
         worker = RegistrationEvaluator(repo.pc_gaussian_list_first[0], repo.pc_gaussian_list_second[0], ui.transformation_matrix, cameras, a.images, a.log,
                                        tuple(a.background), None, not a.cpu_metrics, rotate_sh=a.rotate_sh, with_scaling=a.with_scaling, fuse=fuse,
-                                       match_colors=cm, match_colors_gate=gate)
+                                       match_colors=cm, match_colors_gate=gate, warp=field)
         worker.on_render = keep
         result = worker.run()
     else:
         result = RegistrationController(repo, ui).evaluate_registration(cameras, a.images, a.log, tuple(a.background), not a.cpu_metrics, rotate_sh=a.rotate_sh,
-                                                                        with_scaling=a.with_scaling, fuse=fuse, match_colors=cm, match_colors_gate=gate)
-    print(json.dumps({"match_colors": cm.mode if cm is not None else None, "cameras": len(cameras), "mse": result.mse, "rmse": result.rmse, "psnr": result.psnr, "ssim": result.ssim, "lpips": result.lpips,
+                                                                        with_scaling=a.with_scaling, fuse=fuse, match_colors=cm, match_colors_gate=gate, warp=field)
+    print(json.dumps({"warp": a.warp, "match_colors": cm.mode if cm is not None else None, "cameras": len(cameras), "mse": result.mse, "rmse": result.rmse, "psnr": result.psnr, "ssim": result.ssim, "lpips": result.lpips,
                       "errors": len(result.error_list), "log": a.log}))
 
 

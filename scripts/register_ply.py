@@ -84,6 +84,11 @@ def main():
     add_match_colors_arguments(ap)
     from gaussiansplattingregistration_amd.photo import add_photo_arguments, photo_params_from_args
     add_photo_arguments(ap)
+    ap.add_argument("--nonrigid", type=float, metavar="MAX_CORR", help="non-rigid refinement behind the registration (and behind --photo-refine): a "
+                    "lattice warp of the first scene that absorbs the smooth drift one matrix leaves; correspondences within this distance")
+    ap.add_argument("--nonrigid-levels", type=int, default=3, help="lattices of 2^l + 1 nodes per axis, l = 0 .. levels - 1 (default 3: 2^3, 3^3, 5^3)")
+    ap.add_argument("--nonrigid-smooth", type=float, default=0.01, metavar="LAMBDA", help="weight of the second differences of the node displacements")
+    ap.add_argument("--warp-out", metavar="FIELD.npz", help="write the fitted field (evaluate_registration.py --warp reads it)")
     a = ap.parse_args()
     clean = clean_params_from_args(a)
     photo = photo_params_from_args(a)
@@ -178,6 +183,22 @@ def main():
         print("\n".join("  " + line for line in report_lines(pr)))
         print("transformation after the photometric refinement (first -> second):\n", T_final)
         print(f"photometric refinement {time.perf_counter() - t3:.3f} s")
+    field = None
+    if a.nonrigid is not None:
+        from gaussiansplattingregistration_amd.params import WarpParams
+        tw = time.perf_counter()
+        repo.current_index = 0                                        # the finest clouds the script holds: the original ones
+        ui.transformation_matrix = T_final
+        wr = rc.refine_nonrigid(WarpParams(max_corr=a.nonrigid, levels=a.nonrigid_levels, lam=a.nonrigid_smooth))
+        field = wr.field
+        print(f"non-rigid refinement: point-to-plane RMSE {wr.rmse_before:.6f} without the warp, {wr.rmse_after:.6f} with it "
+              f"({wr.n_corr} correspondences, {wr.n_folded} folded points)")
+        for lv in wr.levels:
+            print(f"  lattice {'x'.join(str(d) for d in lv['dims'])}: " + ", ".join(f"{it['rmse']:.6f}" for it in lv["iterations"]))
+        print(f"non-rigid refinement {time.perf_counter() - tw:.3f} s (accumulate {wr.timings['accumulate']:.3f} s, solve {wr.timings['solve']:.3f} s)")
+        if a.warp_out:
+            field.save(a.warp_out)
+            print(f"warp field -> {a.warp_out}")
     if a.out:
         from gaussiansplattingregistration_amd import harmonize
         from gaussiansplattingregistration_amd.params import FuseOverlapParams
@@ -185,17 +206,17 @@ def main():
         first, second, T = repo.pc_gaussian_list_first[0], repo.pc_gaussian_list_second[0], T_final
         cm, gate = match_colors_from_args(a, fuse)
         if cm is not None:          # move, fit the first scene's colours against the second's, apply: what is merged below is already in place
-            first, (transforms, cinfo) = GaussianModel.move_and_match_colors(first, second, T, a.rotate_sh, a.with_scaling, cm, gate)
-            T = None
+            first, (transforms, cinfo) = GaussianModel.move_and_match_colors(first, second, T, a.rotate_sh, a.with_scaling, cm, gate, warp=field)
+            T, field = None, None
             print("colours (scene 0 = first, scene 1 = second, the reference):")
             print("\n".join("  " + line for line in harmonize.report_lines(transforms, cinfo)))
             if a.colors_out:
                 harmonize.write_json(a.colors_out, transforms, cinfo)
         if fuse is not None:
-            merged, info = GaussianModel.get_fused_gaussian_point_clouds(first, second, T, fuse, rotate_sh=a.rotate_sh, with_scaling=a.with_scaling)
+            merged, info = GaussianModel.get_fused_gaussian_point_clouds(first, second, T, fuse, rotate_sh=a.rotate_sh, with_scaling=a.with_scaling, warp=field)
             print(f"fuse overlap: n_pairs {info['n_pairs']}  n_out {info['n_out']}  (invalid rows: {info['n_invalid_a']} / {info['n_invalid_b']})")
         else:
-            merged = GaussianModel.get_merged_gaussian_point_clouds(first, second, T, rotate_sh=a.rotate_sh, with_scaling=a.with_scaling)
+            merged = GaussianModel.get_merged_gaussian_point_clouds(first, second, T, rotate_sh=a.rotate_sh, with_scaling=a.with_scaling, warp=field)
         merged = prune_unseen_from_args(merged, a)          # (cameras in the frame of the merged cloud: the second / reference scene's)
         merged.save_ply(a.out)
         print(f"merged cloud ({len(merged)} splats) -> {a.out}")
