@@ -152,6 +152,12 @@ SIGNATURES = {
     "gsr_warp_points": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _i32, _i32, _vp]),
     "gsr_model_warp": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, C.POINTER(_i64), _i32, _i32, _vp]),
     "gsr_warp_solve": (_i32, [_vp, _vp, _f64, _f64, _vp, _vp]),
+    "gsr_d2d_create": (_i32, [C.POINTER(_vp), _i32, _vp]),
+    "gsr_d2d_destroy": (_i32, [_vp]),
+    "gsr_d2d_set_target": (_i32, [_vp, _vp, _vp, _vp, _i64, _f64, _i32]),
+    "gsr_d2d_set_source": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32]),
+    "gsr_d2d_accumulate": (_i32, [_vp, _vp, _f64, _f64, _vp]),
+    "gsr_d2d_register": (_i32, [_vp, _vp, _f64, _f64, _f64, _i32, _vp, _vp]),
 }
 # private test hooks (csrc/gsr_test_hooks.h): exported by the library, not part of the public header
 TEST_HOOKS = {
@@ -298,6 +304,16 @@ class WarpReport(C.Structure):
     """gsr_warp_report (include/gsr_hip.h)."""
     _fields_ = [("E_before", C.c_double), ("E_after", C.c_double), ("E_data_before", C.c_double), ("E_data_after", C.c_double), ("n_corr", C.c_int64),
                 ("n_unknowns", C.c_int32), ("half_band", C.c_int32), ("pivot_min", C.c_double), ("pivot_max", C.c_double)]
+
+
+GSR_D2D_SUMS_LEN = 32
+GSR_D2D_STATUS = {0: "converged", 1: "max_iteration", 2: "no_pairs", 3: "degenerate"}
+
+
+class D2DReport(C.Structure):
+    """gsr_d2d_report (include/gsr_hip.h)."""
+    _fields_ = [("score", C.c_double), ("fitness", C.c_double), ("mahalanobis_rmse", C.c_double), ("n_pairs", C.c_int64), ("n_singular", C.c_int64),
+                ("iterations", C.c_int32), ("status", C.c_int32)]
 
 
 GSR_CHECK_EDGE_LENGTH = 0

@@ -145,6 +145,22 @@ class RegistrationController:
         self.warp_field = result.field
         return result
 
+    def execute_mixture_registration(self, max_corr_values, cov_scale_values, iter_values, cov_floor=0.0, relative_score=1e-6, levels=None):
+        """Mixture-to-mixture registration (``MixtureToMixtureRegistrator``) from the current transform, coarse to fine
+        over the repository's two lists of clouds (one value per entry: the coarsest level first), or over ``levels = (list1, list2)``
+        -- e.g. the level dicts of ``hem.create_mixture``, which carry the components' weights.  The result's transform becomes the
+        current one; returns the worker's ``ResultData`` or ``None`` with ``self.errors`` set.  Rigid only."""
+        from ..workers.registrators import MixtureToMixtureRegistrator
+        repo = self.data_repository
+        l1, l2 = levels if levels is not None else (repo.pc_open3d_list_first, repo.pc_open3d_list_second)
+        self.mixture_worker = worker = MixtureToMixtureRegistrator(l1, l2, self.ui_repository.transformation_matrix, max_corr_values, cov_scale_values,
+                                                                   iter_values, cov_floor=cov_floor, relative_score=relative_score)
+        result = worker.run()
+        self.errors = worker.errors
+        if result is not None:
+            self.handle_registration_result_local(result)
+        return result
+
     def handle_registration_result_local(self, result_data):       # :145-163
         self.ui_repository.transformation_matrix = result_data.result.transformation
 

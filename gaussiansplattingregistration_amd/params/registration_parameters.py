@@ -35,6 +35,17 @@ class MultiScaleRegistrationParams:
 
 
 @dataclass
+class MixtureRegistrationParams:
+    """Mixture-to-mixture registration (``d2d.D2DContext``); the reference has no such method.
+    ``max_correspondence`` has no default: scenes have no common unit of length."""
+    max_correspondence: float           # a pair of components counts when its squared centre distance is strictly below this, squared
+    cov_scale: float = 1.0              # the summed covariance of a pair is multiplied by cov_scale^2 (coarse-to-fine: 8, 4, 2, 1)
+    cov_floor: float = 0.0              # added to the diagonal of a pair's covariance (keeps flat-on-flat pairs invertible)
+    max_iteration: int = 30
+    relative_score: float = 1e-6        # stop when the score changes by no more than this, relatively
+
+
+@dataclass
 class RANSACRegistrationParams:
     """The reference's fields and defaults, plus ``seed``: the RANSAC sampler is counter-based and deterministic here."""
     voxel_size: float = 0.05

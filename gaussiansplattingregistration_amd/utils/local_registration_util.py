@@ -258,6 +258,29 @@ def do_icp_registration(point_cloud_first, point_cloud_second, init_transform, r
     return None
 
 
+def do_mixture_registration(source_cloud, target_cloud, init, params, source_weights=None, target_weights=None, device=None):
+    """Mixture-to-mixture registration of two ``PointCloud`` records that carry covariances (``d2d.D2DContext``): every
+    source component against every target component within ``params.max_correspondence``, weighted by the overlap of the two Gaussians;
+    no nearest neighbour.  ``params``: ``MixtureRegistrationParams``; the weights (``(n,)`` float32, e.g. a HEM level's ``weight``)
+    default to 1.  Not a member of ``LocalRegistrationType``, which mirrors the reference's enum.  Returns a ``RegistrationResult``
+    whose ``inlier_rmse`` is the MAHALANOBIS rmse ``sqrt(sum omega m / sum omega)`` (also ``.mahalanobis_rmse``), with ``.score``
+    (``sum omega``, a soft overlap measure of the pair at the transform), ``.status``, ``.n_pairs`` and ``.n_singular`` added."""
+    from .. import d2d as _d2d
+    if not (params.max_correspondence > 0.0):
+        raise RuntimeError("[Open3D Error] Invalid max_correspondence_distance.")
+    if not (source_cloud.has_covariances() and target_cloud.has_covariances()):
+        raise RuntimeError("mixture-to-mixture registration needs covariances on both clouds")
+    r = _d2d.register_pair(source_cloud, target_cloud, np.asarray(init, dtype=np.float64), params.max_correspondence, params.cov_scale, params.cov_floor,
+                           params.relative_score, params.max_iteration, source_weights=source_weights, target_weights=target_weights, device=device)
+    return _mixture_result(r)
+
+
+def _mixture_result(r):
+    res = _icp.RegistrationResult(r["transformation"], r["fitness"], r["mahalanobis_rmse"], r["iterations"])
+    res.score, res.mahalanobis_rmse, res.status, res.n_pairs, res.n_singular = r["score"], r["mahalanobis_rmse"], r["status"], r["n_pairs"], r["n_singular"]
+    return res
+
+
 def get_information_matrix_from_point_clouds(source, target, max_correspondence_distance, transformation, device=None, ctx=None):
     """``o3d.pipelines.registration.get_information_matrix_from_point_clouds`` on ``PointCloud`` records: the (6, 6) float64
     information matrix of the pair at ``transformation`` (``IcpContext.information``: rotation rows first, ``[5, 5]`` = the number

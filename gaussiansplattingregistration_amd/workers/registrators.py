@@ -194,6 +194,37 @@ class MultiScaleRegistratorVoxel(MultiScaleRegistratorMixture):
         return out
 
 
+class MixtureToMixtureRegistrator:
+    """Coarse-to-fine mixture-to-mixture registration (``d2d.register_levels``) over two lists of mixture levels --
+    ``PointCloud`` records or the level dicts of ``hem.create_mixture``; the last entry is the coarsest, as above.  Entry ``k`` of
+    ``max_corr_values`` / ``cov_scale_values`` / ``iter_values`` belongs to the ``k``-th coarsest level.  A level's ``weight`` (the
+    HEM keeps one per component) is handed on where the level carries it.  Errors are returned in ``self.errors``."""
+
+    def __init__(self, levels1, levels2, init_trans, max_corr_values, cov_scale_values, iter_values, cov_floor=0.0, relative_score=1e-6, device=None):
+        self.levels1, self.levels2, self.init_trans = levels1, levels2, init_trans
+        self.max_corr_values, self.cov_scale_values, self.iter_values = list(max_corr_values), list(cov_scale_values), list(iter_values)
+        self.cov_floor, self.relative_score, self.device = cov_floor, relative_score, device
+        self.errors = []
+        self.level_results = []
+
+    def run(self):
+        from .. import d2d
+        from ..utils.local_registration_util import _mixture_result
+        try:
+            last, every = d2d.register_levels(self.levels1, self.levels2, self.init_trans, self.max_corr_values, self.cov_scale_values, self.iter_values,
+                                              cov_floor=self.cov_floor, relative_score=self.relative_score, device=self.device)
+        except (RuntimeError, ValueError) as e:
+            self.errors.append(str(e))
+            return None
+        self.level_results = [_mixture_result(r) for r in every]
+        results = self.level_results[-1]
+        data = MultiScaleRegistrationData(registration_type="Mixture-to-mixture", initial_transformation=self.init_trans, relative_fitness=0.0,
+                                          relative_rmse=self.relative_score, result_fitness=results.fitness, result_inlier_rmse=results.inlier_rmse,
+                                          result_transformation=results.transformation, voxel_values=self.max_corr_values,
+                                          iteration_values=self.iter_values, used_sparse_clouds=False, used_gaussian_mixtures=True)
+        return MultiScaleRegistratorMixture.ResultData(results, data)
+
+
 class RANSACRegistrator:
     """Reference ``qt_ransac_registrator.py``: the first cloud is moved by the current pose, then ``do_ransac_registration``."""
 

@@ -1058,6 +1058,68 @@ int32_t gsr_model_warp(const double* lo3, const double* hi3, const int32_t* dims
                        float* xyz_out, float* cov6_out, int64_t* n_folded, int32_t on_device, int32_t device, void* stream);
 int32_t gsr_warp_solve(const int32_t* dims3, const double* sums, double lam, double lam0, double* U, gsr_warp_report* report);
 
+/* ------------------------------------------------------------- mixture-to-mixture registration */
+/* A Gaussian mixture against a Gaussian mixture: every source component interacts with every target component within max_corr,
+ * weighted by the overlap of the two Gaussians (Stoyanov et al. 2012; the cross term of Jian and Vemuri's L2 distance).  There is no
+ * arg-min and no correspondence.  csrc/d2d.hip, csrc/gsr_d2d.h; restated in float64 in tests/d2d_model.py.
+ *
+ * Inputs.  Source: centres p_i (float32 xyz), covariances A_i (float32, six entries xx xy xz yy yz zz), weights w_i (float32; NULL:
+ * all 1).  Target: q_j, B_j, v_j likewise.  T = [R | t] (float64, 16 values row-major, rigid).  Everything is computed in float64
+ * from the widened float32 values; a sum of products runs left to right; no fused multiply-add.
+ *
+ * Pairs.  p' = R p_i + t.  The pair (i, j) counts when |p' - q_j|^2 < max_corr^2 strictly (d^2 = dx dx + dy dy + dz dz) and the
+ * three coordinates, the six covariance entries and the weight are finite on both sides.  ALL such j, not the nearest.
+ *
+ * Per pair, with s = cov_scale > 0, phi = cov_floor >= 0, S = R A_i R' (G = R A first, then S = G R'), r = p' - q_j:
+ *   C_k = (s s) (S_k + B_k), plus phi for k = xx, yy, zz
+ *   a_xx = C_yy C_zz - C_yz C_yz   a_xy = C_xz C_yz - C_xy C_zz   a_xz = C_xy C_yz - C_xz C_yy
+ *   a_yy = C_xx C_zz - C_xz C_xz   a_yz = C_xy C_xz - C_xx C_yz   a_zz = C_xx C_yy - C_xy C_xy
+ *   det = C_xx a_xx + C_xy a_xy + C_xz a_xz;  not (det > 0 and finite): the pair is skipped and counted in n_singular
+ *   M_k = a_k (1 / det);  M r row by row;  m = r_x (M r)_x + r_y (M r)_y + r_z (M r)_z;  omega = (w_i v_j) exp(-m / 2)
+ *
+ * Sums (out32, host, float64), with J = [-[p']x | I3] (rotation columns first, as gsr_icp_information; the increment acts on the
+ * left, in the world frame):
+ *   [0..20]  upper triangle of H = sum omega J' M J, row by row        [21..26] g = sum omega J' M r
+ *   [27]     S = sum omega, the score                                  [28]     sum omega m
+ *   [29]     the pairs that count                                      [30]     source rows with at least one such pair
+ *   [31]     n_singular
+ * Grouping: J depends on the source row only, so a row adds W = sum_j omega M (six), b = sum_j omega M r (three), sum omega and
+ * sum omega m over its pairs in the order of the walk, and [0..26] are J' W J and J' b formed once per row (P W, then p' x its rows;
+ * P v = p' x v).  The rows are then added in a fixed order that depends on the sizes alone: no float atomics, the same inputs give
+ * the same bits, from host arrays or device arrays.  No pair at all gives thirty-two zeros and GSR_OK.
+ *
+ * gsr_d2d_register, from T = init_T: evaluate; stop without pairs (GSR_D2D_NO_PAIRS); stop when an earlier evaluation exists and
+ * |S - S_previous| <= relative_score S (GSR_D2D_CONVERGED); stop after max_iter steps (GSR_D2D_MAX_ITERATION); else solve
+ * H xi = -g by LDL' with diagonal pivoting (a non-finite xi: GSR_D2D_DEGENERATE, no step), form
+ *   dT = [Rz(xi_2) Ry(xi_1) Rx(xi_0) | (xi_3, xi_4, xi_5)]
+ * -- the matrix the ICP step forms from its six-vector -- and T <- dT T.  M and omega are frozen within a step (IRLS, as
+ * Generalized ICP freezes its M).  The report is taken at the final T: score = S, fitness = [30] / n_source,
+ * mahalanobis_rmse = sqrt([28] / [27]) (a Mahalanobis quantity, not a distance), iterations = the steps taken.
+ *
+ * The context owns the target's point grid, the target's covariances and weights in cell order, and a copy of the source in the
+ * order of the target's cells; the arrays are on the host or the device as on_device says and are not needed after the call.  A new
+ * target keeps the source.  n = 0 is allowed on either side (no pairs).  There is no communicator entry: one context, one device.
+ * GSR_E_INVALID with a message, before any device call: a NULL pointer, a negative size, max_corr or cov_scale not positive and
+ * finite, cov_floor or relative_score negative or not finite, a negative max_iter, a non-finite T. */
+#define GSR_D2D_SUMS_LEN 32
+#define GSR_D2D_CONVERGED 0
+#define GSR_D2D_MAX_ITERATION 1
+#define GSR_D2D_NO_PAIRS 2
+#define GSR_D2D_DEGENERATE 3
+typedef struct gsr_d2d_ctx gsr_d2d_ctx;
+typedef struct gsr_d2d_report {
+    double score, fitness, mahalanobis_rmse;
+    int64_t n_pairs, n_singular;
+    int32_t iterations, status;
+} gsr_d2d_report;
+int32_t gsr_d2d_create(gsr_d2d_ctx** out, int32_t device, void* stream);
+int32_t gsr_d2d_destroy(gsr_d2d_ctx* ctx);
+int32_t gsr_d2d_set_target(gsr_d2d_ctx* ctx, const float* xyz, const float* cov6, const float* weight, int64_t n, double max_corr, int32_t on_device);
+int32_t gsr_d2d_set_source(gsr_d2d_ctx* ctx, const float* xyz, const float* cov6, const float* weight, int64_t n, int32_t on_device);
+int32_t gsr_d2d_accumulate(gsr_d2d_ctx* ctx, const double* T, double cov_scale, double cov_floor, double* out32);
+int32_t gsr_d2d_register(gsr_d2d_ctx* ctx, const double* init_T, double cov_scale, double cov_floor, double relative_score, int32_t max_iter,
+                         double* out_T, gsr_d2d_report* report);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,6 +9,7 @@
            [--prune-unseen CAMERAS.json ... [--min-contribution 0.01]]
            [--match-colors [gain|channel_gain|affine] [--match-colors-huber K] [--match-colors-dist D] [--colors-out colors.json]]
            [--photo-refine CAMERAS.json --photo-max-depth-diff D [--photo-scales 4,2,1] [--photo-lambda L]]
+           [--mixture-refine MAX_CORR [--mixture-cov-scale S] [--mixture-cov-floor F]]
 
 `--with-scaling`: the two scenes do not share a unit of length (separate structure-from-motion runs).  Point-to-point ICP with scaling
 (`--type point` is implied, any other type is refused); without a global method the start is `initial_similarity` (centroids and RMS
@@ -35,6 +36,11 @@ BOTH scenes: a splat outside every frustum is dropped like an occluded one.
 two scenes from these cameras (in the second scene's frame; `PhotometricRefiner`): intensity and depth, coarse to fine over
 `--photo-scales`, for the motions geometry alone does not constrain (a wall, a floor).  D, in scene units, is how far apart the two
 rendered depths of a pixel may be for it to count.  Rigid only: refused with `--with-scaling`.
+
+`--mixture-refine MAX_CORR`: after ICP and before `--photo-refine`, the transform is refined by mixture-to-mixture registration
+(`do_mixture_registration`) on the finest clouds the script holds: every pair of splats within MAX_CORR counts, weighted by the
+overlap of the two Gaussians (covariances times `--mixture-cov-scale` squared, plus `--mixture-cov-floor` on the diagonal), so the
+sampling noise of a one-nearest match does not reach the transform.  Rigid only: refused with `--with-scaling`.
 
 Prints the 4x4 transformation (first -> second), fitness and inlier RMSE; `--out` saves the merged cloud.
 """
@@ -89,7 +95,13 @@ def main():
     ap.add_argument("--nonrigid-levels", type=int, default=3, help="lattices of 2^l + 1 nodes per axis, l = 0 .. levels - 1 (default 3: 2^3, 3^3, 5^3)")
     ap.add_argument("--nonrigid-smooth", type=float, default=0.01, metavar="LAMBDA", help="weight of the second differences of the node displacements")
     ap.add_argument("--warp-out", metavar="FIELD.npz", help="write the fitted field (evaluate_registration.py --warp reads it)")
+    ap.add_argument("--mixture-refine", type=float, metavar="MAX_CORR", help="mixture-to-mixture refinement after ICP (and before --photo-refine): "
+                    "every pair of splats within this distance counts, weighted by the overlap of the two Gaussians")
+    ap.add_argument("--mixture-cov-scale", type=float, default=1.0, metavar="S", help="the covariances of a pair are multiplied by S^2")
+    ap.add_argument("--mixture-cov-floor", type=float, default=0.0, metavar="F", help="added to the diagonal of a pair's summed covariance")
     a = ap.parse_args()
+    if a.mixture_refine is not None and a.with_scaling:
+        raise SystemExit("--mixture-refine estimates a rigid motion: refused with --with-scaling")
     clean = clean_params_from_args(a)
     photo = photo_params_from_args(a)
     if photo is not None and a.with_scaling:
@@ -173,6 +185,16 @@ def main():
     print(f"fitness {res.result.fitness:.4f}  inlier RMSE {res.result.inlier_rmse:.6f}")
     print(f"load {t1 - t0:.2f} s, mixtures {t2 - t1:.3f} s, registration {t3 - t2:.3f} s")
     T_final = res.result.transformation
+    if a.mixture_refine is not None:
+        from gaussiansplattingregistration_amd.params import MixtureRegistrationParams
+        from gaussiansplattingregistration_amd.utils.local_registration_util import do_mixture_registration
+        tm0 = time.perf_counter()
+        mr = do_mixture_registration(repo.pc_open3d_list_first[0], repo.pc_open3d_list_second[0], T_final,
+                                     MixtureRegistrationParams(max_correspondence=a.mixture_refine, cov_scale=a.mixture_cov_scale, cov_floor=a.mixture_cov_floor))
+        T_final = ui.transformation_matrix = mr.transformation
+        print(f"mixture-to-mixture refinement: score {mr.score:.6g}  fitness {mr.fitness:.4f}  Mahalanobis rmse {mr.mahalanobis_rmse:.6f}  "
+              f"{mr.iterations} iterations ({mr.status}), {mr.n_pairs} pairs, {mr.n_singular} singular  {time.perf_counter() - tm0:.3f} s")
+        print("transformation after the mixture-to-mixture refinement (first -> second):\n", T_final)
     if photo is not None:
         from gaussiansplattingregistration_amd.models.camera import load_cameras
         from gaussiansplattingregistration_amd.photo import report_lines
