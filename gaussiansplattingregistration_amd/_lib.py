@@ -141,6 +141,9 @@ SIGNATURES = {
     "gsr_raster_render_aux": (_i32, [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, C.POINTER(_f32), _f32, _f32, _f32, _f32, _i32, _i32, C.POINTER(_f32), _f32,
                                      _vp, _vp, _vp, _vp, _vp, _vp]),
     "gsr_raster_get_timing": (_i32, [_vp, C.POINTER(_f32)]),
+    "gsr_raster_backward": (_i32, [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, C.POINTER(_f32), _f32, _f32, _f32, _f32, _i32, _i32, C.POINTER(_f32), _f32,
+                                   _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gsr_raster_get_backward_timing": (_i32, [_vp, C.POINTER(_f32)]),
     "gsr_image_metrics": (_i32, [_vp, _vp, _i32, _i32, _i32, C.POINTER(_f64), _i32, _vp]),
     "gsr_photo_accumulate": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, C.POINTER(_f64), _f64, _f64, _f64, _f64, _f64, _f64, _f64, _i32,
                                     C.POINTER(_f64), _i32, _vp]),

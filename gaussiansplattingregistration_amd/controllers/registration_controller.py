@@ -130,6 +130,26 @@ class RegistrationController:
             self.ui_repository.transformation_matrix = result.transformation
         return result
 
+    def finetune_merged(self, cameras_list, images, params=None, rotate_sh=False, with_scaling=False, fuse=None, match_colors=None,
+                        match_colors_gate=None, warp=None, device="cuda:0"):
+        """Merges the repository's original clouds with the current transform (the arguments of the merge as in ``evaluate_registration``)
+        and fine-tunes the merged model against photographs (``finetune.ModelFinetuner``).  ``images``: a directory of
+        ``<image_name>.png`` or one ``(H, W, 3)`` image per camera; ``params``: ``FinetuneParams``.  Returns ``(merged model, FinetuneResult)``
+        (the result is ``None`` when cancelled: the merged model is then untouched); the model is kept in ``self.finetuned_model``."""
+        from ..finetune import ModelFinetuner
+        from ..models.gaussian_model import GaussianModel
+        repo = self.data_repository
+        pc1 = repo.pc_gaussian_list_first[repo.current_index]
+        pc2 = repo.pc_gaussian_list_second[repo.current_index]
+        merged = GaussianModel.get_merged_gaussian_point_clouds(pc1, pc2, self.ui_repository.transformation_matrix, rotate_sh=rotate_sh,
+                                                                with_scaling=with_scaling, fuse=fuse, match_colors=match_colors,
+                                                                match_colors_gate=match_colors_gate, warp=warp)
+        merged.move_to_device(device)
+        self.finetune_worker = worker = ModelFinetuner(merged, cameras_list, images, params)
+        result = worker.run()
+        self.finetuned_model = merged
+        return merged, result
+
     def refine_nonrigid(self, params, device=None):
         """Non-rigid refinement behind the current transform (``warp.NonRigidRefiner``) on the repository's current
         clouds: the first cloud is moved by the current matrix (rigid or a similarity), then a lattice warp is fitted that brings it

@@ -1,0 +1,144 @@
+"""Fine-tuning of a (merged) splat model against photographs through the differentiable rasteriser (``raster.render_differentiable``,
+DESIGN.md 26): a short ``torch.optim.Adam`` run on the per-splat appearance -- DC colour, the other SH coefficients, opacity, optionally the
+positions -- that removes what a colour transform per scene (``match_colors``) and the moment-matching of pairs (``fuse_overlap``) leave at a
+seam.  The forward and backward passes are the HIP kernels of ``csrc/raster.hip``; the per-pixel loss and the optimiser are plain torch.
+
+Covariance is NOT tunable here: the model keeps ``_scaling`` / ``_rotation`` beside ``_covariance`` and the ``.ply`` stores those two, so a tuned
+``_covariance`` could not be saved.  No densification, no SSIM term, one camera per iteration.
+"""
+from __future__ import annotations
+
+import math
+import os
+from dataclasses import dataclass, field
+
+import numpy as np
+import torch
+
+from . import raster
+from .utils.rasterization_util import _camera_args
+
+TUNABLE = ("dc", "sh_rest", "opacity", "xyz")
+
+
+@dataclass
+class FinetuneParams:
+    """The learning rates are those published with 3DGS (feature 2.5e-3, the other SH coefficients a twentieth of it, opacity 0.05, position
+    1.6e-4).  ``params``: which tensors are tuned, of ``TUNABLE``.  ``loss``: ``"l2"`` (mean squared error) or ``"l1"``."""
+    iterations: int = 200
+    params: tuple = ("dc", "sh_rest", "opacity")
+    lr_dc: float = 2.5e-3
+    lr_sh_rest: float = 1.25e-4
+    lr_opacity: float = 0.05
+    lr_xyz: float = 1.6e-4
+    loss: str = "l2"
+    background: tuple = (0.0, 0.0, 0.0)
+
+
+@dataclass
+class FinetuneResult:
+    losses: list = field(default_factory=list)              # one per iteration, the loss of the camera visited
+    psnr_before: list = field(default_factory=list)         # per camera, in list order
+    psnr_after: list = field(default_factory=list)
+    iterations: int = 0
+    error_list: list = field(default_factory=list)
+
+
+def _psnr(image, target):
+    mse, _ = raster.image_metrics(image.permute(2, 0, 1).contiguous(), target.permute(2, 0, 1).contiguous())
+    return 20.0 * math.log10(1.0 / math.sqrt(mse)) if mse > 0 else math.inf
+
+
+class ModelFinetuner:
+    """``ModelFinetuner(model, cameras, images, params).run()`` -> ``FinetuneResult`` (``None`` when cancelled: the model is left alone).
+    ``images``: one ``(H, W, 3)`` float32 image in [0, 1] per camera (arrays or tensors), or a directory holding
+    ``<camera.image_name>.png``; a camera whose photograph is missing or of another size is skipped and named in ``error_list``.  Cameras are
+    visited round-robin in list order and nothing draws random numbers: two runs give the same bits.  The tuned tensors are written back
+    into ``model`` (which must be on a CUDA device)."""
+
+    def __init__(self, model, cameras, images, params=None, device=None):
+        self.model = model
+        self.cameras = list(cameras)
+        self.params = params if params is not None else FinetuneParams()
+        unknown = [p for p in self.params.params if p not in TUNABLE]
+        if unknown:
+            raise ValueError(f"FinetuneParams.params: unknown tensor {unknown[0]!r} {TUNABLE} (covariance is not tunable: DESIGN.md 26)")
+        if not self.params.params:
+            raise ValueError("FinetuneParams.params is empty")
+        if self.params.loss not in ("l2", "l1"):
+            raise ValueError(f"FinetuneParams.loss: {self.params.loss!r} (l2, l1)")
+        self.images = images
+        self.device = torch.device(device if device is not None else model.get_xyz.device)
+        if self.device.type != "cuda":
+            raise RuntimeError("ModelFinetuner needs the model on a CUDA device: the rasteriser has no CPU fallback")
+        self.signal_cancel = False
+
+    def cancel(self):
+        self.signal_cancel = True
+
+    def _targets(self, errors):
+        """-> [(camera, target (H, W, 3) on the device)] of the cameras that have a photograph of their size"""
+        pairs = []
+        for k, cam in enumerate(self.cameras):
+            if isinstance(self.images, (str, os.PathLike)):
+                from .workers.evaluator import _read_image
+                path = os.path.join(self.images, cam.image_name + ".png")
+                try:
+                    img = _read_image(path)[0].permute(1, 2, 0)
+                except (OSError, IOError) as e:
+                    errors.append(str(e))
+                    continue
+            else:
+                img = self.images[k]
+                img = img if isinstance(img, torch.Tensor) else torch.as_tensor(np.asarray(img, dtype=np.float32))
+            img = img.detach().to(device=self.device, dtype=torch.float32).contiguous()
+            if tuple(img.shape) != (int(cam.height), int(cam.width), 3):
+                errors.append(f"{cam.image_name}: image is {tuple(img.shape[:2])}, camera renders {(int(cam.height), int(cam.width))}")
+                continue
+            pairs.append((cam, img))
+        return pairs
+
+    def run(self):
+        p, m, dev = self.params, self.model, self.device
+        index = dev.index if dev.index is not None else 0
+        result = FinetuneResult()
+        pairs = self._targets(result.error_list)
+        n = len(m)
+        K = int(m._features_rest.shape[1]) if m._features_rest.numel() else 0
+        tensors = {"xyz": m.get_xyz.detach().to(dev).reshape(n, 3), "dc": m._features_dc.detach().to(dev).reshape(n, 3),
+                   "sh_rest": m._features_rest.detach().to(dev).reshape(n, K, 3) if K else None, "opacity": m._opacity.detach().to(dev).reshape(n)}
+        cov6 = m.get_covariance().detach().to(dev).reshape(n, 6).contiguous()
+        tuned = [name for name in TUNABLE if name in p.params and tensors[name] is not None and tensors[name].numel()]
+        for name in tuned:
+            tensors[name] = tensors[name].clone().contiguous().requires_grad_(True)
+        lr = {"dc": p.lr_dc, "sh_rest": p.lr_sh_rest, "opacity": p.lr_opacity, "xyz": p.lr_xyz}
+
+        def render(cam):
+            return raster.render_differentiable(tensors["xyz"], cov6, tensors["opacity"], tensors["dc"], tensors["sh_rest"], m.sh_degree, *_camera_args(cam),
+                                                background=p.background, radius_clip=3.0, device=index)[0]
+        with torch.no_grad():
+            result.psnr_before = [_psnr(render(cam), tgt) for cam, tgt in pairs]
+        if pairs and tuned and n:
+            opt = torch.optim.Adam([{"params": [tensors[name]], "lr": lr[name]} for name in tuned], eps=1e-15)
+            for it in range(int(p.iterations)):
+                if self.signal_cancel:
+                    return None
+                cam, tgt = pairs[it % len(pairs)]
+                opt.zero_grad(set_to_none=True)
+                diff = render(cam) - tgt
+                loss = (diff * diff).mean() if p.loss == "l2" else diff.abs().mean()
+                loss.backward()
+                opt.step()
+                result.losses.append(float(loss.detach()))
+                result.iterations = it + 1
+        with torch.no_grad():
+            result.psnr_after = [_psnr(render(cam), tgt) for cam, tgt in pairs]
+        if "xyz" in tuned:
+            m._xyz = tensors["xyz"].detach().reshape(m._xyz.shape).to(m._xyz.device)
+        if "dc" in tuned:
+            m._features_dc = tensors["dc"].detach().reshape(m._features_dc.shape).to(m._features_dc.device)
+        if "sh_rest" in tuned:
+            m._features_rest = tensors["sh_rest"].detach().reshape(m._features_rest.shape).to(m._features_rest.device)
+        if "opacity" in tuned:
+            m._opacity = tensors["opacity"].detach().reshape(m._opacity.shape).to(m._opacity.device)
+        return result

@@ -4,6 +4,9 @@
 per-splat largest blending weight) take the SoA arrays ``GaussianModel`` holds, as CUDA tensors
 (zero-copy) or as host arrays (uploaded through torch first: the library's render entry takes device pointers only).  No GPU:
 ``RuntimeError`` -- there is no CPU fallback.
+
+``render_backward`` is the backward pass of ``render_aux`` (``gsr_raster_backward``) and ``render_differentiable`` the
+``torch.autograd.Function`` over the two: image and coverage with gradients for positions, covariances, opacities and SH coefficients.
 """
 from __future__ import annotations
 
@@ -14,6 +17,9 @@ import torch
 
 from . import _lib
 from . import _marshal as _m
+
+
+BACKWARD_OUTPUTS = ("xyz", "cov6", "raw_opacity", "dc", "sh_rest")
 
 
 class RasterContext:
@@ -106,6 +112,54 @@ class RasterContext:
             out["stats"] = stats
         return out
 
+    def render_backward(self, xyz, cov6, raw_opacity, dc, sh_rest, sh_degree, viewmat, fx, fy, cx, cy, width, height, grad_image=None, grad_alpha=None,
+                        background=(0.0, 0.0, 0.0), radius_clip=3.0, wants=BACKWARD_OUTPUTS, with_stats=False):
+        """The backward pass of ``render_aux`` -> dict of float32 CUDA tensors, one per name in ``wants``: ``xyz`` ``(n, 3)``,
+        ``cov6`` ``(n, 6)``, ``raw_opacity`` ``(n,)``, ``dc`` ``(n, 3)``, ``sh_rest`` ``(n, 3K)`` (coefficient-major, as ``render`` takes it), the
+        gradients of a loss whose derivatives with respect to the image ``(H, W, 3)`` and the coverage ``(H, W)`` are ``grad_image`` and
+        ``grad_alpha`` (either may be None, not both; host arrays are uploaded).  Culled splats get exact zeros.  The call renders
+        nothing and relies on no earlier render; with ``with_stats`` also ``stats``."""
+        wants = tuple(wants)
+        unknown = [o for o in wants if o not in BACKWARD_OUTPUTS]
+        if unknown:
+            raise ValueError(f"render_backward: unknown output {unknown[0]!r} {BACKWARD_OUTPUTS}")
+        if not wants:
+            raise ValueError("render_backward: no output requested")
+        if grad_image is None and grad_alpha is None:
+            raise ValueError("render_backward: grad_image and grad_alpha are both None")
+        dev, n, K, (t_xyz, t_cov, t_op, t_dc, t_sh), V, bg = self._inputs(xyz, cov6, raw_opacity, dc, sh_rest, viewmat, background)
+        H, W = int(height), int(width)
+
+        def up(a, shape):
+            if a is None:
+                return None
+            t = a if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a, dtype=np.float32))
+            if tuple(t.shape) != shape:
+                raise ValueError(f"render_backward: a gradient of shape {tuple(t.shape)}, expected {shape}")
+            return t.detach().to(device=dev, dtype=torch.float32).contiguous()
+        g_img, g_alpha = up(grad_image, (H, W, 3)), up(grad_alpha, (H, W))
+        shapes = {"xyz": (n, 3), "cov6": (n, 6), "raw_opacity": (n,), "dc": (n, 3), "sh_rest": (n, 3 * K)}
+        out = {name: torch.empty(shapes[name], dtype=torch.float32, device=dev) for name in wants}
+        stats = torch.zeros(3, dtype=torch.int64, device=dev)
+        if n > 0 and any(t.numel() for t in out.values()):               # (an empty tensor's pointer is NULL: the library would see no output)
+            ptr = lambda name: out[name].data_ptr() if name in out and out[name].numel() else None
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _lib.check(self._L.gsr_raster_backward(self._h, n, K, int(sh_degree), t_xyz.data_ptr(), t_cov.data_ptr(), t_op.data_ptr(), t_dc.data_ptr(),
+                                                   t_sh.data_ptr() if K else None, V, float(fx), float(fy), float(cx), float(cy), W, H, bg, float(radius_clip),
+                                                   g_img.data_ptr() if g_img is not None else None, g_alpha.data_ptr() if g_alpha is not None else None,
+                                                   ptr("xyz"), ptr("cov6"), ptr("raw_opacity"), ptr("dc"), ptr("sh_rest"), stats.data_ptr(), C.c_void_p(stream)),
+                       "gsr_raster_backward")
+            self._keep = (t_xyz, t_cov, t_op, t_dc, t_sh, g_img, g_alpha)         # alive until the next call: the kernels are still enqueued
+        if with_stats:
+            out["stats"] = stats
+        return out
+
+    def backward_timing(self):
+        """-> {"preprocess", "sort", "blend_backward", "splat_backward"} milliseconds of the last ``render_backward`` (device events; waits for it)."""
+        ms = (C.c_float * 4)()
+        _lib.check(self._L.gsr_raster_get_backward_timing(self._h, ms), "gsr_raster_get_backward_timing")
+        return {"preprocess": float(ms[0]), "sort": float(ms[1]), "blend_backward": float(ms[2]), "splat_backward": float(ms[3])}
+
     def timing(self):
         """-> {"preprocess", "sort", "blend"} milliseconds of the last render (device events; waits for it)."""
         ms = (C.c_float * 3)()
@@ -121,6 +175,42 @@ def context(device: int = 0) -> RasterContext:
     if device not in _contexts:
         _contexts[device] = RasterContext(device)
     return _contexts[device]
+
+
+class _RenderFunction(torch.autograd.Function):
+    """``render_aux`` forwards, ``render_backward`` backwards.  Neither holds state in the shared context between the two calls."""
+
+    @staticmethod
+    def forward(ctx, xyz, cov6, raw_opacity, dc, sh_rest, sh_degree, camera, background, radius_clip, device):
+        viewmat, fx, fy, cx, cy, width, height = camera
+        out = context(device).render_aux(xyz, cov6, raw_opacity, dc, sh_rest, sh_degree, viewmat, fx, fy, cx, cy, width, height, background, radius_clip,
+                                         outputs=("image", "alpha"))
+        ctx.save_for_backward(xyz, cov6, raw_opacity, dc, sh_rest)
+        ctx.call = (sh_degree, camera, background, radius_clip, device)
+        return out["image"], out["alpha"]
+
+    @staticmethod
+    def backward(ctx, grad_image, grad_alpha):
+        xyz, cov6, raw_opacity, dc, sh_rest = ctx.saved_tensors
+        sh_degree, (viewmat, fx, fy, cx, cy, width, height), background, radius_clip, device = ctx.call
+        wants = tuple(name for name, need in zip(BACKWARD_OUTPUTS, ctx.needs_input_grad[:5]) if need and not (name == "sh_rest" and sh_rest is None))
+        if not wants:
+            return (None,) * 10
+        got = context(device).render_backward(xyz, cov6, raw_opacity, dc, sh_rest, sh_degree, viewmat, fx, fy, cx, cy, width, height, grad_image, grad_alpha,
+                                              background, radius_clip, wants)
+        shapes = {"xyz": xyz, "cov6": cov6, "raw_opacity": raw_opacity, "dc": dc, "sh_rest": sh_rest}
+        grads = tuple(got[name].reshape(shapes[name].shape).to(shapes[name].dtype) if name in got else None for name in BACKWARD_OUTPUTS)
+        return grads + (None,) * 5
+
+
+def render_differentiable(xyz, cov6, raw_opacity, dc, sh_rest, sh_degree, viewmat, fx, fy, cx, cy, width, height, background=(0.0, 0.0, 0.0),
+                          radius_clip=3.0, device=0):
+    """-> ``(image (H, W, 3), alpha (H, W))``, the bits ``render_aux`` gives, differentiable with respect to the five model tensors (CUDA
+    tensors on ``device``; ``sh_rest`` ``(n, K, 3)``, ``(n, 3K)`` or None).  The camera arguments are not differentiable: pose gradients come
+    from composing the motion in torch in front of this call (``xyz' = R xyz + t``, ``Sigma' = R Sigma R^T``).  Expected depth has no
+    gradient and is not returned."""
+    camera = (viewmat.detach() if isinstance(viewmat, torch.Tensor) else viewmat, float(fx), float(fy), float(cx), float(cy), int(width), int(height))
+    return _RenderFunction.apply(xyz, cov6, raw_opacity, dc, sh_rest, int(sh_degree), camera, tuple(float(b) for b in background), float(radius_clip), int(device))
 
 
 def render_model(model, viewmat, fx, fy, cx, cy, width, height, background=(0.0, 0.0, 0.0), scale=1.0, radius_clip=3.0, device=0, with_stats=False):

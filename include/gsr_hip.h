@@ -892,6 +892,46 @@ int32_t gsr_raster_render_aux(gsr_raster_ctx* ctx, int64_t n, int32_t K, int32_t
 /* ms[3]: preprocess + scan, key emission + sort + tile ranges (the host wait included), blend, of the last render (either entry);
  * waits for it. */
 int32_t gsr_raster_get_timing(gsr_raster_ctx* ctx, float* ms);
+/* The backward pass of the render (csrc/raster.hip, restated in tests/raster_grad_model.py).  The model and camera
+ * arguments are those of gsr_raster_render_aux in the same order.  All pointers but viewmat and background are DEVICE pointers.
+ * grad_image[height*width*3] = dL/d image and grad_alpha[height*width] = dL/d coverage (alpha_out): either may be NULL (zeros), not
+ * both; background is required only with grad_image.  Outputs, float32 with the shapes of their inputs: grad_xyz[n*3], grad_cov6[n*6],
+ * grad_raw_opacity[n], grad_dc[n*3], grad_sh_rest[n*3K]; each may be NULL and is then skipped, at least one must be given; they are
+ * OVERWRITTEN, not accumulated.  Validation, messages (under this entry's name), error codes, stats_out and the memory check follow the
+ * render entries; the records below take 36 more bytes per splat-tile intersection, counted in that check.  The call is stateless: it
+ * runs preprocess, scan, key emission, sort and tile ranges itself on the context's workspaces and relies on no earlier render.
+ *
+ * Definition: the derivative of the forward pass exactly as tests/raster_model.py states it (coverage: DESIGN.md 22.1), with every
+ * discrete decision held at the value the forward took:
+ *  - near/far, det <= 0, the radius and bounds culls and the tile box: a culled splat, or a pixel outside a splat's tiles, gets
+ *    nothing; a culled splat gets exact +0.0 in every output;
+ *  - sigma < 0 and alpha < 1/255: that pixel contributes nothing;
+ *  - alpha clamped at 0.999: the splat's colour still gets its gradient at that pixel, nothing flows to sigma or to the opacity;
+ *  - the stop at T (1 - alpha) <= 1e-4: the stopping splat and everything behind it get nothing from that pixel; T_end is the
+ *    transmittance in front of the stopping splat;
+ *  - colour max(v + 0.5, 0): a clamped channel passes nothing to dc, sh_rest or the view direction;
+ *  - the frustum clamp of x/z, y/z in the Jacobian: on the clamped branch tx = z lim, whose derivative is 0 in x (or y) and lim in z;
+ *  - max(0.01, b^2 - det) affects the radius only: no gradient.
+ * Included: the view direction into xyz through the SH basis and the normalisation; the Jacobian's dependence on the point in
+ * Sigma_2; the 0.3 I dilation as a constant; cov6's off-diagonal entries receive both symmetric positions; coefficients of sh_rest
+ * beyond sh_degree get 0.  Expected depth (depth_out) has NO gradient entry: it is left out.
+ * Per pixel, with w_k = alpha_k T_k, C = sum w_k c_k + T_end bg, A = 1 - T_end, G_C = dL/dC, G_A = dL/dA:
+ *   dL/dc_k = w_k G_C,   dL/dalpha_k = T_k (c_k . G_C) - [(sum_{m>k} w_m c_m + T_end bg) . G_C - T_end G_A] / (1 - alpha_k)
+ * (1 - alpha_k >= 0.001 by the clamp).  The walk goes back to front and recovers T_k by the 3DGS recurrence T <- T / (1 - alpha) from
+ * T_end: its rounding differs from the forward's T and is part of the contract (the float32 model repeats it).
+ * No float atomics, the same inputs give the same bits: every tile folds the nine per-pixel terms of an intersection (mean2d xy, conic
+ * A B C, opacity, r g b) in a fixed tree -- adjacent pairs along a pixel row, then rows in adjacent pairs inside a wave, then the four
+ * waves in order -- into one record per intersection, and every splat adds its records in float32 in the row-major order of its tile
+ * box before running the projection chain backwards in float32.  One thread walks all tiles of a splat, as in the key emission. */
+int32_t gsr_raster_backward(gsr_raster_ctx* ctx, int64_t n, int32_t K, int32_t sh_degree, const float* xyz, const float* cov6,
+                            const float* raw_opacity, const float* dc, const float* sh_rest, const float* viewmat, float fx, float fy,
+                            float cx, float cy, int32_t width, int32_t height, const float* background, float radius_clip,
+                            const float* grad_image, const float* grad_alpha, float* grad_xyz, float* grad_cov6, float* grad_raw_opacity,
+                            float* grad_dc, float* grad_sh_rest, int64_t* stats_out, void* stream);
+/* ms[4]: preprocess + scan, key emission + sort + tile ranges (the host wait included), blend-backward (the records), splat-backward
+ * (the per-splat sums and the chain), of the last gsr_raster_backward on this context; waits for it.  gsr_raster_get_timing is not
+ * affected by a backward pass, nor this by a render. */
+int32_t gsr_raster_get_backward_timing(gsr_raster_ctx* ctx, float* ms);
 
 /* MSE and SSIM of two (3, height, width) float32 images as the reference's src/utils/evaluation_utils.py defines them: SSIM with the
  * 11 x 11 Gaussian window (sigma 1.5, product of the normalised 1-D window), zero padding 5, C1 = 0.01^2, C2 = 0.03^2, mean over all

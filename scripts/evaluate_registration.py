@@ -15,6 +15,9 @@ from every camera, and compared where both cover a pixel (coverage >= ``--covera
 per camera and as means (``GeometryEvaluator``).  With ``--images`` as well, both evaluations run; the geometric log then goes to
 ``<log>.geometry``.
 
+``--finetune N [--finetune-holdout K]``: the merged model is fine-tuned for N iterations (``finetune.ModelFinetuner``) on the cameras that are
+not held out (every K-th is, default 8); MSE / PSNR / SSIM on the held-out cameras without and with it go to ``<log>.finetune``.
+
 ``--photo-refine`` (rigid transforms only): the evaluations asked for run first on the transform as given, their logs beside the others
 as ``<log>.no_photo_refine``; the transform is then refined on renders of the two scenes from the same cameras (``PhotometricRefiner``;
 ``--photo-max-depth-diff`` in scene units is required) and everything is evaluated again with the refined transform, which is printed.
@@ -58,7 +61,12 @@ def main():
     ap.add_argument("--cpu-metrics", action="store_true", help="use_gpu=False: the metrics in host torch arithmetic")
     ap.add_argument("--warp", metavar="FIELD.npz", help="a non-rigid field (register_ply.py --warp-out): every evaluation runs without it first "
                     "(logs with the suffix .no_warp), then with the first cloud warped behind the transform")
+    ap.add_argument("--finetune", type=int, metavar="N", help="fine-tune the merged model for N iterations (finetune.ModelFinetuner, DESIGN.md 26) on the "
+                    "cameras that are not held out and log MSE / PSNR / SSIM on the held-out ones without and with it (log suffix .finetune)")
+    ap.add_argument("--finetune-holdout", type=int, default=8, metavar="K", help="every K-th camera (the first included) is held out of the fine-tuning")
     a = ap.parse_args()
+    if a.finetune is not None and a.images is None:
+        ap.error("--finetune needs --images")
     if a.images is None and not a.geometry:
         ap.error("the following arguments are required: --images")
     photo = photo_params_from_args(a)
@@ -131,6 +139,37 @@ def main():
         print("\n".join("  " + line for line in harmonize.report_lines(transforms, cinfo)))
         if a.colors_out:
             harmonize.write_json(a.colors_out, transforms, cinfo)
+    if a.finetune is not None:
+        from gaussiansplattingregistration_amd.finetune import FinetuneParams
+        from gaussiansplattingregistration_amd.utils.evaluation_utils import metrics
+        from gaussiansplattingregistration_amd.utils.rasterization_util import rasterize_image
+        from gaussiansplattingregistration_amd.workers.evaluator import _json_value, _read_image
+        k = max(2, a.finetune_holdout)
+        held = [c for i, c in enumerate(cameras) if i % k == 0]
+        train = [c for i, c in enumerate(cameras) if i % k != 0]
+        rcf = RegistrationController(repo, ui)
+
+        def held_out(model):
+            rows = []
+            for c in held:
+                try:
+                    gt = _read_image(os.path.join(a.images, c.image_name + ".png")).to("cuda:0")
+                except (OSError, IOError):
+                    continue
+                img = rasterize_image(model, c, 1, tuple(a.background), "cuda:0").permute(0, 3, 1, 2)
+                if tuple(img.shape) == tuple(gt.shape):
+                    rows.append(metrics(img, gt))
+            return {key: float(np.mean([r[key] for r in rows])) if rows else None for key in ("mse", "psnr", "ssim")}
+        merge_args = dict(rotate_sh=a.rotate_sh, with_scaling=a.with_scaling, fuse=fuse, match_colors=cm, match_colors_gate=gate, warp=field)
+        plain, _ = rcf.finetune_merged([], a.images, FinetuneParams(iterations=0, background=tuple(a.background)), **merge_args)
+        before = held_out(plain)
+        tuned, fr = rcf.finetune_merged(train, a.images, FinetuneParams(iterations=a.finetune, background=tuple(a.background)), **merge_args)
+        after = held_out(tuned)
+        record = {"finetune": a.finetune, "train_cameras": len(fr.psnr_before), "held_out_cameras": len(held), "held_out_without": before, "held_out_with": after,
+                  "train_psnr_before": fr.psnr_before, "train_psnr_after": fr.psnr_after, "losses": fr.losses, "error_list": fr.error_list}
+        with open(a.log + ".finetune", "w") as out:
+            json.dump(_json_value(record), out, indent=2)
+        print(json.dumps(_json_value({key: record[key] for key in ("finetune", "train_cameras", "held_out_cameras", "held_out_without", "held_out_with")})))
     if a.save_renders:
         # the controller's call with a hook on the worker: the same evaluation, the renders kept
         os.makedirs(a.save_renders, exist_ok=True)

@@ -42,6 +42,9 @@ rendered depths of a pixel may be for it to count.  Rigid only: refused with `--
 overlap of the two Gaussians (covariances times `--mixture-cov-scale` squared, plus `--mixture-cov-floor` on the diagonal), so the
 sampling noise of a one-nearest match does not reach the transform.  Rigid only: refused with `--with-scaling`.
 
+`--finetune CAMERAS.json --finetune-images DIR [--finetune-iters N] [--finetune-params dc,sh_rest,opacity]` (with `--out`): the merged cloud
+is fine-tuned against the photographs of those cameras (`finetune.ModelFinetuner`) after the merge and before the save.
+
 Prints the 4x4 transformation (first -> second), fitness and inlier RMSE; `--out` saves the merged cloud.
 """
 import argparse
@@ -99,7 +102,14 @@ def main():
                     "every pair of splats within this distance counts, weighted by the overlap of the two Gaussians")
     ap.add_argument("--mixture-cov-scale", type=float, default=1.0, metavar="S", help="the covariances of a pair are multiplied by S^2")
     ap.add_argument("--mixture-cov-floor", type=float, default=0.0, metavar="F", help="added to the diagonal of a pair's summed covariance")
+    ap.add_argument("--finetune", metavar="CAMERAS.json", help="fine-tune the merged cloud against photographs (with --out and --finetune-images): a "
+                    "short Adam run through the differentiable rasteriser, after the merge and before the save; cameras in the merged cloud's frame")
+    ap.add_argument("--finetune-images", metavar="DIR", help="directory of <img_name>.png, one per camera of --finetune")
+    ap.add_argument("--finetune-iters", type=int, default=200, metavar="N")
+    ap.add_argument("--finetune-params", default="dc,sh_rest,opacity", help="comma-separated, of dc, sh_rest, opacity, xyz")
     a = ap.parse_args()
+    if a.finetune and not (a.out and a.finetune_images):
+        raise SystemExit("--finetune needs --out and --finetune-images")
     if a.mixture_refine is not None and a.with_scaling:
         raise SystemExit("--mixture-refine estimates a rigid motion: refused with --with-scaling")
     clean = clean_params_from_args(a)
@@ -240,6 +250,18 @@ def main():
         else:
             merged = GaussianModel.get_merged_gaussian_point_clouds(first, second, T, rotate_sh=a.rotate_sh, with_scaling=a.with_scaling, warp=field)
         merged = prune_unseen_from_args(merged, a)          # (cameras in the frame of the merged cloud: the second / reference scene's)
+        if a.finetune:
+            from gaussiansplattingregistration_amd.finetune import FinetuneParams, ModelFinetuner
+            from gaussiansplattingregistration_amd.models.camera import load_cameras
+            tf = time.perf_counter()
+            merged.move_to_device("cuda:0")
+            fr = ModelFinetuner(merged, load_cameras(a.finetune), a.finetune_images,
+                                FinetuneParams(iterations=a.finetune_iters, params=tuple(x for x in a.finetune_params.split(",") if x))).run()
+            mean = lambda v: sum(v) / len(v) if v else float("nan")
+            print(f"fine-tuning ({a.finetune_params}): {fr.iterations} iterations over {len(fr.psnr_before)} cameras, loss {fr.losses[0] if fr.losses else float('nan'):.6g} -> "
+                  f"{fr.losses[-1] if fr.losses else float('nan'):.6g}, mean PSNR {mean(fr.psnr_before):.3f} -> {mean(fr.psnr_after):.3f} dB  {time.perf_counter() - tf:.3f} s")
+            for e in fr.error_list:
+                print("  " + e)
         merged.save_ply(a.out)
         print(f"merged cloud ({len(merged)} splats) -> {a.out}")
 
