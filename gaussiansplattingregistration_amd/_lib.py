@@ -169,6 +169,7 @@ TEST_HOOKS = {
     "gsr_debug_kl_gate": (_i32, [_vp, _vp, _vp, _i64, _f32, _vp, _vp, _vp, _i32]),
     "gsr_debug_stage1": (_i32, [_vp, _vp, _vp, _vp, _i64, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _i32]),
     "gsr_debug_ransac_sample": (_i32, [_u64, _i64, _i64, _i64, _i32, _vp]),
+    "gsr_debug_fold": (_i32, [_vp, _i64, _i32, _i32, _vp, _i32]),
 }
 
 _lib = None

@@ -8,12 +8,13 @@
 //   gsr_d2d_accumulate       k_d2d_accumulate: one lane per source row.  R A R' once, then grid_box_walk over
 //                            grid_rings_for_radius(max_corr) rings; per accepted pair the closed-form inverse, one exp and eleven
 //                            float64 additions (sum w M, sum w M r, sum w, sum w m); the 27 entries of H and g are formed ONCE per row
-//                            from those (J depends on the row only).  A row's 32 values are folded lane -> wave -> block in a fixed
-//                            order; k_d2d_finalize adds the blocks' partials in a fixed order.  No float atomics: the grid is
-//                            ceil(n / 256) blocks whatever the device, so the same inputs give the same bits.
+//                            from those (J depends on the row only).  A row's 32 values are folded lane -> wave -> block, and the
+//                            blocks' partials by k_fold_partials, in the fixed order of gsr_fold.h (the xor tree).  No float atomics:
+//                            the grid is ceil(n / 256) blocks whatever the device, so the same inputs give the same bits.
 //   gsr_d2d_register         the IRLS loop on the host: accumulate, pivoted LDL' (solve6), T <- dT T
 #include "gsr_common.h"
 #include "gsr_d2d.h"
+#include "gsr_fold.h"
 #include "gsr_grid.h"
 #include "gsr_oneshot.h"
 #include "gsr_solve.h"
@@ -62,24 +63,6 @@ __global__ __launch_bounds__(256) void k_d2d_gather_source(int64_t n, const unsi
     }
 }
 
-// The fold of the ICP sums (csrc/icp.hip, block_reduce_store): the lanes of a wave in a butterfly, the four waves in order
-__device__ __forceinline__ void d2d_block_store(double (&v)[D2D_LEN], double* __restrict__ partials) {
-    __shared__ double s_red[4][D2D_LEN];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < D2D_LEN; ++k) {
-        double s = v[k];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-        if (lane == 0) s_red[wv][k] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x < D2D_LEN) {
-        const int k = threadIdx.x;
-        partials[(int64_t)blockIdx.x * D2D_LEN + k] = ((s_red[0][k] + s_red[1][k]) + s_red[2][k]) + s_red[3][k];
-    }
-}
-
 __global__ __launch_bounds__(256) void k_d2d_accumulate(int64_t ns, const float4* __restrict__ p4, const float* __restrict__ A6, D2DXform T, double s2,
                                                         double phi, IcpGrid g, const int* __restrict__ cellStart, const float4* __restrict__ Tq,
                                                         const float4* __restrict__ rec, int rings, double max_corr2, double* __restrict__ partials) {
@@ -119,16 +102,7 @@ __global__ __launch_bounds__(256) void k_d2d_accumulate(int64_t ns, const float4
             d2d::row_expand(p, acc, out);
         }
     }
-    d2d_block_store(out, partials);
-}
-
-// One wave per sum: lane l adds the partials of blocks l, l + 64, ... in order, then a fixed butterfly (k_icp_finalize's order)
-__global__ __launch_bounds__(64) void k_d2d_finalize(int nblocks, const double* __restrict__ partials, double* __restrict__ out) {
-    const int k = blockIdx.x, lane = threadIdx.x;
-    double s = 0.0;
-    for (int b = lane; b < nblocks; b += 64) s += partials[(int64_t)b * D2D_LEN + k];
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    if (lane == 0) out[k] = s;
+    block_fold_store<D2D_LEN, D2D_LEN, wave_sum_xor>(out, partials, (int)blockIdx.x);
 }
 
 }  // namespace gsr
@@ -165,22 +139,15 @@ int32_t sort_source(gsr_d2d_ctx* c) {
     return GSR_OK;
 }
 
-// dT of xi = -H^-1 g: rotation Rz(x2) Ry(x1) Rx(x0), translation x3..5 -- the matrix the ICP step forms (gsr_solve.h, estimate_update).
-// false: the solve gave something that is not finite (no update).
+// dT = the rigid update of xi = -H^-1 g (gsr_solve.h, rigid_from_euler6).  false: the solve gave something that is not finite (no update).
 bool d2d_step(const double* s, double dT[16]) {
     double H[6][6], nb[6], x[6];
-    int t = 0;
-    for (int a = 0; a < 6; ++a)
-        for (int b = a; b < 6; ++b) { H[a][b] = s[t]; H[b][a] = s[t]; ++t; }
+    sym6_from_upper(s, H);
     for (int a = 0; a < 6; ++a) nb[a] = -s[21 + a];
     solve6(H, nb, x);
     for (int a = 0; a < 6; ++a)
         if (!d2d::finite(x[a])) return false;
-    const double ca = cos(x[0]), sa = sin(x[0]), cb = cos(x[1]), sb = sin(x[1]), cg = cos(x[2]), sg = sin(x[2]);
-    mat4_identity(dT);
-    dT[0] = cg * cb; dT[1] = cg * sb * sa - sg * ca; dT[2] = cg * sb * ca + sg * sa; dT[3] = x[3];
-    dT[4] = sg * cb; dT[5] = sg * sb * sa + cg * ca; dT[6] = sg * sb * ca - cg * sa; dT[7] = x[4];
-    dT[8] = -sb;     dT[9] = cb * sa;                dT[10] = cb * ca;               dT[11] = x[5];
+    rigid_from_euler6(x, dT);
     return true;
 }
 
@@ -204,7 +171,7 @@ int32_t accumulate(gsr_d2d_ctx* c, const double* T, double cov_scale, double cov
     const GridView gv = c->index.view();
     hipLaunchKernelGGL(k_d2d_accumulate, dim3(nb), dim3(256), 0, st, c->ns, c->src4.as<float4>(), c->srcA.as<float>(), X, cov_scale * cov_scale, cov_floor, gv.g,
                        gv.cellStart, gv.Tq, c->trec.as<float4>(), grid_rings_for_radius(gv.g, c->max_corr), c->max_corr * c->max_corr, c->partials.as<double>());
-    hipLaunchKernelGGL(k_d2d_finalize, dim3(D2D_LEN), dim3(64), 0, st, nb, c->partials.as<double>(), c->sums.as<double>());
+    hipLaunchKernelGGL(k_fold_partials<64>, dim3(D2D_LEN), dim3(64), 0, st, nb64, D2D_LEN, (const double*)c->partials.as<double>(), c->sums.as<double>());
     GSR_HIP(hipGetLastError());
     GSR_HIP(hipMemcpyAsync(out, c->sums.p, D2D_LEN * 8, hipMemcpyDeviceToHost, st));
     GSR_HIP(hipStreamSynchronize(st));

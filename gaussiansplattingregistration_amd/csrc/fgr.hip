@@ -12,6 +12,7 @@
 // No floating-point atomics: every sum has a fixed order, so the same inputs give the same bits.
 #include "gsr_common.h"
 #include "gsr_features.h"
+#include "gsr_fold.h"
 #include "gsr_oneshot.h"
 #include "gsr_solve.h"
 
@@ -143,12 +144,7 @@ struct FgrState {
     int iterations, done, bad_rows, pad;
 };
 
-// sum over the wave by a fixed shuffle tree (lane 0 holds it), then the waves in index order: thread 0 returns the block's sum
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
+// the largest value of the wave by a fixed shuffle tree (lane 0 holds it)
 __device__ __forceinline__ double wave_max(double v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_down(v, o, 64));
@@ -159,7 +155,6 @@ __device__ __forceinline__ double wave_max(double v) {
 // block * 256 + t, + g * 256, ... in ascending order
 __global__ __launch_bounds__(FGR_BLOCK) void k_fgr_centre_partial(const float* __restrict__ sx, int64_t ns, const float* __restrict__ tx, int64_t nt,
                                                                   double* __restrict__ part) {
-    __shared__ double s_w[FGR_WAVES][3];
     const float* x = blockIdx.y ? tx : sx;
     const int64_t n = blockIdx.y ? nt : ns;
     // the cloud's own block count g = min(ceil(n / 256), grid): its order of summation does not depend on the other cloud's size
@@ -169,18 +164,7 @@ __global__ __launch_bounds__(FGR_BLOCK) void k_fgr_centre_partial(const float* _
     for (int64_t i = (int64_t)blockIdx.x * FGR_BLOCK + threadIdx.x; i < n && blockIdx.x < g; i += g * FGR_BLOCK) {
         s[0] += (double)x[3 * i]; s[1] += (double)x[3 * i + 1]; s[2] += (double)x[3 * i + 2];
     }
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-        const double v = wave_sum(s[r]);
-        if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6][r] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        double v = 0.0;
-#pragma unroll
-        for (int w = 0; w < FGR_WAVES; ++w) v += s_w[w][threadIdx.x];
-        part[((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 3 + threadIdx.x] = v;
-    }
+    block_fold_store<3, 3, wave_sum_xor>(s, part, (int)(blockIdx.y * gridDim.x + blockIdx.x));
 }
 
 // mean[cloud * 3 + r] = (the block partials in block order) / n
@@ -251,10 +235,9 @@ __global__ __launch_bounds__(FGR_BLOCK) void k_fgr_gather(int64_t m, const int* 
 //   JTJ = l * [[yy+zz, -xy, -xz, 0, -z, y], [., xx+zz, -yz, z, 0, -x], [., ., xx+yy, -y, x, 0], [., ., ., 1, 0, 0], [.., 1, 0], [.., 1]]
 //   JTr = l * [z ry - y rz, x rz - z rx, y rx - x ry, -rx, -ry, -rz]
 // so 16 sums carry all 27 entries: S0..5 = l (yy+zz, xy, xz, xx+zz, yz, xx+yy), S6..8 = l (x, y, z), S9 = l, S10..15 = JTr.
-// Thread t takes the pairs block * 256 + t, + grid * 256, ... in ascending order; wave shuffle tree, waves in order; partials[block][16].
+// Thread t takes the pairs block * 256 + t, + grid * 256, ... in ascending order; block_fold_store (gsr_fold.h, the xor tree); partials[block][16].
 __global__ __launch_bounds__(FGR_BLOCK) void k_fgr_accumulate(int64_t m, double* __restrict__ pq, const FgrState* __restrict__ st,
                                                               double* __restrict__ partials) {
-    __shared__ double s_w[FGR_WAVES][FGR_NSUM];
     if (st->done) return;
     double D[12];
 #pragma unroll
@@ -279,18 +262,7 @@ __global__ __launch_bounds__(FGR_BLOCK) void k_fgr_accumulate(int64_t m, double*
         S[10] += l * (z * ry - y * rz); S[11] += l * (x * rz - z * rx); S[12] += l * (y * rx - x * ry);
         S[13] -= l * rx; S[14] -= l * ry; S[15] -= l * rz;
     }
-#pragma unroll
-    for (int e = 0; e < FGR_NSUM; ++e) {
-        const double v = wave_sum(S[e]);
-        if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6][e] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < FGR_NSUM) {
-        double v = 0.0;
-#pragma unroll
-        for (int w = 0; w < FGR_WAVES; ++w) v += s_w[w][threadIdx.x];
-        partials[(int64_t)blockIdx.x * FGR_NSUM + threadIdx.x] = v;
-    }
+    block_fold_store<FGR_NSUM, FGR_NSUM, wave_sum_xor>(S, partials, (int)blockIdx.x);
 }
 
 // Folds the block partials in block order (a sum per thread), then thread 0: (-JTJ) x = JTr, delta, trans = delta trans, mu.
@@ -328,12 +300,8 @@ __global__ __launch_bounds__(64) void k_fgr_step(int nblk, const double* __restr
 #pragma unroll
     for (int r = 0; r < 6; ++r) ok = ok && isfinite(x[r]);
     if (!ok) { st->done = 1; return; }
-    const double ca = cos(x[0]), sa = sin(x[0]), cb = cos(x[1]), sb = sin(x[1]), cg = cos(x[2]), sg = sin(x[2]);
     double d[16];
-    d[0] = cg * cb; d[1] = cg * sb * sa - sg * ca; d[2] = cg * sb * ca + sg * sa; d[3] = x[3];
-    d[4] = sg * cb; d[5] = sg * sb * sa + cg * ca; d[6] = sg * sb * ca - cg * sa; d[7] = x[4];
-    d[8] = -sb;     d[9] = cb * sa;                d[10] = cb * ca;               d[11] = x[5];
-    d[12] = 0.0; d[13] = 0.0; d[14] = 0.0; d[15] = 1.0;
+    rigid_from_euler6(x, d);
     double T[16];
 #pragma unroll
     for (int e = 0; e < 16; ++e) T[e] = st->trans[e];

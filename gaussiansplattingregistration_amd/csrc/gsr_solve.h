@@ -1,5 +1,6 @@
-// gsr_solve.h -- float64 solves shared by csrc/icp.hip (the ICP estimators) and csrc/features.hip (the RANSAC hypotheses):
-// 3x3 Jacobi SVD (Eigen::umeyama), 6x6 LDL^T (Eigen's LDLT), and the estimator update from reduced accumulators.
+// gsr_solve.h -- float64 solves shared by csrc/icp.hip (the ICP estimators), csrc/features.hip (the RANSAC hypotheses), csrc/d2d.hip
+// and csrc/fgr.hip (their 6-DoF steps): 3x3 Jacobi SVD (Eigen::umeyama), 6x6 LDL^T (Eigen's LDLT), the symmetric 6x6 from its 21
+// upper-triangle sums, the rigid update of a 6-vector, and the estimator update from reduced accumulators.
 #pragma once
 #include "gsr_common.h"
 
@@ -130,6 +131,22 @@ __host__ __device__ static void mat4_mul(const double A[16], const double B[16],
     for (int i = 0; i < 4; ++i) for (int j = 0; j < 4; ++j) { double s = 0; for (int k = 0; k < 4; ++k) s += A[4 * i + k] * B[4 * k + j]; R[4 * i + j] = s; }
     for (int i = 0; i < 16; ++i) C[i] = R[i];
 }
+// A = the symmetric 6 x 6 whose upper triangle, row by row, is u21[0..20]
+__host__ __device__ static inline void sym6_from_upper(const double* u21, double A[6][6]) {
+    int t = 0;
+#pragma unroll
+    for (int a = 0; a < 6; ++a)
+#pragma unroll
+        for (int b = a; b < 6; ++b) { A[a][b] = u21[t]; A[b][a] = u21[t]; ++t; }
+}
+// M = the 4 x 4 (row-major) of the 6-DoF step x: rotation Rz(x2) Ry(x1) Rx(x0), translation x3..5
+__host__ __device__ static inline void rigid_from_euler6(const double x[6], double M[16]) {
+    const double ca = cos(x[0]), sa = sin(x[0]), cb = cos(x[1]), sb = sin(x[1]), cg = cos(x[2]), sg = sin(x[2]);
+    M[0] = cg * cb; M[1] = cg * sb * sa - sg * ca; M[2] = cg * sb * ca + sg * sa; M[3] = x[3];
+    M[4] = sg * cb; M[5] = sg * sb * sa + cg * ca; M[6] = sg * sb * ca - cg * sa; M[7] = x[4];
+    M[8] = -sb;     M[9] = cb * sa;                M[10] = cb * ca;               M[11] = x[5];
+    M[12] = 0.0;    M[13] = 0.0;                   M[14] = 0.0;                   M[15] = 1.0;
+}
 
 // estimator update from the reduced accumulators (Open3D TransformationEstimation*.ComputeTransformation)
 // GSR_ICP_POINT_TO_POINT_SCALED is Eigen::umeyama(src, dst, true): mp, mq, sigma, the SVD and the sign matrix S as for kind 0, then
@@ -163,20 +180,13 @@ __host__ __device__ static void estimate_update(const double ctr[3], int kind, c
             for (int col = 0; col < 3; ++col) Rp += R[r][col] * (mp[col] + ctr[col]);
             update[4 * r + 3] = mq[r] + ctr[r] - Rp;
         }
-    } else {                                                 // x = solve(JTJ, -JTr); Rz(x2) Ry(x1) Rx(x0), t = x3..5
+    } else {                                                 // x = solve(JTJ, -JTr)
         double JTJ[6][6], nb[6], x[6];
-        int t = 2;
-#pragma unroll
-        for (int a = 0; a < 6; ++a)
-#pragma unroll
-            for (int b = a; b < 6; ++b) { JTJ[a][b] = acc[t]; JTJ[b][a] = acc[t]; ++t; }
+        sym6_from_upper(acc + 2, JTJ);
 #pragma unroll
         for (int a = 0; a < 6; ++a) nb[a] = -acc[23 + a];
         solve6(JTJ, nb, x);
-        const double ca = cos(x[0]), sa = sin(x[0]), cb = cos(x[1]), sb = sin(x[1]), cg = cos(x[2]), sg = sin(x[2]);
-        update[0] = cg * cb; update[1] = cg * sb * sa - sg * ca; update[2] = cg * sb * ca + sg * sa; update[3] = x[3];
-        update[4] = sg * cb; update[5] = sg * sb * sa + cg * ca; update[6] = sg * sb * ca - cg * sa; update[7] = x[4];
-        update[8] = -sb;     update[9] = cb * sa;                update[10] = cb * ca;               update[11] = x[5];
+        rigid_from_euler6(x, update);
     }
 }
 

@@ -28,6 +28,9 @@ int32_t gsr_debug_stage1(const float* parent_mean, const float* parent_cov6, con
 /* The RANSAC sampler's raw draws (csrc/features.hip, formula in include/gsr_hip.h), on the host by the same __host__ __device__
  * function the kernels call: out[t * n + j] = row j of hypothesis k0 + t among m correspondences, before sorting. */
 int32_t gsr_debug_ransac_sample(uint64_t seed, int64_t k0, int64_t count, int64_t m, int32_t n, int32_t* out);
+/* The fixed-order float64 fold (csrc/gsr_fold.h) on x [n][3] (host): thread t of block b holds row 256 b + t, zeros past n;
+ * block_fold_store<3, 4, order> (0: wave_sum_xor, 1: wave_sum_rows), then k_fold_partials<final_threads> (64 or 256) into out3. */
+int32_t gsr_debug_fold(const double* x, int64_t n, int32_t order, int32_t final_threads, double* out3, int32_t device);
 #ifdef __cplusplus
 }
 #endif

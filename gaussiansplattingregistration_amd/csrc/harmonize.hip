@@ -2,11 +2,12 @@
 // include/gsr_hip.h).  The definitions are restated in float64 in tests/color_model.py.
 //
 //   k_color_sums      a lane per pair, grid-stride: the two gathers (dc, opacity of either side), the residual at the current
-//                     transforms, the Huber weight, 39 float64 sums in registers; the block fold and k_color_finalize's fixed-order
-//                     fold are k_icp_information / k_icp_finalize's idiom.  The two counts are integer atomics.
+//                     transforms, the Huber weight, 39 float64 sums in registers, folded by block_fold_store and k_fold_partials
+//                     (gsr_fold.h, the xor tree).  The two counts are integer atomics.
 //   k_color_apply     a lane per colour triple of the model (n DC triples, then n K SH triples): float64, narrowed once.
 // gsr_color_solve is host code (csrc/gsr_colorsolve.h); gsr_model_match, the pair list, lives beside gsr_model_fuse in fuse.hip.
 #include "gsr_common.h"
+#include "gsr_fold.h"
 #include "gsr_oneshot.h"
 #include "gsr_colorsolve.h"
 
@@ -79,34 +80,13 @@ __global__ __launch_bounds__(256) void k_color_sums(int64_t n_pairs, const int32
 #pragma unroll
             for (int c = r; c < 4; ++c) acc[t++] += wb[r] * b[c];
     }
-    // the block fold: a shuffle tree per wave, the four waves in order
-    __shared__ double s_red[4][GSR_COLOR_SUMS_LEN];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < COLOR_NACC; ++k) {
-        double v = acc[k];
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-        if (lane == 0) s_red[wv][k] = v;
-    }
     for (int o = 32; o > 0; o >>= 1) { skipped += __shfl_xor(skipped, o); outside += __shfl_xor(outside, o); }
-    if (lane == 0) {
+    if ((threadIdx.x & 63) == 0) {
         if (skipped) atomicAdd(&counters[0], (unsigned long long)skipped);
         if (outside) atomicAdd(&counters[1], (unsigned long long)outside);
     }
-    __syncthreads();
-    if (threadIdx.x < GSR_COLOR_SUMS_LEN) {
-        const int k = threadIdx.x;
-        partials[(int64_t)blockIdx.x * GSR_COLOR_SUMS_LEN + k] = k < COLOR_NACC ? ((s_red[0][k] + s_red[1][k]) + s_red[2][k]) + s_red[3][k] : 0.0;
-    }
-}
-
-// One wavefront per sum: lane l adds the partials of blocks l, l + 64, ... in order, then a fixed shuffle tree
-__global__ __launch_bounds__(64) void k_color_finalize(int nblocks, const double* __restrict__ partials, double* __restrict__ out) {
-    const int k = blockIdx.x, lane = threadIdx.x;
-    double s = 0.0;
-    for (int b = lane; b < nblocks; b += 64) s += partials[(int64_t)b * GSR_COLOR_SUMS_LEN + k];
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    if (lane == 0) out[k] = s;
+    block_fold_store<COLOR_NACC, GSR_COLOR_SUMS_LEN, wave_sum_xor>(acc, partials, (int)blockIdx.x);
+    if (threadIdx.x >= COLOR_NACC && threadIdx.x < GSR_COLOR_SUMS_LEN) partials[(int64_t)blockIdx.x * GSR_COLOR_SUMS_LEN + threadIdx.x] = 0.0;   // the row's padding
 }
 
 // X.m[0..8] = M (row-major), X.m[9..11] = the DC offset.  A lane reads its triple before it writes it: in place is safe.
@@ -171,7 +151,7 @@ extern "C" int32_t gsr_color_sums(const float* s_dc, const float* s_opacity, int
     GSR_TRY(os.scratch(2 * 8, &counters));
     GSR_HIP(hipMemsetAsync(counters, 0, 2 * 8, st));
     hipLaunchKernelGGL(k_color_sums, dim3(nblk), dim3(256), 0, st, n_pairs, dpairs, dsdc, dsop, ns, dtdc, dtop, nt, Xs, Xt, huber_k, partials, counters);
-    hipLaunchKernelGGL(k_color_finalize, dim3(GSR_COLOR_SUMS_LEN), dim3(64), 0, st, nblk, (const double*)partials, dsums);
+    hipLaunchKernelGGL(k_fold_partials<64>, dim3(GSR_COLOR_SUMS_LEN), dim3(64), 0, st, (int64_t)nblk, GSR_COLOR_SUMS_LEN, (const double*)partials, dsums);
     GSR_HIP(hipMemcpyAsync(hs, dsums, sizeof(hs), hipMemcpyDeviceToHost, st));
     GSR_HIP(hipMemcpyAsync(hc, counters, sizeof(hc), hipMemcpyDeviceToHost, st));
     GSR_TRY(os.finish());

@@ -13,7 +13,7 @@
 //                           search over contiguous row spans of the sorted target, exact 1-NN
 //                           (ties -> lowest input index), strict d^2 < max_corr^2, residual and
 //                           Jacobian, float64 accumulators reduced wave -> block -> per-block
-//                           partials; k_icp_finalize sums the partials in a fixed order.
+//                           partials; k_fold_partials sums the partials (the fixed order: gsr_fold.h).
 //                           No per-point writes; algorithmic bytes 24 (point-to-point) or
 //                           48 (point-to-plane, float64 normals) per source point.
 //   k_icp_nn                the search alone (thread per point, 56 VGPRs): used with a streaming accumulate kernel
@@ -29,11 +29,13 @@
 //
 // Accumulator layout (GSR_ICP_ACC_LEN = 32 doubles), see include/gsr_hip.h.
 #include "gsr_common.h"
+#include "gsr_fold.h"
 #include "gsr_normals.h"
 #include "gsr_solve.h"
 #include "gsr_features.h"
 #include "gsr_grid.h"
 #include "gsr_oneshot.h"
+#include "gsr_test_hooks.h"
 
 #include <float.h>
 #include <math.h>
@@ -466,63 +468,59 @@ __global__ __launch_bounds__(256) void k_icp_intensity(int64_t n, const unsigned
     }
 }
 
-// Sum of a double over the 64 lanes (every lane gets it) in a fixed order, without the LDS crossbar: four DPP row rotations
-// and the two permlane swaps, on the two dwords of the value.  (30 accumulators x 6 steps of __shfl_xor were 360
-// ds_bpermute per wave, 24 LDS-pipe cycles each: a third of the accumulate kernel on a 185 k-point level.)
-template <int CTRL>
-__device__ __forceinline__ double dpp_d(double v) {
-    const long long b = __builtin_bit_cast(long long, v);
-    const int lo = __builtin_amdgcn_update_dpp(0, (int)b, CTRL, 0xf, 0xf, false);
-    const int hi = __builtin_amdgcn_update_dpp(0, (int)(b >> 32), CTRL, 0xf, 0xf, false);
-    return __builtin_bit_cast(double, ((long long)hi << 32) | (unsigned)lo);
-}
-template <bool HALF>        // HALF: lanes l and l ^ 32, else l and l ^ 16
-__device__ __forceinline__ double swap_sum_d(double v) {
-    const long long b = __builtin_bit_cast(long long, v);
-    const unsigned lo = (unsigned)b, hi = (unsigned)(b >> 32);
-    const auto rl = HALF ? __builtin_amdgcn_permlane32_swap(lo, lo, false, false) : __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
-    const auto rh = HALF ? __builtin_amdgcn_permlane32_swap(hi, hi, false, false) : __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
-    const double a = __builtin_bit_cast(double, ((long long)(unsigned)rh[0] << 32) | (unsigned)rl[0]);
-    const double c = __builtin_bit_cast(double, ((long long)(unsigned)rh[1] << 32) | (unsigned)rl[1]);
-    return a + c;
-}
-__device__ __forceinline__ double wave_sum_d(double v) {
-    v += dpp_d<0x128>(v);       // row_ror:8
-    v += dpp_d<0x124>(v);       // row_ror:4
-    v += dpp_d<0x122>(v);       // row_ror:2
-    v += dpp_d<0x121>(v);       // row_ror:1
-    v = swap_sum_d<false>(v);
-    v = swap_sum_d<true>(v);
-    return v;
-}
-
-template <int NACC>
-__device__ __forceinline__ void block_reduce_store(double (&acc)[NACC], double* __restrict__ partials, int row = -1) {
-    if (row < 0) row = (int)blockIdx.x;
-    __shared__ double s_red[4][NACC];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < NACC; ++k) {
-        const double v = wave_sum_d(acc[k]);
-        if (lane == 0) s_red[wv][k] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < NACC) {
-        const int k = threadIdx.x;
-        const double v = ((s_red[0][k] + s_red[1][k]) + s_red[2][k]) + s_red[3][k];
-        partials[(int64_t)row * GSR_ICP_ACC_LEN + k] = v;
-    }
-}
-
 // KIND 0: point-to-point sums (17 values); KIND 1: point-to-plane normal equations (30 values); KIND 4: kind 0's 17 sums in the same
 // order plus slot 17 = sum |a|^2 (18 values) -- an instantiation of its own: the kind-0 kernels carry no trace of it
+constexpr int icp_nacc(int kind) { return kind == 0 ? 17 : (kind == 4 ? 18 : 30); }
+
+// One accepted correspondence: source row i moved to p = T p0, matched to the target's sorted row j.  Both accumulate kernels call
+// this; they differ only in where T lives (a kernel argument, the device-resident state).
+template <int KIND>
+__device__ __forceinline__ void icp_rows(double (&acc)[icp_nacc(KIND)], const double* T, const IcpGrid& g, const float4* __restrict__ Tq,
+                                         const double* __restrict__ Tn, const double* __restrict__ Sc, const ColorArgs& ca, double px, double py,
+                                         double pz, int64_t i, int j, int loss, double kparam) {
+    constexpr int NACC = icp_nacc(KIND);
+    const float4 q = Tq[j];
+    const double qx = (double)q.x, qy = (double)q.y, qz = (double)q.z;
+    const double ddx = px - qx, ddy = py - qy, ddz = pz - qz;
+    const double d2 = ddx * ddx + ddy * ddy + ddz * ddz;
+    acc[0] += 1.0;
+    acc[1] += d2;
+    if constexpr (KIND == 0 || KIND == 4) {
+        const double ax = px - g.cx, ay = py - g.cy, az = pz - g.cz;
+        const double bx = qx - g.cx, by = qy - g.cy, bz = qz - g.cz;
+        acc[2] += ax; acc[3] += ay; acc[4] += az;
+        acc[5] += bx; acc[6] += by; acc[7] += bz;
+        acc[8] += ax * bx; acc[9] += ax * by; acc[10] += ax * bz;
+        acc[11] += ay * bx; acc[12] += ay * by; acc[13] += ay * bz;
+        acc[14] += az * bx; acc[15] += az * by; acc[16] += az * bz;
+        if constexpr (KIND == 4) acc[17] += ax * ax + ay * ay + az * az;        // Umeyama's source variance (with_scaling)
+    } else if constexpr (KIND == 2) {
+        icp_gicp_rows<NACC>(acc, T, px, py, pz, qx, qy, qz, Sc + 6 * i, Tn + 6 * (int64_t)j, loss, kparam);
+    } else if constexpr (KIND == 3) {
+        icp_colored_rows<NACC>(acc, ca, px, py, pz, qx, qy, qz, Tn[3 * (int64_t)j], Tn[3 * (int64_t)j + 1], Tn[3 * (int64_t)j + 2], i, j, loss, kparam);
+    } else {
+        const double nx = Tn[3 * (int64_t)j], ny = Tn[3 * (int64_t)j + 1], nz = Tn[3 * (int64_t)j + 2];
+        const double r = (px - qx) * nx + (py - qy) * ny + (pz - qz) * nz;
+        const double w = icp_weight(loss, kparam, r);
+        const double J[6] = {py * nz - pz * ny, pz * nx - px * nz, px * ny - py * nx, nx, ny, nz};
+        int t = 2;
+#pragma unroll
+        for (int a = 0; a < 6; ++a)
+#pragma unroll
+            for (int b = a; b < 6; ++b) acc[t++] += J[a] * w * J[b];
+#pragma unroll
+        for (int a = 0; a < 6; ++a) acc[23 + a] += J[a] * w * r;
+        acc[29] += r * r;
+    }
+}
+
 template <int KIND>
 __global__ __launch_bounds__(256) void k_icp_accumulate(int64_t ns, const float* __restrict__ src, Xform T, IcpGrid g,
                                                         const int* __restrict__ cellStart, const int* __restrict__ nn_j,
                                                         const float4* __restrict__ Tq, const double* __restrict__ Tn,
                                                         const double* __restrict__ Sc, ColorArgs ca, double max_corr2,
                                                         int loss, double kparam, double* __restrict__ partials) {
-    constexpr int NACC = KIND == 0 ? 17 : (KIND == 4 ? 18 : 30);
+    constexpr int NACC = icp_nacc(KIND);
     double acc[NACC];
 #pragma unroll
     for (int k = 0; k < NACC; ++k) acc[k] = 0.0;
@@ -540,41 +538,9 @@ __global__ __launch_bounds__(256) void k_icp_accumulate(int64_t ns, const float*
             j = icp_nearest<0>(g, cellStart, Tq, px, py, pz, dd, max_corr2);
             if (j < 0 || !(dd < max_corr2)) continue;
         }
-        const float4 q = Tq[j];
-        const double qx = (double)q.x, qy = (double)q.y, qz = (double)q.z;
-        const double ddx = px - qx, ddy = py - qy, ddz = pz - qz;
-        const double d2 = ddx * ddx + ddy * ddy + ddz * ddz;
-        acc[0] += 1.0;
-        acc[1] += d2;
-        if constexpr (KIND == 0 || KIND == 4) {
-            const double ax = px - g.cx, ay = py - g.cy, az = pz - g.cz;
-            const double bx = qx - g.cx, by = qy - g.cy, bz = qz - g.cz;
-            acc[2] += ax; acc[3] += ay; acc[4] += az;
-            acc[5] += bx; acc[6] += by; acc[7] += bz;
-            acc[8] += ax * bx; acc[9] += ax * by; acc[10] += ax * bz;
-            acc[11] += ay * bx; acc[12] += ay * by; acc[13] += ay * bz;
-            acc[14] += az * bx; acc[15] += az * by; acc[16] += az * bz;
-            if constexpr (KIND == 4) acc[17] += ax * ax + ay * ay + az * az;        // Umeyama's source variance (with_scaling)
-        } else if constexpr (KIND == 2) {
-            icp_gicp_rows<NACC>(acc, T.m, px, py, pz, qx, qy, qz, Sc + 6 * i, Tn + 6 * (int64_t)j, loss, kparam);
-        } else if constexpr (KIND == 3) {
-            icp_colored_rows<NACC>(acc, ca, px, py, pz, qx, qy, qz, Tn[3 * (int64_t)j], Tn[3 * (int64_t)j + 1], Tn[3 * (int64_t)j + 2], i, j, loss, kparam);
-        } else {
-            const double nx = Tn[3 * (int64_t)j], ny = Tn[3 * (int64_t)j + 1], nz = Tn[3 * (int64_t)j + 2];
-            const double r = (px - qx) * nx + (py - qy) * ny + (pz - qz) * nz;
-            const double w = icp_weight(loss, kparam, r);
-            const double J[6] = {py * nz - pz * ny, pz * nx - px * nz, px * ny - py * nx, nx, ny, nz};
-            int t = 2;
-#pragma unroll
-            for (int a = 0; a < 6; ++a)
-#pragma unroll
-                for (int b = a; b < 6; ++b) acc[t++] += J[a] * w * J[b];
-#pragma unroll
-            for (int a = 0; a < 6; ++a) acc[23 + a] += J[a] * w * r;
-            acc[29] += r * r;
-        }
+        icp_rows<KIND>(acc, T.m, g, Tq, Tn, Sc, ca, px, py, pz, i, j, loss, kparam);
     }
-    block_reduce_store<NACC>(acc, partials);
+    block_fold_store<NACC, GSR_ICP_ACC_LEN, wave_sum_rows>(acc, partials, (int)blockIdx.x);
 }
 
 // Information matrix of a registered pair (gsr_icp_information): Lambda = sum G^T G over the correspondences, G = [-[q]x | I3] at the
@@ -609,17 +575,7 @@ __global__ __launch_bounds__(256) void k_icp_information(int64_t ns, const float
         acc[4] += qx * qx; acc[5] += qx * qy; acc[6] += qx * qz;
         acc[7] += qy * qy; acc[8] += qy * qz; acc[9] += qz * qz;
     }
-    block_reduce_store<ICP_INFO_NACC>(acc, partials);
-}
-
-// One wavefront per accumulator: lane l sums the partials of blocks l, l+64, ... in order, then a fixed
-// shuffle tree combines the 64 lane sums -- a deterministic order whatever the launch.
-__global__ __launch_bounds__(64) void k_icp_finalize(int nblocks, const double* __restrict__ partials, double* __restrict__ out) {
-    const int k = blockIdx.x, lane = threadIdx.x;
-    double s = 0.0;
-    for (int b = lane; b < nblocks; b += 64) s += partials[(int64_t)b * GSR_ICP_ACC_LEN + k];
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    if (lane == 0) out[k] = s;
+    block_fold_store<ICP_INFO_NACC, GSR_ICP_ACC_LEN, wave_sum_rows>(acc, partials, (int)blockIdx.x);
 }
 
 __global__ __launch_bounds__(256) void k_icp_correspond(int64_t ns, const float* __restrict__ src, Xform T, const int* __restrict__ nn_j,
@@ -687,7 +643,7 @@ __global__ __launch_bounds__(256) void k_cov_from_normals(int64_t n, const doubl
 // doubles.  Driving it from the host costs a device->host copy and a stream synchronisation per
 // iteration (~60 us, comparable to the kernel itself on small levels); here the transform, the
 // convergence test and the solve stay on the device: k_icp_accumulate_dev reads T from IcpState,
-// k_icp_step reduces the block partials (same fixed order as k_icp_finalize), tests convergence,
+// k_icp_step reduces the block partials (the fixed order of gsr_fold.h), tests convergence,
 // solves and updates T in ONE thread.  The host enqueues iterations in chunks and looks at `done` once
 // per chunk; iterations enqueued after convergence return immediately.
 struct IcpState {
@@ -711,7 +667,7 @@ __global__ __launch_bounds__(256, 1) void k_icp_accumulate_dev(int64_t ns, const
                                                             const float4* __restrict__ Tq, const double* __restrict__ Tn,
                                                             const double* __restrict__ Sc, ColorArgs ca, double max_corr2,
                                                             int loss, double kparam, double* partials, int nb_logical) {
-    constexpr int NACC = KIND == 0 ? 17 : (KIND == 4 ? 18 : 30);
+    constexpr int NACC = icp_nacc(KIND);
     const IcpRange rg = icp_block_range(ns, nb_logical < 0 ? -nb_logical : nb_logical, nb_logical > 0);
     if (st->done) return;                           // converged: nothing to search
     double T[12];
@@ -735,57 +691,21 @@ __global__ __launch_bounds__(256, 1) void k_icp_accumulate_dev(int64_t ns, const
             j = icp_nearest<BLOCK>(g, cellStart, Tq, px, py, pz, dd, max_corr2);
             if (j < 0 || !(dd < max_corr2)) continue;
         }
-        const float4 q = Tq[j];
-        const double qx = (double)q.x, qy = (double)q.y, qz = (double)q.z;
-        const double ddx = px - qx, ddy = py - qy, ddz = pz - qz;
-        const double d2 = ddx * ddx + ddy * ddy + ddz * ddz;
-        acc[0] += 1.0;
-        acc[1] += d2;
-        if constexpr (KIND == 0 || KIND == 4) {
-            const double ax = px - g.cx, ay = py - g.cy, az = pz - g.cz;
-            const double bx = qx - g.cx, by = qy - g.cy, bz = qz - g.cz;
-            acc[2] += ax; acc[3] += ay; acc[4] += az;
-            acc[5] += bx; acc[6] += by; acc[7] += bz;
-            acc[8] += ax * bx; acc[9] += ax * by; acc[10] += ax * bz;
-            acc[11] += ay * bx; acc[12] += ay * by; acc[13] += ay * bz;
-            acc[14] += az * bx; acc[15] += az * by; acc[16] += az * bz;
-            if constexpr (KIND == 4) acc[17] += ax * ax + ay * ay + az * az;        // Umeyama's source variance (with_scaling)
-        } else if constexpr (KIND == 2) {
-            icp_gicp_rows<NACC>(acc, T, px, py, pz, qx, qy, qz, Sc + 6 * i, Tn + 6 * (int64_t)j, loss, kparam);
-        } else if constexpr (KIND == 3) {
-            icp_colored_rows<NACC>(acc, ca, px, py, pz, qx, qy, qz, Tn[3 * (int64_t)j], Tn[3 * (int64_t)j + 1], Tn[3 * (int64_t)j + 2], i, j, loss, kparam);
-        } else {
-            const double nx = Tn[3 * (int64_t)j], ny = Tn[3 * (int64_t)j + 1], nz = Tn[3 * (int64_t)j + 2];
-            const double r = (px - qx) * nx + (py - qy) * ny + (pz - qz) * nz;
-            const double w = icp_weight(loss, kparam, r);
-            const double J[6] = {py * nz - pz * ny, pz * nx - px * nz, px * ny - py * nx, nx, ny, nz};
-            int t = 2;
-#pragma unroll
-            for (int a = 0; a < 6; ++a)
-#pragma unroll
-                for (int b = a; b < 6; ++b) acc[t++] += J[a] * w * J[b];
-#pragma unroll
-            for (int a = 0; a < 6; ++a) acc[23 + a] += J[a] * w * r;
-            acc[29] += r * r;
-        }
+        icp_rows<KIND>(acc, T, g, Tq, Tn, Sc, ca, px, py, pz, i, j, loss, kparam);
     }
-    block_reduce_store<NACC>(acc, partials, rg.row);
+    block_fold_store<NACC, GSR_ICP_ACC_LEN, wave_sum_rows>(acc, partials, rg.row);
 }
 
 // `reduced` == NULL: fold the block partials here (single GPU).  Multi-GPU source split: k_icp_reduce folds them into a
 // device vector, the all-reduce callback sums that vector over the ranks (RCCL, on this stream), and this kernel starts
 // from the reduced vector -- every rank then takes the identical decision and the identical update.
 // 512 threads: the single-thread solve behind the reduction needs ~150 registers (a 1024-thread launch bound allows 128: it
-// spilled to scratch).  The reduction keeps k_icp_finalize's summation ORDER per accumulator k -- s_l = sum over the blocks
-// b = l, l + 64, ... ascending, then the butterfly s_l + s_(l ^ 32), + (l ^ 16), ... down to lane 0 -- but reads the
-// partials as rows: thread (g = t / 32, k = t % 32) forms s_g, s_(g+16), s_(g+32), s_(g+48) of accumulator k (32 threads
-// read one 256-byte row per load; the old wave-per-accumulator loop read 8 bytes of 64 different rows), folds the two
-// butterfly steps it holds both operands of, and an LDS tree over g does the remaining four.
+// spilled to scratch).
 #define ICP_STEP_THREADS 512
-// The fold in k_icp_finalize's summation ORDER per accumulator k -- s_l = sum over the blocks b = l, l + 64, ... ascending, then the
-// butterfly s_l + s_(l ^ 32), + (l ^ 16), ... down to lane 0 -- with THREADS = 32 G threads: thread (g = t / 32, k = t % 32) forms
-// the lane sums s_g, s_(g + G), ... of accumulator k (32 threads read one 256-byte row per load, four rounds of loads in flight),
-// folds the butterfly steps it holds both operands of, and an LDS tree over g does the remaining log2 G.  Result: s_x[0][k].
+// k_fold_partials<64>'s sums, bit for bit (the order: gsr_fold.h), read as rows: with THREADS = 32 G threads, thread (g = t / 32,
+// k = t % 32) forms the lane sums s_g, s_(g + G), ... of accumulator k (32 threads read one 256-byte row per load, four rounds of
+// loads in flight; a wave per accumulator read 8 bytes of 64 different rows), folds the steps of the tree it holds both operands of,
+// and an LDS tree over g does the remaining log2 G.  Result: s_x[0][k].
 template <int THREADS>
 __device__ __forceinline__ void icp_fold_partials(int nblocks, const double* partials, const double* __restrict__ reduced, double (*s_x)[32]) {
     constexpr int G = THREADS / 32, NL = 64 / G;
@@ -857,7 +777,7 @@ __global__ __launch_bounds__(ICP_STEP_THREADS) void k_icp_step(int nblocks, cons
     icp_step_solve(&s_x[0][0], s_st, st);
 }
 
-// rank-local accumulator vector of one iteration (same fixed summation order as k_icp_finalize); zeros once converged, so
+// rank-local accumulator vector of one iteration (k_fold_partials<64>'s sums, 16 waves over the 32 of them); zeros once converged, so
 // that the ranks keep calling the collective in step
 __global__ __launch_bounds__(1024) void k_icp_reduce(int nblocks, const double* __restrict__ partials, const IcpState* __restrict__ st,
                                                      double* __restrict__ out) {
@@ -867,9 +787,19 @@ __global__ __launch_bounds__(1024) void k_icp_reduce(int nblocks, const double* 
         double s = 0.0;
         if (!done)
             for (int b = lane; b < nblocks; b += 64) s += partials[(int64_t)b * GSR_ICP_ACC_LEN + k];
-        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+        s = wave_sum_xor(s);
         if (lane == 0) out[k] = s;
     }
+}
+
+// gsr_debug_fold: thread t of block b holds row 256 b + t of x [n][3], zeros past n; block_fold_store and nothing else
+template <double (*WaveSum)(double)>
+__global__ __launch_bounds__(256) void k_debug_fold(int64_t n, const double* __restrict__ x, double* __restrict__ partials) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    double acc[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) acc[k] = i < n ? x[3 * i + k] : 0.0;
+    block_fold_store<3, 4, WaveSum>(acc, partials, (int)blockIdx.x);
 }
 
 }  // namespace gsr
@@ -1023,7 +953,7 @@ int32_t run_accumulate(gsr_icp_ctx* c, const double* T, int kind, int loss, doub
     else
         hipLaunchKernelGGL(k_icp_accumulate<2>, dim3(nb), dim3(256), 0, st, c->ns, c->src.as<float>(), X, c->index.grid, c->index.cellStart.as<int>(), nnj,
                            c->index.Tq.as<float4>(), c->Tc.as<double>(), c->Sc.as<double>(), cargs, mc2, loss, k, c->partials.as<double>());
-    hipLaunchKernelGGL(k_icp_finalize, dim3(GSR_ICP_ACC_LEN), dim3(64), 0, st, nb, c->partials.as<double>(), c->acc_dev.as<double>());
+    hipLaunchKernelGGL(k_fold_partials<64>, dim3(GSR_ICP_ACC_LEN), dim3(64), 0, st, (int64_t)nb, GSR_ICP_ACC_LEN, (const double*)c->partials.as<double>(), c->acc_dev.as<double>());
     if (timed) GSR_HIP(hipEventRecord(c->e1, st));
     GSR_HIP(hipMemcpyAsync(acc, c->acc_dev.p, GSR_ICP_ACC_LEN * 8, hipMemcpyDeviceToHost, st));
     GSR_HIP(hipStreamSynchronize(st));
@@ -1396,7 +1326,7 @@ int32_t gsr_icp_information(gsr_icp_ctx* c, const double* T, double* info36, int
     }
     hipLaunchKernelGGL(k_icp_information, dim3(nb), dim3(256), 0, st, c->ns, c->src.as<float>(), X, c->index.grid, c->index.cellStart.as<int>(), nnj, c->index.Tq.as<float4>(),
                        mc2, c->partials.as<double>());
-    hipLaunchKernelGGL(k_icp_finalize, dim3(ICP_INFO_NACC), dim3(64), 0, st, nb, c->partials.as<double>(), c->acc_dev.as<double>());
+    hipLaunchKernelGGL(k_fold_partials<64>, dim3(ICP_INFO_NACC), dim3(64), 0, st, (int64_t)nb, GSR_ICP_ACC_LEN, (const double*)c->partials.as<double>(), c->acc_dev.as<double>());
     double a[ICP_INFO_NACC];
     GSR_HIP(hipMemcpyAsync(a, c->acc_dev.p, sizeof(a), hipMemcpyDeviceToHost, st));
     GSR_HIP(hipStreamSynchronize(st));
@@ -1516,6 +1446,27 @@ int32_t gsr_cov_from_normals(const double* normals, int64_t n, double epsilon, d
     GSR_TRY(os.in(normals, (size_t)n * 24, &in));
     GSR_TRY(os.out(cov6, (size_t)n * 48, &out));
     hipLaunchKernelGGL(k_cov_from_normals, dim3(stride_grid(n)), dim3(256), 0, os.st, n, in, epsilon, out);
+    return os.finish();
+}
+
+// test hook (gsr_test_hooks.h): the two stages of gsr_fold.h on caller-supplied rows
+int32_t gsr_debug_fold(const double* x, int64_t n, int32_t order, int32_t final_threads, double* out3, int32_t device) {
+    if (n < 0 || n >= ((int64_t)1 << 31) || (n > 0 && !x) || !out3 || (order != 0 && order != 1) || (final_threads != 64 && final_threads != 256))
+        return fail(GSR_E_INVALID, "gsr_debug_fold: bad argument");
+    GSR_TRY(open_device(device, "gsr_debug_fold"));
+    out3[0] = out3[1] = out3[2] = 0.0;
+    if (n == 0) return GSR_OK;
+    OneShot os(nullptr, false, "gsr_debug_fold");
+    const int nb = (int)((n + 255) / 256);
+    const double* dx = nullptr;
+    double *partials = nullptr, *dout = nullptr;
+    GSR_TRY(os.in(x, (size_t)n * 24, &dx));
+    GSR_TRY(os.scratch((size_t)nb * 4 * 8, &partials));
+    GSR_TRY(os.out(out3, 3 * 8, &dout));
+    if (order == 0) hipLaunchKernelGGL(k_debug_fold<wave_sum_xor>, dim3(nb), dim3(256), 0, os.st, n, dx, partials);
+    else hipLaunchKernelGGL(k_debug_fold<wave_sum_rows>, dim3(nb), dim3(256), 0, os.st, n, dx, partials);
+    if (final_threads == 64) hipLaunchKernelGGL(k_fold_partials<64>, dim3(3), dim3(64), 0, os.st, (int64_t)nb, 4, (const double*)partials, dout);
+    else hipLaunchKernelGGL(k_fold_partials<256>, dim3(3), dim3(256), 0, os.st, (int64_t)nb, 4, (const double*)partials, dout);
     return os.finish();
 }
 

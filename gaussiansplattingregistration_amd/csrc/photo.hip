@@ -4,11 +4,12 @@
 //   k_photo_tiles     a group per 16 x 16 tile, a lane per pixel.  The tile's target intensity (float64), depth and coverage with a
 //                     one-pixel halo go to LDS (zeros outside the image) for the Sobel taps and the nine-pixel coverage test; every
 //                     lane forms its two Jacobian rows and residuals in float64 (14 values), and each of the 30 terms is folded as
-//                     it is formed: a shuffle tree per wave, the four waves in order.  No per-lane array of 30 accumulators lives
-//                     across the fold.
-//   k_photo_finalize  one group of 256 per sum adds the groups' partials in a fixed order (k_metrics_final's idiom).
+//                     it is formed, in the fixed order of gsr_fold.h (the xor tree per wave, the four waves in order).  No per-lane
+//                     array of 30 accumulators lives across the fold.
+//   k_fold_partials<256>  one group of 256 per sum adds the groups' partials (gsr_fold.h).
 // No atomics: the same inputs give the same bits.
 #include "gsr_common.h"
+#include "gsr_fold.h"
 #include "gsr_oneshot.h"
 
 #include <float.h>
@@ -95,15 +96,13 @@ __global__ __launch_bounds__(PT * PT) void k_photo_tiles(int32_t H, int32_t W, P
             rD = cam.sD * (dt - z);
         }
     }
-    // the group's fold, one term at a time: a shuffle tree per wave, the four waves in order.  A pixel that does not count adds +0.0.
+    // the group's fold (block_fold_store's, gsr_fold.h), one term at a time.  A pixel that does not count adds +0.0.
     const int lane = t & 63, wv = t >> 6;
     const bool any = __any(ok) != 0;                 // a wave without a counted pixel: thirty zeros, no tree
 #define PHOTO_FOLD(K, TERM)                                                        \
     {                                                                              \
-        double v_ = (TERM);                                                        \
-        if (any)                                                                   \
-            for (int o = 32; o > 0; o >>= 1) v_ += __shfl_xor(v_, o);              \
-        if (lane == 0) s_red[wv][K] = any ? v_ : 0.0;                              \
+        const double v_ = any ? wave_sum_xor(TERM) : 0.0;                          \
+        if (lane == 0) s_red[wv][K] = v_;                                          \
     }
     {
         int k = 0;
@@ -123,19 +122,6 @@ __global__ __launch_bounds__(PT * PT) void k_photo_tiles(int32_t H, int32_t W, P
         const int64_t g = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
         partial[g * GSR_PHOTO_SUMS_LEN + t] = ((s_red[0][t] + s_red[1][t]) + s_red[2][t]) + s_red[3][t];
     }
-}
-
-// One group of 256 per sum: thread t adds the partials of groups t, t + 256, ... in order, then a shuffle tree per wave and the four
-// waves in order (a single wavefront per sum would walk a chain of dependent loads four times as long)
-__global__ __launch_bounds__(256) void k_photo_finalize(int64_t groups, const double* __restrict__ partial, double* __restrict__ out) {
-    __shared__ double s_w[4];
-    const int k = blockIdx.x, t = threadIdx.x, lane = t & 63;
-    double s = 0.0;
-    for (int64_t g = t; g < groups; g += 256) s += partial[g * GSR_PHOTO_SUMS_LEN + k];
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    if (lane == 0) s_w[t >> 6] = s;
-    __syncthreads();
-    if (t == 0) out[k] = ((s_w[0] + s_w[1]) + s_w[2]) + s_w[3];
 }
 
 }  // namespace gsr
@@ -183,7 +169,7 @@ extern "C" int32_t gsr_photo_accumulate(const float* I_s, const float* D_s, cons
         GSR_TRY(os.scratch((size_t)groups * GSR_PHOTO_SUMS_LEN * sizeof(double), &partial));
         GSR_TRY(os.scratch(GSR_PHOTO_SUMS_LEN * sizeof(double), &res));
         hipLaunchKernelGGL(k_photo_tiles, grid, dim3(PT * PT), 0, os.st, height, width, cam, dIs, dDs, dAs, dIt, dDt, dAt, partial);
-        hipLaunchKernelGGL(k_photo_finalize, dim3(GSR_PHOTO_SUMS_LEN), dim3(256), 0, os.st, groups, (const double*)partial, res);
+        hipLaunchKernelGGL(k_fold_partials<256>, dim3(GSR_PHOTO_SUMS_LEN), dim3(256), 0, os.st, groups, GSR_PHOTO_SUMS_LEN, (const double*)partial, res);
         hipError_t e = hipGetLastError();
         if (e == hipSuccess) e = hipMemcpyAsync(host, res, sizeof(host), hipMemcpyDeviceToHost, os.st);
         GSR_TRY(os.wait(e));
