@@ -39,7 +39,8 @@ def main():
     print("%-74s %-22s %s" % ("kernel", "file parent -> head", "  ".join("%10s" % k for k in keys)))
     for n, d in zip(names, dem):
         p, h = parent.get(n), head.get(n)
-        short = re.sub(r"\(.*", "", d).replace("void ", "").replace("gsr::", "")
+        # without the anonymous namespace and the parameter list (the last parenthesis group: a template argument may hold a cast)
+        short = re.sub(r"\((?:[^()]|\([^()]*\))*\)$", "", d.replace("(anonymous namespace)::", "")).replace("void ", "").replace("gsr::", "")
         cols = []
         for k in keys:
             a, b = (p or {}).get(k, "-"), (h or {}).get(k, "-")
