@@ -58,7 +58,7 @@ def test_fit_planes_reference_compat_several_planes():
 
 def test_fit_planes_several_planes_and_exhaustion():
     """Three planes one after the other: every plane found once, inliers disjoint, original indices; and the device scoring
-    equals a float32 numpy restatement of the same test on every candidate."""
+    lies inside the bounds of the float64 model (tests/plane_model.py) on every candidate."""
     import sys
     from gaussiansplattingregistration_amd.utils import plane_fitting_util as pf
     sys.path.insert(0, GOLDEN)
@@ -85,12 +85,13 @@ def test_fit_planes_several_planes_and_exhaustion():
     counts = np.zeros(40, np.uint32); best = C.c_int32(-1); mask = np.empty(len(p32), np.uint8)
     assert L.gsr_plane_score(p32.ctypes.data, n32.ctypes.data, len(p32), cands.ctypes.data, 40, 0.02, 0.9, counts.ctypes.data, mask.ctypes.data,
                              C.byref(best), 0, 0, None) == 0
-    want = []
-    for c in cands:
-        dist = (p32 @ c[:3] + c[3]) / c[7]
-        want.append(int(((np.abs(dist) < np.float32(0.02)) & (np.abs(n32 @ c[4:7]) > np.float32(0.9))).sum()))
-    assert np.abs(counts.astype(np.int64) - np.array(want)).max() <= 3                # float32 summation order of the dot products
-    assert best.value == int(np.argmax(counts)) and mask.sum() == counts[best.value]
+    import plane_model
+    sure_in, undecided = plane_model.score(p32, n32, cands, 0.02, 0.9)                # float64; undecided: inside the float32 rounding band
+    lo = sure_in.sum(1)
+    assert (lo <= counts).all() and (counts <= lo + undecided.sum(1)).all(), (counts, lo, undecided.sum(1))
+    assert best.value == plane_model.best(counts) == int(np.argmax(counts)) and mask.sum() == counts[best.value]
+    decided = ~undecided[best.value]
+    assert np.array_equal(mask[decided].astype(bool), sure_in[best.value][decided])
     # nothing to find: no plane, empty lists
     torch.manual_seed(1)
     assert pf.fit_planes(_PC(pts[:50], nrm[:50]), 2, 20, 1e-9, 0.999999, 0.0) == ([], [])
