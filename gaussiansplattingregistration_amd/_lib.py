@@ -161,6 +161,9 @@ SIGNATURES = {
     "gsr_d2d_set_source": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32]),
     "gsr_d2d_accumulate": (_i32, [_vp, _vp, _f64, _f64, _vp]),
     "gsr_d2d_register": (_i32, [_vp, _vp, _f64, _f64, _f64, _i32, _vp, _vp]),
+    "gsr_loss_create": (_i32, [_i32, C.POINTER(_vp)]),
+    "gsr_loss_destroy": (_i32, [_vp]),
+    "gsr_loss_l1_dssim": (_i32, [_vp, _vp, _vp, _i32, _i32, _f64, _vp, _vp, _vp]),
 }
 # private test hooks (csrc/gsr_test_hooks.h): exported by the library, not part of the public header
 TEST_HOOKS = {

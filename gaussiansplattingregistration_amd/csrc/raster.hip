@@ -31,6 +31,7 @@
 
 #include "gsr_common.h"
 #include "gsr_oneshot.h"
+#include "gsr_ssim_window.h"
 
 using namespace gsr;
 
@@ -911,9 +912,7 @@ extern "C" int32_t gsr_raster_get_backward_timing(gsr_raster_ctx* c, float* ms) 
 // ---- image metrics ---------------------------------------------------------------------------------------------------------------
 namespace {
 
-constexpr int MT = 16, WIN = 11, HALO = 5, MTH = MT + 2 * HALO;       // 16 x 16 pixels per group, 26 x 26 with the halo
-
-struct SsimWindow { double w[WIN]; };
+constexpr int MT = 16, WIN = SSIM_WIN, HALO = 5, MTH = MT + 2 * HALO;       // 16 x 16 pixels per group, 26 x 26 with the halo
 
 // One group per 16 x 16 tile of one channel.  The halo of both images goes to LDS (zeros outside: the padding of the convolution),
 // a horizontal pass leaves the five moment rows (a, b, a a, b b, a b) in LDS, the vertical pass gives every pixel its SSIM term.
@@ -988,10 +987,7 @@ __global__ __launch_bounds__(256) void k_metrics_final(int64_t groups, double co
 extern "C" int32_t gsr_image_metrics(const float* a, const float* b, int32_t height, int32_t width, int32_t on_device, double* out, int32_t device, void* stream) {
     if (!a || !b || !out || height <= 0 || width <= 0) return fail(GSR_E_INVALID, "gsr_image_metrics: bad argument");
     GSR_TRY(open_device(device, "gsr_image_metrics"));
-    SsimWindow win;
-    double sum = 0.0;
-    for (int j = 0; j < WIN; ++j) { win.w[j] = exp(-(double)((j - WIN / 2) * (j - WIN / 2)) / (2.0 * 1.5 * 1.5)); sum += win.w[j]; }
-    for (int j = 0; j < WIN; ++j) win.w[j] /= sum;
+    const SsimWindow win = ssim_window();
     const size_t bytes = (size_t)3 * (size_t)height * (size_t)width * sizeof(float);
     const dim3 grid((width + MT - 1) / MT, (height + MT - 1) / MT, 3);
     if (grid.y > 65535u) return fail(GSR_E_INVALID, "gsr_image_metrics: image too tall");

@@ -1,10 +1,13 @@
 """Fine-tuning of a (merged) splat model against photographs through the differentiable rasteriser (``raster.render_differentiable``,
 DESIGN.md 26): a short ``torch.optim.Adam`` run on the per-splat appearance -- DC colour, the other SH coefficients, opacity, optionally the
 positions -- that removes what a colour transform per scene (``match_colors``) and the moment-matching of pairs (``fuse_overlap``) leave at a
-seam.  The forward and backward passes are the HIP kernels of ``csrc/raster.hip``; the per-pixel loss and the optimiser are plain torch.
+seam.  The forward and backward passes are the HIP kernels of ``csrc/raster.hip``; the optimiser is plain torch, and so are the per-pixel
+losses ``"l2"`` and ``"l1"``.  ``loss="l1_dssim"`` is the loss 3DGS scenes were trained with, ``(1 - lambda) L1 + lambda (1 - SSIM)`` with
+``lambda_dssim = 0.2``: value and gradient come from one fused HIP kernel (``loss.l1_dssim``, ``csrc/imgloss.hip``) in
+float64 with a fixed order of summation, so the promise below -- two runs give the same bits -- holds with it too.
 
 Covariance is NOT tunable here: the model keeps ``_scaling`` / ``_rotation`` beside ``_covariance`` and the ``.ply`` stores those two, so a tuned
-``_covariance`` could not be saved.  No densification, no SSIM term, one camera per iteration.
+``_covariance`` could not be saved.  No densification, one camera per iteration.
 """
 from __future__ import annotations
 
@@ -15,6 +18,7 @@ from dataclasses import dataclass, field
 import numpy as np
 import torch
 
+from . import loss as image_loss
 from . import raster
 from .utils.rasterization_util import _camera_args
 
@@ -24,7 +28,8 @@ TUNABLE = ("dc", "sh_rest", "opacity", "xyz")
 @dataclass
 class FinetuneParams:
     """The learning rates are those published with 3DGS (feature 2.5e-3, the other SH coefficients a twentieth of it, opacity 0.05, position
-    1.6e-4).  ``params``: which tensors are tuned, of ``TUNABLE``.  ``loss``: ``"l2"`` (mean squared error) or ``"l1"``."""
+    1.6e-4).  ``params``: which tensors are tuned, of ``TUNABLE``.  ``loss``: ``"l2"`` (mean squared error), ``"l1"`` or
+    ``"l1_dssim"`` (``(1 - lambda_dssim) L1 + lambda_dssim (1 - SSIM)``, the fused kernel of ``loss.l1_dssim``)."""
     iterations: int = 200
     params: tuple = ("dc", "sh_rest", "opacity")
     lr_dc: float = 2.5e-3
@@ -33,6 +38,7 @@ class FinetuneParams:
     lr_xyz: float = 1.6e-4
     loss: str = "l2"
     background: tuple = (0.0, 0.0, 0.0)
+    lambda_dssim: float = 0.2
 
 
 @dataclass
@@ -65,8 +71,10 @@ class ModelFinetuner:
             raise ValueError(f"FinetuneParams.params: unknown tensor {unknown[0]!r} {TUNABLE} (covariance is not tunable: DESIGN.md 26)")
         if not self.params.params:
             raise ValueError("FinetuneParams.params is empty")
-        if self.params.loss not in ("l2", "l1"):
-            raise ValueError(f"FinetuneParams.loss: {self.params.loss!r} (l2, l1)")
+        if self.params.loss not in ("l2", "l1", "l1_dssim"):
+            raise ValueError(f"FinetuneParams.loss: {self.params.loss!r} (l2, l1, l1_dssim)")
+        if self.params.loss == "l1_dssim" and not 0.0 <= float(self.params.lambda_dssim) <= 1.0:
+            raise ValueError(f"FinetuneParams.lambda_dssim: {self.params.lambda_dssim!r} outside [0, 1]")
         self.images = images
         self.device = torch.device(device if device is not None else model.get_xyz.device)
         if self.device.type != "cuda":
@@ -125,8 +133,11 @@ class ModelFinetuner:
                     return None
                 cam, tgt = pairs[it % len(pairs)]
                 opt.zero_grad(set_to_none=True)
-                diff = render(cam) - tgt
-                loss = (diff * diff).mean() if p.loss == "l2" else diff.abs().mean()
+                if p.loss == "l1_dssim":
+                    loss = image_loss.l1_dssim(render(cam), tgt, p.lambda_dssim)
+                else:
+                    diff = render(cam) - tgt
+                    loss = (diff * diff).mean() if p.loss == "l2" else diff.abs().mean()
                 loss.backward()
                 opt.step()
                 result.losses.append(float(loss.detach()))

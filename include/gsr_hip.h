@@ -1160,6 +1160,42 @@ int32_t gsr_d2d_accumulate(gsr_d2d_ctx* ctx, const double* T, double cov_scale, 
 int32_t gsr_d2d_register(gsr_d2d_ctx* ctx, const double* init_T, double cov_scale, double cov_floor, double relative_score, int32_t max_iter,
                          double* out_T, gsr_d2d_report* report);
 
+/* ------------------------------------------------------- photometric loss of the fine-tuner */
+/* loss = (1 - lambda) L1 + lambda (1 - SSIM) of an image against a target, and its gradient with respect to the image, in one fused
+ * kernel.  csrc/imgloss.hip; restated in tests/ssim_loss_model.py.  The SSIM is the one gsr_image_metrics defines (11 x 11 Gaussian
+ * window, sigma 1.5, the outer product of the normalised 1-D window -- both entries take it from one host function --, zero padding,
+ * C1 = 0.01^2, C2 = 0.03^2, mean over all 3 H W terms), here on the INTERLEAVED (H, W, 3) layout the rasteriser writes.
+ *
+ * For an image a and a target b, both (height, width, 3) float32, N = 3 height width, one channel at a time, G* the zero-padded
+ * 11 x 11 filter (horizontal pass first, taps in ascending order):
+ *   mu1 = G*a   mu2 = G*b   m_aa = G*(a a)   m_bb = G*(b b)   m_ab = G*(a b)
+ *   s1 = m_aa - mu1^2   s2 = m_bb - mu2^2   s12 = m_ab - mu1 mu2
+ *   A1 = 2 mu1 mu2 + C1   A2 = 2 s12 + C2   B1 = mu1^2 + mu2^2 + C1   B2 = s1 + s2 + C2
+ *   S = A1 A2 / (B1 B2)
+ *   l1 = sum |a - b| / N     ssim = sum S / N     loss = (1 - lambda) l1 + lambda (1 - ssim)
+ * Gradient with respect to a (the target gets none).  Three maps, ZERO outside the image (a padded pixel has no SSIM term):
+ *   D1 = 2 mu2 A2 / (B1 B2) - 2 mu2 A1 / (B1 B2) - 2 mu1 S / B1 + 2 mu1 S / B2      D2 = -S / B2      D3 = 2 A1 / (B1 B2)
+ *   dloss/da = (1 - lambda) sign(a - b) / N - (lambda / N) (G*D1 + 2 a (G*D2) + b (G*D3)),   sign(0) = 0
+ * (the window is symmetric, so the zero-padded filter is its own adjoint).
+ *
+ * Arithmetic: float64 from the widened float32 pixels up to ONE rounding to float32 at the store of the gradient; no fused
+ * multiply-add; the sums l1 and ssim are folded in the fixed order of csrc/gsr_fold.h (every thread its own pixel over the channels
+ * in ascending order, the xor tree per wave, the four waves in order, k_fold_partials<256> over the tiles in row-major order): no
+ * atomics, the same inputs give the same bits.  Non-finite pixels are not treated specially.
+ *
+ * gsr_loss_create / gsr_loss_destroy: an owning context with a grow-only buffer of two float64 per 16 x 16 tile.
+ * gsr_loss_l1_dssim: image, target, loss_out and grad_image are DEVICE pointers on the context's device.  loss_out: double[3] =
+ * (loss, l1, ssim).  grad_image: (height, width, 3) float32, every entry OVERWRITTEN; NULL: the adjoint half is skipped and
+ * loss_out has the same bits.  The call is enqueued on `stream`, waits for nothing and allocates nothing once the context has grown
+ * to the image size (growing it frees the old buffer, which waits for the device).  GSR_E_INVALID with a message, before any device
+ * call: a NULL context, image, target or loss_out, a non-positive size, lambda outside [0, 1] (a NaN included), more than 65535 rows
+ * of tiles.  No device visible: GSR_E_NO_DEVICE. */
+typedef struct gsr_loss_ctx gsr_loss_ctx;
+int32_t gsr_loss_create(int32_t device, gsr_loss_ctx** out);
+int32_t gsr_loss_destroy(gsr_loss_ctx* ctx);
+int32_t gsr_loss_l1_dssim(gsr_loss_ctx* ctx, const float* image, const float* target, int32_t height, int32_t width, double lambda,
+                          double* loss_out, float* grad_image, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

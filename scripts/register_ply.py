@@ -42,8 +42,10 @@ rendered depths of a pixel may be for it to count.  Rigid only: refused with `--
 overlap of the two Gaussians (covariances times `--mixture-cov-scale` squared, plus `--mixture-cov-floor` on the diagonal), so the
 sampling noise of a one-nearest match does not reach the transform.  Rigid only: refused with `--with-scaling`.
 
-`--finetune CAMERAS.json --finetune-images DIR [--finetune-iters N] [--finetune-params dc,sh_rest,opacity]` (with `--out`): the merged cloud
-is fine-tuned against the photographs of those cameras (`finetune.ModelFinetuner`) after the merge and before the save.
+`--finetune CAMERAS.json --finetune-images DIR [--finetune-iters N] [--finetune-params dc,sh_rest,opacity] [--finetune-loss l2|l1|l1_dssim]
+[--finetune-lambda L]` (with `--out`): the merged cloud is fine-tuned against the photographs of those cameras (`finetune.ModelFinetuner`,
+DESIGN.md 26) after the merge and before the save.  `l1_dssim` is (1 - L) L1 + L (1 - SSIM), L = 0.2 by default, from the fused loss
+kernel.
 
 Prints the 4x4 transformation (first -> second), fitness and inlier RMSE; `--out` saves the merged cloud.
 """
@@ -107,6 +109,8 @@ def main():
     ap.add_argument("--finetune-images", metavar="DIR", help="directory of <img_name>.png, one per camera of --finetune")
     ap.add_argument("--finetune-iters", type=int, default=200, metavar="N")
     ap.add_argument("--finetune-params", default="dc,sh_rest,opacity", help="comma-separated, of dc, sh_rest, opacity, xyz")
+    ap.add_argument("--finetune-loss", choices=("l2", "l1", "l1_dssim"), default="l2", help="l1_dssim: (1 - lambda) L1 + lambda (1 - SSIM), the fused loss kernel")
+    ap.add_argument("--finetune-lambda", type=float, default=0.2, metavar="L", help="the weight of the SSIM term of --finetune-loss l1_dssim")
     a = ap.parse_args()
     if a.finetune and not (a.out and a.finetune_images):
         raise SystemExit("--finetune needs --out and --finetune-images")
@@ -256,9 +260,11 @@ def main():
             tf = time.perf_counter()
             merged.move_to_device("cuda:0")
             fr = ModelFinetuner(merged, load_cameras(a.finetune), a.finetune_images,
-                                FinetuneParams(iterations=a.finetune_iters, params=tuple(x for x in a.finetune_params.split(",") if x))).run()
+                                FinetuneParams(iterations=a.finetune_iters, params=tuple(x for x in a.finetune_params.split(",") if x), loss=a.finetune_loss,
+                                               lambda_dssim=a.finetune_lambda)).run()
             mean = lambda v: sum(v) / len(v) if v else float("nan")
-            print(f"fine-tuning ({a.finetune_params}): {fr.iterations} iterations over {len(fr.psnr_before)} cameras, loss {fr.losses[0] if fr.losses else float('nan'):.6g} -> "
+            which = "loss" if a.finetune_loss == "l2" else f"{a.finetune_loss} loss (lambda {a.finetune_lambda:g})" if a.finetune_loss == "l1_dssim" else f"{a.finetune_loss} loss"
+            print(f"fine-tuning ({a.finetune_params}): {fr.iterations} iterations over {len(fr.psnr_before)} cameras, {which} {fr.losses[0] if fr.losses else float('nan'):.6g} -> "
                   f"{fr.losses[-1] if fr.losses else float('nan'):.6g}, mean PSNR {mean(fr.psnr_before):.3f} -> {mean(fr.psnr_after):.3f} dB  {time.perf_counter() - tf:.3f} s")
             for e in fr.error_list:
                 print("  " + e)
