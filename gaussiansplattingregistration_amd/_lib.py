@@ -109,6 +109,8 @@ SIGNATURES = {
     "gsr_normals_knn": (_i32, [_vp, _i64, _i32, _vp, _i32, _i32, _vp]),
     "gsr_cov_from_normals": (_i32, [_vp, _i64, _f64, _vp, _i32, _i32, _vp]),
     "gsr_decompose_cov": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _i32, _i32, _vp]),
+    "gsr_cov_build": (_i32, [_vp, _vp, _i64, _vp, _i32, _i32, _vp]),
+    "gsr_cov_build_backward": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _i32, _i32, _vp]),
     "gsr_ply_unpack": (_i32, [_vp, _i64, _i32, C.POINTER(_i32), _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
     "gsr_ply_pack": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _vp]),
     "gsr_sh_rotation": (_i32, [_vp, _i32, _vp]),

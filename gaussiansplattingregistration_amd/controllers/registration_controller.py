@@ -134,7 +134,9 @@ class RegistrationController:
                         match_colors_gate=None, warp=None, device="cuda:0"):
         """Merges the repository's original clouds with the current transform (the arguments of the merge as in ``evaluate_registration``)
         and fine-tunes the merged model against photographs (``finetune.ModelFinetuner``).  ``images``: a directory of
-        ``<image_name>.png`` or one ``(H, W, 3)`` image per camera; ``params``: ``FinetuneParams``.  Returns ``(merged model, FinetuneResult)``
+        ``<image_name>.png`` or one ``(H, W, 3)`` image per camera; ``params``: ``FinetuneParams``, handed on as it is -- with ``"scaling"`` /
+        ``"rotation"`` in ``params.params`` the shape of the splats is tuned too and the merged model comes back with a consistent
+        ``_scaling`` / ``_rotation`` / ``_covariance`` triple that ``save_ply`` stores.  Returns ``(merged model, FinetuneResult)``
         (the result is ``None`` when cancelled: the merged model is then untouched); the model is kept in ``self.finetuned_model``."""
         from ..finetune import ModelFinetuner
         from ..models.gaussian_model import GaussianModel

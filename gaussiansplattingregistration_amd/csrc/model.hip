@@ -25,6 +25,7 @@
 // largest magnitude of every eigenvector is positive (first maximum on ties).  Everything the reference path derives from
 // V is invariant under column sign flips except the signs inside the scattered rows; tests compare up to those.
 #include "gsr_common.h"
+#include "gsr_covbuild.h"
 #include "gsr_oneshot.h"
 
 #include <float.h>
@@ -668,16 +669,9 @@ __global__ __launch_bounds__(256) void k_ply_unpack(int64_t n, const unsigned ch
         scale[3 * i] = s0; scale[3 * i + 1] = s1; scale[3 * i + 2] = s2;
         rot[4 * i] = qw; rot[4 * i + 1] = qx; rot[4 * i + 2] = qy; rot[4 * i + 3] = qz;
         // build_rotation (general_utils.py:43-66) on the normalised quaternion, L = R diag(exp(scale)), covariance = L L^T (:69-80), float32
-        const float nrm = sqrtf(qw * qw + qx * qx + qy * qy + qz * qz);
-        const float w = qw / nrm, x = qx / nrm, y = qy / nrm, z = qz / nrm;
-        const float e0 = expf(s0), e1 = expf(s1), e2 = expf(s2);
-        const float R00 = 1.0f - 2.0f * (y * y + z * z), R01 = 2.0f * (x * y - w * z), R02 = 2.0f * (x * z + w * y);
-        const float R10 = 2.0f * (x * y + w * z), R11 = 1.0f - 2.0f * (x * x + z * z), R12 = 2.0f * (y * z - w * x);
-        const float R20 = 2.0f * (x * z - w * y), R21 = 2.0f * (y * z + w * x), R22 = 1.0f - 2.0f * (x * x + y * y);
-        const float l00 = R00 * e0, l01 = R01 * e1, l02 = R02 * e2, l10 = R10 * e0, l11 = R11 * e1, l12 = R12 * e2, l20 = R20 * e0, l21 = R21 * e1, l22 = R22 * e2;
-        cov6[6 * i] = (l00 * l00 + l01 * l01) + l02 * l02; cov6[6 * i + 1] = (l00 * l10 + l01 * l11) + l02 * l12;
-        cov6[6 * i + 2] = (l00 * l20 + l01 * l21) + l02 * l22; cov6[6 * i + 3] = (l10 * l10 + l11 * l11) + l12 * l12;
-        cov6[6 * i + 4] = (l10 * l20 + l11 * l21) + l12 * l22; cov6[6 * i + 5] = (l20 * l20 + l21 * l21) + l22 * l22;
+        float c[6];
+        cov_build(s0, s1, s2, qw, qx, qy, qz, c);
+        cov6[6 * i] = c[0]; cov6[6 * i + 1] = c[1]; cov6[6 * i + 2] = c[2]; cov6[6 * i + 3] = c[3]; cov6[6 * i + 4] = c[4]; cov6[6 * i + 5] = c[5];
     }
     // SH rest: a thread per output float, consecutive threads on consecutive output addresses; sh[i][k][c] = file f_rest[c * K + k]
     if (F > 0) {

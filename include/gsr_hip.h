@@ -445,6 +445,27 @@ int32_t gsr_cov_from_normals(const double* normals, int64_t n, double epsilon, d
 int32_t gsr_decompose_cov(const float* cov6, int64_t n, int32_t mode, float* scaling, float* rotation, float* matrix,
                           int32_t on_device, int32_t device, void* stream);
 
+/* The other direction, and its derivative (csrc/covgrad.hip, csrc/gsr_covbuild.h): the covariance of every splat from its
+ * log-scales and RAW quaternion (w, x, y, z; any norm but 0), cov = R(q / |q|) diag(exp(scaling))^2 R^T in float32 -- the arithmetic
+ * gsr_ply_unpack runs on the rows of a file, so gsr_cov_build of the scale / rot it returned gives the cov6 it returned, bit for bit.
+ * gsr_cov_build_backward takes grad_cov6 = dLoss/dcov6 in the convention of gsr_raster_backward (an off-diagonal entry stands for both
+ * symmetric positions) and returns dLoss/dscaling and dLoss/drotation; the map does not depend on |q|, so rotation . grad_rotation = 0
+ * up to rounding and grad_rotation scales with 1 / |q|.
+ * scaling[n*3], rotation[n*4], cov6 / grad_cov6[n*6] (xx,xy,xz,yy,yz,zz), grad_scaling[n*3], grad_rotation[n*4]; float32, all host or
+ * all device as on_device says (host arrays are staged and copied back; the call returns when the stream has finished).
+ *   - n == 0: GSR_OK, no array is touched.  n < 0, or a NULL scaling / rotation / cov6 / grad_cov6 with n > 0: GSR_E_INVALID and a
+ *     message that names the argument.
+ *   - backward: grad_scaling or grad_rotation may be NULL and is then skipped; both NULL: GSR_E_INVALID.  What is computed for one
+ *     output does not depend on whether the other is asked for.
+ *   - outputs are overwritten, never accumulated into.
+ *   - a row whose six grad_cov6 entries are all zero (the rasteriser gives every culled splat exact zeros) gets exact +0.0 in both
+ *     outputs, whatever its scaling and rotation: 0 * exp(100) does not become NaN.
+ *   - a row with |q| = 0 or a non-finite input yields what the arithmetic yields (NaN), in that row only -- as the loader does.
+ *   - one thread per splat, no atomics: the same inputs give the same bits. */
+int32_t gsr_cov_build(const float* scaling, const float* rotation, int64_t n, float* cov6, int32_t on_device, int32_t device, void* stream);
+int32_t gsr_cov_build_backward(const float* scaling, const float* rotation, const float* grad_cov6, int64_t n, float* grad_scaling,
+                               float* grad_rotation, int32_t on_device, int32_t device, void* stream);
+
 /* 3DGS .ply vertex rows -> the level-0 arrays, on the device (replaces the plyfile -> numpy -> torch.tensor(device=
  * "cuda") chain of GaussianModel.from_ply, src/models/gaussian_model.py:98-139, and the covariance it builds, :34-38 +
  * src/utils/general_utils.py:43-80).  rows_dev: n rows of row_bytes bytes as they are in the file (binary little endian), already in

@@ -15,7 +15,7 @@ from every camera, and compared where both cover a pixel (coverage >= ``--covera
 per camera and as means (``GeometryEvaluator``).  With ``--images`` as well, both evaluations run; the geometric log then goes to
 ``<log>.geometry``.
 
-``--finetune N [--finetune-holdout K] [--finetune-loss l2|l1|l1_dssim] [--finetune-lambda L]``: the merged model is fine-tuned for N
+``--finetune N [--finetune-holdout K] [--finetune-params dc,sh_rest,opacity] [--finetune-loss l2|l1|l1_dssim] [--finetune-lambda L]``: the merged model is fine-tuned for N
 iterations (``finetune.ModelFinetuner``) on the cameras that are not held out (every K-th is, default 8); MSE / PSNR / SSIM on the held-out
 cameras without and with it go to ``<log>.finetune``.  ``l1_dssim`` is (1 - L) L1 + L (1 - SSIM), L = 0.2 by default.
 
@@ -67,6 +67,8 @@ def main():
     ap.add_argument("--finetune-holdout", type=int, default=8, metavar="K", help="every K-th camera (the first included) is held out of the fine-tuning")
     ap.add_argument("--finetune-loss", choices=("l2", "l1", "l1_dssim"), default="l2", help="l1_dssim: (1 - lambda) L1 + lambda (1 - SSIM), the fused loss kernel")
     ap.add_argument("--finetune-lambda", type=float, default=0.2, metavar="L", help="the weight of the SSIM term of --finetune-loss l1_dssim")
+    ap.add_argument("--finetune-params", default="dc,sh_rest,opacity", help="the tensors --finetune tunes: comma-separated, of dc, sh_rest, opacity, xyz, "
+                    "scaling, rotation (the last two tune the shape of the splats, DESIGN.md 31)")
     a = ap.parse_args()
     if a.finetune is not None and a.images is None:
         ap.error("--finetune needs --images")
@@ -166,8 +168,9 @@ def main():
         merge_args = dict(rotate_sh=a.rotate_sh, with_scaling=a.with_scaling, fuse=fuse, match_colors=cm, match_colors_gate=gate, warp=field)
         plain, _ = rcf.finetune_merged([], a.images, FinetuneParams(iterations=0, background=tuple(a.background)), **merge_args)
         before = held_out(plain)
-        tuned, fr = rcf.finetune_merged(train, a.images, FinetuneParams(iterations=a.finetune, background=tuple(a.background), loss=a.finetune_loss,
-                                                                       lambda_dssim=a.finetune_lambda), **merge_args)
+        tuned, fr = rcf.finetune_merged(train, a.images, FinetuneParams(iterations=a.finetune, params=tuple(x for x in a.finetune_params.split(",") if x),
+                                                                       background=tuple(a.background), loss=a.finetune_loss, lambda_dssim=a.finetune_lambda),
+                                        **merge_args)
         after = held_out(tuned)
         record = {"finetune": a.finetune, "loss": a.finetune_loss, "train_cameras": len(fr.psnr_before), "held_out_cameras": len(held), "held_out_without": before, "held_out_with": after,
                   "train_psnr_before": fr.psnr_before, "train_psnr_after": fr.psnr_after, "losses": fr.losses, "error_list": fr.error_list}

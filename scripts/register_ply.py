@@ -45,7 +45,8 @@ sampling noise of a one-nearest match does not reach the transform.  Rigid only:
 `--finetune CAMERAS.json --finetune-images DIR [--finetune-iters N] [--finetune-params dc,sh_rest,opacity] [--finetune-loss l2|l1|l1_dssim]
 [--finetune-lambda L]` (with `--out`): the merged cloud is fine-tuned against the photographs of those cameras (`finetune.ModelFinetuner`,
 DESIGN.md 26) after the merge and before the save.  `l1_dssim` is (1 - L) L1 + L (1 - SSIM), L = 0.2 by default, from the fused loss
-kernel.
+kernel.  `--finetune-params` names the tensors to tune, of dc, sh_rest, opacity, xyz, scaling, rotation; with `scaling` /
+`rotation` the shape of the splats is tuned and the saved file holds the tuned scales and quaternions.
 
 Prints the 4x4 transformation (first -> second), fitness and inlier RMSE; `--out` saves the merged cloud.
 """
@@ -108,7 +109,8 @@ def main():
                     "short Adam run through the differentiable rasteriser, after the merge and before the save; cameras in the merged cloud's frame")
     ap.add_argument("--finetune-images", metavar="DIR", help="directory of <img_name>.png, one per camera of --finetune")
     ap.add_argument("--finetune-iters", type=int, default=200, metavar="N")
-    ap.add_argument("--finetune-params", default="dc,sh_rest,opacity", help="comma-separated, of dc, sh_rest, opacity, xyz")
+    ap.add_argument("--finetune-params", default="dc,sh_rest,opacity", help="comma-separated, of dc, sh_rest, opacity, xyz, scaling, rotation (the last two tune the shape of "
+                    "the splats: the saved file holds the tuned scales and quaternions, DESIGN.md 31)")
     ap.add_argument("--finetune-loss", choices=("l2", "l1", "l1_dssim"), default="l2", help="l1_dssim: (1 - lambda) L1 + lambda (1 - SSIM), the fused loss kernel")
     ap.add_argument("--finetune-lambda", type=float, default=0.2, metavar="L", help="the weight of the SSIM term of --finetune-loss l1_dssim")
     a = ap.parse_args()
@@ -266,6 +268,8 @@ def main():
             which = "loss" if a.finetune_loss == "l2" else f"{a.finetune_loss} loss (lambda {a.finetune_lambda:g})" if a.finetune_loss == "l1_dssim" else f"{a.finetune_loss} loss"
             print(f"fine-tuning ({a.finetune_params}): {fr.iterations} iterations over {len(fr.psnr_before)} cameras, {which} {fr.losses[0] if fr.losses else float('nan'):.6g} -> "
                   f"{fr.losses[-1] if fr.losses else float('nan'):.6g}, mean PSNR {mean(fr.psnr_before):.3f} -> {mean(fr.psnr_after):.3f} dB  {time.perf_counter() - tf:.3f} s")
+            if fr.geometry_source:
+                print(f"  scaling / rotation tuned from the {fr.geometry_source} factors of the covariances")
             for e in fr.error_list:
                 print("  " + e)
         merged.save_ply(a.out)
