@@ -181,11 +181,11 @@ __device__ __forceinline__ bool kl_gate_rejects(float s2, float det_c, float det
 // scanning (E is inscribed in the query sphere; for a flat disc it holds a few percent of its volume).
 
 // The span (first sorted position, length) of one grid row (ry, rz) for a parent at pm: the row's cells within the
-// sphere of radius sqrt(Ra2), clipped to the pre-reject ellipsoid when `clip`.  IRR: positions in the irregular list.
+// sphere of radius sqrt(Ra2), clipped to the pre-reject ellipsoid when `clip`.  cs: the grid's prefix table of the list the pass
+// scans (SelectArgs::cellStartC for the children's stream, ::cellStartI for the irregular list).
 // ONE definition shared by k_select (every mode) and k_spans: the capacities must equal what the passes scan.
 // (The square roots are the hardware's 1-ulp v_sqrt_f32: every one of them sits behind a margin of 1e-5 or more.)
-template <bool IRR>
-__device__ __forceinline__ void select_row_span(const SelectArgs& a, const GridParams& g, const f3& pm, const EllClip& ec, bool clip,
+__device__ __forceinline__ void select_row_span(const int* cs, const GridParams& g, const f3& pm, const EllClip& ec, bool clip,
                                                 float Ra2, int x0, int x1, int ry, int rz, int& s, int& len) {
     // distance from the parent to the row's y/z slab (widened by the rounding slack)
     // (the first / last row of the grid also holds every centre clamped in from outside: half-infinite)
@@ -222,10 +222,8 @@ __device__ __forceinline__ void select_row_span(const SelectArgs& a, const GridP
             xa = xa < x0 ? x0 : xa;
             xb = xb > x1 ? x1 : xb;
             const int rowbase = (rz * g.gy + ry) * g.gx;
-            int e;
-            if (IRR) { s = a.cellStartI[rowbase + xa]; e = a.cellStartI[rowbase + xb + 1]; }      // positions in the irregular list
-            else { s = a.cellStartC[rowbase + xa]; e = a.cellStartC[rowbase + xb + 1]; }      // positions in the children's stream
-            len = e - s;
+            s = cs[rowbase + xa];
+            len = cs[rowbase + xb + 1] - s;
         }
     }
 }

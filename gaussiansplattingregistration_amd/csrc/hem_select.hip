@@ -52,10 +52,12 @@ __device__ __forceinline__ void select_stage3(const SelectArgs& a, const ParLds*
 
 // stage 2 on up to 64 queued survivors (lane < cnt holds one): radius test, colour gate, KL gate, parent rule -- the
 // reference's decisions, every expression in its operand order; accepted pairs go to the third-stage queue.
-// count_v: lane k holds the number of pairs parent k has had accepted so far (read and advanced here).
+// npair[k]: the number of pairs parent k has had accepted so far (read and advanced here).  Uniform values in SCALAR registers: as
+// lane k of a vector register they cost a v_readlane and a masked v_add per parent of the batch, and the four `lane == k` masks eight
+// scalar registers for the whole kernel (scripts/isa_loop_mix.py, profiles/select_isa_before.txt).
 template <int MODE>
 __device__ __forceinline__ void select_stage2(const SelectArgs& a, const ParLds* par, int lane, int cnt, const unsigned* q, int qh,
-                                              unsigned& count_v, Q3& q3) {
+                                              unsigned (&npair)[SEL_NP], Q3& q3) {
     SEL_PROF_T(tp2);
     SEL_PROF_CNT(8, 1, lane); SEL_PROF_CNT(9, cnt, lane);
     bool acc = false;
@@ -72,7 +74,9 @@ __device__ __forceinline__ void select_stage2(const SelectArgs& a, const ParLds*
         const float4* row = a.geo + 4 * (int64_t)j;
         float4 ca = row[0], cb = row[1], cc = row[2], cd = row[3];   // 64 contiguous bytes, all four up front: one round trip
         // (an empty statement the compiler cannot see through: without it the loads of the covariance and the determinant sink into the
-        // branch behind the radius / colour gates -- a SECOND round trip per batch, +2 800 cycles, found in the phase profile)
+        // branch behind the radius / colour gates -- a SECOND round trip per batch, +2 800 cycles, found in the phase profile.  Kept: the
+        // census (scripts/isa_loop_mix.py, profiles/select_isa_after.txt) shows what it costs -- 7 v_mov_b32 per batch of 64 behind the loads,
+        // which line the sixteen values up in the registers the statement pins; no lane read, no nop)
         asm volatile("" : "+v"(ca.x), "+v"(ca.y), "+v"(ca.z), "+v"(ca.w), "+v"(cb.x), "+v"(cb.y), "+v"(cb.z), "+v"(cb.w),
                           "+v"(cc.x), "+v"(cc.y), "+v"(cc.z), "+v"(cc.w), "+v"(cd.x), "+v"(cd.y), "+v"(cd.z), "+v"(cd.w));
         const f3 cm = {ca.x, ca.y, ca.z};
@@ -109,9 +113,8 @@ __device__ __forceinline__ void select_stage2(const SelectArgs& a, const ParLds*
     for (int kk = 0; kk < SEL_NP; ++kk) {
         if (kk < k_lo || kk > k_hi) continue;                 // (uniform)
         const unsigned long long mk = __ballot(acc && k == kk);
-        const unsigned ck = (unsigned)__builtin_amdgcn_readlane((int)count_v, kk);
-        if (acc && k == kk) rel = ck + (unsigned)mbcnt64(mk, 0);
-        if (lane == kk) count_v += (unsigned)__popcll(mk);
+        if (acc && k == kk) rel = npair[kk] + (unsigned)mbcnt64(mk, 0);
+        npair[kk] += (unsigned)__popcll(mk);
     }
     if (MODE == SEL_COUNT) { SEL_PROF_ADD(2, tp2, lane); return; }
     if (acc) {
@@ -165,6 +168,63 @@ __global__ __launch_bounds__(256) void k_parent_prep(int P, const unsigned* __re
     }
 }
 
+// The parent record in SGPRs, in two parts.  As inline assembly: the scan runs in a loop behind the wave's own stores (pcnt, the
+// pairs), the compiler cannot tell that they leave prec[] alone, and a load that "may be clobbered" is not made a scalar load however
+// uniform its address -- it became ten global_load_dwordx4 with 64 lanes reading the same 160 bytes, and 40 v_readfirstlane behind
+// them (SQ_INSTS_VMEM_RD +16 M per 5 M level, profiles/archive/r04o_*).
+// ParHot: what every parent's scan keeps for its whole run -- six dwords; the filter constants go straight on to vector registers.
+// ScanCold: what only the walk over the box needs (select_scan, a parent without a row list), fetched where it is used.
+typedef unsigned sel_u4v __attribute__((ext_vector_type(4)));
+typedef unsigned sel_u8v __attribute__((ext_vector_type(8)));
+struct ParHot { float R2, white; int js, active, selfq, rows; };
+struct ScanCold { f3 pm; float R, ey, ez; EllClip ec; GridParams g; };
+static_assert(offsetof(ParentRec, R) == 60 && offsetof(ParentRec, R2) == 64 && offsetof(ParentRec, u00) == 72 && offsetof(ParentRec, T1) == 96 &&
+              offsetof(ParentRec, ec) == 100 && offsetof(ParentRec, js) == 136 && offsetof(ParentRec, ey) == 148 && offsetof(ParentRec, rows) == 156 &&
+              sizeof(EllClip) == 36 && sizeof(GridParams) == 40 && offsetof(GridParams, gz) == 32,
+              "the selection's scalar loads read the record and the grid by offsets");
+__device__ __forceinline__ float sel_f(unsigned u) { return __builtin_bit_cast(float, u); }
+
+// A member of k_select's argument block, fetched WHERE IT IS USED (one scalar load from the kernel's argument segment, whose only
+// entry is the SelectArgs: a member lies at its offset in the struct).  The compiler loads every member the kernel touches once, at
+// its top, and keeps it: 40 scalar registers across the parent, row-batch and chunk loops for values that are read once per parent or
+// per work item, or only on the walk over the box.  The members the chunk and stage-2/3 loops read stay plain `a.member`.
+// ONLY inside k_select and what is inlined into it: the offset is right because that kernel's single parameter is the SelectArgs by
+// value (KARG0 = 0, the parameter's place in the argument segment; k_select checks its own signature against it below).  A kernel
+// with another parameter in front, or another kernel that inlined select_parent, would read the wrong words without a diagnostic.
+constexpr int SEL_KARG0 = 0;            // where k_select's SelectArgs starts in its argument segment
+template <typename T, int OFF>
+__device__ __forceinline__ T sel_karg() {
+    static_assert(sizeof(T) == 4 || sizeof(T) == 8, "one or two dwords");
+    const auto kp = __builtin_amdgcn_kernarg_segment_ptr();
+    if constexpr (sizeof(T) == 8) {
+        unsigned long long v;
+        asm volatile("s_load_dwordx2 %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=s"(v) : "s"(kp), "n"(OFF));
+        return __builtin_bit_cast(T, v);
+    } else {
+        unsigned v;
+        asm volatile("s_load_dword %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=s"(v) : "s"(kp), "n"(OFF));
+        return __builtin_bit_cast(T, v);
+    }
+}
+#define SEL_KARG(member) sel_karg<decltype(SelectArgs::member), SEL_KARG0 + (int)offsetof(SelectArgs, member)>()
+template <typename... P> struct sel_only_args : std::false_type {};
+template <> struct sel_only_args<SelectArgs> : std::true_type {};
+template <typename... P> constexpr bool sel_kernel_takes_only_args(void (*)(P...)) { return sel_only_args<P...>::value; }
+__device__ __forceinline__ void select_load_cold(const ParentRec* rp, const GridParams* gp, ScanCold& c) {
+    sel_u4v w0; sel_u8v w1, wg;
+    unsigned wR, wT, wgz;
+    unsigned long long we;
+    asm volatile("s_load_dwordx4 %0, %7, 0x0\n\ts_load_dword %1, %7, 0x3c\n\ts_load_dwordx8 %2, %7, 0x64\n\ts_load_dword %3, %7, 0x84\n\t"
+                 "s_load_dwordx2 %4, %7, 0x94\n\ts_load_dwordx8 %5, %8, 0x0\n\ts_load_dword %6, %8, 0x20\n\ts_waitcnt lgkmcnt(0)"
+                 : "=&s"(w0), "=&s"(wR), "=&s"(w1), "=&s"(wT), "=&s"(we), "=&s"(wg), "=&s"(wgz) : "s"(rp), "s"(gp) : "memory");
+    c.pm = {sel_f(w0[0]), sel_f(w0[1]), sel_f(w0[2])};
+    c.R = sel_f(wR);
+    c.ec = {sel_f(w1[0]), sel_f(w1[1]), sel_f(w1[2]), sel_f(w1[3]), sel_f(w1[4]), sel_f(w1[5]), sel_f(w1[6]), sel_f(w1[7]), sel_f(wT)};
+    c.ey = sel_f((unsigned)we); c.ez = sel_f((unsigned)(we >> 32));
+    c.g.ox = sel_f(wg[0]); c.g.oy = sel_f(wg[1]); c.g.oz = sel_f(wg[2]); c.g.c = sel_f(wg[3]); c.g.inv_c = sel_f(wg[4]); c.g.slack = sel_f(wg[5]);
+    c.g.gx = (int)wg[6]; c.g.gy = (int)wg[7]; c.g.gz = (int)wgz; c.g.ncells = 0;      // (ncells: not used by the row walk)
+}
+
 // One pass of a parent over its grid rows: IRR = false scans the cell-sorted components themselves and keeps the
 // REGULAR ones; IRR = true scans the list of irregular components (ipos, addressed through irank at the cell
 // boundaries).  Survivors of the stage-1 filter go to the LDS ring.
@@ -174,51 +234,56 @@ __global__ __launch_bounds__(256) void k_parent_prep(int P, const unsigned* __re
 // VGPRs.  With the parent record in scalar registers both forms need 65, and this one is 5 % faster: no suspended scans (6 % of the
 // parents recomputed a batch of row spans), half the ring.  profiles/archive/r04o_*.)
 template <int MODE, bool IRR>
-__device__ __forceinline__ void select_scan(const SelectArgs& a, const GridParams& g, const ParentRec& pr, const ParLds* par, unsigned ktag,
-                                            const float (&vc)[11], int lane, unsigned long long* bits, unsigned* q, int& qh, int& qn, unsigned& count_v,
+__device__ __forceinline__ void select_scan(const SelectArgs& a, const ParentRec* rp, const ParHot& pr, const ParLds* par, unsigned ktag,
+                                            const float (&vc)[11], int lane, unsigned long long* bits, unsigned* q, int& qh, int& qn, unsigned (&npair)[SEL_NP],
                                             Q3& q3, unsigned& cum, unsigned lo, unsigned hi, const int2* rl, int lcnt) {
-    const f3 pm = pr.pm;
-    const EllClip& ec = pr.ec;
     // rl != NULL: the spans of the parent's lcnt non-empty rows, in scan order, as k_spans left them (it computes every span anyway,
     // for the capacities): one 8-byte load per row instead of the box, ~80 instructions per row and two dependent look-ups in the
     // prefix table.  The candidates, their order and with it the pairs are the same either way (select_row_span made both).
     const bool listed = rl != nullptr;
-    bool clip = false;
-    int x0 = 0, x1 = 0, y0 = 0, z0 = 0, ny = 1, nrows = lcnt;
-    float Ra2 = 0.0f;
-    if (!listed) {
-        // (uniform values, but float arithmetic is VALU work and its results would sit in vector registers for the whole scan: the box
-        // goes back to the scalar file.  The compiler knows the values are uniform and folds a plain readfirstlane away -- leaving them
-        // where they are; a zero it cannot see through, added to the bit pattern, keeps the instruction)
-        int vz;
-        asm volatile("v_mov_b32 %0, 0" : "=v"(vz));
-        const auto uni = [vz](int v) { return __builtin_amdgcn_readfirstlane(v + vz); };
-        const auto unif = [vz](float v) { return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v) + vz)); };
-        const float Ra = unif(fabsf(pr.R) * 1.00001f + g.slack);       // conservative search extent
-        clip = !IRR && ec.on != 0.0f;
-        // rows: the sphere's box, cut down to the pre-reject ellipsoid's box when the rows are clipped to it (rows beyond its y / z
-        // extent would come out empty one by one)
-        const float Ry = clip ? fminf(Ra, pr.ey + g.slack) : Ra, Rz = clip ? fminf(Ra, pr.ez + g.slack) : Ra;
-        x0 = uni(cell_of(pm.x - Ra, g.ox, g.inv_c, g.gx)); x1 = uni(cell_of(pm.x + Ra, g.ox, g.inv_c, g.gx));
-        y0 = uni(cell_of(pm.y - Ry, g.oy, g.inv_c, g.gy));
-        const int y1 = uni(cell_of(pm.y + Ry, g.oy, g.inv_c, g.gy));
-        z0 = uni(cell_of(pm.z - Rz, g.oz, g.inv_c, g.gz));
-        const int z1 = uni(cell_of(pm.z + Rz, g.oz, g.inv_c, g.gz));
-        ny = y1 - y0 + 1;
-        nrows = ny * (z1 - z0 + 1);
-        Ra2 = unif(Ra * Ra);
-    }
+    int nrows = listed ? lcnt : 0x40000000;                     // not listed: the first batch computes it
     const bool white = !IRR && pr.white != 0.0f;                // wave-uniform
-    SEL_PROF_CNT(10, nrows, lane);
     for (int rb = 0; rb < nrows; rb += 64) {
         SEL_PROF_T(tpr);
         SEL_PROF_CNT(11, 1, lane);
         const int r = rb + lane;
         int s = 0, len = 0;
-        if (r < nrows) {
-            if (listed) { const int2 e = rl[r]; s = e.x; len = e.y; }
-            else select_row_span<IRR>(a, g, pm, ec, clip, Ra2, x0, x1, y0 + r % ny, z0 + r / ny, s, len);
+        if (listed) {
+            if (r < nrows) { const int2 e = rl[r]; s = e.x; len = e.y; }
+        } else {
+            // A parent whose row list overflowed (more than SEL_ROWS non-empty rows) walks the box of its search
+            // region.  What that takes -- the grid's geometry, the clipping ellipsoid, the radius: 28 dwords -- is fetched HERE, per batch
+            // of 64 rows, and the box is derived again: held across the scan these values (and the box) were 40 scalar registers that
+            // every parent's chunk, stage-2 and stage-3 loops spilled around (44 spills, profiles/select_isa_before.txt).
+            ScanCold c;
+            select_load_cold(rp, SEL_KARG(gp), c);
+            const int* cs = IRR ? SEL_KARG(cellStartI) : SEL_KARG(cellStartC);
+            const GridParams& g = c.g;
+            const f3 pm = c.pm;
+            // (uniform values, but float arithmetic is VALU work and its results would sit in vector registers for the whole batch: the box
+            // goes back to the scalar file.  The compiler knows the values are uniform and folds a plain readfirstlane away -- leaving them
+            // where they are; a zero it cannot see through, added to the bit pattern, keeps the instruction.  The census: 1 v_mov, 8
+            // v_readfirstlane and 8 v_add per batch of this path.)
+            int vz;
+            asm volatile("v_mov_b32 %0, 0" : "=v"(vz));
+            const auto uni = [vz](int v) { return __builtin_amdgcn_readfirstlane(v + vz); };
+            const auto unif = [vz](float v) { return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v) + vz)); };
+            const float Ra = unif(fabsf(c.R) * 1.00001f + g.slack);       // conservative search extent
+            const bool clip = !IRR && c.ec.on != 0.0f;
+            // rows: the sphere's box, cut down to the pre-reject ellipsoid's box when the rows are clipped to it (rows beyond its y / z
+            // extent would come out empty one by one)
+            const float Ry = clip ? fminf(Ra, c.ey + g.slack) : Ra, Rz = clip ? fminf(Ra, c.ez + g.slack) : Ra;
+            const int x0 = uni(cell_of(pm.x - Ra, g.ox, g.inv_c, g.gx)), x1 = uni(cell_of(pm.x + Ra, g.ox, g.inv_c, g.gx));
+            const int y0 = uni(cell_of(pm.y - Ry, g.oy, g.inv_c, g.gy));
+            const int y1 = uni(cell_of(pm.y + Ry, g.oy, g.inv_c, g.gy));
+            const int z0 = uni(cell_of(pm.z - Rz, g.oz, g.inv_c, g.gz));
+            const int z1 = uni(cell_of(pm.z + Rz, g.oz, g.inv_c, g.gz));
+            const int ny = y1 - y0 + 1;
+            nrows = ny * (z1 - z0 + 1);
+            const float Ra2 = unif(Ra * Ra);
+            if (r < nrows) select_row_span(cs, g, pm, c.ec, clip, Ra2, x0, x1, y0 + r % ny, z0 + r / ny, s, len);
         }
+        if (rb == 0) SEL_PROF_CNT(10, nrows, lane);
         len = len > 0 ? len : 0;
         const unsigned long long nz_m = __ballot(len > 0);
         if (nz_m == 0ull) continue;
@@ -277,6 +342,7 @@ __device__ __forceinline__ void select_scan(const SelectArgs& a, const GridParam
                         // vc = {pm, U, T1} in VECTOR registers: a VALU instruction with an SGPR operand issues at half rate
                         in = !(white_smd(vc, cm.x, cm.y, cm.z) > vc[9]);
                     } else {                                                  // the reference's radius test (pointindex.cpp:137)
+                        const f3 pm = {vc[0], vc[1], vc[2]};
                         const f3 dq = sub3(pm, cm);
                         in = dot3(dq, dq) < pr.R2;
                     }
@@ -298,7 +364,7 @@ __device__ __forceinline__ void select_scan(const SelectArgs& a, const GridParam
                 SEL_PROF_ADD(4, tps, lane);
                 // drain: stage 2 appears ONCE in the code (not once per unrolled u), on full batches of 64
                 while (qn >= 64) {
-                    select_stage2<MODE>(a, par, lane, 64, q, qh, count_v, q3);
+                    select_stage2<MODE>(a, par, lane, 64, q, qh, npair, q3);
                     qh = (qh + 64) & (SEL_QCAP - 1);
                     qn -= 64;
                 }
@@ -322,37 +388,29 @@ __device__ __forceinline__ void select_fill_par(const SelectArgs& a, int p, int6
 
 // One work item: parent p (the wave's k-th), part [lo, hi) of its flat candidate space (the whole parent: 0, 2^32 - 1); its pairs
 // go to par[k].base on (FILL / SPARSE; select_fill_par has filled par[k]).  Survivors and accepted pairs may stay behind in the
-// rings: select_flush ends a wave's (a work item's) run.  The number of accepted pairs accumulates in lane k of count_v.
+// rings: select_flush ends a wave's (a work item's) run.  The number of accepted pairs accumulates in npair[k].
 template <int MODE>
-__device__ __forceinline__ void select_parent(const SelectArgs& a, const GridParams& g, int p, int k, unsigned lo, unsigned hi, int lane,
-                                              const ParLds* par, unsigned* q, int& qh, int& qn, unsigned long long* bits, unsigned& count_v, Q3& q3) {
+__device__ __forceinline__ void select_parent(const SelectArgs& a, int p, int k, unsigned lo, unsigned hi, int lane,
+                                              const ParLds* par, unsigned* q, int& qh, int& qn, unsigned long long* bits, unsigned (&npair)[SEL_NP], Q3& q3) {
     SEL_PROF_T(tp0);
-    // The record lives in SGPRs.  As inline assembly: this body runs in a loop behind the wave's own stores (pcnt, the pairs), the
-    // compiler cannot tell that they leave prec[] alone, and a load that "may be clobbered" is not made a scalar load however uniform
-    // its address -- it became ten global_load_dwordx4 with 64 lanes reading the same 160 bytes, and 40 v_readfirstlane behind them
-    // (SQ_INSTS_VMEM_RD +16 M per 5 M level, profiles/archive/r04o_*).
-    ParentRec pr;
-    {
-        typedef unsigned u16v __attribute__((ext_vector_type(16)));
-        typedef unsigned u8v __attribute__((ext_vector_type(8)));
-        u16v w0, w1; u8v w2;
-        const ParentRec* rp = a.prec + p;
-        asm volatile("s_load_dwordx16 %0, %3, 0x0\n\ts_load_dwordx16 %1, %3, 0x40\n\ts_load_dwordx8 %2, %3, 0x80\n\ts_waitcnt lgkmcnt(0)"
-                     : "=&s"(w0), "=&s"(w1), "=&s"(w2) : "s"(rp) : "memory");
-        unsigned raw[40];
-        static_assert(sizeof(raw) == sizeof(ParentRec), "the three scalar loads cover the record");
-#pragma unroll
-        for (int i = 0; i < 16; ++i) { raw[i] = w0[i]; raw[16 + i] = w1[i]; }
-#pragma unroll
-        for (int i = 0; i < 8; ++i) raw[32 + i] = w2[i];
-        __builtin_memcpy(&pr, raw, sizeof(pr));
-    }
-    // the constants of the stage-1 filter in vector registers (v_mov from the SGPRs once per parent)
+    // The record's hot part in SGPRs (see ParHot): the mean, R2 ... u22, T1 and the six integers at its end -- 21 of its 40 dwords are
+    // loaded (the stage-2/3 fields come from the ParLds slot), and six of them stay.
+    const ParentRec* rp = SEL_KARG(prec) + p;
+    ParHot pr;
+    // the constants of the stage-1 filter in vector registers (v_mov from the SGPRs once per parent: ten of them, kept -- a VALU
+    // instruction with an SGPR operand issues at half rate, and the filter runs once per candidate)
     float vc[11];
+    vc[10] = 0.0f;                      // (white_smd's array has a spare element)
     {
-        const float src[11] = {pr.pm.x, pr.pm.y, pr.pm.z, pr.u00, pr.u01, pr.u02, pr.u11, pr.u12, pr.u22, pr.T1, 0.0f};
+        sel_u4v w0; sel_u8v w1, w2;
+        unsigned wT;
+        asm volatile("s_load_dwordx4 %0, %4, 0x0\n\ts_load_dwordx8 %1, %4, 0x40\n\ts_load_dword %2, %4, 0x60\n\ts_load_dwordx8 %3, %4, 0x80\n\ts_waitcnt lgkmcnt(0)"
+                     : "=&s"(w0), "=&s"(w1), "=&s"(wT), "=&s"(w2) : "s"(rp) : "memory");
+        pr.R2 = sel_f(w1[0]); pr.white = sel_f(w1[1]);
+        pr.js = (int)w2[2]; pr.active = (int)w2[3]; pr.selfq = (int)w2[4]; pr.rows = (int)w2[7];
+        const unsigned src[10] = {w0[0], w0[1], w0[2], w1[2], w1[3], w1[4], w1[5], w1[6], w1[7], wT};      // pm, u00 ... u22, T1
 #pragma unroll
-        for (int i = 0; i < 11; ++i) asm volatile("v_mov_b32 %0, %1" : "=v"(vc[i]) : "s"(src[i]));
+        for (int i = 0; i < 10; ++i) asm volatile("v_mov_b32 %0, %1" : "=v"(vc[i]) : "s"(src[i]));
     }
     const unsigned ktag = (unsigned)k << SEL_TAG_SHIFT;
     unsigned cum = 0;                   // flat candidates of the batches behind the scan
@@ -368,7 +426,7 @@ __device__ __forceinline__ void select_parent(const SelectArgs& a, const GridPar
         // a following parent's first group of SEL_U * 64 survivors would wrap onto the oldest entries (an accepted pair lost silently,
         // ADVICE r04).  So a full batch goes through stage 2 right here: qn <= 63 again in front of every scan.
         if (qn >= 64) {
-            select_stage2<MODE>(a, par, lane, 64, q, qh, count_v, q3);
+            select_stage2<MODE>(a, par, lane, 64, q, qh, npair, q3);
             qh = (qh + 64) & (SEL_QCAP - 1);
             qn -= 64;
         }
@@ -378,10 +436,11 @@ __device__ __forceinline__ void select_parent(const SelectArgs& a, const GridPar
         // pass B: the irregular children, which the pre-reject never applies to (rows clipped to the sphere only)
         // the row lists k_spans left for this parent (bit 31 of pr.rows), per pass: a count of at most SEL_ROWS is a complete list
         const int cA = pr.rows & 0xff, cB = (pr.rows >> 8) & 0xff;
-        const int2* rlp = (a.rowlist != nullptr && pr.rows < 0) ? a.rowlist + (int64_t)p * (2 * SEL_ROWS) : nullptr;
-        select_scan<MODE, false>(a, g, pr, par, ktag, vc, lane, bits, q, qh, qn, count_v, q3, cum, lo, hi,
+        int2* const rowlist = SEL_KARG(rowlist);
+        const int2* rlp = (rowlist != nullptr && pr.rows < 0) ? rowlist + (int64_t)p * (2 * SEL_ROWS) : nullptr;
+        select_scan<MODE, false>(a, rp, pr, par, ktag, vc, lane, bits, q, qh, qn, npair, q3, cum, lo, hi,
                                  rlp != nullptr && cA <= SEL_ROWS ? rlp : nullptr, cA);
-        if (a.n_irr > 0) select_scan<MODE, true>(a, g, pr, par, ktag, vc, lane, bits, q, qh, qn, count_v, q3, cum, lo, hi,
+        if (SEL_KARG(n_irr) > 0) select_scan<MODE, true>(a, rp, pr, par, ktag, vc, lane, bits, q, qh, qn, npair, q3, cum, lo, hi,
                                                  rlp != nullptr && cB <= SEL_ROWS ? rlp + SEL_ROWS : nullptr, cB);
     }
     SEL_PROF_ADD(0, tp0, lane);
@@ -391,10 +450,10 @@ __device__ __forceinline__ void select_parent(const SelectArgs& a, const GridPar
 // The partial batches at the end of a wave's run: the survivors left in the ring, then the accepted pairs left in the queue.
 template <int MODE>
 __device__ __forceinline__ void select_flush(const SelectArgs& a, const ParLds* par, int lane, const unsigned* q, int& qh, int& qn,
-                                             unsigned& count_v, Q3& q3) {
+                                             unsigned (&npair)[SEL_NP], Q3& q3) {
     while (qn > 0) {                    // (the parent's own entry may have made it 64)
         const int c = qn < 64 ? qn : 64;
-        select_stage2<MODE>(a, par, lane, c, q, qh, count_v, q3);
+        select_stage2<MODE>(a, par, lane, c, q, qh, npair, q3);
         qh = (qh + c) & (SEL_QCAP - 1);
         qn -= c;
     }
@@ -417,6 +476,7 @@ __global__ __launch_bounds__(64 * WPB) void k_select(SelectArgs a) {
     __shared__ float s_q3f[WPB][4][SEL_Q3CAP];
     __shared__ unsigned long long s_bits[WPB][SEL_MCAP / 64 + SEL_U];
     __shared__ ParLds s_par[WPB][SEL_NP];
+    static_assert(SEL_KARG0 == 0 && sel_kernel_takes_only_args(&k_select<MODE, WPB, QUEUE>), "SEL_KARG reads the argument segment by offsetof(SelectArgs, member)");
     const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     a.logtab = k_logf_tab;                                  // (the exact logf is a rare path: its table stays in constant memory, 256 bytes of LDS less)
     if (lane < SEL_MCAP / 64 + SEL_U) s_bits[wv][lane] = 0ull;
@@ -424,7 +484,6 @@ __global__ __launch_bounds__(64 * WPB) void k_select(SelectArgs a) {
     ParLds* par = s_par[wv];
     Q3 q3 = {s_q3u[wv][0], s_q3u[wv][1], s_q3f[wv][0], s_q3f[wv][1], s_q3f[wv][2], s_q3f[wv][3], 0, 0};
     __builtin_amdgcn_wave_barrier();
-    const GridParams g = *a.gp;
     int qh = 0, qn = 0;                 // survivor ring: head and fill (uniform)
 
     if constexpr (QUEUE) {
@@ -432,34 +491,36 @@ __global__ __launch_bounds__(64 * WPB) void k_select(SelectArgs a) {
         const unsigned part = *a.part_p;
         int item = (int)blockIdx.x * WPB + wv;
         while (item < n_items) {
-            const uint2 it = a.hitem[item];
-            const int p = __builtin_amdgcn_readfirstlane((int)a.porder[it.x]);
+            const uint2 it = SEL_KARG(hitem)[item];
+            const int p = __builtin_amdgcn_readfirstlane((int)SEL_KARG(porder)[it.x]);
             const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(it.y * part));
             const unsigned hi = lo + part > lo ? lo + part : 0xffffffffu;
             int64_t base = 0;
-            if (MODE == SEL_SPARSE) base = a.poff[p] + lo;          // accepted <= candidates of the part: the parts cannot collide
-            if (MODE == SEL_SPARSE && a.cap_pairs && (unsigned long long)base + part > a.cap_pairs) {      // beyond the buffers: no pairs, the level reruns
-                if (lane == 0) { a.part_cnt[item] = 0u; *a.abort_p = 1; }
+            if (MODE == SEL_SPARSE) base = SEL_KARG(poff)[p] + lo;          // accepted <= candidates of the part: the parts cannot collide
+            const unsigned long long cap_pairs = MODE == SEL_SPARSE ? SEL_KARG(cap_pairs) : 0ull;
+            if (MODE == SEL_SPARSE && cap_pairs && (unsigned long long)base + part > cap_pairs) {      // beyond the buffers: no pairs, the level reruns
+                if (lane == 0) { SEL_KARG(part_cnt)[item] = 0u; *SEL_KARG(abort_p) = 1; }
                 int nxt0 = 0;
-                if (lane == 0) nxt0 = atomicAdd(&a.hq[1], 1);
+                if (lane == 0) nxt0 = atomicAdd(&SEL_KARG(hq)[1], 1);
                 item = __builtin_amdgcn_readfirstlane(nxt0);
                 continue;
             }
             if (MODE == SEL_FILL) {
-                base = a.poff[p];
-                for (int k = a.hfirst[p]; k < item; ++k) base += a.part_cnt[k];
+                base = SEL_KARG(poff)[p];
+                const unsigned* part_cnt = SEL_KARG(part_cnt);
+                for (int k = SEL_KARG(hfirst)[p]; k < item; ++k) base += part_cnt[k];
             }
-            unsigned count_v = 0u;
+            unsigned npair[SEL_NP] = {};
             if (lane == 0) select_fill_par(a, p, base, par);
             __builtin_amdgcn_wave_barrier();
-            select_parent<MODE>(a, g, p, 0, lo, hi, lane, par, q, qh, qn, s_bits[wv], count_v, q3);
-            select_flush<MODE>(a, par, lane, q, qh, qn, count_v, q3);
+            select_parent<MODE>(a, p, 0, lo, hi, lane, par, q, qh, qn, s_bits[wv], npair, q3);
+            select_flush<MODE>(a, par, lane, q, qh, qn, npair, q3);
             if (lane == 0 && (MODE == SEL_COUNT || MODE == SEL_SPARSE)) {
-                a.part_cnt[item] = count_v;
-                atomicAdd(&a.pcnt[p], count_v);                     // integer sum: the order of the parts does not matter
+                SEL_KARG(part_cnt)[item] = npair[0];
+                atomicAdd(&SEL_KARG(pcnt)[p], npair[0]);                     // integer sum: the order of the parts does not matter
             }
             int nxt = 0;
-            if (lane == 0) nxt = atomicAdd(&a.hq[1], 1);
+            if (lane == 0) nxt = atomicAdd(&SEL_KARG(hq)[1], 1);
             item = __builtin_amdgcn_readfirstlane(nxt);
             __builtin_amdgcn_wave_barrier();
         }
@@ -494,19 +555,24 @@ __global__ __launch_bounds__(64 * WPB) void k_select(SelectArgs a) {
             }
         }
         unsigned long long todo = __ballot(p_v >= 0);
-        unsigned count_v = 0u;
+        unsigned npair[SEL_NP] = {};
         __builtin_amdgcn_wave_barrier();
         SEL_PROF_ADD(5, tpk, lane);
         while (todo != 0ull) {
             const int k = __builtin_ctzll(todo);
             todo &= todo - 1ull;
             const int p = __builtin_amdgcn_readlane(p_v, k);
-            select_parent<MODE>(a, g, p, k, 0u, 0xffffffffu, lane, par, q, qh, qn, s_bits[wv], count_v, q3);
+            select_parent<MODE>(a, p, k, 0u, 0xffffffffu, lane, par, q, qh, qn, s_bits[wv], npair, q3);
         }
         SEL_PROF_T(tpf);
-        select_flush<MODE>(a, par, lane, q, qh, qn, count_v, q3);
+        select_flush<MODE>(a, par, lane, q, qh, qn, npair, q3);
         SEL_PROF_ADD(6, tpf, lane);
-        if (p_v >= 0 && (MODE == SEL_COUNT || MODE == SEL_SPARSE)) a.pcnt[p_v] = count_v;      // no global atomics: totals come from the scans
+        if (p_v >= 0 && (MODE == SEL_COUNT || MODE == SEL_SPARSE)) {      // no global atomics: totals come from the scans
+            unsigned mine = npair[0];                                 // lane k: parent k's count
+#pragma unroll
+            for (int kk = 1; kk < SEL_NP; ++kk) mine = lane == kk ? npair[kk] : mine;
+            a.pcnt[p_v] = mine;
+        }
     }
 }
 
@@ -560,7 +626,7 @@ __global__ __launch_bounds__(256) void k_spans(SelectArgs a) {
                 const int ny = y1 - y0 + 1, nrows = ny * (z1 - z0 + 1);
                 for (int r = sub; r < nrows; r += 16) {
                     int s = 0, len = 0;
-                    select_row_span<false>(a, g, pm, ec, clip, Ra2, x0, x1, y0 + r % ny, z0 + r / ny, s, len);
+                    select_row_span(a.cellStartC, g, pm, ec, clip, Ra2, x0, x1, y0 + r % ny, z0 + r / ny, s, len);
                     scanned += (unsigned long long)(len > 0 ? len : 0);
                     keep_span(0, s, len, nA);
                 }
@@ -571,7 +637,7 @@ __global__ __launch_bounds__(256) void k_spans(SelectArgs a) {
                 const int ny = y1 - y0 + 1, nrows = ny * (z1 - z0 + 1);
                 for (int r = sub; r < nrows; r += 16) {
                     int s = 0, len = 0;
-                    select_row_span<true>(a, g, pm, ec, false, Ra2, x0, x1, y0 + r % ny, z0 + r / ny, s, len);
+                    select_row_span(a.cellStartI, g, pm, ec, false, Ra2, x0, x1, y0 + r % ny, z0 + r / ny, s, len);
                     scanned += (unsigned long long)(len > 0 ? len : 0);
                     keep_span(1, s, len, nB);
                 }

@@ -83,7 +83,11 @@ for d in ("pmc_fetch", "pmc_write", "pmc_l2", "pmc_sq", "pmc_sq2", "pmc_tc"):
                 seen.add(key); launches[k] += 1
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench  # noqa: E402  (kernel_build_id: the kernel sources these counters belong to)
-out = {"kernel_build": bench.kernel_build_id(),
+import __graft_entry__ as ge  # noqa: E402
+# (kernel_build hashes the kernel SOURCES only; the flags they were compiled with are recorded beside it -- counters taken before a flag
+# change are stale although the hash still matches: compare build_flags with __graft_entry__ before quoting them)
+BUILD_FLAGS = " ".join(ge.HIPCC_FLAGS) + "".join("; %s: %s" % (k, " ".join(v)) for k, v in sorted(ge.EXTRA_FLAGS.items()))      # (one string: every dict in the summary is a kernel)
+out = {"kernel_build": bench.kernel_build_id(), "build_flags": BUILD_FLAGS,
        "command": "scripts/prof_hem.py 5000000 1 2  (ONE level of a 5 M-splat cloud, SH degree 3: the level-1 launch alone; per-launch averages)"}
 for k, v in pmc.items():
     n = max(1, launches.get(k, 1))
@@ -141,7 +145,7 @@ def pmc_set(dirs, prefix, command, fetch_dir, marker=None, levels=4):
                     seen_.add(key); nl[k] += 1
     if not acc:
         return None
-    o = {"kernel_build": bench.kernel_build_id(), "command": command,
+    o = {"kernel_build": bench.kernel_build_id(), "build_flags": BUILD_FLAGS, "command": command,
          "note": "FETCH_SIZE / WRITE_SIZE in KiB; on gfx950 FETCH_SIZE reports 1/2 of the bytes of a streaming read, x1.0 of random 64-byte "
                  "records, x0.67 of random 192-byte rows (profiles/archive/r03_fetch_calibration.txt): raw and x2 figures are both given"}
     for k, v in acc.items():
