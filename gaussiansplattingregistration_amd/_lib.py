@@ -135,6 +135,7 @@ SIGNATURES = {
     "gsr_ransac_correspondence": (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _i32, _i32, _vp]),
     "gsr_fgr_tuple_test": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, C.POINTER(_i64), C.POINTER(_i64), _i32, _i32, _vp]),
     "gsr_fgr_optimize": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i32, _i32, _vp]),
+    "gsr_sc2_correspondence": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i32, _i32, _vp]),
     "gsr_posegraph_optimize": (_i32, [_i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "gsr_raster_create": (_i32, [C.POINTER(_vp), _i32, _vp]),
     "gsr_raster_destroy": (_i32, [_vp]),
@@ -175,6 +176,9 @@ TEST_HOOKS = {
     "gsr_debug_stage1": (_i32, [_vp, _vp, _vp, _vp, _i64, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _i32]),
     "gsr_debug_ransac_sample": (_i32, [_u64, _i64, _i64, _i64, _i32, _vp]),
     "gsr_debug_fold": (_i32, [_vp, _i64, _i32, _i32, _vp, _i32]),
+    "gsr_test_i8_gemm_nt": (_i32, [_vp, _i64, _vp, _i64, _i64, _vp, _i32]),
+    "gsr_test_sc2_timed": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i32, _i32, _vp]),
+    "gsr_test_sc2_stages": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32]),
 }
 
 _lib = None
@@ -222,6 +226,18 @@ class FgrResult(C.Structure):
     """gsr_fgr_result (include/gsr_hip.h)."""
     _fields_ = [("T", C.c_double * 16), ("n_corres", C.c_int64), ("n_reciprocal", C.c_int64), ("n_trials", C.c_int64),
                 ("n_tuples", C.c_int64), ("iterations", C.c_int32), ("host_waits", C.c_int32), ("scale_global", C.c_double)]
+
+
+class Sc2Params(C.Structure):
+    """gsr_sc2_params (include/gsr_hip.h)."""
+    _fields_ = [("d_thr", C.c_double), ("seed_ratio", C.c_double), ("max_seeds", C.c_int32), ("k1", C.c_int32), ("k2", C.c_int32),
+                ("refine_iters", C.c_int32)]
+
+
+class Sc2Result(C.Structure):
+    """gsr_sc2_result (include/gsr_hip.h)."""
+    _fields_ = [("T", C.c_double * 16), ("fitness", C.c_double), ("inlier_rmse", C.c_double), ("best_seed", C.c_int64), ("best_index", C.c_int64),
+                ("n_seeds", C.c_int64), ("n_valid", C.c_int64), ("n_edges", C.c_int64), ("refine_steps", C.c_int32), ("host_waits", C.c_int32)]
 
 
 class ModelView(C.Structure):
@@ -330,6 +346,8 @@ GSR_CHECK_DISTANCE = 1
 GSR_CHECK_NORMAL = 2
 GSR_RANSAC_MAX_N = 16
 GSR_HYBRID_MAX_NN = 512
+GSR_SC2_MAX_CORRES = 32768
+GSR_SC2_MAX_K = 64
 
 
 def load(require_device: bool = False):

@@ -4,7 +4,7 @@ from __future__ import annotations
 import numpy as np
 
 from ..workers.registrators import (FGRRegistrator, LocalRegistrator, MultiScaleRegistratorMixture, MultiScaleRegistratorVoxel,
-                                    RANSACRegistrator)
+                                    RANSACRegistrator, SC2Registrator)
 
 
 class RegistrationController:
@@ -41,6 +41,17 @@ class RegistrationController:
         return result
 
     execute_fgr_registration = execute_fgr_registration_normal
+
+    def execute_sc2_registration_normal(self, params):          # the compatibility-graph method, handled like the two above
+        repo = self.data_repository
+        pc1 = repo.pc_open3d_list_first[repo.current_index]
+        pc2 = repo.pc_open3d_list_second[repo.current_index]
+        worker = SC2Registrator(pc1, pc2, self.ui_repository.transformation_matrix, params)
+        result = worker.run()
+        self.handle_registration_result_global(result)
+        return result
+
+    execute_sc2_registration = execute_sc2_registration_normal
 
     def execute_multiscale_registration(self, use_corresponding, sparse_first, sparse_second, registration_type,
                                         relative_fitness, relative_rmse, voxel_values, iter_values, rejection_type, k_value,

@@ -31,6 +31,20 @@ int32_t gsr_debug_ransac_sample(uint64_t seed, int64_t k0, int64_t count, int64_
 /* The fixed-order float64 fold (csrc/gsr_fold.h) on x [n][3] (host): thread t of block b holds row 256 b + t, zeros past n;
  * block_fold_store<3, 4, order> (0: wave_sum_xor, 1: wave_sum_rows), then k_fold_partials<final_threads> (64 or 256) into out3. */
 int32_t gsr_debug_fold(const double* x, int64_t n, int32_t order, int32_t final_threads, double* out3, int32_t device);
+/* D[M x N] int32 = A[M x K] B[N x K]^T (int8, row-major, host) through the tile code of k_sc2_rows (csrc/sc2.hip): the operands are
+ * copied into zero-padded device arrays of that kernel's layout and the kernel runs without its mask. */
+int32_t gsr_test_i8_gemm_nt(const int8_t* A, int64_t M, const int8_t* B, int64_t N, int64_t K, int32_t* D, int32_t device);
+/* gsr_sc2_correspondence on host arrays, leaving its stages in host arrays (any may be NULL): deg [m], seeds [n_seeds] (the
+ * correspondence of every rank), rows [n_seeds * m] (masked second-order rows), k1 / k2 [n_seeds * 64] (selection order, -1 behind
+ * the end), hyp [n_seeds * 12], good [n_seeds] (-1: invalid seed), rmse [n_seeds].  params / out: struct gsr_sc2_params / _result. */
+int32_t gsr_test_sc2_stages(const float* src_xyz, int64_t ns, const float* tgt_xyz, int64_t nt, const int32_t* corres, int64_t m,
+                            const void* params, void* out, int32_t* deg, int32_t* seeds, int32_t* rows, int32_t* k1, int32_t* k2,
+                            double* hyp, int32_t* good, double* rmse, int32_t device);
+/* gsr_sc2_correspondence itself (arrays host or device as on_device says) with a timed stream event between its stages:
+ * stage_ms[6] = gather + compatibility, seed sort, second-order rows (k_sc2_rows), consensus sets + hypotheses, scoring, refinement
+ * (the host's reads between its steps included).  scripts/bench_sc2.py. */
+int32_t gsr_test_sc2_timed(const float* src_xyz, int64_t ns, const float* tgt_xyz, int64_t nt, const int32_t* corres, int64_t m,
+                           const void* params, void* out, float* stage_ms, int32_t on_device, int32_t device, void* stream);
 #ifdef __cplusplus
 }
 #endif

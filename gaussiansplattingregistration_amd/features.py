@@ -1,6 +1,6 @@
 """Global registration on the GPU: ctypes front of ``gsr_hybrid_search``, ``gsr_fpfh``, ``gsr_feature_match``,
-``gsr_ransac_correspondence`` (``csrc/features.hip``), ``gsr_fgr_tuple_test`` and ``gsr_fgr_optimize`` (``csrc/fgr.hip``), all
-declared in ``include/gsr_hip.h``.
+``gsr_ransac_correspondence`` (``csrc/features.hip``), ``gsr_fgr_tuple_test`` and ``gsr_fgr_optimize`` (``csrc/fgr.hip``) and
+``gsr_sc2_correspondence`` (``csrc/sc2.hip``), all declared in ``include/gsr_hip.h``.
 
 Reference behaviour: ``compute_fpfh_feature``, ``registration_ransac_based_on_feature_matching`` and
 ``registration_fgr_based_on_feature_matching`` of Open3D 0.16.0 as the reference's ``src/utils/global_registration_util.py`` calls
@@ -21,7 +21,7 @@ try:
 except Exception:  # pragma: no cover
     torch = None
 
-__all__ = ["hybrid_search", "fpfh", "feature_match", "ransac_correspondence", "fgr_tuple_test", "fgr_optimize", "KIND_POINT_TO_POINT",
+__all__ = ["hybrid_search", "fpfh", "feature_match", "ransac_correspondence", "fgr_tuple_test", "fgr_optimize", "sc2_correspondence", "KIND_POINT_TO_POINT",
            "KIND_POINT_TO_PLANE",
            "CHECK_EDGE_LENGTH", "CHECK_DISTANCE", "CHECK_NORMAL"]
 
@@ -118,6 +118,35 @@ def ransac_correspondence(src_xyz, tgt_xyz, corres, max_corr, kind=KIND_POINT_TO
                                            C.c_void_p(_m.stream_ptr(device, on))), "gsr_ransac_correspondence")
     return {"transformation": np.array(R.T[:], dtype=np.float64).reshape(4, 4), "fitness": R.fitness, "inlier_rmse": R.inlier_rmse,
             "best_index": int(R.best_index), "n_evaluated": int(R.n_evaluated), "n_valid": int(R.n_valid), "exit_index": int(R.exit_index)}
+
+
+def _sc2_params(d_thr, seed_ratio, max_seeds, k1, k2, refine_iters):
+    P = _lib.Sc2Params()
+    P.d_thr, P.seed_ratio, P.max_seeds = float(d_thr), float(seed_ratio), int(max_seeds)
+    P.k1, P.k2, P.refine_iters = int(k1), int(k2), int(refine_iters)
+    return P
+
+
+def _sc2_dict(R):
+    return {"transformation": np.array(R.T[:], dtype=np.float64).reshape(4, 4), "fitness": R.fitness, "inlier_rmse": R.inlier_rmse,
+            "best_seed": int(R.best_seed), "best_index": int(R.best_index), "n_seeds": int(R.n_seeds), "n_valid": int(R.n_valid),
+            "n_edges": int(R.n_edges), "refine_steps": int(R.refine_steps), "host_waits": int(R.host_waits)}
+
+
+def sc2_correspondence(src_xyz, tgt_xyz, corres, d_thr, seed_ratio=0.2, max_seeds=4096, k1=30, k2=20, refine_iters=20, device=0):
+    """Compatibility-graph global registration over ``corres (m, 2)`` (``gsr_sc2_correspondence``, ``include/gsr_hip.h``): rigid,
+    deterministic, no sampling.  Returns a dict: transformation (source -> target), fitness, inlier_rmse, best_seed (rank), best_index
+    (correspondence), n_seeds, n_valid, n_edges, refine_steps, host_waits."""
+    L = _lib.load(require_device=True)
+    on = _m.is_cuda(src_xyz)
+    ps, ks, ns = _rows(src_xyz, 3, np.float32, device, on)
+    pt, kt, nt = _rows(tgt_xyz, 3, np.float32, device, on)
+    pc, kc, m = _rows(corres, 2, np.int32, device, on)
+    P = _sc2_params(d_thr, seed_ratio, max_seeds, k1, k2, refine_iters)
+    R = _lib.Sc2Result()
+    _lib.check(L.gsr_sc2_correspondence(ps, ns, pt, nt, pc, m, C.byref(P), C.byref(R), 1 if on else 0, int(device),
+                                        C.c_void_p(_m.stream_ptr(device, on))), "gsr_sc2_correspondence")
+    return _sc2_dict(R)
 
 
 def _fgr_options(division_factor=1.4, use_absolute_scale=False, decrease_mu=False, maximum_correspondence_distance=0.025,

@@ -75,6 +75,20 @@ class FGRRegistrationParams:
 
 
 @dataclass
+class SC2RegistrationParams:
+    """Compatibility-graph global registration (``do_sc2_registration``); the reference has no such method.  Rigid
+    only, deterministic, no seed: nothing is drawn."""
+    voxel_size: float = 0.05
+    mutual_filter: bool = True
+    max_correspondence: float = 0.075   # compatibility and inlier threshold d_thr (1.5 voxels)
+    seed_ratio: float = 0.2             # share of the correspondences taken as seeds
+    max_seeds: int = 4096
+    k1: int = 30                        # first consensus set
+    k2: int = 20                        # second consensus set: 3 <= k2 <= k1 <= 64
+    refine_iterations: int = 20
+
+
+@dataclass
 class PhotometricParams:
     """Render-based photometric refinement (``photo.PhotometricRefiner``); the reference has no such step.
     ``max_depth_diff`` has no default: scenes have no common unit of length."""

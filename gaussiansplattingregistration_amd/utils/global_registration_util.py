@@ -1,5 +1,5 @@
 """Global registration: the reference's ``src/utils/global_registration_util.py`` on the GPU (``features.py``,
-``csrc/features.hip``, ``csrc/fgr.hip``), with Open3D-named shims for what it reaches through open3d==0.16.0.
+``csrc/features.hip``, ``csrc/fgr.hip``, ``csrc/sc2.hip``), with Open3D-named shims for what it reaches through open3d==0.16.0.
 
 ``preprocess_point_cloud`` follows the project's conventions: ``PointCloud.voxel_down_sample`` then ``estimate_normals()`` (the
 averaged covariances of a splat cloud, KNN-30 without covariances -- so the reference's normal radius ``2 * voxel`` is inert, as
@@ -9,7 +9,9 @@ normal's sign, and with arbitrary signs only ~7 % of the mutual feature matches 
 DESIGN.md section 12).  The centroid moves with the cloud, so the orientation is the same for a cloud and its rigidly moved copy.
 ``orient="consistent"`` propagates the signs along the neighbour graph instead (``orient_normals_consistent``).
 Both methods of the reference's tab are here: ``do_ransac_registration`` and ``do_fgr_registration`` (Fast Global Registration;
-its tuple test draws with the library's counter-based sampler, so it is deterministic for a given ``seed``).
+its tuple test draws with the library's counter-based sampler, so it is deterministic for a given ``seed``).  A third method, which the
+reference does not have, stands beside them: ``do_sc2_registration``, the compatibility-graph method of ``csrc/sc2.hip`` (DESIGN.md
+section 33) -- rigid, deterministic, without sampling.
 """
 from __future__ import annotations
 
@@ -38,6 +40,7 @@ class GlobalRegistrationType(Enum):
 
     RANSAC = "RANSAC"
     FGR = "FGR"
+    SC2 = "SC2"              # the compatibility-graph method (not in the reference): appended, so the two above keep their values
 
 
 class RANSACEstimationMethod(Enum):
@@ -353,3 +356,45 @@ def do_fgr_registration(point_cloud_first, point_cloud_second, registration_para
     result = registration_fgr_based_on_feature_matching(source_down, target_down, source_fpfh, target_fpfh, options)
 
     return result
+
+
+class SC2Option:
+    """The parameters of the compatibility-graph method (``gsr_sc2_params`` without the threshold, which the shims take as
+    ``max_correspondence_distance``)."""
+
+    def __init__(self, seed_ratio=0.2, max_seeds=4096, k1=30, k2=20, refine_iterations=20):
+        self.seed_ratio, self.max_seeds = float(seed_ratio), int(max_seeds)
+        self.k1, self.k2, self.refine_iterations = int(k1), int(k2), int(refine_iterations)
+
+
+def registration_sc2_based_on_correspondence(source, target, corres, max_correspondence_distance, option=None):
+    """Compatibility-graph global registration over given correspondences ``(m, 2)`` (source row, target row): rigid, deterministic,
+    no sampling (``features.sc2_correspondence``).  ``max_correspondence_distance`` is both the compatibility and the inlier
+    threshold.  ``fitness`` and ``inlier_rmse`` are over the correspondences, as for RANSAC."""
+    o = option or SC2Option()
+    r = _F.sc2_correspondence(source.xyz32, target.xyz32, corres, max_correspondence_distance, seed_ratio=o.seed_ratio,
+                              max_seeds=o.max_seeds, k1=o.k1, k2=o.k2, refine_iters=o.refine_iterations, device=source.device_index)
+    info = {k: r[k] for k in ("best_seed", "best_index", "n_seeds", "n_valid", "n_edges", "refine_steps", "host_waits")}
+    return RegistrationResult(r["transformation"], r["fitness"], r["inlier_rmse"], info=info)
+
+
+def registration_sc2_based_on_feature_matching(source, target, source_feature, target_feature, mutual_filter,
+                                               max_correspondence_distance, option=None):
+    """Exact feature 1-NN, optional mutual filter (RANSAC's rule: the one-way set below 9 reciprocal pairs), then
+    ``registration_sc2_based_on_correspondence``."""
+    if not (max_correspondence_distance > 0.0):
+        return RegistrationResult()
+    corres, used_mutual = _F.feature_match(source_feature.rows, target_feature.rows, mutual=bool(mutual_filter), ransac_n=3,
+                                           device=source.device_index)
+    res = registration_sc2_based_on_correspondence(source, target, corres, max_correspondence_distance, option)
+    res.info["used_mutual"] = used_mutual
+    res.info["n_corres"] = int(corres.shape[0])
+    return res
+
+
+def do_sc2_registration(point_cloud_first, point_cloud_second, params):
+    source_down, source_fpfh = preprocess_point_cloud(point_cloud_first, params.voxel_size, orient=getattr(params, "orient_normals", "centroid"))
+    target_down, target_fpfh = preprocess_point_cloud(point_cloud_second, params.voxel_size, orient=getattr(params, "orient_normals", "centroid"))
+    option = SC2Option(params.seed_ratio, params.max_seeds, params.k1, params.k2, params.refine_iterations)
+    return registration_sc2_based_on_feature_matching(source_down, target_down, source_fpfh, target_fpfh, params.mutual_filter,
+                                                      params.max_correspondence, option)

@@ -11,7 +11,7 @@ from __future__ import annotations
 import copy
 
 from ..models.registration_data import LocalRegistrationData, MultiScaleRegistrationData
-from ..utils.global_registration_util import do_fgr_registration, do_ransac_registration
+from ..utils.global_registration_util import do_fgr_registration, do_ransac_registration, do_sc2_registration
 from ..utils.local_registration_util import do_icp_registration
 
 
@@ -249,3 +249,17 @@ class FGRRegistrator:
 
     def run(self):
         return do_fgr_registration(self.pc1, self.pc2, self.registration_params)
+
+
+class SC2Registrator:
+    """The worker of the compatibility-graph method, shaped like the two above: the first cloud is moved by the current pose, then
+    ``do_sc2_registration``."""
+
+    def __init__(self, pc1, pc2, init_transformation, registration_params):
+        self.pc1 = copy.deepcopy(pc1)
+        self.pc2 = copy.deepcopy(pc2)
+        self.pc1.transform(init_transformation)
+        self.registration_params = registration_params
+
+    def run(self):
+        return do_sc2_registration(self.pc1, self.pc2, self.registration_params)

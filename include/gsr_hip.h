@@ -690,6 +690,59 @@ int32_t gsr_fgr_tuple_test(const float* src_xyz, int64_t ns, const float* tgt_xy
 int32_t gsr_fgr_optimize(const float* src_xyz, int64_t ns, const float* tgt_xyz, int64_t nt, const int32_t* corres, int64_t m,
                          const gsr_fgr_options* options, gsr_fgr_result* result, int32_t on_device, int32_t device, void* stream);
 
+/* Compatibility-graph global registration, the project's own definition "after SC2-PCR" (Chen, Sun, Yang, Tao, CVPR 2022): the third
+ * global method, deterministic and without sampling.  csrc/sc2.hip; tests/sc2_model.py is this comment in
+ * float64 NumPy.  Rigid only.  With p_c = P[corres[c][0]], q_c = Q[corres[c][1]] in float64 from the float32 coordinates:
+ *   1 compatibility  a_ij = sqrt((dx * dx + dy * dy) + dz * dz) of p_i - p_j (no fused multiply-add, correctly rounded square root:
+ *                    the |d| of gsr_fgr_tuple_test), b_ij the same on q.  C_ij = 1 iff i != j and |a_ij - b_ij| < d_thr.  A NaN
+ *                    compares false: a non-finite point is an isolated row.  C is symmetric, C_ii = 0.
+ *   2 seeds          deg_i = sum_j C_ij;  n_seeds = min(max_seeds, ceil(seed_ratio * m), m);  the seeds are the first n_seeds
+ *                    correspondences in the order (deg descending, index ascending); a seed's place in that order is its RANK.
+ *   3 second order   for a seed s:  r_sj = C_sj * sum_k C_sk C_kj  (integers <= m; one product of 0/1 matrices on the i8 MFMA).
+ *   4 consensus      K1(s) = s and the first k1 - 1 indices j with C_sj = 1 in the order (r_sj descending, j ascending);
+ *                    l_j = #{k in K1(s) : C_jk = 1} for j in K1(s);  K2(s) = s and the first k2 - 1 of K1(s) \ {s} in the order
+ *                    (l_j descending, j ascending).  A seed with |K2| < 3 is invalid.
+ *   5 hypothesis     T_s = Umeyama without scaling on the members of K2(s) in ascending index: the point-to-point sums about
+ *                    ctr = the first member's source point, then the estimator update of the ICP (GSR_ICP_POINT_TO_POINT).  A
+ *                    non-finite T_s makes the seed invalid.
+ *   6 score          good_s = #{c : |T_s p_c - q_c|^2 < d_thr^2} over all m, rmse_s = sqrt(sum d2 / good_s): the evaluation of
+ *                    gsr_ransac_correspondence, sums in a fixed order.  The winner is the best valid seed by (good descending, rmse
+ *                    ascending, rank ascending).
+ *   7 refinement     at most refine_iters times: Umeyama on all current inliers (sums about the winner's source point, fixed order;
+ *                    fewer than 3 inliers or a non-finite result ends it), score the result, keep it iff good rose or good is equal
+ *                    and rmse fell, otherwise stop.
+ * Every discrete decision up to step 4 is integer arithmetic on C, whose bits step 1 fixes: they do not depend on scheduling.
+ * Not covered: similarity hypotheses (the test of step 1 is not scale-invariant), the paper's leading-eigenvector seed score, spatial
+ * non-maximum suppression and weighted SVD, point-to-plane estimation, more than GSR_SC2_MAX_CORRES correspondences. */
+#define GSR_SC2_MAX_CORRES 32768  /* C is m^2 bytes: 1 GiB here */
+#define GSR_SC2_MAX_K 64          /* largest k1 */
+typedef struct gsr_sc2_params {
+    double d_thr;              /* compatibility and inlier threshold (> 0; otherwise the empty result) */
+    double seed_ratio;         /* (0.2) share of the correspondences taken as seeds, in (0, 1] */
+    int32_t max_seeds;         /* (4096) cap on the number of seeds, >= 1 */
+    int32_t k1;                /* (30) size of the first consensus set */
+    int32_t k2;                /* (20) size of the second: 3 <= k2 <= k1 <= GSR_SC2_MAX_K */
+    int32_t refine_iters;      /* (20) cap on refinement steps, >= 0 */
+} gsr_sc2_params;
+typedef struct gsr_sc2_result {
+    double T[16];              /* row-major, source -> target; identity when no seed won */
+    double fitness;            /* good / m */
+    double inlier_rmse;        /* sqrt(sum d2 / good) */
+    int64_t best_seed;         /* rank of the winning seed, -1 if none */
+    int64_t best_index;        /* its correspondence, -1 if none */
+    int64_t n_seeds;
+    int64_t n_valid;           /* seeds with |K2| >= 3 and a finite hypothesis */
+    int64_t n_edges;           /* sum deg / 2 */
+    int32_t refine_steps;      /* refinement steps kept */
+    int32_t host_waits;        /* stream waits of the call: one for the winner, one per refinement step tried */
+} gsr_sc2_result;
+/* corres[m*2] int32 (source row, target row); xyz float32; the arrays host or device as on_device says, params and out host.
+ * m < 3 or d_thr <= 0 give the empty result of gsr_ransac_correspondence (identity, zeros, -1); so does a call without a valid
+ * seed, which still reports n_seeds, n_edges and host_waits.  GSR_E_INVALID with a message: a row outside [0, ns) x [0, nt) (device
+ * arrays are checked by the kernel: nothing is read out of bounds), m > GSR_SC2_MAX_CORRES, a parameter out of range. */
+int32_t gsr_sc2_correspondence(const float* src_xyz, int64_t ns, const float* tgt_xyz, int64_t nt, const int32_t* corres, int64_t m,
+                               const gsr_sc2_params* params, gsr_sc2_result* out, int32_t on_device, int32_t device, void* stream);
+
 /* ------------------------------------------------------------------- overlap-aware merge */
 
 /* Fuse two splat models that are ALREADY IN ONE FRAME (move one first: gsr_model_transform / gsr_model_similarity): a splat of A

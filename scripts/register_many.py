@@ -3,7 +3,7 @@
 registered pair, a pose graph with a line process that prunes wrongly registered pairs, and the merged cloud.
 
     python scripts/register_many.py a.ply b.ply c.ply ... --out merged.ply [--poses-out poses.json]
-           [--edges sequential|all] [--edge S T ...] [--global-fgr VOXEL | --global-ransac VOXEL]
+           [--edges sequential|all] [--edge S T ...] [--global-fgr VOXEL | --global-ransac VOXEL | --global-sc2 VOXEL]
            [--type point|plane|color|general] [--loss none|tukey|cauchy|gm|huber --k 0.1] [--max-corr 0.05] [--iters 30]
            [--prune 0.25] [--preference 1.0] [--reference 0] [--rotate-sh]
            [--clean-knn K --clean-std R [--clean-radius R --clean-nb N] [--clean-min-opacity A] [--clean-max-extent S]]
@@ -47,6 +47,8 @@ def main():
     method = ap.add_mutually_exclusive_group()
     method.add_argument("--global-fgr", type=float, metavar="VOXEL", help="initial transform of every pair by Fast Global Registration at this voxel size")
     method.add_argument("--global-ransac", type=float, metavar="VOXEL", help="initial transform of every pair by FPFH + RANSAC at this voxel size")
+    method.add_argument("--global-sc2", type=float, metavar="VOXEL", help="initial transform of every pair by the compatibility-graph method at this voxel "
+                        "size (deterministic, no sampling)")
     ap.add_argument("--ransac-iters", type=int, default=100000)
     ap.add_argument("--type", choices=["point", "plane", "color", "general"], default="plane")
     ap.add_argument("--loss", choices=["none", "tukey", "cauchy", "gm", "huber"], default="none")
@@ -75,7 +77,7 @@ def main():
     g.build_hip()
     from gaussiansplattingregistration_amd.models.gaussian_model import GaussianModel
     from gaussiansplattingregistration_amd.params.registration_parameters import (FGRRegistrationParams, LocalRegistrationParams,
-                                                                                  RANSACRegistrationParams)
+                                                                                  RANSACRegistrationParams, SC2RegistrationParams)
     from gaussiansplattingregistration_amd.utils import global_registration_util as G
     from gaussiansplattingregistration_amd.utils.local_registration_util import KernelLossFunctionType as K, LocalRegistrationType as T
     from gaussiansplattingregistration_amd.utils.point_cloud_converter import convert_gs_to_open3d_pc
@@ -103,6 +105,9 @@ def main():
     if a.global_fgr:
         gp = FGRRegistrationParams(voxel_size=a.global_fgr, maximum_correspondence=1.5 * a.global_fgr)
         init = lambda s, t, cs, ct: G.do_fgr_registration(cs, ct, gp).transformation
+    elif a.global_sc2:
+        gp = SC2RegistrationParams(voxel_size=a.global_sc2, max_correspondence=1.5 * a.global_sc2)
+        init = lambda s, t, cs, ct: G.do_sc2_registration(cs, ct, gp).transformation
     elif a.global_ransac:
         v = a.global_ransac
         gp = RANSACRegistrationParams(voxel_size=v, max_correspondence=1.5 * v, max_iteration=a.ransac_iters, confidence=0.999,

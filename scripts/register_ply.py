@@ -78,6 +78,9 @@ def main():
                     "reference's Global tab); its pose is the multiscale ICP's initial transform")
     method.add_argument("--global-fgr", type=float, metavar="VOXEL", help="global registration first by Fast Global Registration (FPFH + FGR at "
                     "this voxel size, the tab's other method); its pose is the multiscale ICP's initial transform")
+    method.add_argument("--global-sc2", type=float, metavar="VOXEL", help="global registration first by the compatibility-graph method (FPFH + "
+                        "second-order consensus at this voxel size: deterministic, no sampling, rigid only); its pose is the multiscale ICP's "
+                        "initial transform")
     ap.add_argument("--ransac-iters", type=int, default=100000, help="RANSAC hypotheses (max_iteration) of --global-ransac")
     ap.add_argument("--orient-normals", choices=("centroid", "consistent"), default="centroid", help="how --global-ransac / --global-fgr fix the "
                     "normals' signs before FPFH: towards the cloud's centroid, or propagated along the neighbour graph's spanning forest "
@@ -116,6 +119,9 @@ def main():
     a = ap.parse_args()
     if a.finetune and not (a.out and a.finetune_images):
         raise SystemExit("--finetune needs --out and --finetune-images")
+    if a.global_sc2 and a.with_scaling:
+        raise SystemExit("--global-sc2 compares lengths of the two clouds and estimates a rigid motion: refused with --with-scaling "
+                         "(--global-ransac is the scaled global method)")
     if a.mixture_refine is not None and a.with_scaling:
         raise SystemExit("--mixture-refine estimates a rigid motion: refused with --with-scaling")
     clean = clean_params_from_args(a)
@@ -189,6 +195,16 @@ def main():
         g = rc.execute_fgr_registration_normal(fp)
         print(f"global FGR: fitness {g.fitness:.4f}  rmse {g.inlier_rmse:.6f}  reciprocal pairs {g.info.get('n_reciprocal')}  "
               f"tuples {g.info.get('n_tuples')} of {g.info.get('n_trials')} trials  {time.perf_counter() - tg:.3f} s")
+    if a.global_sc2:
+        from gaussiansplattingregistration_amd.params.registration_parameters import SC2RegistrationParams
+        v = a.global_sc2
+        tg = time.perf_counter()
+        sp = SC2RegistrationParams(voxel_size=v, max_correspondence=1.5 * v)
+        sp.orient_normals = a.orient_normals
+        g = rc.execute_sc2_registration_normal(sp)
+        print(f"global SC2: fitness {g.fitness:.4f}  rmse {g.inlier_rmse:.6f}  correspondences {g.info.get('n_corres')}  "
+              f"seeds {g.info.get('n_valid')} valid of {g.info.get('n_seeds')}  edges {g.info.get('n_edges')}  "
+              f"refinement steps {g.info.get('refine_steps')}  {time.perf_counter() - tg:.3f} s")
     res = rc.execute_multiscale_registration(False, "", "", rtype, 1e-6, 1e-6, a.max_corr, a.iters, loss, a.k, not a.voxel, with_scaling=a.with_scaling)
     t3 = time.perf_counter()
     if res is None:
